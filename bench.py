@@ -39,6 +39,7 @@ Prints ONE JSON line (rank 0).  Keys beyond the driver's contract:
                  [4] cut into this run's N blocks (strong scaling: total bootstraps / slowest rank, decrypt-checked on
                  every rank)
   clock          shader clock of this process's GPU read from sysfs while the timed steps run (boxes differ by +-3 %)
+  dumped_outputs with --dump-outputs DIR: what dump_outputs wrote (the last timed step's output ciphertexts, rank 0)
 """
 import argparse
 import glob
@@ -63,6 +64,7 @@ FP64_PEAK_TFLOPS = 78.6  # datasheet FP64 vector peak (256 CUs x 4 SIMDs x 16 FM
 PREFLIGHT_STEPS = 16
 L2_ROWS_GBPS_LO, L2_ROWS_GBPS_HI = 16800.0, 18800.0  # MI355X_MICROARCH.md "Indexed rows": rows served by the XCD's L2
 FP64_SUSTAINED_TFLOPS = 62.0  # pure v_fma_f64 loop, tools/fp64_issue_bench.hip: the clock drops under FP64 load
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def algorithmic_flops(p):
@@ -392,7 +394,12 @@ def main():
                     help="N > 1: total gates of the configs[3] leg (2^20 in BASELINE.json; a rehearsal may shrink it)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 path with several ranks sharing one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write rank 0's output ciphertexts of the last timed step to DIR (see dump_outputs); the inputs "
+                         "are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line, the JSON result: everything else that libraries print there (RCCL's
     # version banner, for one) is sent to stderr by pointing fd 1 at fd 2 until the result is written
@@ -477,8 +484,9 @@ def main():
     def step_wallclock():  # first H2D of the inputs -> last D2H of the outputs, one synchronous call
         eoc.gate_batch(op, pin[0].array, pin[1].array, out=pin[2].array)
 
-    def make_workload(name, instances):
-        """(step, bootstraps per step, description, check) of a secondary workload on this rank's shard"""
+    def make_workload(name, instances, outputs=None):
+        """(step, bootstraps per step, description, check) of a secondary workload on this rank's shard; `outputs`, when
+        given, receives under "cts" the device tensor of the output ciphertexts each step writes"""
         from eoc_tfhe_amd import circuits
         wrng = np.random.default_rng(7000 + rank)
         if name in ("adder8", "adder8_optimized", "adder8_optimized_boots_gates", "adder8_prefix", "streq32"):
@@ -520,6 +528,8 @@ def main():
                 planes = np.stack([sk.encrypt_bits(bb[:, i].astype(np.uint8), 9000 + w0 + i, 0) for i in range(bb.shape[1])])
                 wires[w0: w0 + bb.shape[1]] = torch.from_numpy(planes).to(dev)
             boots = eoc.circuit_bootstraps(gates) * S
+            if outputs is not None:
+                outputs["cts"] = wires[sw[0]: sw[0] + 9] if name.startswith("adder8") else wires[outw]
 
             def wstep():
                 eng.circuit_run_device(gates, wires.data_ptr(), n_wires, S, stream=stream)
@@ -541,6 +551,8 @@ def main():
         mout = torch.empty_like(mc[0])
         boots = S + int((mops == eoc.OPS["MUX"]).sum())
         desc = f"{S} mixed NAND/XOR/MUX gates per GPU (BASELINE configs[3] shard), MUX = 2 bootstraps"
+        if outputs is not None:
+            outputs["cts"] = mout
 
         def wstep():
             eng.gate_batch_device(0, mc[0].data_ptr(), mc[1].data_ptr(), mc[2].data_ptr(), mout.data_ptr(), S,
@@ -657,8 +669,9 @@ def main():
     workload_desc = None
     circuit_check = None
     host_path = args.workload == "nand"
+    headline_out = {"cts": dout}
     if not host_path:  # the circuit / mixed shapes as a headline run on device-resident wires (secondary use of this script)
-        step, boots_per_step, workload_desc, circuit_check = make_workload(args.workload, args.instances)
+        step, boots_per_step, workload_desc, circuit_check = make_workload(args.workload, args.instances, headline_out)
 
     # ---- everything the later legs need is prepared BEFORE anything is timed, and the short secondary passes run first:
     # the device drops its clock within milliseconds of going idle and takes ~12 steps (40 ms) of load to come back
@@ -770,6 +783,8 @@ def main():
     kt = eng.kernel_times(reset=True)
     eng.set_profiling(False)
     wide_headline = eng.stats()["br_wide_launches"] > wide_launches_before_timed
+    # the last timed step's result, copied out before the later legs write the same buffers again
+    last_out = headline_out["cts"].cpu().numpy() if args.dump_outputs and rank == 0 else None
 
     # the same step captured once into a hipGraph and replayed K times (the engine is capturable once its workspace has its
     # size): what is left of the launch path is one graph launch per step.  Reported beside `value`, never as it.
@@ -1045,6 +1060,8 @@ def main():
                                        "definition; rounds 1-2 reported the same quantity; round 3's `value` was the "
                                        "PCIe-inclusive synchronous call, now `wallclock_gates_per_s`: SURVEY.md 8(d)'s first "
                                        "H2D -> last D2H, one eoc_gate_batch call per step on eoc_host_alloc buffers)")
+        if last_out is not None:
+            res["dumped_outputs"] = dump_outputs(args.dump_outputs, last_out, sk)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(res) + "\n").encode())
     for a in pin:
@@ -1058,6 +1075,23 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(out_dir, cts, sk):
+    """--dump-outputs: the output ciphertexts of the last timed step, one row per output bit, as out_dir/ciphertexts.npy
+    (torus values, float64 holds every int32 exactly), their decryptions as bits.npy (float32) and the rows written as
+    rows.npy (float64).  Above DUMP_BYTES in all, a fixed sample of rows (seed 0), the same from run to run."""
+    cts = cts.reshape(-1, cts.shape[-1])
+    rows = np.arange(cts.shape[0])
+    row_bytes = cts.shape[1] * 8 + 4 + 8
+    if rows.size * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(rows.size, DUMP_BYTES // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"ciphertexts": cts[rows].astype(np.float64), "bits": sk.decrypt_bits(cts[rows]).astype(np.float32),
+              "rows": rows.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "rows": int(rows.size), "of": int(cts.shape[0]), "files": sorted(n + ".npy" for n in arrays)}
 
 
 def cpu_baseline(args, p, c0, c1, gpu_out, key_seed, op):
