@@ -1,0 +1,298 @@
+// Body of k_blind_rotate / k_blind_rotate_tv (kernels.hip.h), included into both.  In scope: template parameters L, BGBIT,
+// SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test polynomials, used when TV).
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    d2 *s_tw = reinterpret_cast<d2 *>(smem);
+    d2 *s_twist = s_tw + kTwEntries;
+    d2 *s_scr_all = s_twist + kNH;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int h = __builtin_amdgcn_readfirstlane(tid >> 6);
+    d2 *scr = s_scr_all + h * kScr;
+    d2 *scr_partner = s_scr_all + (h ^ 1) * kScr;
+    int32_t *ext = reinterpret_cast<int32_t *>(scr); // [2N] signed periodic image of ACC_h (between steps)
+
+    const uint32_t job = blockIdx.x; // grid = number of jobs
+    // the rotation amounts of this job are wave-uniform and constant during the kernel: read as dwords (rows are 64-byte
+    // aligned: bara_stride is a multiple of 32 entries) by vector loads of a uniform address, or (SABAR) by scalar loads
+    // through the constant address space
+    typedef const __attribute__((address_space(4))) uint32_t *cu32p;
+    unsigned long long bara_addr = (unsigned long long)(uintptr_t)(A.bara + (size_t)job * A.bara_stride);
+
+    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128);
+    if (A.prep && A.step_begin == 0) { // folded k_prepare: this workgroup's row of rotation amounts
+        const uint32_t gjob = A.job0 + job, g = gjob / A.ks_S;
+        prepare_row(A.inline_desc ? A.desc0 : A.ks_descs[g], gjob - g * A.ks_S, A.n, A.bara + (size_t)job * A.bara_stride, tid, 128);
+        if constexpr (SABAR) eoc_row_stores_to_l2();
+        __syncthreads();
+        if constexpr (SABAR) eoc_scalar_cache_acquire();
+    }
+    // loads through the constant address space may be moved freely by the compiler (the memory is assumed invariant): the
+    // row's address is made opaque HERE, behind the prologue that may just have written the row, so that no load of it can
+    // be scheduled above this point
+    asm volatile("" : "+s"(bara_addr));
+    const cu32p bara32 = (cu32p)bara_addr;
+    // shipped form: the row is copied into LDS once (vector loads behind the barrier above: the workgroup's own stores,
+    // or an earlier kernel's) and every step reads its amount from there
+    uint16_t *s_abar = reinterpret_cast<uint16_t *>(s_scr_all + 2 * kScr);
+    if constexpr (!SABAR) {
+        const uint32_t *bara_v = reinterpret_cast<const uint32_t *>(A.bara + (size_t)job * A.bara_stride);
+        for (int m = tid; m < (A.n + 2) / 2; m += 128) reinterpret_cast<uint32_t *>(s_abar)[m] = bara_v[m];
+        __syncthreads();
+    }
+    auto load_abar = [&](int idx) __attribute__((always_inline)) {
+        if constexpr (SABAR) return (int)((bara32[idx >> 1] >> ((idx & 1) * 16)) & 0xffffu);
+        else return (int)s_abar[idx];
+    };
+
+    // ACC = (0, X^(2N - barb) * testvect), testvect = (mu, ..., mu), or (TV) the job's test polynomial
+    uint32_t racc[16]; // register copy of ACC_h: coefficient lane + 64 r in racc[r] (r < 8), lane + 64 r + 512 in racc[8 + r]
+    {
+        const int barb = load_abar(A.n);
+        const int rot = (2 * kN - barb) & (2 * kN - 1);
+        const int32_t *st = A.acc_state + ((size_t)job * 2 + h) * kN;
+        const int32_t *tvj = TV ? tv + (size_t)((A.job0 + job) / tv_rows) * kN : nullptr; // jobs are [table][row]
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
+            int idx = (j - rot) & (2 * kN - 1);
+            int32_t v;
+            if constexpr (TV) {
+                const uint32_t c = (uint32_t)tvj[idx & (kN - 1)]; // X^N = -1: the upper half of the period is negated
+                v = (int32_t)((idx & kN) ? 0u - c : c);
+            } else {
+                v = (idx & kN) ? -A.mu : A.mu;
+            }
+            v = h ? v : 0;
+            if (A.step_begin > 0) v = st[j]; // continue a blind rotation started by an earlier launch
+            racc[r] = (uint32_t)v;
+        }
+    }
+    __syncthreads();
+
+    const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
+    const uint32_t Bg = 1u << Bgbit, maskBg = Bg - 1, halfBg = Bg >> 1;
+    uint32_t offset = 0;
+#pragma unroll
+    for (int p = 1; p <= L; p++) offset += halfBg << (32 - p * Bgbit);
+    constexpr int KPL = 2 * L;
+    const __amdgpu_buffer_rsrc_t bk_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(A.bkfft), 0, (int)((size_t)A.n * KPL * 2 * kNH * 16), 0x00020000);
+    // digits arrive biased, u = digit + Bg/2 in [0, Bg); as_double(2^52 | u) - (2^52 + Bg/2) is the digit, exactly;
+    // the stage-0 sums p - q and p + q are formed on the biased integers and converted the same way
+    const double bias1 = 4503599627370496.0 + (double)halfBg, bias2 = 4503599627370496.0 + (double)Bg;
+
+#ifdef EOC_STAMPS
+    unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long st_prev = __builtin_amdgcn_s_memtime();
+    st_acc[12] = st_prev;                                          // loop entry time
+    st_acc[14] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));  // HW_REG_HW_ID: CU / SE / SIMD / wave slot
+    st_acc[13] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11)); // HW_REG_XCC_ID
+#endif
+    const int prio_slot = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (3 << 11)); // HW_ID.WAVE_ID: slot on the SIMD
+    // gadget length 2 has registers to spare: the forward transform's last four twiddles stay resident
+    constexpr bool kResT2 = L == 2;
+    d2 res_t2[4];
+    if constexpr (kResT2) tw_load(res_t2, s_tw + kTwF2 + lane, 64);
+    constexpr bool kResT1 = L == 2; // ... and the inverse transform's first table pass
+    d2 res_t1[4];
+    if constexpr (kResT1) tw_load(res_t1, s_tw + kTwI1 + (lane & 7), 8);
+    int abar_next = load_abar(A.step_begin);
+    for (int i = A.step_begin; i < A.step_end; i++) {
+        EOC_STAMP(15);
+        // The two waves that share a SIMD belong to different workgroups, and the issue arbiter favours the older
+        // one: in a launch that exactly fills the chip (1024 gates = 512 workgroups) the first half of the grid
+        // finishes at 0.82x and the second half at 1.19x of the mean, and the launch lasts as long as its slowest
+        // workgroup.  The two waves occupy different wave slots, so the slot parity tells them apart: the
+        // later-placed (odd) one holds the high priority A.prio_duty sixteenths of the steps, the other one the
+        // rest.  12/16 makes both halves finish together (-10 % on the launch).  Launches of several rounds are
+        // faster WITHOUT it (the arbiter's run-to-completion bias suits them: +4 %), so the host passes a
+        // negative duty there.
+        if (A.prio_duty >= 0) {
+            const bool first_part = (i & 15) < A.prio_duty;
+            if (first_part == ((prio_slot & 1) != 0))
+                __builtin_amdgcn_s_setprio(1);
+            else
+                __builtin_amdgcn_s_setprio(0);
+        } else if (A.prio_duty <= -2) {
+            // launches of several rounds: the co-resident waves are at unrelated steps, so the alternation is taken
+            // from the shader clock both of them read (phase length 2^(-prio_duty) cycles), even shares
+            const unsigned long long now = __builtin_amdgcn_s_memtime();
+            if ((int)((now >> (-A.prio_duty)) & 1) == (prio_slot & 1))
+                __builtin_amdgcn_s_setprio(1);
+            else
+                __builtin_amdgcn_s_setprio(0);
+        }
+        const int abar = __builtin_amdgcn_readfirstlane(abar_next);
+        // one step ahead (entry n is barb: always in bounds): an LDS read that retires with the rotation's ds_bpermutes, or
+        // (SABAR) an s_load that retires with the key rows
+        abar_next = load_abar(i + 1);
+        // (X^abar - 1) * ACC_h.  abar == 0 gives an all-zero polynomial, all-zero digits and an exact
+        // zero update, which is what skipping the step (as libtfhe does) amounts to.
+        // rows (h, p), p = 1..L, of BK_i by buffer loads: the row's byte offset is wave-uniform (SGPR), the lane part one
+        // loop-invariant VGPR
+        auto load_row = [&](int p, int c, d2 (&b)[8]) __attribute__((always_inline)) {
+            const uint32_t row_off = (uint32_t)((((size_t)i * KPL + h * L) * 2 + (size_t)(p - 1) * 2 + c) * kNH * 16);
+#pragma unroll
+            for (int r = 0; r < 8; r++)
+                b[r] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(bk_rsrc, lane * 16, (int)(row_off + r * 1024), 0));
+        };
+        d2 ra[8], rb[8];
+        uint32_t dlo[8], dhi[8];
+        {
+            const int s = abar & 63;
+            const int src = ((lane - s) & 63) << 2;
+            uint32_t t[16], d[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) t[r] = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)racc[r]);
+            const bool borrow = lane < s;
+#define EOC_RQ(q) case q: rot_digits<q>(t, racc, borrow, offset, d); break;
+            switch (abar >> 6) {
+                EOC_RQ(0) EOC_RQ(1) EOC_RQ(2) EOC_RQ(3) EOC_RQ(4) EOC_RQ(5) EOC_RQ(6) EOC_RQ(7)
+                EOC_RQ(8) EOC_RQ(9) EOC_RQ(10) EOC_RQ(11) EOC_RQ(12) EOC_RQ(13) EOC_RQ(14) EOC_RQ(15)
+                EOC_RQ(16) EOC_RQ(17) EOC_RQ(18) EOC_RQ(19) EOC_RQ(20) EOC_RQ(21) EOC_RQ(22) EOC_RQ(23)
+                EOC_RQ(24) EOC_RQ(25) EOC_RQ(26) EOC_RQ(27) EOC_RQ(28) EOC_RQ(29) EOC_RQ(30)
+                default: rot_digits<31>(t, racc, borrow, offset, d); break;
+            }
+#undef EOC_RQ
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                dlo[r] = d[r];
+                dhi[r] = d[8 + r];
+            }
+        }
+        EOC_STAMP(0);
+        // digit p of the 16 coefficients of this lane, first pass of its forward transform (stages 0-2)
+        auto make_x0 = [&](int p, d2 (&x)[8]) __attribute__((always_inline)) {
+            const int shift = 32 - p * Bgbit;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const uint32_t ua = (dlo[r] >> shift) & maskBg, ub = (dhi[r] >> shift) & maskBg;
+                const uint32_t up = (dlo[r + 4] >> shift) & maskBg, uq = (dhi[r + 4] >> shift) & maskBg;
+                const double a = __hiloint2double(0x43300000, (int)ua) - bias1;
+                const double b = __hiloint2double(0x43300000, (int)ub) - bias1;
+                const double dm = __hiloint2double(0x43300000, (int)(up - uq + Bg)) - bias2;
+                const double dp = __hiloint2double(0x43300000, (int)(up + uq)) - bias2;
+                fwd_stage0(x[r], x[r + 4], a, b, dm, dp);
+            }
+            fwd_pass0_tail(x);
+        };
+        auto mac = [&](bool first, const d2 (&x)[8], const d2 (&b)[8], d2 (&acc_)[8]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                if (first) {
+                    acc_[r].x = EOC_FMA(-x[r].y, b[r].y, x[r].x * b[r].x);
+                    acc_[r].y = EOC_FMA(x[r].y, b[r].x, x[r].x * b[r].y);
+                } else {
+                    acc_[r].x = EOC_FMA(-x[r].y, b[r].y, EOC_FMA(x[r].x, b[r].x, acc_[r].x));
+                    acc_[r].y = EOC_FMA(x[r].y, b[r].x, EOC_FMA(x[r].x, b[r].y, acc_[r].y));
+                }
+            }
+        };
+        // forward transforms of the l digits (two at a time, skewed on the one scratch; an odd last one alone) and
+        // the chain for the partner's output polynomial.  The spectra stay in registers for the own chain below.
+        d2 xs[L][8], S[8];
+#pragma unroll
+        for (int p0 = 0; p0 + 1 < L; p0 += 2) {
+            load_row(p0 + 1, 1 - h, ra);
+            load_row(p0 + 2, 1 - h, rb);
+            make_x0(p0 + 1, xs[p0]);
+            EOC_STAMP(1);
+            fft_fwd_rest_x2(xs[p0], xs[p0 + 1], [&]() __attribute__((always_inline)) { make_x0(p0 + 2, xs[p0 + 1]); },
+                            s_tw, scr, lane, kResT2 ? &res_t2 : nullptr);
+            EOC_STAMP(2);
+            mac(p0 == 0, xs[p0], ra, S);
+            mac(false, xs[p0 + 1], rb, S);
+            EOC_STAMP(3);
+        }
+        if constexpr ((L & 1) != 0) {
+            load_row(L, 1 - h, ra);
+            make_x0(L, xs[L - 1]);
+            EOC_STAMP(1);
+            fft_fwd_rest(xs[L - 1], s_tw, scr, lane);
+            EOC_STAMP(2);
+            mac(L == 1, xs[L - 1], ra, S);
+            EOC_STAMP(3);
+        }
+        // own rows: the first two are requested before the exchange (requesting the first one a register pass
+        // earlier into a third buffer, or the second one only after the exchange, changes nothing: measured)
+        load_row(1, h, ra);
+        if constexpr (L >= 2) load_row(2, h, rb);
+#pragma unroll
+        for (int r = 0; r < 8; r++) scr[r * 64 + lane] = S[r];
+        EOC_STAMP(4);
+        __syncthreads();
+        EOC_STAMP(5);
+#pragma unroll
+        for (int r = 0; r < 8; r++) S[r] = scr_partner[r * 64 + lane]; // the chain of the other input polynomial
+        mac(false, xs[0], ra, S);
+        if constexpr (L >= 3) load_row(3, h, ra);
+        if constexpr (L >= 2) mac(false, xs[1], rb, S);
+        if constexpr (L >= 4) load_row(4, h, rb);
+        if constexpr (L >= 3) mac(false, xs[2], ra, S);
+        if constexpr (L >= 4) mac(false, xs[3], rb, S);
+        EOC_STAMP(6);
+        __syncthreads(); // the partner has read this wave's scratch before the inverse transform overwrites it
+        EOC_STAMP(7);
+        d2 ut[8];
+        fft_inv_wave(S, ut, s_tw, s_twist, scr, lane, kResT1 ? &res_t1 : nullptr);
+        EOC_STAMP(8);
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            d2 y = cmulc(S[r], ut[r]); // 1/512 is in the key image
+            racc[r] += wrap_trunc(y.x);
+            racc[8 + r] += wrap_trunc(y.y);
+        }
+        wave_lds_fence();
+        EOC_STAMP(9);
+    }
+    if (A.step_end >= A.n) { // the sample extraction below reads the image: written once, after the last step
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int j = lane + 64 * r;
+            ext[j] = (int32_t)racc[r];
+            ext[j + kN] = (int32_t)(0u - racc[r]);
+        }
+        wave_lds_fence();
+    }
+#ifdef EOC_STAMPS
+    st_acc[11] = __builtin_amdgcn_s_memtime(); // loop exit time
+    if (A.stamps && lane == 0)
+        for (int k = 0; k < 16; k++) A.stamps[((size_t)blockIdx.x * 2 + h) * 16 + k] = st_acc[k];
+#endif
+
+    // the lane index again, from the hardware (not from threadIdx): nothing lane-derived then has to stay live across
+    // the step loop just for these stores
+    const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    if (A.step_end < A.n) { // not the last part: park the accumulator for the next launch
+        int32_t *st = A.acc_state + ((size_t)job * 2 + h) * kN;
+#pragma unroll
+        for (int r = 0; r < 16; r++) st[lane_e + 64 * (r & 7) + (r >> 3) * kNH] = (int32_t)racc[r];
+        return;
+    }
+    // tLweExtractLweSample, index 0: u_0 = ACC_0[0], u_j = -ACC_0[N - j] = ext[2N - j]; b = ACC_1[0]
+    if (A.ks_descs) { // + lweKeySwitch set-up: ubar_j = u_j + 2^(31 - t basebit), out = (0, ..., 0, b)
+        const uint32_t gjob = A.job0 + job;
+        if (h == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                int j = lane + 64 * r;
+                A.ubar[(size_t)gjob * kN + j] = (uint32_t)ext[(2 * kN - j) & (2 * kN - 1)] + A.ks_prec_offset;
+            }
+        } else {
+            const uint32_t g = gjob / A.ks_S, si = gjob - g * A.ks_S;
+            int32_t *o = (A.inline_desc ? A.desc0.out : A.ks_descs[g].out) + (size_t)si * (A.n + 1);
+            for (int m = lane; m < A.n; m += 64) o[m] = 0;
+            if (lane == 0) o[A.n] = ext[0];
+        }
+    } else {
+        int32_t *u = A.u + (size_t)job * (kN + 1);
+        if (h == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                int j = lane + 64 * r;
+                u[j] = ext[(2 * kN - j) & (2 * kN - 1)];
+            }
+        } else if (lane == 0) {
+            u[kN] = ext[0];
+        }
+    }

@@ -571,9 +571,11 @@ typedef eoc_engine::Workspace WS;
 // which every workgroup is resident from the start runs with the wave-priority alternation and finishes all its
 // workgroups within half a per cent of each other (3.0 ms per 1024 jobs), while a launch of several rounds settles at
 // a 10 % lower rate (the arbiter's age bias), so wide levels are cut into back-to-back single-round launches.
+// tv != nullptr (programmable bootstrapping): every job starts from test polynomial tv[job / tv_rows] instead of the gate
+// accumulator, on the *_tv twin of the kernel the policy below picks (same shapes, same segmentation)
 static int launch_blind_rotate(eoc_engine *e, WS &W, uint32_t njobs_total, hipStream_t st,
                                const GateDesc *fold_descs = nullptr, uint32_t fold_S = 0, const GateDesc *inline_desc = nullptr,
-                               bool fold_prep = true)
+                               bool fold_prep = true, const int32_t *tv = nullptr, uint32_t tv_rows = 1)
 {
     SpanGuard span(e, st, KIND_BLIND_ROTATE);
     // Two kernel shapes (kernels.hip.h).  The pair kernel (one ciphertext = one wave pair) fills the chip with 4 x CUs
@@ -645,7 +647,12 @@ static int launch_blind_rotate(eoc_engine *e, WS &W, uint32_t njobs_total, hipSt
             // SABAR: the rotation amounts read back by scalar loads (EOC_TFHE_SCALAR_ABAR=1) instead of vector loads
 #define EOC_BR_LAUNCH(KERNEL_, LDS_, ...)                                                                          \
     do {                                                                                                          \
-        if (e->scalar_abar) hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, true>), grid, block, LDS_, st, a, e->d_tw, e->d_twist);  \
+        if (tv) {                                                                                                 \
+            if (e->scalar_abar)                                                                                   \
+                hipLaunchKernelGGL((KERNEL_##_tv<__VA_ARGS__, true>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows); \
+            else                                                                                                  \
+                hipLaunchKernelGGL((KERNEL_##_tv<__VA_ARGS__, false>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows); \
+        } else if (e->scalar_abar) hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, true>), grid, block, LDS_, st, a, e->d_tw, e->d_twist);  \
         else hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, false>), grid, block, LDS_, st, a, e->d_tw, e->d_twist);     \
     } while (0)
             if (wide) {
@@ -1199,6 +1206,58 @@ extern "C" int eoc_keyswitch_device(eoc_engine *e, const int32_t *d_u, int32_t *
     rc = launch_keyswitch(e, W, dd, 1, (uint32_t)count, st);
     ring_mark(W, st);
     return rc;
+}
+
+// ---- programmable bootstrapping -------------------------------------------------------------
+// One level of n_luts x rows jobs, [table][row]: one OP_RAW descriptor per table (all read the same input rows, job_base =
+// table x rows, out = the table's output block) serves k_prepare, the blind rotation and the key switch.  Levels wider than
+// 2^20 jobs run in row slices, as circuit levels do.
+extern "C" int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n_luts, const int32_t *d_in, int32_t *d_out,
+                                    size_t count, void *hip_stream)
+{
+    if (!e || !d_tv || !d_in || !d_out || n_luts == 0 || n_luts > kMaxGatesPerLaunch) {
+        eoc_set_error("eoc_lut_batch_device: null argument or n_luts outside [1, %zu]", kMaxGatesPerLaunch);
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->bkfft || !e->ksk) {
+        eoc_set_error("eoc_lut_batch_device: no cloud key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    WS &W = e->ws;
+    const int n = e->p.n;
+    const size_t stride = (size_t)n + 1;
+    const size_t rows = std::min(count, std::max<size_t>(1, ((size_t)1 << 20) / n_luts));
+    int rc = ensure_ws(e, W, n_luts * rows, n_luts, 0, st);
+    if (rc) return rc;
+    std::vector<GateDesc> descs(n_luts);
+    for (size_t r0 = 0; r0 < count; r0 += rows) {
+        const size_t S = std::min(rows, count - r0);
+        for (size_t t = 0; t < n_luts; t++)
+            descs[t] = GateDesc{OP_RAW, (uint32_t)(t * S), d_in + r0 * stride, nullptr, nullptr, d_out + (t * count + r0) * stride};
+        GateDesc *dd = nullptr;
+        rc = push_descs(W, descs.data(), n_luts, st, &dd);
+        if (rc) return rc;
+        {
+            SpanGuard span(e, st, KIND_PREPARE);
+            dim3 grid((unsigned)S, (unsigned)((n + 1 + 255) / 256), (unsigned)n_luts);
+            hipLaunchKernelGGL(k_prepare, grid, dim3(256), 0, st, dd, n, (uint32_t)S, W.d_bara, e->bara_stride);
+            HIP_TRY(hipGetLastError());
+        }
+        const uint32_t jobs = (uint32_t)(n_luts * S);
+        rc = launch_blind_rotate(e, W, jobs, st, nullptr, 0, nullptr, true, d_tv, (uint32_t)S);
+        if (rc) return rc;
+        rc = launch_keyswitch(e, W, dd, (uint32_t)n_luts, (uint32_t)S, st);
+        if (rc) return rc;
+        e->stats[0] += 1;
+        e->stats[1] += jobs;
+        e->stats[2] += jobs;
+    }
+    ring_mark(W, st);
+    return EOC_OK;
 }
 
 extern "C" int eoc_engine_set_profiling(eoc_engine *e, int on)

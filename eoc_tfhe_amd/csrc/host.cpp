@@ -440,6 +440,52 @@ extern "C" int eoc_decrypt_bits(const eoc_secret_key *sk, const int32_t *cts, si
     return EOC_OK;
 }
 
+// ---- small integers for programmable bootstrapping (include/eoc_tfhe_gpu.h) -------------
+static bool lut_p_ok(int p) { return p == 2 || p == 4 || p == 8; }
+// m in Z_p at phase m / (2p): the upper half of the torus is the padding half
+static int32_t int_phase(unsigned m, int p) { return (int32_t)(uint32_t)(((uint64_t)m << 32) / (2u * (unsigned)p)); }
+// enc_key != NULL: secure-mode stream (enc_key, first_idx + s); else the reproducible stream (enc_seed, first_idx + s)
+static int encrypt_ints(const eoc_secret_key *sk, const uint8_t *enc_key, uint64_t enc_seed, uint64_t first_idx, int p,
+                        const uint8_t *values, size_t count, int32_t *cts)
+{
+    if (!sk || !values || !cts || !lut_p_ok(p)) return EOC_ERR_ARG;
+    for (size_t i = 0; i < count; i++)
+        if (values[i] >= p) return EOC_ERR_ARG;
+    const size_t st = size_t(sk->p.n) + 1;
+#pragma omp parallel for schedule(static) num_threads(usable_threads()) if (count >= 64)
+    for (size_t i = 0; i < count; i++) {
+        const int32_t mu = int_phase(values[i], p);
+        if (enc_key) eoc_host::lwe_encrypt_secure(sk, enc_key, first_idx + i, mu, sk->p.ks_stdev, cts + i * st);
+        else eoc_lwe_encrypt(sk, enc_seed, first_idx + i, mu, sk->p.ks_stdev, cts + i * st);
+    }
+    return EOC_OK;
+}
+extern "C" int eoc_encrypt_ints(const eoc_secret_key *sk, uint64_t enc_seed, uint64_t first_idx, int p, const uint8_t *values,
+                                size_t count, int32_t *cts)
+{
+    return encrypt_ints(sk, nullptr, enc_seed, first_idx, p, values, count, cts);
+}
+extern "C" int eoc_decrypt_ints(const eoc_secret_key *sk, int p, const int32_t *cts, size_t count, uint8_t *values)
+{
+    if (!sk || !cts || !values || !lut_p_ok(p)) return EOC_ERR_ARG;
+    const size_t st = size_t(sk->p.n) + 1;
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t ph = (uint32_t)eoc_lwe_phase(sk, cts + i * st);
+        values[i] = (uint8_t)(((ph * (2u * (unsigned)p) + (1ull << 31)) >> 32) % (unsigned)p); // round(phase 2p / 2^32) mod p
+    }
+    return EOC_OK;
+}
+// tv[k] = table[round(k p / N)] for k < N - N / (2p), -table[0] above: the rotation X^-k with k = m N / p +- (N / (2p) - 1)
+// puts table[m] in the constant coefficient, and k slightly below 0 (= 2N - small) reads -tv[N - small] = table[0]
+extern "C" int eoc_lut_test_polynomial(int p, const int32_t *table, int32_t *tv)
+{
+    if (!table || !tv || !lut_p_ok(p)) return EOC_ERR_ARG;
+    const int top = EOC_N - EOC_N / (2 * p);
+    for (int k = 0; k < EOC_N; k++)
+        tv[k] = k < top ? table[(k * p + EOC_N / 2) / EOC_N] : (int32_t)(0u - (uint32_t)table[0]);
+    return EOC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // base64 + the LWE sample wire format (export_lweSample_toStream bytes, eoc-tfhe-run.cpp:293-295:
 // little-endian a[n] | b | f64 current_variance)
@@ -732,6 +778,28 @@ extern "C" int eoc_global_decrypt_bits(const int32_t *cts, size_t count, uint8_t
         return EOC_ERR_NO_KEY;
     }
     return eoc_decrypt_bits(c.sk, cts, count, bits);
+}
+extern "C" int eoc_global_encrypt_ints(int p, const uint8_t *values, size_t count, int32_t *cts)
+{
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (!c.sk) {
+        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
+        return EOC_ERR_NO_KEY;
+    }
+    int rc = encrypt_ints(c.sk, c.enc_secure ? c.enc_key : nullptr, c.enc_seed, c.enc_counter, p, values, count, cts);
+    if (rc == EOC_OK) c.enc_counter += count;
+    return rc;
+}
+extern "C" int eoc_global_decrypt_ints(int p, const int32_t *cts, size_t count, uint8_t *values)
+{
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (!c.sk) {
+        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
+        return EOC_ERR_NO_KEY;
+    }
+    return eoc_decrypt_ints(c.sk, p, cts, count, values);
 }
 // batch of gates on the global key's engine (created and loaded on first use); no CPU fallback
 extern "C" int eoc_global_gate_batch(int op, const uint8_t *ops, const int32_t *in0, const int32_t *in1,

@@ -126,6 +126,9 @@ struct Slot {
     // persistent wire buffer of the circuit path
     int32_t *d_wires = nullptr;
     size_t cap_wire_ints = 0;
+    // persistent buffer of the table-lookup path: test polynomials | input rows | output rows
+    int32_t *d_lut = nullptr;
+    size_t cap_lut_ints = 0;
     uint64_t grows = 0; // buffer growths (0 in steady state)
     // asynchronous batch path (eoc_gate_batch_submit / _wait): two buffer sets, so that batch k + 1's operands arrive
     // while batch k computes and batch k's results leave under batch k + 1's kernels
@@ -374,6 +377,50 @@ int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *
     return EOC_OK;
 }
 
+// one device's block [lo, hi) of a table-lookup batch: in [count][stride], out [n_luts][count][stride] on the host
+int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in, int32_t *out, size_t count, size_t lo,
+                   size_t hi, size_t stride_ints)
+{
+    const size_t blk = hi - lo;
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t tv_ints = n_luts * EOC_N, need = tv_ints + (1 + n_luts) * blk * stride_ints;
+    if (need > s.cap_lut_ints) {
+        HIP_TRY(hipDeviceSynchronize());
+        hipFree(s.d_lut);
+        s.d_lut = nullptr;
+        s.cap_lut_ints = 0;
+        HIP_TRY(hipMalloc(&s.d_lut, need * 4));
+        s.cap_lut_ints = need;
+        s.grows++;
+    }
+    int32_t *d_tv = s.d_lut, *d_in = d_tv + tv_ints, *d_out = d_in + blk * stride_ints;
+    hipStream_t st = s.st[0];
+    const size_t row_bytes = stride_ints * 4;
+    int rc = EOC_OK;
+    auto copies = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_tv, tv, tv_ints * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_in, in + lo * stride_ints, blk * row_bytes, hipMemcpyHostToDevice, st));
+        return EOC_OK;
+    };
+    rc = copies();
+    if (rc == EOC_OK) rc = eoc_lut_batch_device(s.e, d_tv, n_luts, d_in, d_out, blk, st);
+    if (rc == EOC_OK) { // table t's block lands at rows [t count + lo, t count + hi) of the caller's array
+        hipError_t e = hipMemcpy2DAsync(out + lo * stride_ints, count * row_bytes, d_out, blk * row_bytes, blk * row_bytes, n_luts,
+                                        hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) {
+            eoc_set_error("hipMemcpy2DAsync failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+            rc = EOC_ERR_HIP;
+        }
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(st); // no copy may outlive the call
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return EOC_OK;
+}
+
 void destroy_slots_locked()
 {
     for (auto &s : G.slots)
@@ -389,6 +436,7 @@ void destroy_slots_locked()
         }
         for (int k = 0; k < 4; k++) hipFree(s.d_io[k]);
         hipFree(s.d_wires);
+        hipFree(s.d_lut);
         for (int k = 0; k < 3; k++)
             if (s.st[k]) hipStreamDestroy(s.st[k]);
         for (auto e : s.ev) hipEventDestroy(e);
@@ -999,6 +1047,35 @@ extern "C" int eoc_gate_batch(int op, const uint8_t *ops, const int32_t *in0, co
         return slot_gate_block(G.slots[i], op, ops ? ops + lo : nullptr, in0 ? in0 + lo * stride : nullptr,
                                in1 ? in1 + lo * stride : nullptr, in2 ? in2 + lo * stride : nullptr, out + lo * stride,
                                hi - lo, stride);
+    });
+}
+
+extern "C" int eoc_lut_batch(int p, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out, size_t count)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_lut_batch: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        return EOC_ERR_NO_DEVICE;
+    }
+    if (!tables || !in || !out || n_luts == 0) {
+        eoc_set_error("eoc_lut_batch: null argument or no table");
+        return EOC_ERR_ARG;
+    }
+    std::vector<int32_t> tv(n_luts * EOC_N);
+    for (size_t t = 0; t < n_luts; t++)
+        if (eoc_lut_test_polynomial(p, tables + t * (size_t)p, tv.data() + t * EOC_N) != EOC_OK) {
+            eoc_set_error("eoc_lut_batch: message space p = %d is not one of 2, 4, 8", p);
+            return EOC_ERR_ARG;
+        }
+    if (!count) return EOC_OK;
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    const size_t stride = (size_t)G.p.n + 1;
+    const int32_t *tvp = tv.data();
+    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
+        return slot_lut_block(G.slots[i], tvp, n_luts, in, out, count, lo, hi, stride);
     });
 }
 

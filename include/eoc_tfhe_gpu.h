@@ -115,6 +115,34 @@ size_t eoc_ksk_len(const eoc_params *p);
 int eoc_encrypt_bits(const eoc_secret_key *sk, uint64_t enc_seed, uint64_t first_idx,
                      const uint8_t *bits, size_t count, int32_t *cts);
 int eoc_decrypt_bits(const eoc_secret_key *sk, const int32_t *cts, size_t count, uint8_t *bits);
+/* Small integers for programmable bootstrapping (eoc_lut_batch_device).
+ *   Encoding   m in Z_p, p in {2, 4, 8}, at phase m / (2p) (Torus32 m * 2^32 / (2p)) with the ks_stdev noise of a fresh bit
+ *              ciphertext.  The upper half of the torus, [1/2, 1), is a padding half: a phase m / (2p) with m in [p, 2p) is
+ *              not a message, and a table lookup maps it to -table[m - p] (negacyclic, X^N = -1).  Ciphertexts add as
+ *              int32 arrays (wrapping): x + y encrypts x + y as long as the sum stays below p.
+ *   Decryption round(phase * 2p / 2^32) mod p.
+ *   Noise      (computed with eoc_tfhe_amd/noise.predict for the default sets and a random key, not measured): output sigma
+ *              after the key switch ~0.0042 (Set A) / ~0.0035 (Set B), the mod switch to 2N adds ~0.0022 / ~0.0025; the
+ *              decision margin is 1 / (4p):
+ *                  p   Set A, one input / sum of two     Set B, one input / sum of two
+ *                  2        26 sigma / 20 sigma               29 sigma / 23 sigma
+ *                  4        13 sigma / 9.8 sigma              15 sigma / 11 sigma
+ *                  8       6.6 sigma / 4.9 sigma             7.3 sigma / 5.7 sigma
+ *                 16       3.3 sigma / 2.5 sigma             3.7 sigma / 2.8 sigma
+ *              hence p <= 8; p = 16 is refused.  At p = 8 an input that is the SUM of two ciphertexts decodes wrongly
+ *              about once in 10^6 lookups on Set A.
+ * eoc_encrypt_ints: values[count] (each < p) -> cts[count][n+1]; sample s uses stream (enc_seed, first_idx + s) as
+ * eoc_encrypt_bits does.  EOC_ERR_ARG for a p outside {2, 4, 8}, a null pointer or a value >= p (nothing is written). */
+int eoc_encrypt_ints(const eoc_secret_key *sk, uint64_t enc_seed, uint64_t first_idx, int p, const uint8_t *values,
+                     size_t count, int32_t *cts);
+int eoc_decrypt_ints(const eoc_secret_key *sk, int p, const int32_t *cts, size_t count, uint8_t *values);
+/* Test polynomial tv[N] of a table: table[m] (m < p) is the Torus32 OUTPUT value for input m -- +-2^29 gives a bit
+ * ciphertext (the gates' encoding), k * 2^32 / (2p') an integer in Z_p'.  Rule:
+ *   tv[k] = table[round(k p / N)]   for k < N - N / (2p)   (round half up: (k p + N / 2) / N)
+ *   tv[k] = -table[0]               for the last N / (2p) coefficients, so that a phase slightly below 0 still gives f(0).
+ * A blind rotation by b (the mod-switched phase, in [0, 2N)) leaves tv[b] (b < N) or -tv[b - N] in the constant
+ * coefficient: every b within N / (2p) - 1 of m N / p gives table[m] for m < p, and -table[m - p] for m in [p, 2p). */
+int eoc_lut_test_polynomial(int p, const int32_t *table, int32_t *tv);
 /* lweSymEncrypt / lwePhase with an arbitrary message and noise (eoc-tfhe-run.cpp:149,161) */
 int eoc_lwe_encrypt(const eoc_secret_key *sk, uint64_t enc_seed, uint64_t idx, int32_t mu,
                     double sigma, int32_t *ct);
@@ -296,6 +324,19 @@ int eoc_blind_rotate_device(eoc_engine *e, const int32_t *d_t, int32_t *d_u, siz
 /* u[count][N+1] -> out[count][n+1]  (lweKeySwitch) */
 int eoc_keyswitch_device(eoc_engine *e, const int32_t *d_u, int32_t *d_out, size_t count,
                          void *hip_stream);
+/* Programmable bootstrapping: table lookups on small integers (encoding and noise: eoc_encrypt_ints above).
+ *   d_tv   DEVICE array [n_luts][N] of test polynomials (eoc_lut_test_polynomial), 1 <= n_luts <= 32 768
+ *   d_in   DEVICE array [count][n+1] of input samples
+ *   d_out  DEVICE array [n_luts][count][n+1]: out[t][r] = KeySwitch(BlindRotate(in[r], tv[t]))
+ * Every table is applied to every row in ONE level of n_luts x count blind rotations (k_prepare, the blind rotation, the key
+ * switch), so that one input yields several functions of itself -- a value and its carry, say -- for the depth of one
+ * bootstrap.  The blind rotation is the gate kernel's with its accumulator seeded from the job's test polynomial
+ * (k_blind_rotate_tv / k_blind_rotate_wide_tv); shapes and segmentation are those of a gate level of the same job count.
+ * Workspace and capture rules: those of eoc_engine_reserve above, with max_jobs = n_luts x count (a call of more than
+ * 2^20 jobs runs as several levels of at most 2^20 jobs and needs max_jobs = that slice) and max_descs >= n_luts.
+ * Asynchronous on hip_stream.  EOC_ERR_ARG for a null pointer or n_luts outside [1, 32 768]. */
+int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n_luts, const int32_t *d_in, int32_t *d_out,
+                         size_t count, void *hip_stream);
 /* per-kernel timing with HIP events recorded on the launch stream.  kinds: [0] prepare,
  * [1] blind_rotate, [2] keyswitch.  eoc_engine_kernel_times synchronises the device. */
 int eoc_engine_set_profiling(eoc_engine *e, int on);
@@ -364,6 +405,11 @@ int eoc_gate_batch(int op, const uint8_t *ops, const int32_t *in0, const int32_t
                    const int32_t *in2, int32_t *out, size_t count);
 int eoc_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires,
                     size_t instances);
+/* Table lookups on the global context (host buffers, synchronous): tables [n_luts][p] of Torus32 output values (see
+ * eoc_lut_test_polynomial), in [count][n+1] encrypted at message space p (eoc_encrypt_ints), out [n_luts][count][n+1].
+ * Rows are cut into eoc_shard_range blocks, one per engine, as eoc_gate_batch does; the cloud key alone suffices (a
+ * server context).  EOC_ERR_ARG for p outside {2, 4, 8}, n_luts = 0 or a null pointer. */
+int eoc_lut_batch(int p, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out, size_t count);
 
 /* ------------------------------------------------------------------------------------------------
  * string API (reference style; global key context)
@@ -433,6 +479,9 @@ int eoc_engine_create_from_cloud_key_blob(int device, const void *buf, size_t le
 int eoc_global_params(eoc_params *out);
 int eoc_global_encrypt_bits(const uint8_t *bits, size_t count, int32_t *cts);
 int eoc_global_decrypt_bits(const int32_t *cts, size_t count, uint8_t *bits);
+/* eoc_encrypt_ints / eoc_decrypt_ints on the global key (secure-mode randomness, as eoc_global_encrypt_bits) */
+int eoc_global_encrypt_ints(int p, const uint8_t *values, size_t count, int32_t *cts);
+int eoc_global_decrypt_ints(int p, const int32_t *cts, size_t count, uint8_t *values);
 int eoc_global_gate_batch_submit(int op, const uint8_t *ops, const int32_t *in0, const int32_t *in1,
                                  const int32_t *in2, int32_t *out, size_t count, uint64_t *ticket);
 int eoc_global_gate_batch(int op, const uint8_t *ops, const int32_t *in0, const int32_t *in1,
