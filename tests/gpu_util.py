@@ -20,3 +20,10 @@ def dev_empty(shape, dtype):
 
 def sync():
     torch_cuda().cuda.synchronize()
+
+
+def br_segments(jobs, resident):
+    """first job of every launch segment a pair-kernel blind rotation of `jobs` is cut into (launch_blind_rotate): as few
+    even slices as fit the resident set, e.g. 1 030 jobs at 1 024 -> 515 + 515.  Set B runs each segment as two launches."""
+    nsl = -(-jobs // resident)
+    return list(range(0, jobs, -(-jobs // nsl)))

@@ -26,6 +26,23 @@ def rig(eoc):
     return p, sk, eng
 
 
+@pytest.fixture(scope="module", params=[0, 1], ids=["setA", "setB"])
+def rig_set(request, eoc):
+    """(params, sk, engine, oracle) on Set A (the `rig` engine itself) and on Set B (n = 630, l = 3: what
+    eoc_params_for_lambda(128) selects), key seed 1 on both"""
+    if request.param == 0:
+        p, sk, eng = request.getfixturevalue("rig")
+    else:
+        p = eoc.default_params(1)
+        sk = eoc.SecretKey(p, 1)
+        eng = eoc.Engine(p)
+        eng.load_cloud_key(sk)
+        assert (p.n, p.l, p.Bgbit) == (630, 3, 7)
+    yield p, sk, eng, ol.Oracle(request.param, 1)
+    if request.param == 1:
+        eng.close()
+
+
 def _enc_planes(sk, bits, seed0):
     """bits [S, nbits] -> wires [nbits][S][n+1], one encryption stream per bit plane"""
     return np.stack([sk.encrypt_bits(bits[:, i], seed0 + i, 0) for i in range(bits.shape[1])])
@@ -96,12 +113,13 @@ def _run_adder(eoc, rig, gates, n_wires, aw, bw, sw, S, seed):
 
 
 @pytest.mark.parametrize("S", [4096, 8])
-def test_config3_adder_rewritten_and_log_depth_forms(eoc, rig, S):
+def test_config3_adder_rewritten_and_log_depth_forms(eoc, rig_set, S):
     """VERDICT r5 task 1: BASELINE configs[2]'s literal 40-gate netlist through eoc_netlist_optimize -- with the extension
     gates (a full adder = XOR3 + MAJ: 16 bootstraps on 8 levels) and inside libtfhe's gate family (the carry as MUX +
     constant folding: 30 on 8) --, the XOR3 / MAJ and MUX-carry adders written directly and the parallel-prefix adder
     (48 bootstraps on 5 levels), over 4096 pairs and over 8: all sums decrypt, and EVERY wire the rewritten netlist writes
-    equals the oracle's evaluation of that rewritten netlist on the first 16 (or all 8) instances, bit for bit"""
+    equals the oracle's evaluation of that rewritten netlist on the first 16 (or all 8) instances, bit for bit -- on Set A
+    and on Set B (k_prepare with grid.z = gates, the n1p = 768 key switch with grid.y = gates, 631-word rows)"""
     from eoc_tfhe_amd import circuits
     lit, n_wires, aw, bw, sw = circuits.ripple_carry_adder(8, carry_in_zero=True)
     as_t = lambda gs: [(g.op, g.in0, g.in1, g.in2, g.out) for g in gs]
@@ -114,27 +132,35 @@ def test_config3_adder_rewritten_and_log_depth_forms(eoc, rig, S):
              ("prefix", circuits.prefix_adder(8)), ("optimized literal, boots* gates only", (boots_only, n_wires, aw, bw, sw)),
              ("maj", circuits.maj_adder(8))]
     assert eoc.netlist_levels(forms[2][1][0])[2] == 5
-    orc = ol.Oracle(0, 1)
+    p, sk, eng, orc = rig_set
     for name, (gates, nw, a, b, s) in forms:
-        wires, inputs = _run_adder(eoc, rig, gates, nw, a, b, s, S, 3)
+        wires, inputs = _run_adder(eoc, (p, sk, eng), gates, nw, a, b, s, S, 3)
         k = min(S, ORACLE_INSTANCES)
         want = _oracle_netlist(orc, gates, inputs[:, :k])
         got = wires[:, :k].cpu().numpy()
         for g in gates:
             assert np.array_equal(got[g.out], want[g.out]), f"{name}: wire {g.out} (op {g.op})"
     # the chooser: 8 instances take the prefix form, 4096 the XOR3 / MAJ form (the engine's own resident set)
-    assert circuits.pick_form({k: v for k, v in circuits.ADDER_FORMS.items() if k != "ripple"}, 8, S,
-                              rig[2].resident_jobs() // 2)[0] == ("prefix" if S == 8 else "maj")
+    candidates = {k: v for k, v in circuits.ADDER_FORMS.items() if k != "ripple"}
+    if p.l == 2:
+        assert circuits.pick_form(candidates, 8, S, eng.resident_jobs() // 2)[0] == ("prefix" if S == 8 else "maj")
+    else:
+        # Set B has no wide kernel: resident_jobs() is the pair kernel's 4 x CUs.  At 1 024 (256 CUs) netlist_cost gives
+        # S = 8: prefix 90, maj 144, mux 144;  S = 4096: maj 1 920, mux 3 600, prefix 5 760
+        R = eng.resident_jobs()
+        costs = {k: eoc.netlist_cost(v(8)[0], S, R) for k, v in candidates.items()}
+        assert costs["prefix" if S == 8 else "maj"] == min(costs.values()), costs
+        assert circuits.pick_form(candidates, 8, S, R)[0] == ("prefix" if S == 8 else "maj"), costs
 
 
 @pytest.mark.parametrize("S", [1024, 8])
-def test_less_than_tree_and_ripple_bit_exact(eoc, rig, S):
+def test_less_than_tree_and_ripple_bit_exact(eoc, rig_set, S):
     """the log-depth comparator (29 bootstraps on 4 levels), the ripple one (22 on 8) and the MAJ chain (8 on 8: the borrow
-    of a - b, one bootstrap per bit): decrypt to a < b, every written wire of the first 16 instances equals the oracle's"""
+    of a - b, one bootstrap per bit): decrypt to a < b, every written wire of the first 16 instances equals the oracle's;
+    Set A and Set B"""
     from eoc_tfhe_amd import circuits
-    p, sk, eng = rig
+    p, sk, eng, orc = rig_set
     torch = torch_cuda()
-    orc = ol.Oracle(0, 1)
     rng = np.random.default_rng(17)
     A, B = rng.integers(0, 256, S), rng.integers(0, 256, S)
     B[::5] = A[::5]                                             # equal operands: a < b is false through every EQ
@@ -154,10 +180,10 @@ def test_less_than_tree_and_ripple_bit_exact(eoc, rig, S):
             assert np.array_equal(got[g.out], want[g.out]), f"{build.__name__}: wire {g.out} (op {g.op})"
 
 
-def test_config5_string_equality_1024x32(eoc, rig):
-    """ASCII-string equality (per-bit XOR + OR tree + NOT) on 1024 pairs of 32-byte strings, half equal."""
+def test_config5_string_equality_1024x32(eoc, rig_set):
+    """ASCII-string equality (per-bit XOR + OR tree + NOT) on 1024 pairs of 32-byte strings, half equal; Set A and Set B."""
     from eoc_tfhe_amd import circuits
-    p, sk, eng = rig
+    p, sk, eng, orc = rig_set
     torch = torch_cuda()
     gates, n_wires, xw, yw, out = circuits.string_equal(32)
     assert eoc.circuit_bootstraps(gates) == 511
@@ -180,7 +206,7 @@ def test_config5_string_equality_1024x32(eoc, rig):
 
     assert np.array_equal(got, (~diff).astype(np.uint8))
     # ciphertexts vs oracle: every wire of the 511-bootstrap circuit, first 16 pairs (8 equal, 8 different)
-    want = _oracle_netlist(ol.Oracle(0, 1), gates, inputs)
+    want = _oracle_netlist(orc, gates, inputs)
     gotw = wires[:, :ORACLE_INSTANCES].cpu().numpy()
     for g in gates:
         assert np.array_equal(gotw[g.out], want[g.out]), f"wire {g.out} (op {g.op})"

@@ -238,6 +238,53 @@ def test_string_api_and_host_batch_api(eoc):
         T.resetGateKey()
 
 
+def test_string_api_and_word_calls_at_lambda_128(eoc):
+    """the reference-style facade under the key users of the drop-in surface get: generateGateKey(128) selects Set B
+    (n = 630, l = 3).  Sample length, truth tables of every gate of the string API, and the word-level batch calls at 8 bits
+    over 300 pairs (ties at 0 and 255) and a 4 x 4-bit product -- all against plaintext (bytes: the Set B parity tests)"""
+    import base64
+    T = eoc.Tfhe
+    try:
+        assert T.generateGateKey(128, 13) is not None
+        gp = eoc.global_params()
+        assert (gp.n, gp.l, gp.Bgbit) == (630, 3, 7)
+        c0, c1 = T.encryptBit(0), T.encryptBit(1)
+        assert len(base64.b64decode(c1)) == 4 * 631 + 8                 # a[n] | b | f64 variance
+        assert T.decryptBit(c0) == 0 and T.decryptBit(c1) == 1
+        c = (c0, c1)
+        for x in (0, 1):
+            assert T.decryptBit(T.not_(c[x])) == 1 - x
+            for y in (0, 1):
+                assert T.decryptBit(T.nand(c[x], c[y])) == 1 - (x & y) and T.decryptBit(T.xor(c[x], c[y])) == x ^ y, (x, y)
+                for z in (0, 1):
+                    assert T.decryptBit(T.mux(c[x], c[y], c[z])) == (y if x else z), (x, y, z)
+                    assert T.decryptBit(T.maj(c[x], c[y], c[z])) == int(x + y + z >= 2), (x, y, z)
+                    assert T.decryptBit(T.xor3(c[x], c[y], c[z])) == x ^ y ^ z, (x, y, z)
+        k0, k1 = T.constantBit(0), T.constantBit(1)
+        assert T.decryptBit(k0) == 0 and T.decryptBit(k1) == 1
+        assert base64.b64decode(k1)[: 4 * 630] == bytes(4 * 630)
+        assert T.decryptBit(T.nand(k1, c1)) == 0 and T.decryptBit(T.xor(k1, c0)) == 1
+        planes = lambda v, nb: np.stack([eoc.global_encrypt_bits(((v >> i) & 1).astype(np.uint8)) for i in range(nb)])
+        word = lambda w: sum(eoc.global_decrypt_bits(w[i]).astype(np.int64) << i for i in range(w.shape[0]))
+        assert planes(np.arange(2), 1).shape == (1, 2, 631)
+        rng = np.random.default_rng(128)
+        S = 300
+        A, B = rng.integers(0, 256, S), rng.integers(0, 256, S)
+        A[:4], B[:4] = [0, 255, 0, 255], [0, 255, 255, 0]                 # ties at 0 and 255, and the extremes crossed
+        B[4::7] = A[4::7]                                                 # more ties
+        pa, pb = planes(A, 8), planes(B, 8)
+        assert np.array_equal(word(T.addBitsBatch(pa, pb)), A + B)
+        diff = T.subtractBitsBatch(pa, pb)
+        assert np.array_equal(word(diff[:8]), (A - B) % 256) and np.array_equal(word(diff[8:]), A < B)
+        assert np.array_equal(eoc.global_decrypt_bits(T.lessThanBitsBatch(pa, pb)), (A < B).astype(np.uint8))
+        mn, mx = T.minMaxBitsBatch(pa, pb)
+        assert np.array_equal(word(mn), np.minimum(A, B)) and np.array_equal(word(mx), np.maximum(A, B))
+        a4, b4 = np.array([0, 15, 15, 7, 9]), np.array([0, 15, 1, 11, 6])
+        assert np.array_equal(word(T.multiplyBitsBatch(planes(a4, 4), planes(b4, 4))), a4 * b4)
+    finally:
+        T.resetGateKey()
+
+
 def test_string_api_on_a_device_list(eoc):
     """eoc_gpu_set_devices: the reference-style global key in front of two engines (both on device 0 on this box);
     the string calls and the host-buffer batch call shard over them and give the single-engine bits"""

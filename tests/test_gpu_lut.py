@@ -8,7 +8,7 @@ import pytest
 import lut_oracle as lo
 import oracle_lib as ol
 from eoc_tfhe_amd import noise
-from gpu_util import dev_empty, sync, to_dev, torch_cuda
+from gpu_util import br_segments, dev_empty, sync, to_dev, torch_cuda
 
 pytestmark = pytest.mark.gpu
 N = 1024
@@ -88,6 +88,74 @@ def test_lut_bit_exact_against_composed_oracle(eoc, monkeypatch, shape, p):
         dec = sk.decrypt_ints(got[t], p)
         exp = np.array([f(x) if x < p else (-f(x - p)) % p for x in m])
         assert np.array_equal(dec, exp), (t, np.flatnonzero(dec != exp)[:8])
+
+
+def _lut_engine(eoc, monkeypatch, pset, readback):
+    if readback == "scalar-abar":
+        monkeypatch.setenv("EOC_TFHE_SCALAR_ABAR", "1")       # read at engine creation: the SABAR instances
+    params, sk, orc = keys(eoc, pset)
+    eng = eoc.Engine(params)
+    eng.load_cloud_key(sk)
+    return params, sk, orc, eng
+
+
+def _check_decrypts(sk, got, fs, m, p):
+    for t, f in enumerate(fs):
+        dec = sk.decrypt_ints(got[t], p)
+        exp = np.array([f(x) if x < p else (-f(x - p)) % p for x in m])
+        assert np.array_equal(dec, exp), (t, np.flatnonzero(dec != exp)[:8])
+
+
+@pytest.mark.parametrize("readback", ["default", "scalar-abar"])
+def test_lut_set_b_segment_starts_inside_a_table(eoc, monkeypatch, readback):
+    """Set B, 3 tables x 500 rows = 1 500 jobs: the launch policy cuts them into two even segments (750 + 750 at 1 024
+    resident jobs) of two launches each, so the second segment's kernels start at job0 = 750 -- row 250 of table 1 -- and
+    take the table index (job0 + job) / tv_rows inside a launch.  Every output decrypts; the rows around the cut, and the
+    first and last rows, of every table equal the composed oracle byte for byte."""
+    p, rows = 4, 500
+    params, sk, orc, eng = _lut_engine(eoc, monkeypatch, 1, readback)
+    fs, tabs = tables_for(p)
+    tvs = np.stack([eoc.lut_test_polynomial(p, t) for t in tabs])
+    m, cts = inputs(eoc, sk, p, rows, 7400)
+    segs = br_segments(3 * rows, eng.resident_jobs())
+    assert len(segs) == 2 and segs[1] % rows != 0, segs                 # the cut lies inside a table
+    before = eng.stats()
+    got = run_device(eoc, eng, tvs, cts)
+    st = eng.stats()
+    assert st["br_launches"] - before["br_launches"] == 2 * len(segs)   # two segments x two parts
+    assert st["br_wide_launches"] == before["br_wide_launches"]
+    _check_decrypts(sk, got, fs, m, p)
+    cut = segs[1] % rows
+    check = np.r_[0:4, cut - 10:cut + 10, rows - 4:rows]
+    assert np.array_equal(got[:, check], lo.lut_batch(orc, tvs, cts[check]))
+    eng.close()
+
+
+@pytest.mark.parametrize("readback", ["default", "scalar-abar"])
+def test_lut_set_a_pair_remainder_inside_a_table(eoc, monkeypatch, readback):
+    """Set A, 3 tables x 700 rows = 2 100 jobs: one full wide launch (8 x CUs = 2 048 jobs) and a pair-kernel remainder at
+    job0 = 2 048 -- row 648 of table 2 -- on the _tv kernels.  Every output decrypts; the remainder's rows and the rows
+    just before it in table 2, and the first rows of tables 0 and 1, equal the composed oracle byte for byte."""
+    p, rows = 4, 700
+    params, sk, orc, eng = _lut_engine(eoc, monkeypatch, 0, readback)
+    fs, tabs = tables_for(p)
+    tvs = np.stack([eoc.lut_test_polynomial(p, t) for t in tabs])
+    m, cts = inputs(eoc, sk, p, rows, 7500)
+    jobs, Rw = 3 * rows, eng.resident_jobs()
+    n_wide, rem = divmod(jobs, Rw)
+    assert n_wide >= 1 and 0 < rem <= Rw // 2 and (n_wide * Rw) % rows != 0, (jobs, Rw)
+    before = eng.stats()
+    got = run_device(eoc, eng, tvs, cts)
+    st = eng.stats()
+    assert st["br_wide_launches"] - before["br_wide_launches"] == n_wide
+    assert st["br_launches"] - before["br_launches"] == n_wide + 1     # the wide launches + one pair-kernel launch
+    _check_decrypts(sk, got, fs, m, p)
+    t_cut, r_cut = divmod(n_wide * Rw, rows)
+    tail = np.r_[r_cut - 8:rows]
+    assert np.array_equal(got[t_cut, tail], lo.lut_batch(orc, tvs[t_cut], cts[tail])[0])
+    for t in range(t_cut):
+        assert np.array_equal(got[t, :4], lo.lut_batch(orc, tvs[t], cts[:4])[0]), t
+    eng.close()
 
 
 def test_lut_scale_and_bits_into_gates(eoc):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from gpu_util import dev_empty, sync, to_dev, torch_cuda
+from gpu_util import br_segments, dev_empty, sync, to_dev, torch_cuda
 
 pytestmark = pytest.mark.gpu
 N = 1024
@@ -185,20 +185,29 @@ def test_gates_small_bit_exact(eoc, rig_small, name):
     assert np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("pset,n,widths", [(0, 24, (1, 9, 130)), (1, 20, (7,)), (0, 500, (5, 1030, 2300))],
-                         ids=["setA-small", "setB-small", "setA-full-pair-and-wide"])
+@pytest.mark.parametrize("pset,n,widths", [(0, 24, (1, 9, 130)), (1, 20, (7,)), (0, 500, (5, 1030, 2300)), (1, 630, (5, 1030))],
+                         ids=["setA-small", "setB-small", "setA-full-pair-and-wide", "setB-full-two-part"])
 def test_extension_gates_maj_and_xor3_bit_exact(eoc, pset, n, widths):
     """round 6: the extension gates -- EOC_MAJ (t = a + b + c: a full adder's carry) and EOC_XOR3 (t = -2 (a + b + c): its sum),
     one bootstrap each behind a three-operand linear stage (k_prepare; the folded key-switch set-up stays).  Bit for bit against
     the oracle on both kernels (1 030 rows = a full pair launch + remainder, 2 300 = a wide launch + a pair remainder), both
     parameter sets, and through the truth table on all eight input combinations; inputs that are themselves gate outputs;
-    a mixed batch and a netlist that contain them"""
+    a mixed batch and a netlist that contain them.  Full Set B: 1 030 rows are two segments x two parts (accumulators
+    parked in between), the second segment starting at job0 > 0; the rows on both sides of the cut are in the sample."""
     r = Rig(eoc, pset, 13, n_override=None if n in (500, 630) else n)
+    full_b = pset == 1 and r.n == 630
     for cnt in widths:
         bits, cts = zip(*[_rand_cts(r, cnt, 300 + k, 40 * k) for k in range(3)])
         sample = slice(None) if r.n < 100 else np.random.default_rng(cnt).choice(cnt, min(cnt, 24), replace=False)
+        if full_b:
+            segs = br_segments(cnt, r.eng.resident_jobs())
+            assert cnt != 1030 or len(segs) == 2, segs                     # 515 + 515 at 4 x 256 CUs
+            sample = np.union1d(sample, np.concatenate([np.r_[max(0, s0 - 8):min(cnt, s0 + 8)] for s0 in segs[1:]] + [[cnt - 1]]))
         for name, truth in (("MAJ", (bits[0].astype(int) + bits[1] + bits[2]) >= 2), ("XOR3", bits[0] ^ bits[1] ^ bits[2])):
+            br0 = r.eng.stats()["br_launches"]
             got = r.gate(eoc.OPS[name], cts[0], cts[1], cts[2])
+            if full_b:
+                assert r.eng.stats()["br_launches"] - br0 == 2 * len(segs), (name, cnt, segs)
             assert np.array_equal(r.sk.decrypt_bits(got), truth.astype(np.uint8)), (name, cnt)
             assert np.array_equal(got[sample], r.orc.gate_batch(ol.OPS[name], cts[0][sample], cts[1][sample], cts[2][sample])), (name, cnt)
     b8 = [np.array([(k >> j) & 1 for k in range(8)], np.uint8) for j in range(3)]
@@ -506,6 +515,113 @@ def test_mixed_all_opcodes_run_as_one_level(eoc, no_fold, monkeypatch):
     r.eng.gate_batch_device(0, da.data_ptr(), db.data_ptr(), dc.data_ptr(), da.data_ptr(), cnt, ops=ops3)
     sync()
     assert np.array_equal(da.cpu().numpy(), r.orc.gate_batch(0, a, b, c, ops=ops3))
+    r.eng.close()
+
+
+def _truth(ops, x, y, z):
+    """plaintext of every opcode (OPS numbering) on bits x, y, z"""
+    tt = [1 - (x & y), x & y, x | y, 1 - (x | y), x ^ y, 1 - (x ^ y), (1 - x) & y, x & (1 - y), (1 - x) | y, x | (1 - y),
+          np.where(x == 1, y, z), 1 - x, x, 0 * x, 0 * x + 1, (x + y + z >= 2).astype(x.dtype), x ^ y ^ z]
+    return np.choose(ops, tt).astype(np.uint8)
+
+
+def _pool_job_rows(ops, gather):
+    """the caller's row behind every job of a mixed batch's pooled blind rotation, in job order: with the gather (opcode-
+    sorted, stable) the two-input block (OP_MULTI), then the MUX, MAJ and XOR3 runs; without it the bootstrapped runs in
+    the caller's order.  A MUX row owns two jobs: its run's k-th row is job k and job m + k of that run."""
+    order = np.argsort(ops, kind="stable") if gather else np.arange(len(ops))
+    o = ops[order]
+    cut = np.flatnonzero(np.diff(o)) + 1
+    groups = [g for g in np.split(order, cut) if ops[g[0]] == 10 or ops[g[0]] < 10 or ops[g[0]] >= 15]
+    if gather:
+        two = [g for g in groups if ops[g[0]] < 10]
+        groups = [np.concatenate(two)] + [g for g in groups if ops[g[0]] >= 10]
+    return np.concatenate([np.concatenate([g, g]) if ops[g[0]] == 10 else g for g in groups])
+
+
+def _gate_on(eng, a, b, c, ops, out_alias=False):
+    """a mixed batch on engine `eng`; out_alias: in place (out = in0)"""
+    torch = torch_cuda()
+    da, db, dc = to_dev(a), to_dev(b), to_dev(c)
+    out = da if out_alias else torch.empty_like(da)
+    eng.gate_batch_device(0, da.data_ptr(), db.data_ptr(), dc.data_ptr(), out.data_ptr(), len(ops), ops=ops)
+    sync()
+    return out.cpu().numpy()
+
+
+def test_mixed_all_opcodes_set_b_full(eoc, monkeypatch):
+    """Set B at n = 630: a 4 096-row mixed batch over all seventeen opcodes in random order takes the gather path
+    (k_gather_rows at stride 631, the opcode in the permutation's top four bits) and ONE pool (run_pool: OP_MULTI, MUX, MAJ and
+    XOR3 groups, a k_prepare and a key switch per group) whose blind rotation is cut into several segments of two launches
+    each; every row decrypts, a slice -- every segment boundary on both sides included -- equals the oracle, and the same
+    inputs with every group as a level of its own (EOC_TFHE_NO_POOL) give the same bytes on all 4 096 rows.  Then a few-runs
+    batch (no gather) of 1 500 rows, out of place and in place."""
+    r = Rig(eoc, 1, 21)
+    assert (r.n, r.p.l) == (630, 3)
+    R = r.eng.resident_jobs()
+    cnt = 4096
+    rng = np.random.default_rng(1630)
+    ops = rng.integers(0, 17, cnt).astype(np.uint8)
+    assert len(set(ops.tolist())) == 17
+    x, a = _rand_cts(r, cnt, 161)
+    y, b = _rand_cts(r, cnt, 162)
+    z, c = _rand_cts(r, cnt, 163)
+    _gate_on(r.eng, a, b, c, ops)                                       # workspace growth outside the counted call
+    r.eng.set_profiling(True)
+    r.eng.kernel_times(reset=True)
+    before = r.eng.stats()
+    got = _gate_on(r.eng, a, b, c, ops)
+    after = r.eng.stats()
+    kt = r.eng.kernel_times(reset=True)
+    r.eng.set_profiling(False)
+    n_two, n_mux, n_lin3 = int((ops < 10).sum()), int((ops == 10).sum()), int((ops >= 15).sum())
+    jobs = n_two + 2 * n_mux + n_lin3
+    job_rows = _pool_job_rows(ops, gather=True)
+    assert len(job_rows) == jobs
+    segs = br_segments(jobs, R)
+    assert len(segs) >= 2, segs
+    assert after["batches"] - before["batches"] == 1                   # one pool
+    assert kt["blind_rotate"]["launches"] == 1, kt                     # one blind-rotate span ...
+    assert kt["keyswitch"]["launches"] == 4, kt                        # ... and a key switch per group
+    assert after["bootstraps"] - before["bootstraps"] == jobs
+    assert after["br_launches"] - before["br_launches"] == 2 * len(segs), (before, after, segs)
+    assert after["br_wide_launches"] == before["br_wide_launches"]
+    assert np.array_equal(r.sk.decrypt_bits(got), _truth(ops, x, y, z))
+    per_op = [np.flatnonzero(ops == o)[:8] for o in range(17)]
+    edges = [job_rows[max(0, s0 - 16):s0 + 16] for s0 in segs[1:]]
+    check = np.unique(np.concatenate([np.arange(64)] + per_op + edges))
+    want = r.orc.gate_batch(0, a[check], b[check], c[check], ops=ops[check])
+    bad = np.flatnonzero((got[check] != want).any(axis=1))
+    assert bad.size == 0, (check[bad][:8], ops[check[bad][:8]])
+    # every opcode group as a level of its own: a fresh engine (the variable is read at creation), the same bytes
+    monkeypatch.setenv("EOC_TFHE_NO_POOL", "1")
+    e2 = eoc.Engine(r.p)
+    monkeypatch.delenv("EOC_TFHE_NO_POOL")
+    e2.load_cloud_key(r.sk)
+    s0 = e2.stats()
+    got_np = _gate_on(e2, a, b, c, ops)
+    assert e2.stats()["batches"] - s0["batches"] == 4                  # two-input, MUX, MAJ, XOR3: four levels
+    assert np.array_equal(got_np, got)
+    e2.close()
+    # few runs (no gather): NAND, MUX, XOR3 and NOT runs, the bootstrapped ones one pool of 1 500 jobs
+    m = 1500
+    ops3 = np.concatenate([np.full(500, 0), np.full(300, 10), np.full(400, 16), np.full(300, 11)]).astype(np.uint8)
+    segs3 = br_segments(500 + 2 * 300 + 400, R)
+    r.eng.set_profiling(True)
+    r.eng.kernel_times(reset=True)
+    before = r.eng.stats()
+    got3 = _gate_on(r.eng, a[:m], b[:m], c[:m], ops3)
+    after = r.eng.stats()
+    kt3 = r.eng.kernel_times(reset=True)
+    r.eng.set_profiling(False)
+    assert kt3["blind_rotate"]["launches"] == 1 and kt3["keyswitch"]["launches"] == 3, kt3
+    assert after["br_launches"] - before["br_launches"] == 2 * len(segs3), (before, after, segs3)
+    assert np.array_equal(r.sk.decrypt_bits(got3), _truth(ops3, x[:m], y[:m], z[:m]))
+    jr3 = _pool_job_rows(ops3, gather=False)
+    check3 = np.unique(np.concatenate([np.r_[0:8, 496:504, 796:804, 1196:1204, 1492:1500]] +
+                                      [jr3[max(0, s0 - 16):s0 + 16] for s0 in segs3[1:]]))
+    assert np.array_equal(got3[check3], r.orc.gate_batch(0, a[check3], b[check3], c[check3], ops=ops3[check3]))
+    assert np.array_equal(_gate_on(r.eng, a[:m], b[:m], c[:m], ops3, out_alias=True), got3)
     r.eng.close()
 
 
