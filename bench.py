@@ -16,7 +16,13 @@ next to `pipelined_gates_per_s` (two batches in flight) and `pageable_gates_per_
 runs its own batch of 1024 gates (weak scaling, independent gates shard with no data-path collective); the
 cloud key is built once on rank 0 and RCCL-broadcast to the other ranks before the timed region.
 
-Prints ONE JSON line (rank 0).  Keys beyond the driver's contract:
+A plain run is lean: it sets up (keys, inputs), runs the pre-flight and the W + K steps, decrypt-checks what the timed
+steps computed, writes --dump-outputs and prints the line.  `--full` adds every other leg below (CPU baseline, host-buffer
+legs, secondary workloads, Set B, noise, graph replay, the live PMC passes, the in-library child, the N > 1 configs[3] / [4]
+blocks); with --full, each --no-* option drops its own legs again.  The timed steps are the same code in both.
+
+Prints ONE JSON line (rank 0).  Keys beyond the driver's contract (`kernels_ms`, `roofline` and `clock` come from the timed
+steps themselves and are in every line; the others need --full):
   roofline       dominant kernel (k_blind_rotate), bound = FP64 vector issue: SURVEY.md 8(d)'s algorithmic flops per
                  blind rotation x jobs per launch / the HIP-event duration measured in this run, against the 78.6
                  TFLOP/s datasheet peak.  Co-bounds in the same block, so that the fraction explains itself:
@@ -24,9 +30,10 @@ Prints ONE JSON line (rank 0).  Keys beyond the driver's contract:
                  measures for rows served by the XCDs' L2), `lds` (PMC: share of wave cycles in which an LDS
                  instruction is ready but the LDS pipe is taken, LDS instructions per wave-step, bank conflicts),
                  `traffic` / `hbm_measured` (PMC bytes per launch / this run's launch duration, GB/s and fraction of
-                 8 TB/s).  At N = 1 the PMC figures are MEASURED IN THE RUN (live_traffic: the resident steps again as
-                 children under `rocprofv3 --pmc`, one pass per counter group, ~6 s per parameter set; profiles/traffic.json
-                 is the labelled fallback); the algorithmic HBM figure is a secondary key (a batch serves BK from L2)
+                 8 TB/s).  With --full at N = 1 the PMC figures are MEASURED IN THE RUN (live_traffic: the resident steps
+                 again as children under `rocprofv3 --pmc`, one pass per counter group, ~6 s per parameter set); otherwise
+                 they are profiles/traffic.json's, labelled; the algorithmic HBM figure is a secondary key (a batch serves
+                 BK from L2)
   wallclock      the same K steps through the host-buffer call (PCIe inclusive): `wallclock_gates_per_s`,
                  `wallclock_ms_per_step`; `pipelined_gates_per_s` = eoc_gate_batch_submit / _wait two deep;
                  `pageable_gates_per_s` = the host-buffer call on ordinary malloc'ed arrays
@@ -38,7 +45,9 @@ Prints ONE JSON line (rank 0).  Keys beyond the driver's contract:
                  own roofline block.  N > 1: `config3_mixed_1M` and `config4_streq_1024x32`, BASELINE configs[3] and
                  [4] cut into this run's N blocks (strong scaling: total bootstraps / slowest rank, decrypt-checked on
                  every rank)
-  clock          shader clock of this process's GPU read from sysfs while the timed steps run (boxes differ by +-3 %)
+  clock          shader clock of this process's GPU read from sysfs while the timed steps run (boxes differ by +-3 %).  The
+                 sysfs figure trails a change of load: after a plain run's short pre-flight it reads ~10 % low while the
+                 kernel times match a --full run's, so compare clocks (and roofline.pipes) between --full lines
   dumped_outputs with --dump-outputs DIR: what dump_outputs wrote (the last timed step's output ciphertexts, rank 0)
 """
 import argparse
@@ -228,7 +237,7 @@ def live_traffic(gates, n_steps, pset="A", timeout_s=110):
         for k, counters in enumerate(LIVE_PMC_PASSES):
             cmd = [prof, "--pmc", *counters, "--output-format", "csv", "-d", os.path.join(tmp, f"pass{k}"), "--",
                    sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                   "--gates", str(gates), "--pset", pset, "--no-cpu-baseline", "--no-secondary", "--no-host-legs"]
+                   "--gates", str(gates), "--pset", pset]
             proc = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True,
                                     start_new_session=True)
             try:
@@ -378,14 +387,16 @@ def main():
     ap.add_argument("--gates", type=int, default=1024, help="gates per GPU per step")
     ap.add_argument("--pset", default="A", choices=["A", "B"])
     ap.add_argument("--op", default="NAND")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beyond the headline too: CPU baseline, host-buffer legs, secondary workloads, Set B, "
+                         "noise, graph replay, live PMC passes, in-library child (N = 1); configs[3] / [4] blocks (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--cpu-sample", type=int, default=1024)
     ap.add_argument("--no-host-legs", action="store_true",
-                    help="skip the PCIe-inclusive legs (wallclock / pipelined / pageable): the timed resident steps only -- "
-                         "what tools/collect_profiles.sh traces, so that rocprofv3's per-kernel average covers the same "
-                         "calls as the HIP events of the line")
+                    help="with --full: skip the PCIe-inclusive legs (wallclock / pipelined / pageable)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary legs (N = 1: adder8 / streq32 / mixed / Set B; N > 1: configs[3] / [4] blocks)")
+                    help="with --full: skip the secondary legs (N = 1: adder8 / streq32 / mixed / Set B; N > 1: configs[3] / "
+                         "[4] blocks)")
     ap.add_argument("--workload", default="nand", choices=["nand", "adder8", "streq32", "mixed"],
                     help="nand = BASELINE configs[1] (headline); adder8 / streq32 / mixed = configs[2] / [4] / [3] "
                          "shapes on this rank's shard (secondary lines, same metric)")
@@ -400,6 +411,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    # without --full only what the headline needs runs; every other leg is gated by one of these three
+    secondary = args.full and not args.no_secondary
+    host_legs = args.full and not args.no_host_legs and args.workload == "nand"
+    cpu_legs = args.full and not args.no_cpu_baseline
 
     # stdout carries exactly ONE line, the JSON result: everything else that libraries print there (RCCL's
     # version banner, for one) is sent to stderr by pointing fd 1 at fd 2 until the result is written
@@ -473,9 +488,11 @@ def main():
     d1 = torch.from_numpy(c1).to(dev)
     dout = torch.empty_like(d0)
     stream = torch.cuda.current_stream().cuda_stream
-    pin = [eoc.PinnedArray(c0.shape) for _ in range(3)]   # I/O buffers from eoc_host_alloc (pinned: true DMA)
-    pin[0].array[:] = c0
-    pin[1].array[:] = c1
+    pin = []
+    if host_legs:
+        pin = [eoc.PinnedArray(c0.shape) for _ in range(3)]   # I/O buffers from eoc_host_alloc (pinned: true DMA)
+        pin[0].array[:] = c0
+        pin[1].array[:] = c1
     hout = np.empty_like(c0)
 
     def step():  # the headline step: operands resident in HBM, one eoc_gate_batch_device call on the current stream
@@ -682,7 +699,7 @@ def main():
     single_nand = world == 1 and headline_nand and dist is None
     sec_runs = []
     latency_runs = []
-    if single_nand and not args.no_secondary:
+    if single_nand and secondary:
         for wname, inst in (("adder8", 0), ("adder8_optimized", 0), ("adder8_optimized_boots_gates", 0), ("streq32", 256),
                             ("mixed", 32768)):
             sec_runs.append((wname,) + make_workload(wname, inst))
@@ -690,11 +707,11 @@ def main():
         if args.pset == "A":
             sec_runs.append(("nand16384_wide",) + make_wide_leg())
     multi_legs = []
-    if dist is not None and headline_nand and not args.no_secondary:   # world > 1, or the forced one-rank RCCL smoke
+    if dist is not None and headline_nand and secondary:   # world > 1, or the forced one-rank RCCL smoke
         multi_legs.append(("config3_mixed_1M",) + make_config3_block())
         multi_legs.append(("config4_streq_1024x32",) + make_config4_block())
     setb = None
-    if single_nand and not args.no_secondary and args.pset == "A":
+    if single_nand and secondary and args.pset == "A":
         # the headline workload on the parameter set the reference's own keygen selects (minimum_lambda = 128,
         # eoc-tfhe-run.cpp:34,230 => n = 630, l = 3, Bgbit = 7): its own key, engine and inputs
         pb = eoc.default_params(PSETS["B"])
@@ -757,8 +774,8 @@ def main():
         lat[lname] = float(np.median(ts)) * 1e3
     # pre-flight (set-up, untimed, not one of the W warm-up steps; reported as `preflight_steps`): the key images just
     # built/received are exercised so that a bad broadcast or key load fails here, before anything is measured -- and
-    # for long enough (16 batches, 50 ms) that a rank which had nothing to run before (N > 1: no secondary passes)
-    # starts its W + K steps at the same sustained clock as the N = 1 run does
+    # for long enough (16 batches, 50 ms) that a run which had nothing to run before (a plain run, or N > 1: no secondary
+    # passes) starts its W + K steps at the same sustained clock as a --full run at N = 1 does
     for _ in range(PREFLIGHT_STEPS):
         step()
     torch.cuda.synchronize()
@@ -789,7 +806,7 @@ def main():
     # the same step captured once into a hipGraph and replayed K times (the engine is capturable once its workspace has its
     # size): what is left of the launch path is one graph launch per step.  Reported beside `value`, never as it.
     graph_res = None
-    if single_nand and not args.no_secondary and world == 1:
+    if single_nand and secondary and world == 1:
         try:
             eager_out = dout.clone()
             gst = torch.cuda.Stream()
@@ -819,7 +836,6 @@ def main():
     # `value`), its asynchronous two-deep form, and the host-buffer call on ordinary pageable arrays
     wallclock = pageable = pipelined = None
     pipelined_ok = True
-    host_legs = host_path and not args.no_host_legs
     if host_legs:
         for _ in range(3):
             step_wallclock()
@@ -885,7 +901,7 @@ def main():
         setb_res = (tb, ktb, int(eoc.lib().eoc_engine_blind_rotate_launches(eb.h)) - lb0)
 
     noise_res = None
-    if single_nand and not args.no_secondary and rank == 0:
+    if single_nand and secondary and rank == 0:
         noise_res = {f"set{args.pset}": noise_leg(eng, sk, p, 1)}
         if setb:
             noise_res["setB"] = noise_leg(setb["eng"], setb["sk"], setb["p"], 2)
@@ -927,7 +943,7 @@ def main():
     # process has finished with the GPU and before the line is printed.  A failure or a time-out becomes an `error` entry.
     in_library = None
     inlib_devices = os.environ.get("EOC_BENCH_INLIB_DEVICES", "all" if ndev >= 2 else "")  # "0,0": one-GPU rehearsal
-    if single_nand and not args.no_secondary and inlib_devices and os.environ.get("EOC_BENCH_NO_INLIB") != "1":
+    if single_nand and secondary and inlib_devices and os.environ.get("EOC_BENCH_NO_INLIB") != "1":
         import subprocess
         for a in pin:
             a.free()
@@ -946,7 +962,7 @@ def main():
     # roofline.traffic measured in THIS run (N = 1, the headline workload on the pair kernel): two PMC child passes after
     # every timed leg is over; a failure falls back to the stored figure and says so
     live = live_b = None
-    if (single_nand and not args.no_secondary and world == 1 and rank == 0 and args.pset == "A" and not wide_headline
+    if (single_nand and secondary and world == 1 and rank == 0 and args.pset == "A" and not wide_headline
             and os.environ.get("EOC_BENCH_NO_LIVE_PMC") != "1"):
         live = live_traffic(G, p.n)
         if setb_res:                                      # Set B's blind rotation runs as nlaunch_b / steps launches
@@ -975,6 +991,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": args.full,
             "config": {"workload": workload_desc or (f"{G} independent bootsNAND gates per GPU per step (BASELINE configs[1])"
                        if args.op == "NAND" else f"{G} independent {args.op} gates per GPU per step"),
                        "param_set": args.pset, "n": n, "N": 1024, "k": 1, "l": p.l, "Bgbit": p.Bgbit,
@@ -999,7 +1016,7 @@ def main():
                       "source": "sysfs hwmon freq1_input of this process's GPU, sampled every 4 ms during the timed "
                                 "steps (median); the package sits at its power cap under this kernel (DESIGN.md 7)"},
         }
-        if not args.no_cpu_baseline and world == 1 and args.workload == "nand":
+        if cpu_legs and world == 1 and args.workload == "nand":
             res["cpu_baseline"] = cpu_baseline(args, p, c0, c1, out, key_seed, op)
         if sec:
             for wname, _, _, _, wcheck in sec_runs:

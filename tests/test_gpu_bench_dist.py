@@ -34,7 +34,7 @@ def _run_bench(nproc, extra, env_extra=None):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--gates", "128", "--steps", "2", "--warmup", "1",
-           "--config3-total", "8192"] + extra
+           "--config3-total", "8192", "--full"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:] + "\n---\n" + r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

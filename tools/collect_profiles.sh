@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU-box call that regenerates the evidence under profiles/ from ONE box and ONE build, so that the files agree with
-# each other: the driver's bench line (Set A headline with cpu_baseline, secondary legs, the Set B leg and wallclock_8d),
+# each other: the --full bench line (Set A headline with cpu_baseline, secondary legs, the Set B leg and wallclock_8d),
 # rocprofv3 kernel-trace stats of the same command, the PMC passes for both sets, traffic.json, the box's clock.
 # Usage (GPU box): bash tools/collect_profiles.sh <tag>     -> gpurun_out/<tag>/...   (copy what is to be judged into profiles/)
 set -e
@@ -9,9 +9,9 @@ export EOC_PROFILE_TAG="$TAG"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$TAG
 mkdir -p "$O"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_A.json" 2> "$O/bench_A.err"
-echo "bench A (driver command) done"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --pset B --no-cpu-baseline --no-secondary > "$O/bench_B.json" 2> "$O/bench_B.err"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_A.json" 2> "$O/bench_A.err"
+echo "bench A (--full) done"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --pset B --full --no-cpu-baseline --no-secondary > "$O/bench_B.json" 2> "$O/bench_B.err"
 echo "bench B done"
 # the traced run times the resident steps only (--no-host-legs): rocprofv3's average then covers the calls the line's HIP
 # events cover (plus pre-flight and warm-up, i.e. one clock ramp); the PCIe-inclusive legs are in bench_A.json

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The in-library multi-GPU path on every visible device: ONE process, ONE global key (the reference's shape,
 eoc-tfhe-run.cpp:38-40), one engine per GPU behind eoc_gate_batch; keys replicated by the library's own RCCL broadcast.
-Prints one JSON line.  bench.py runs it as a child process at N = 1 when more than one GPU is visible (on a one-GPU box it
+Prints one JSON line.  bench.py --full runs it as a child process at N = 1 when more than one GPU is visible (on a one-GPU box it
 has nothing to add); usable on its own:  python tools/in_library_multi.py [--devices 0,1] [--steps 10] [--pset A]"""
 import argparse
 import json
