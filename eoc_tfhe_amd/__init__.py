@@ -137,6 +137,9 @@ def lib():
         "eoc_decrypt_ints": (C.c_int, [vp, C.c_int, vp, sz, vp]),
         "eoc_lut_test_polynomial": (C.c_int, [C.c_int, vp, vp]),
         "eoc_lut_batch": (C.c_int, [C.c_int, vp, sz, vp, vp, sz]),
+        "eoc_lut_many_test_polynomial": (C.c_int, [C.c_int, C.c_int, vp, vp]),
+        "eoc_lut_many_batch_device": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, sz, vp]),
+        "eoc_lut_many_batch": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp, sz]),
         "eoc_global_encrypt_ints": (C.c_int, [C.c_int, vp, sz, vp]),
         "eoc_global_decrypt_ints": (C.c_int, [C.c_int, vp, sz, vp]),
         "eoc_engine_stats": (C.c_int, [vp, C.POINTER(u64 * 3)]),
@@ -400,6 +403,19 @@ def lut_test_polynomial(p, table):
     return tv
 
 
+def lut_many_test_polynomial(p, tables):
+    """Packed test polynomial [N] int32 of T = len(tables) tables (eoc_lut_many_test_polynomial): tables
+    [T][p] of Torus32 output values as in lut_test_polynomial, T in {2, 4, 8}, p T <= 16.  tv[kT + j] = table j's
+    lut_test_polynomial coefficient kT: one blind rotation on the T-grid gives all T lookups (Engine.lut_many_batch_device)."""
+    tables = np.ascontiguousarray(np.asarray(tables, np.int64).astype(np.int32))
+    if tables.ndim != 2 or tables.shape[1] != int(p):
+        raise EocError(f"lut_many_test_polynomial: tables must be [T][p], got {tables.shape} for p = {p}")
+    tv = np.empty(N, np.int32)
+    _check(lib().eoc_lut_many_test_polynomial(int(p), tables.shape[0], tables.ctypes.data, tv.ctypes.data),
+           "eoc_lut_many_test_polynomial")
+    return tv
+
+
 
 class Engine:
     """One HIP engine (one GPU).  All array arguments are DEVICE pointers (ints) unless noted."""
@@ -536,6 +552,13 @@ class Engine:
         [count][n+1], d_out [n_luts][count][n+1]; every table on every row in one level of n_luts x count bootstraps.
         Encoding and supported p: SecretKey.encrypt_ints."""
         _check(self.L.eoc_lut_batch_device(self.h, d_tv, n_luts, d_in, d_out, count, stream), "eoc_lut_batch_device")
+
+    def lut_many_batch_device(self, n_tables, d_tv, n_luts, d_in, d_out, count, stream=None):
+        """Many-LUT lookups (eoc_lut_many_batch_device): d_tv [n_luts][N] packed polynomials of T = n_tables tables each
+        (lut_many_test_polynomial), d_in [count][n+1], d_out [n_luts][T][count][n+1]; one blind rotation per (polynomial,
+        row) and T key switches."""
+        _check(self.L.eoc_lut_many_batch_device(self.h, int(n_tables), d_tv, n_luts, d_in, d_out, count, stream),
+               "eoc_lut_many_batch_device")
 
     def resident_jobs(self):
         """blind rotations that fill the device in one launch (8 x CUs where the one-wave-per-ciphertext kernel applies,
@@ -737,6 +760,26 @@ def lut_batch(p, tables, cts):
     out = np.empty((tables.shape[0],) + cts.shape, np.int32)
     _check(lib().eoc_lut_batch(int(p), tables.ctypes.data, tables.shape[0], cts.ctypes.data, out.ctypes.data,
                                cts.shape[0]), "eoc_lut_batch")
+    return out
+
+
+def lut_many_batch(p, tables, cts):
+    """eoc_lut_many_batch on the global context: tables [T][p] or [n_luts][T][p] Torus32 output values
+    (lut_many_test_polynomial), cts [count][n+1] encrypted at message space p (SecretKey.encrypt_ints), p T <= 16.
+    Returns [n_luts][T][count][n+1]."""
+    tables = np.asarray(tables, np.int64).astype(np.int32)
+    if tables.ndim == 2:
+        tables = tables[None]
+    tables = np.ascontiguousarray(tables)
+    if tables.ndim != 3 or tables.shape[2] != int(p):
+        raise EocError(f"lut_many_batch: tables must be [T][p] or [n_luts][T][p], got {tables.shape} for p = {p}")
+    cts = np.ascontiguousarray(cts, np.int32)
+    if cts.ndim != 2:
+        raise EocError("lut_many_batch: cts is a 2-d array [count][n+1]")
+    n_luts, T = tables.shape[:2]
+    out = np.empty((n_luts, T) + cts.shape, np.int32)
+    _check(lib().eoc_lut_many_batch(int(p), T, tables.ctypes.data, n_luts, cts.ctypes.data, out.ctypes.data, cts.shape[0]),
+           "eoc_lut_many_batch")
     return out
 
 

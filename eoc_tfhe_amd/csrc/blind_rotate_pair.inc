@@ -1,5 +1,6 @@
-// Body of k_blind_rotate / k_blind_rotate_tv (kernels.hip.h), included into both.  In scope: template parameters L, BGBIT,
-// SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test polynomials, used when TV).
+// Body of k_blind_rotate / k_blind_rotate_tv / k_lut_many (kernels.hip.h), included into each.  In scope: template
+// parameters L, BGBIT, SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test polynomials, used
+// when TV); constexpr bool MANY; n_tables (interleaved tables per test polynomial, extracted when MANY).
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     d2 *s_tw = reinterpret_cast<d2 *>(smem);
     d2 *s_twist = s_tw + kTwEntries;
@@ -270,7 +271,27 @@
         return;
     }
     // tLweExtractLweSample, index 0: u_0 = ACC_0[0], u_j = -ACC_0[N - j] = ext[2N - j]; b = ACC_1[0]
-    if (A.ks_descs) { // + lweKeySwitch set-up: ubar_j = u_j + 2^(31 - t basebit), out = (0, ..., 0, b)
+    // MANY: index j = 0 .. n_tables - 1, u_i = ext[(2N + j - i) mod 2N], b = ACC_1[j].  The engine passes no ks_descs to
+    // these kernels; the test of it stays a run-time one on purpose: with the folded branch discarded at compile time, the
+    // Set B instance (<3, 7>) is allocated differently and spills ~90 VGPRs.
+    if (MANY && !A.ks_descs) {
+        // slot j of job (table g, row s) goes to workspace row (g T + j) S + s, S = tv_rows; A.u is this launch's job0
+        const uint32_t gjob = A.job0 + job, g = gjob / tv_rows, si = gjob - g * tv_rows;
+        int32_t *u0 = A.u - (size_t)A.job0 * (kN + 1) + ((size_t)g * n_tables * tv_rows + si) * (kN + 1);
+        const size_t slot_stride = (size_t)tv_rows * (kN + 1);
+        if (h == 0) {
+            for (uint32_t jt = 0; jt < n_tables; jt++) {
+                int32_t *u = u0 + jt * slot_stride;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int j = lane_e + 64 * r;
+                    u[j] = ext[(2 * kN + (int)jt - j) & (2 * kN - 1)];
+                }
+            }
+        } else if ((uint32_t)lane_e < n_tables) {
+            u0[lane_e * slot_stride + kN] = ext[lane_e];
+        }
+    } else if (A.ks_descs) { // + lweKeySwitch set-up: ubar_j = u_j + 2^(31 - t basebit), out = (0, ..., 0, b)
         const uint32_t gjob = A.job0 + job;
         if (h == 0) {
 #pragma unroll

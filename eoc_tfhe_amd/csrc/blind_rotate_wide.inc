@@ -1,5 +1,6 @@
-// Body of k_blind_rotate_wide / k_blind_rotate_wide_tv (kernels.hip.h), included into both.  In scope: template parameters
-// BGBIT, SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test polynomials, used when TV).
+// Body of k_blind_rotate_wide / k_blind_rotate_wide_tv / k_lut_many_wide (kernels.hip.h), included into each.  In scope:
+// template parameters BGBIT, SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test
+// polynomials, used when TV); constexpr bool MANY; n_tables (tables per test polynomial, extracted when MANY).
     constexpr int L = 2, KPL = 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     d2 *s_tw = reinterpret_cast<d2 *>(smem);
@@ -214,6 +215,22 @@
         ext[j + kN] = (int32_t)(0u - racc0[r]);
     }
     wave_lds_fence();
+    if constexpr (MANY) { // index j = 0 .. n_tables - 1 into slot rows (g T + j) S + s (see k_lut_many); b = ACC_1[j] is
+                          // coefficient j of lane j's register 0
+        const uint32_t gjob = A.job0 + job, g = gjob / tv_rows, si = gjob - g * tv_rows;
+        int32_t *u0 = A.u - (size_t)A.job0 * (kN + 1) + ((size_t)g * n_tables * tv_rows + si) * (kN + 1);
+        const size_t slot_stride = (size_t)tv_rows * (kN + 1);
+        for (uint32_t jt = 0; jt < n_tables; jt++) {
+            int32_t *u = u0 + jt * slot_stride;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int j = lane_e + 64 * r;
+                u[j] = ext[(2 * kN + (int)jt - j) & (2 * kN - 1)];
+            }
+        }
+        if ((uint32_t)lane_e < n_tables) u0[lane_e * slot_stride + kN] = (int32_t)racc1[0];
+        return;
+    }
     const int32_t bval = (int32_t)__builtin_amdgcn_readfirstlane((int)racc1[0]); // ACC_1[0]: lane 0, register 0
     if (A.ks_descs) { // + lweKeySwitch set-up: ubar_j = u_j + 2^(31 - t basebit), out = (0, ..., 0, b)
         const uint32_t gjob = A.job0 + job;

@@ -572,10 +572,11 @@ typedef eoc_engine::Workspace WS;
 // workgroups within half a per cent of each other (3.0 ms per 1024 jobs), while a launch of several rounds settles at
 // a 10 % lower rate (the arbiter's age bias), so wide levels are cut into back-to-back single-round launches.
 // tv != nullptr (programmable bootstrapping): every job starts from test polynomial tv[job / tv_rows] instead of the gate
-// accumulator, on the *_tv twin of the kernel the policy below picks (same shapes, same segmentation)
+// accumulator, on the *_tv twin of the kernel the policy below picks (same shapes, same segmentation); n_tables > 0 (many-LUT
+// bootstrapping): on the k_lut_many* twin instead, which extracts n_tables samples per job into the workspace's slot rows
 static int launch_blind_rotate(eoc_engine *e, WS &W, uint32_t njobs_total, hipStream_t st,
                                const GateDesc *fold_descs = nullptr, uint32_t fold_S = 0, const GateDesc *inline_desc = nullptr,
-                               bool fold_prep = true, const int32_t *tv = nullptr, uint32_t tv_rows = 1)
+                               bool fold_prep = true, const int32_t *tv = nullptr, uint32_t tv_rows = 1, uint32_t n_tables = 0)
 {
     SpanGuard span(e, st, KIND_BLIND_ROTATE);
     // Two kernel shapes (kernels.hip.h).  The pair kernel (one ciphertext = one wave pair) fills the chip with 4 x CUs
@@ -645,9 +646,14 @@ static int launch_blind_rotate(eoc_engine *e, WS &W, uint32_t njobs_total, hipSt
                           : (njobs <= resident ? kPrioDuty : e->prio_multi);
             dim3 grid(njobs), block(128);
             // SABAR: the rotation amounts read back by scalar loads (EOC_TFHE_SCALAR_ABAR=1) instead of vector loads
-#define EOC_BR_LAUNCH(KERNEL_, LDS_, ...)                                                                          \
+#define EOC_BR_LAUNCH(KERNEL_, MANY_, LDS_, ...)                                                                   \
     do {                                                                                                          \
-        if (tv) {                                                                                                 \
+        if (n_tables) {                                                                                           \
+            if (e->scalar_abar)                                                                                   \
+                hipLaunchKernelGGL((MANY_<__VA_ARGS__, true>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows, n_tables); \
+            else                                                                                                  \
+                hipLaunchKernelGGL((MANY_<__VA_ARGS__, false>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows, n_tables); \
+        } else if (tv) {                                                                                          \
             if (e->scalar_abar)                                                                                   \
                 hipLaunchKernelGGL((KERNEL_##_tv<__VA_ARGS__, true>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows); \
             else                                                                                                  \
@@ -658,17 +664,17 @@ static int launch_blind_rotate(eoc_engine *e, WS &W, uint32_t njobs_total, hipSt
             if (wide) {
                 grid = dim3((njobs + kBRWideJobsPerWG - 1) / kBRWideJobsPerWG);
                 block = dim3(64 * kBRWideJobsPerWG);
-                if (e->p.Bgbit == 10) EOC_BR_LAUNCH(k_blind_rotate_wide, kBRWideLds, 10); // Set A
-                else EOC_BR_LAUNCH(k_blind_rotate_wide, kBRWideLds, 0);
+                if (e->p.Bgbit == 10) EOC_BR_LAUNCH(k_blind_rotate_wide, k_lut_many_wide, kBRWideLds, 10); // Set A
+                else EOC_BR_LAUNCH(k_blind_rotate_wide, k_lut_many_wide, kBRWideLds, 0);
                 e->br_wide_launches++;
-            } else if (e->p.l == 2 && e->p.Bgbit == 10) EOC_BR_LAUNCH(k_blind_rotate, kBRLds, 2, 10); // Set A
-            else if (e->p.l == 3 && e->p.Bgbit == 7) EOC_BR_LAUNCH(k_blind_rotate, kBRLds, 3, 7);     // Set B
+            } else if (e->p.l == 2 && e->p.Bgbit == 10) EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 2, 10); // Set A
+            else if (e->p.l == 3 && e->p.Bgbit == 7) EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 3, 7);     // Set B
             else
                 switch (e->p.l) {
-                case 1: EOC_BR_LAUNCH(k_blind_rotate, kBRLds, 1, 0); break;
-                case 2: EOC_BR_LAUNCH(k_blind_rotate, kBRLds, 2, 0); break;
-                case 3: EOC_BR_LAUNCH(k_blind_rotate, kBRLds, 3, 0); break;
-                case 4: EOC_BR_LAUNCH(k_blind_rotate, kBRLds, 4, 0); break;
+                case 1: EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 1, 0); break;
+                case 2: EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 2, 0); break;
+                case 3: EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 3, 0); break;
+                case 4: EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 4, 0); break;
                 default: return EOC_ERR_ARG;
                 }
 #undef EOC_BR_LAUNCH
@@ -1255,6 +1261,65 @@ extern "C" int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n
         e->stats[0] += 1;
         e->stats[1] += jobs;
         e->stats[2] += jobs;
+    }
+    ring_mark(W, st);
+    return EOC_OK;
+}
+
+// ---- many-LUT bootstrapping ------------------------------------------------
+// One level of n_luts x rows blind rotations, [polynomial][row], each extracting T samples: n_luts OP_RAW descriptors
+// (job_base = g x rows) for the coarse mod switch, n_luts x T for the key switch (job_base = (g T + j) x rows, out = slot
+// j's block of polynomial g).  Rows are sliced so that the workspace holds the n_luts x T x rows extracted samples.
+extern "C" int eoc_lut_many_batch_device(eoc_engine *e, int n_tables, const int32_t *d_tv, size_t n_luts, const int32_t *d_in,
+                                         int32_t *d_out, size_t count, void *hip_stream)
+{
+    const bool t_ok = n_tables == 2 || n_tables == 4 || n_tables == 8;
+    if (!e || !d_tv || !d_in || !d_out || !t_ok || n_luts == 0 || n_luts > kMaxGatesPerLaunch / (size_t)n_tables) {
+        eoc_set_error("eoc_lut_many_batch_device: null argument, n_tables = %d not one of 2, 4, 8, or n_luts x n_tables "
+                      "outside [1, %zu]", n_tables, kMaxGatesPerLaunch);
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->bkfft || !e->ksk) {
+        eoc_set_error("eoc_lut_many_batch_device: no cloud key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    WS &W = e->ws;
+    const int n = e->p.n;
+    const size_t stride = (size_t)n + 1, T = (size_t)n_tables, slots = n_luts * T;
+    const int theta = n_tables == 2 ? 1 : (n_tables == 4 ? 2 : 3);
+    const size_t rows = std::min(count, std::max<size_t>(1, ((size_t)1 << 20) / slots));
+    int rc = ensure_ws(e, W, slots * rows, n_luts + slots, 0, st);
+    if (rc) return rc;
+    std::vector<GateDesc> descs(n_luts + slots);
+    for (size_t r0 = 0; r0 < count; r0 += rows) {
+        const size_t S = std::min(rows, count - r0);
+        for (size_t g = 0; g < n_luts; g++) {
+            descs[g] = GateDesc{OP_RAW, (uint32_t)(g * S), d_in + r0 * stride, nullptr, nullptr, nullptr};
+            for (size_t j = 0; j < T; j++)
+                descs[n_luts + g * T + j] = GateDesc{OP_RAW, (uint32_t)((g * T + j) * S), nullptr, nullptr, nullptr,
+                                                     d_out + ((g * T + j) * count + r0) * stride};
+        }
+        GateDesc *dd = nullptr;
+        rc = push_descs(W, descs.data(), descs.size(), st, &dd);
+        if (rc) return rc;
+        {
+            SpanGuard span(e, st, KIND_PREPARE);
+            dim3 grid((unsigned)S, (unsigned)((n + 1 + 255) / 256), (unsigned)n_luts);
+            hipLaunchKernelGGL(k_modswitch_coarse, grid, dim3(256), 0, st, dd, n, theta, W.d_bara, e->bara_stride);
+            HIP_TRY(hipGetLastError());
+        }
+        const uint32_t jobs = (uint32_t)(n_luts * S);
+        rc = launch_blind_rotate(e, W, jobs, st, nullptr, 0, nullptr, true, d_tv, (uint32_t)S, (uint32_t)n_tables);
+        if (rc) return rc;
+        rc = launch_keyswitch(e, W, dd + n_luts, (uint32_t)slots, (uint32_t)S, st);
+        if (rc) return rc;
+        e->stats[0] += 1;
+        e->stats[1] += jobs;
+        e->stats[2] += slots * S;
     }
     ring_mark(W, st);
     return EOC_OK;

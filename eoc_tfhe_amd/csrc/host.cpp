@@ -485,6 +485,20 @@ extern "C" int eoc_lut_test_polynomial(int p, const int32_t *table, int32_t *tv)
         tv[k] = k < top ? table[(k * p + EOC_N / 2) / EOC_N] : (int32_t)(0u - (uint32_t)table[0]);
     return EOC_OK;
 }
+// many-LUT: T = n_tables tables interleaved, tv[kT + j] = F_j(kT) with F_j the rule above for table j --
+// every rotation the coarse mod switch makes is a multiple of T, and leaves F_j(kT) in coefficient j
+extern "C" int eoc_lut_many_test_polynomial(int p, int n_tables, const int32_t *tables, int32_t *tv)
+{
+    const bool t_ok = n_tables == 2 || n_tables == 4 || n_tables == 8;
+    if (!tables || !tv || !lut_p_ok(p) || !t_ok || p * n_tables > 16) return EOC_ERR_ARG;
+    const int top = EOC_N - EOC_N / (2 * p);
+    for (int k = 0; k < EOC_N; k += n_tables)
+        for (int j = 0; j < n_tables; j++) {
+            const int32_t *table = tables + (size_t)j * p;
+            tv[k + j] = k < top ? table[(k * p + EOC_N / 2) / EOC_N] : (int32_t)(0u - (uint32_t)table[0]);
+        }
+    return EOC_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // base64 + the LWE sample wire format (export_lweSample_toStream bytes, eoc-tfhe-run.cpp:293-295:

@@ -548,6 +548,20 @@ __global__ __launch_bounds__(256) void k_prepare(const GateDesc *__restrict__ de
     bara[(size_t)(d.job_base + y) * bara_stride + m] = (uint16_t)(((t + (1u << 20)) >> 21) & 2047u);
 }
 
+// Many-LUT levels: modSwitchFromTorus32 rounded to the grid of T = 2^theta, every word of the OP_RAW row
+// in0[s] -> a multiple of T in [0, 2N): ((t + 2^(20 + theta)) >> (21 + theta)) << theta.  theta = 0 is k_prepare's rounding.
+// A kernel of its own: k_prepare runs in every gate level and stays as it is.  grid: x = S, y = ceil((n+1)/256), z = tables
+__global__ __launch_bounds__(256) void k_modswitch_coarse(const GateDesc *__restrict__ descs, int n, int theta,
+                                                          uint16_t *__restrict__ bara, int bara_stride)
+{
+    const GateDesc d = descs[blockIdx.z];
+    const uint32_t s = blockIdx.x;
+    const int m = blockIdx.y * 256 + threadIdx.x;
+    if (m > n) return;
+    const uint32_t t = (uint32_t)d.in0[(size_t)s * (n + 1) + m];
+    bara[(size_t)(d.job_base + s) * bara_stride + m] = (uint16_t)((((t + (1u << (20 + theta))) >> (21 + theta)) << theta) & 2047u);
+}
+
 // The folded prologue writes the job's row of rotation amounts with vector stores; the step loop reads it back.
 // SHIPPED FORM (SABAR = false): behind the workgroup barrier the row is copied ONCE into LDS (vector loads: writer and
 // reader share the CU's vector L1 and the barrier carries a workgroup-scope release / acquire -- inside the formal memory
@@ -727,9 +741,9 @@ template <int L, int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(128, 2) void k_blind_rotate(BRArgs A, const d2 *__restrict__ g_tw,
                                                          const d2 *__restrict__ g_twist)
 {
-    constexpr bool TV = false;
+    constexpr bool TV = false, MANY = false;
     const int32_t *const tv = nullptr;
-    const uint32_t tv_rows = 1;
+    const uint32_t tv_rows = 1, n_tables = 1;
 #include "blind_rotate_pair.inc"
 }
 // Programmable bootstrapping: job j starts from test polynomial tv[(job0 + j) / tv_rows] ([tables][N] int32), read once
@@ -739,7 +753,20 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_tv(BRArgs A, const d2 *
                                                             const d2 *__restrict__ g_twist, const int32_t *__restrict__ tv,
                                                             uint32_t tv_rows)
 {
-    constexpr bool TV = true;
+    constexpr bool TV = true, MANY = false;
+    const uint32_t n_tables = 1;
+#include "blind_rotate_pair.inc"
+}
+// Many-LUT bootstrapping: the _tv kernel's prologue and step loop on rotation amounts of the T-grid
+// (k_modswitch_coarse), and n_tables = T sample extractions at indices 0 .. T - 1 of the one accumulator instead of one:
+// slot j of job (table g, row s) is workspace row (g T + j) tv_rows + s, which the key switch reads as n_luts x T
+// descriptors.  No folded key-switch set-up (ks_descs must be null).  The name avoids "k_blind_rotate": the ISA tests
+// count the kernels of that name.
+template <int L, int BGBIT = 0, bool SABAR = false>
+__global__ __launch_bounds__(128, 2) void k_lut_many(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist,
+                                                     const int32_t *__restrict__ tv, uint32_t tv_rows, uint32_t n_tables)
+{
+    constexpr bool TV = true, MANY = true;
 #include "blind_rotate_pair.inc"
 }
 
@@ -842,9 +869,9 @@ template <int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(64 * kBRWideJobsPerWG, 2) void k_blind_rotate_wide(BRArgs A, const d2 *__restrict__ g_tw,
                                                               const d2 *__restrict__ g_twist)
 {
-    constexpr bool TV = false;
+    constexpr bool TV = false, MANY = false;
     const int32_t *const tv = nullptr;
-    const uint32_t tv_rows = 1;
+    const uint32_t tv_rows = 1, n_tables = 1;
 #include "blind_rotate_wide.inc"
 }
 template <int BGBIT = 0, bool SABAR = false>
@@ -852,7 +879,18 @@ __global__ __launch_bounds__(64 * kBRWideJobsPerWG, 2) void k_blind_rotate_wide_
                                                                  const d2 *__restrict__ g_twist,
                                                                  const int32_t *__restrict__ tv, uint32_t tv_rows)
 {
-    constexpr bool TV = true;
+    constexpr bool TV = true, MANY = false;
+    const uint32_t n_tables = 1;
+#include "blind_rotate_wide.inc"
+}
+// the many-LUT twin of the wide kernel (see k_lut_many)
+template <int BGBIT = 0, bool SABAR = false>
+__global__ __launch_bounds__(64 * kBRWideJobsPerWG, 2) void k_lut_many_wide(BRArgs A, const d2 *__restrict__ g_tw,
+                                                                            const d2 *__restrict__ g_twist,
+                                                                            const int32_t *__restrict__ tv, uint32_t tv_rows,
+                                                                            uint32_t n_tables)
+{
+    constexpr bool TV = true, MANY = true;
 #include "blind_rotate_wide.inc"
 }
 

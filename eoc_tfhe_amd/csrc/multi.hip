@@ -377,14 +377,16 @@ int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *
     return EOC_OK;
 }
 
-// one device's block [lo, hi) of a table-lookup batch: in [count][stride], out [n_luts][count][stride] on the host
+// one device's block [lo, hi) of a table-lookup batch: in [count][stride], out [n_luts][count][stride] on the host; n_tables
+// > 0: many-LUT lookups (eoc_lut_many_batch_device), out [n_luts][n_tables][count][stride]
 int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in, int32_t *out, size_t count, size_t lo,
-                   size_t hi, size_t stride_ints)
+                   size_t hi, size_t stride_ints, int n_tables = 0)
 {
     const size_t blk = hi - lo;
     if (!blk) return EOC_OK;
     HIP_TRY(hipSetDevice(s.device));
-    const size_t tv_ints = n_luts * EOC_N, need = tv_ints + (1 + n_luts) * blk * stride_ints;
+    const size_t n_out = n_luts * (size_t)std::max(1, n_tables);
+    const size_t tv_ints = n_luts * EOC_N, need = tv_ints + (1 + n_out) * blk * stride_ints;
     if (need > s.cap_lut_ints) {
         HIP_TRY(hipDeviceSynchronize());
         hipFree(s.d_lut);
@@ -404,9 +406,11 @@ int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in,
         return EOC_OK;
     };
     rc = copies();
-    if (rc == EOC_OK) rc = eoc_lut_batch_device(s.e, d_tv, n_luts, d_in, d_out, blk, st);
+    if (rc == EOC_OK)
+        rc = n_tables ? eoc_lut_many_batch_device(s.e, n_tables, d_tv, n_luts, d_in, d_out, blk, st)
+                      : eoc_lut_batch_device(s.e, d_tv, n_luts, d_in, d_out, blk, st);
     if (rc == EOC_OK) { // table t's block lands at rows [t count + lo, t count + hi) of the caller's array
-        hipError_t e = hipMemcpy2DAsync(out + lo * stride_ints, count * row_bytes, d_out, blk * row_bytes, blk * row_bytes, n_luts,
+        hipError_t e = hipMemcpy2DAsync(out + lo * stride_ints, count * row_bytes, d_out, blk * row_bytes, blk * row_bytes, n_out,
                                         hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) {
             eoc_set_error("hipMemcpy2DAsync failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
@@ -1076,6 +1080,37 @@ extern "C" int eoc_lut_batch(int p, const int32_t *tables, size_t n_luts, const 
     const int32_t *tvp = tv.data();
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
         return slot_lut_block(G.slots[i], tvp, n_luts, in, out, count, lo, hi, stride);
+    });
+}
+
+extern "C" int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out,
+                                  size_t count)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_lut_many_batch: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        return EOC_ERR_NO_DEVICE;
+    }
+    if (!tables || !in || !out || n_luts == 0) {
+        eoc_set_error("eoc_lut_many_batch: null argument or no table");
+        return EOC_ERR_ARG;
+    }
+    std::vector<int32_t> tv(n_luts * EOC_N);
+    for (size_t t = 0; t < n_luts; t++)
+        if (eoc_lut_many_test_polynomial(p, n_tables, tables + t * (size_t)n_tables * p, tv.data() + t * EOC_N) != EOC_OK) {
+            eoc_set_error("eoc_lut_many_batch: (p, n_tables) = (%d, %d) is not supported (p, T in {2, 4, 8}, p T <= 16)", p,
+                          n_tables);
+            return EOC_ERR_ARG;
+        }
+    if (!count) return EOC_OK;
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    const size_t stride = (size_t)G.p.n + 1;
+    const int32_t *tvp = tv.data();
+    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
+        return slot_lut_block(G.slots[i], tvp, n_luts, in, out, count, lo, hi, stride, n_tables);
     });
 }
 

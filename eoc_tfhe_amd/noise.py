@@ -275,3 +275,20 @@ def compare(pred, e_br, e_ks, e_tot):
         "total_std": float(e_tot.std()), "total_std_pred": float(np.sqrt(pred["total_var"])),
         "max_abs_err": float(np.abs(e_tot).max()),
     }
+
+
+def modswitch_var(lwe_key, n_tables=1):
+    """variance (torus units) of the mod switch to 2N of a sample under `lwe_key`, every amount rounded to the grid of
+    T = n_tables (many-LUT bootstrapping): b and the |s| active a_i each carry a rounding error uniform
+    over a step of T / (2N), (1 + |s|) T^2 / (48 N^2) in all -- T = 1 is the gate bootstrap's mod switch"""
+    w = int(np.asarray(lwe_key, np.int64).sum())
+    return (1 + w) * float(n_tables) ** 2 / (48.0 * N * N)
+
+
+def lut_margin_sigma(params, lwe_key, tlwe_key, p, n_tables=1, inputs=1):
+    """decision margin of a table lookup at message space p, in predicted standard deviations at the
+    blind rotation's input: 1/(4p) over sqrt(inputs x V_out + V_ms(T)).  The input is the sum of `inputs` bootstrap outputs
+    (each of variance predict()['total_var'], average-key key switch), mod-switched on the grid of T = n_tables.  The
+    OUTPUT noise of a many-LUT lookup is the gate bootstrap's: the grid only widens the rounding at the input."""
+    v_out = predict(params, lwe_key, tlwe_key)["total_var"]
+    return (1.0 / (4 * int(p))) / float(np.sqrt(inputs * v_out + modswitch_var(lwe_key, n_tables)))

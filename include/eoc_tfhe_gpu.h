@@ -143,6 +143,12 @@ int eoc_decrypt_ints(const eoc_secret_key *sk, int p, const int32_t *cts, size_t
  * A blind rotation by b (the mod-switched phase, in [0, 2N)) leaves tv[b] (b < N) or -tv[b - N] in the constant
  * coefficient: every b within N / (2p) - 1 of m N / p gives table[m] for m < p, and -table[m - p] for m in [p, 2p). */
 int eoc_lut_test_polynomial(int p, const int32_t *table, int32_t *tv);
+/* Many-LUT test polynomial (eoc_lut_many_batch_device): T = n_tables tables interleaved in one polynomial,
+ * tables [T][p] of Torus32 output values as above.  Rule: tv[kT + j] = F_j(kT), F_j(x) = table_j[(x p + N/2) / N] for
+ * x < N - N / (2p), -table_j[0] otherwise -- eoc_lut_test_polynomial's rule for table j sampled at x = kT, so that a
+ * rotation by any multiple b = kT of T leaves table j's value in coefficient j.  T in {2, 4, 8}, p in {2, 4, 8}, p T <= 16
+ * (the coarse mod switch multiplies its noise by T: DESIGN.md 10.1's margins); EOC_ERR_ARG otherwise or for a null pointer. */
+int eoc_lut_many_test_polynomial(int p, int n_tables, const int32_t *tables, int32_t *tv);
 /* lweSymEncrypt / lwePhase with an arbitrary message and noise (eoc-tfhe-run.cpp:149,161) */
 int eoc_lwe_encrypt(const eoc_secret_key *sk, uint64_t enc_seed, uint64_t idx, int32_t mu,
                     double sigma, int32_t *ct);
@@ -337,6 +343,19 @@ int eoc_keyswitch_device(eoc_engine *e, const int32_t *d_u, int32_t *d_out, size
  * Asynchronous on hip_stream.  EOC_ERR_ARG for a null pointer or n_luts outside [1, 32 768]. */
 int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n_luts, const int32_t *d_in, int32_t *d_out,
                          size_t count, void *hip_stream);
+/* Many-LUT bootstrapping: T = n_tables functions of every row from ONE blind rotation.
+ *   d_tv   DEVICE array [n_luts][N] of packed test polynomials (eoc_lut_many_test_polynomial), T tables each
+ *   d_in   DEVICE array [count][n+1] of input samples (eoc_encrypt_ints encoding, p T <= 16)
+ *   d_out  DEVICE array [n_luts][T][count][n+1]: out[g][j][r] = table j of polynomial g applied to row r
+ * One level per row slice: the mod switch to multiples of T (k_modswitch_coarse), n_luts x count blind rotations through the
+ * gate levels' launch policy (k_lut_many / k_lut_many_wide: the _tv kernels' prologue and step loop, T extractions), then
+ * the key switch of n_luts x T x count samples.  Output noise is the gate bootstrap's.  Stats: bootstraps += n_luts x count,
+ * keyswitches += n_luts x T x count.
+ * Workspace and capture rules: those of eoc_engine_reserve, with max_jobs = n_luts x T x rows of a slice (a slice holds at
+ * most 2^20 extracted samples: rows = min(count, 2^20 / (n_luts T))) and max_descs >= n_luts x (T + 1) per slice.
+ * Asynchronous on hip_stream.  EOC_ERR_ARG for a null pointer, T outside {2, 4, 8} or n_luts x T outside [1, 32 768]. */
+int eoc_lut_many_batch_device(eoc_engine *e, int n_tables, const int32_t *d_tv, size_t n_luts, const int32_t *d_in,
+                              int32_t *d_out, size_t count, void *hip_stream);
 /* per-kernel timing with HIP events recorded on the launch stream.  kinds: [0] prepare,
  * [1] blind_rotate, [2] keyswitch.  eoc_engine_kernel_times synchronises the device. */
 int eoc_engine_set_profiling(eoc_engine *e, int on);
@@ -410,6 +429,12 @@ int eoc_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_
  * Rows are cut into eoc_shard_range blocks, one per engine, as eoc_gate_batch does; the cloud key alone suffices (a
  * server context).  EOC_ERR_ARG for p outside {2, 4, 8}, n_luts = 0 or a null pointer. */
 int eoc_lut_batch(int p, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out, size_t count);
+/* Many-LUT lookups on the global context (host buffers, synchronous): tables [n_luts][T][p] (eoc_lut_many_test_polynomial
+ * builds one polynomial per n_luts entry on the host), in [count][n+1], out [n_luts][T][count][n+1].  Rows are sharded per
+ * engine as in eoc_lut_batch; the cloud key alone suffices.  EOC_ERR_ARG for an unsupported (p, T), n_luts = 0 or a null
+ * pointer. */
+int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out,
+                       size_t count);
 
 /* ------------------------------------------------------------------------------------------------
  * string API (reference style; global key context)
