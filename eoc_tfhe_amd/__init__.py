@@ -225,6 +225,17 @@ def lib():
         "eoc_global_cloud_key_export": (sz, [vp, sz]),
         "eoc_global_import_cloud_key_blob": (C.c_int, [vp, sz]),
         "eoc_global_key_mode": (C.c_int, []),
+        # compact public-key encryption
+        "eoc_public_key_blob_bytes": (sz, [PP]),
+        "eoc_public_key_export": (C.c_int, [vp, vp, sz]),
+        "eoc_public_key_blob_params": (C.c_int, [vp, sz, PP]),
+        "eoc_pk_encrypt_bits": (C.c_int, [vp, sz, u64, u64, vp, sz, vp]),
+        "eoc_pk_encrypt_bits_keyed": (C.c_int, [vp, sz, vp, u64, vp, sz, vp]),
+        "eoc_pk_encrypt_ints": (C.c_int, [vp, sz, u64, u64, C.c_int, vp, sz, vp]),
+        "eoc_pk_encrypt_ints_keyed": (C.c_int, [vp, sz, vp, u64, C.c_int, vp, sz, vp]),
+        "eoc_compact_expand_device": (C.c_int, [vp, vp, sz, vp, vp]),
+        "eoc_compact_expand": (C.c_int, [vp, sz, vp]),
+        "eoc_global_public_key_export": (sz, [vp, sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -347,6 +358,13 @@ class SecretKey:
         _check(self.L.eoc_cloud_key_export(self.h, buf.ctypes.data, need), "eoc_cloud_key_export")
         return buf
 
+    def public_key_bytes(self):
+        """EOCPK1 blob (params | A | B, 8 236 bytes): the compact public key of this secret key (PublicKey)"""
+        need = self.L.eoc_public_key_blob_bytes(C.byref(self.params))
+        buf = (C.c_ubyte * need)()
+        _check(self.L.eoc_public_key_export(self.h, buf, need), "eoc_public_key_export")
+        return bytes(buf)
+
     def encrypt_bits(self, bits, enc_seed, first_idx=0):
         bits = np.ascontiguousarray(np.asarray(bits).ravel(), np.uint8)
         out = np.empty((bits.size, self.n + 1), np.int32)
@@ -388,6 +406,74 @@ class SecretKey:
         out = np.empty(cts.shape[0], np.uint8)
         _check(self.L.eoc_decrypt_ints(self.h, int(p), cts.ctypes.data, cts.shape[0], out.ctypes.data), "eoc_decrypt_ints")
         return out
+
+
+class PublicKey:
+    """Compact public key (EOCPK1 blob): anyone holding it encrypts into compact lists -- one TLWE sample
+    [2][N] int32 carries N = 1024 messages -- which a server turns into LWE samples with the cloud key alone
+    (Engine.compact_expand_device, compact_expand).  Encryption runs on the CPU."""
+
+    def __init__(self, blob):
+        self.L = lib()
+        self.blob = bytes(blob)
+        self.params = Params()
+        _check(self.L.eoc_public_key_blob_params(self.blob, len(self.blob), C.byref(self.params)),
+               "eoc_public_key_blob_params")
+        self.n = self.params.n
+
+    @classmethod
+    def from_bytes(cls, blob):
+        return cls(blob)
+
+    def to_bytes(self):
+        return self.blob
+
+    @property
+    def A(self):
+        return np.frombuffer(self.blob, np.int32, N, len(self.blob) - 8 * N)
+
+    @property
+    def B(self):
+        return np.frombuffer(self.blob, np.int32, N, len(self.blob) - 4 * N)
+
+    @staticmethod
+    def list_count(count):
+        """lists that hold `count` messages"""
+        return (int(count) + N - 1) // N
+
+    def _encrypt(self, values, p, enc_seed, first_list):
+        values = np.ascontiguousarray(np.asarray(values).ravel(), np.uint8)
+        out = np.empty((self.list_count(values.size), 2, N), np.int32)
+        if enc_seed is not None:            # reproducible test mode: NOT secure (include/eoc_tfhe_gpu.h)
+            rc = (self.L.eoc_pk_encrypt_bits(self.blob, len(self.blob), enc_seed, first_list, values.ctypes.data, values.size,
+                                             out.ctypes.data) if p is None else
+                  self.L.eoc_pk_encrypt_ints(self.blob, len(self.blob), enc_seed, first_list, int(p), values.ctypes.data,
+                                             values.size, out.ctypes.data))
+            _check(rc, "eoc_pk_encrypt")
+            return out
+        if first_list:
+            raise EocError("first_list is a test-mode argument: secure encryption draws a fresh key per call")
+        key = np.frombuffer(os.urandom(32), np.uint8).copy()    # fresh per call (raises if the OS has no entropy): a
+        try:                                                    # (key, list index) pair can never repeat
+            rc = (self.L.eoc_pk_encrypt_bits_keyed(self.blob, len(self.blob), key.ctypes.data, 0, values.ctypes.data,
+                                                   values.size, out.ctypes.data) if p is None else
+                  self.L.eoc_pk_encrypt_ints_keyed(self.blob, len(self.blob), key.ctypes.data, 0, int(p), values.ctypes.data,
+                                                   values.size, out.ctypes.data))
+        finally:
+            key[:] = 0
+        _check(rc, "eoc_pk_encrypt_keyed")
+        return out
+
+    def encrypt_bits(self, bits, enc_seed=None, first_list=0):
+        """bits -> compact lists [ceil(count / N)][2][N] (bits at +-2^29, the gates' encoding).  enc_seed=None: ChaCha20
+        under a fresh key from the OS; an int: the reproducible test streams (enc_seed, first_list + L) -- NOT secure, and
+        two calls must never cover the same (enc_seed, list index)."""
+        return self._encrypt(bits, None, enc_seed, first_list)
+
+    def encrypt_ints(self, values, p, enc_seed=None, first_list=0):
+        """small integers m < p, p in {2, 4, 8} (SecretKey.encrypt_ints' encoding) -> compact lists; randomness as
+        encrypt_bits"""
+        return self._encrypt(values, p, enc_seed, first_list)
 
 
 def lut_test_polynomial(p, table):
@@ -559,6 +645,11 @@ class Engine:
         row) and T key switches."""
         _check(self.L.eoc_lut_many_batch_device(self.h, int(n_tables), d_tv, n_luts, d_in, d_out, count, stream),
                "eoc_lut_many_batch_device")
+
+    def compact_expand_device(self, d_lists, count, d_out, stream=None):
+        """Compact lists -> LWE samples (eoc_compact_expand_device): d_lists [ceil(count / N)][2][N] (PublicKey.encrypt_*),
+        d_out [count][n+1]; slot extraction and the key switch, with the key-switch key alone"""
+        _check(self.L.eoc_compact_expand_device(self.h, d_lists, count, d_out, stream), "eoc_compact_expand_device")
 
     def resident_jobs(self):
         """blind rotations that fill the device in one launch (8 x CUs where the one-wave-per-ciphertext kernel applies,
@@ -781,6 +872,36 @@ def lut_many_batch(p, tables, cts):
     _check(lib().eoc_lut_many_batch(int(p), T, tables.ctypes.data, n_luts, cts.ctypes.data, out.ctypes.data, cts.shape[0]),
            "eoc_lut_many_batch")
     return out
+
+
+def compact_expand(lists, count=None):
+    """eoc_compact_expand on the global context (a cloud key alone suffices): lists [L][2][N] (PublicKey.encrypt_*) ->
+    [count][n+1] LWE samples, count = L N unless given (the messages the lists were made for)"""
+    lists = np.ascontiguousarray(lists, np.int32)
+    if lists.ndim != 3 or lists.shape[1:] != (2, N):
+        raise EocError(f"compact_expand: lists must be [L][2][{N}], got {lists.shape}")
+    count = lists.shape[0] * N if count is None else int(count)
+    if count > lists.shape[0] * N:
+        raise EocError(f"compact_expand: {lists.shape[0]} lists hold at most {lists.shape[0] * N} samples, not {count}")
+    out = np.empty((count, global_params().n + 1), np.int32) if lib().eoc_global_key_mode() else None
+    if out is None:
+        e0 = lib().eoc_global_engine()
+        if not e0:
+            raise EocError("compact_expand: no key and no GPU engine on the global context")
+        out = np.empty((count, lib().eoc_engine_params(e0).contents.n + 1), np.int32)
+    _check(lib().eoc_compact_expand(lists.ctypes.data, count, out.ctypes.data), "eoc_compact_expand")
+    return out
+
+
+def global_public_key_export():
+    """EOCPK1 blob of the global secret key (key mode 1)"""
+    need = lib().eoc_global_public_key_export(None, 0)
+    if not need:
+        raise EocError("eoc_global_public_key_export: no secret key on the global context")
+    buf = (C.c_ubyte * need)()
+    if lib().eoc_global_public_key_export(buf, need) != need:
+        raise EocError("eoc_global_public_key_export failed")
+    return bytes(buf)
 
 
 def circuit_run(gates, wires, instances):

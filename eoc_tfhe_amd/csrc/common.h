@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdarg>
 #include <cstddef>
+#include <cstdint>
 #include <cstdio>
 
 // last error message (also echoed on stderr, the reference's convention:
@@ -15,3 +16,12 @@ void eoc_adopt_error(const char *msg);
 // gates must have been checked (valid opcodes, wire ids below n_wires).  Returns the number of levels.
 struct eoc_gate;
 int eoc_levelise(const eoc_gate *gates, size_t n_gates, size_t n_wires, int *level_of);
+
+// compact public-key lists.  eoc_compact_expand_device with sample 0 at slot `first_slot` of d_lists (counted
+// from slot 0 of list 0): what a shard of the global context that starts inside a list needs (engine.hip)
+struct eoc_engine;
+int eoc_compact_expand_device_from(eoc_engine *e, const int32_t *d_lists, size_t first_slot, size_t count, int32_t *d_out,
+                                   void *hip_stream);
+// eoc_compact_expand's GPU half on the process-global engines (multi.hip): samples cut into eoc_shard_range blocks, one per
+// engine; the caller (host.cpp) has brought the engines up behind the global key
+int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out);

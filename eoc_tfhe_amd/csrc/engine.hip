@@ -1214,6 +1214,53 @@ extern "C" int eoc_keyswitch_device(eoc_engine *e, const int32_t *d_u, int32_t *
     return rc;
 }
 
+// ---- compact public-key lists ------------------------------------------------
+// k_compact_expand writes the key switch's operand rows and the (0, ..., 0, b') output rows, then the key switch runs as it
+// does behind a folded blind rotation (init_done).  The descriptor travels as a kernel argument: no ring slot, nothing
+// copied, so a captured call needs only the workspace of one slice.  Slices of at most 2^20 samples.
+int eoc_compact_expand_device_from(eoc_engine *e, const int32_t *d_lists, size_t first_slot, size_t count, int32_t *d_out,
+                                   void *hip_stream)
+{
+    if (!e || !d_lists || !d_out) {
+        eoc_set_error("eoc_compact_expand_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->ksk) {
+        eoc_set_error("eoc_compact_expand_device: no key-switch key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    WS &W = e->ws;
+    constexpr size_t kSlice = (size_t)1 << 20;
+    int rc = ensure_ws(e, W, std::min(count, kSlice), 0, 0, st);
+    if (rc) return rc;
+    const size_t stride = (size_t)e->p.n + 1;
+    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    for (size_t r0 = 0; r0 < count; r0 += kSlice) {
+        const size_t S = std::min(kSlice, count - r0);
+        const uint64_t first = (uint64_t)(first_slot + r0);
+        const unsigned nwg = (unsigned)((first % kCompactSlotsPerWG + S + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
+        {
+            SpanGuard span(e, st, KIND_PREPARE);
+            hipLaunchKernelGGL(k_compact_expand, dim3(nwg), dim3(256), 0, st, d_lists, first, (uint32_t)S, W.d_ubar,
+                               d_out + r0 * stride, e->p.n, prec_offset);
+            HIP_TRY(hipGetLastError());
+        }
+        const GateDesc d{OP_RAW, 0, nullptr, nullptr, nullptr, d_out + r0 * stride};
+        rc = launch_keyswitch(e, W, nullptr, 1, (uint32_t)S, st, true, &d);
+        if (rc) return rc;
+        e->stats[2] += S;
+    }
+    return EOC_OK;
+}
+extern "C" int eoc_compact_expand_device(eoc_engine *e, const int32_t *d_lists, size_t count, int32_t *d_out, void *hip_stream)
+{
+    return eoc_compact_expand_device_from(e, d_lists, 0, count, d_out, hip_stream);
+}
+
 // ---- programmable bootstrapping -------------------------------------------------------------
 // One level of n_luts x rows jobs, [table][row]: one OP_RAW descriptor per table (all read the same input rows, job_base =
 // table x rows, out = the table's output block) serves k_prepare, the blind rotation and the key switch.  Levels wider than

@@ -167,7 +167,7 @@ extern "C" void eoc_dbg_chacha20_block(const uint8_t key[32], uint32_t counter, 
 namespace {
 
 struct Stream {
-    enum Tag : uint32_t { LweKey = 1, TlweKey = 2, Bk = 3, Ksk = 4, Enc = 5 };
+    enum Tag : uint32_t { LweKey = 1, TlweKey = 2, Bk = 3, Ksk = 4, Enc = 5, PublicKey = 6, CompactEnc = 7 };
     bool secure = false;
     uint64_t key = 0;           // v1
     uint32_t sub[8];            // v2: this stream's ChaCha20 key
@@ -498,6 +498,108 @@ extern "C" int eoc_lut_many_test_polynomial(int p, int n_tables, const int32_t *
             tv[k + j] = k < top ? table[(k * p + EOC_N / 2) / EOC_N] : (int32_t)(0u - (uint32_t)table[0]);
         }
     return EOC_OK;
+}
+
+// ---- compact public-key encryption (include/eoc_tfhe_gpu.h) ---------------------------------------------
+// acc += u * P in Z_2^32[X]/(X^N + 1) for a binary u given by the positions of its ones: a sum of signed rotations of P
+static void add_binary_product(const std::vector<int> &ones, const uint32_t *P, uint32_t *acc)
+{
+    for (int m : ones) { // X^m * P: coefficient j gets +P[j-m] (j >= m) or -P[j-m+N] (j < m)
+        const uint32_t *src = P + (EOC_N - m);
+        for (int j = 0; j < m; j++) acc[j] -= src[j];
+        for (int j = m; j < EOC_N; j++) acc[j] += P[j - m];
+    }
+}
+namespace eoc_host {
+// pk = (A, B = A s' + e): one bootstrapping-key row with message 0 (make_bk), stream (key's source, PublicKey, 0)
+void make_public_key(const eoc_secret_key *sk, int32_t *A, int32_t *B)
+{
+    const Stream st(*sk, Stream::PublicKey, 0);
+    uint32_t *a = reinterpret_cast<uint32_t *>(A), *b = reinterpret_cast<uint32_t *>(B);
+    std::vector<int> ones;
+    for (int j = 0; j < EOC_N; j++) {
+        a[j] = st.torus(uint64_t(j));
+        b[j] = st.gaussian(uint64_t(EOC_N) + 2 * uint64_t(j), 0u, sk->p.bk_stdev);
+        if (sk->tlwe[j]) ones.push_back(j);
+    }
+    add_binary_product(ones, a, b);
+}
+// list L of msgs[count] (Torus32 messages): stream (encryptor's source, CompactEnc, first_list + L) -- ChaCha20 under enc_key
+// when it is given, else the seeded test stream of enc_seed.  u[i] = bit(i), e1[j] = gaussian(N + 2j), e2[j] = gaussian(3N + 2j);
+// c0 = u A + e1, c1 = u B + e2 + M; slots past `count` encrypt 0
+void compact_encrypt(const eoc_params &p, const int32_t *A, const int32_t *B, const uint8_t *enc_key, uint64_t enc_seed,
+                     uint64_t first_list, const int32_t *msgs, size_t count, int32_t *lists)
+{
+    const size_t n_lists = (count + EOC_N - 1) / EOC_N;
+    const uint32_t *a = reinterpret_cast<const uint32_t *>(A), *b = reinterpret_cast<const uint32_t *>(B);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(usable_threads()) if (n_lists >= 2)
+    for (size_t L = 0; L < n_lists; L++) {
+        const Stream st = enc_key ? Stream(enc_key, Stream::CompactEnc, first_list + L)
+                                  : Stream(enc_seed, Stream::CompactEnc, first_list + L);
+        uint32_t *c0 = reinterpret_cast<uint32_t *>(lists + L * 2 * EOC_N), *c1 = c0 + EOC_N;
+        std::vector<int> ones;
+        for (int i = 0; i < EOC_N; i++)
+            if (st.bit(uint64_t(i))) ones.push_back(i);
+        for (int j = 0; j < EOC_N; j++) {
+            const size_t k = L * EOC_N + size_t(j);
+            c0[j] = st.gaussian(uint64_t(EOC_N) + 2 * uint64_t(j), 0u, p.bk_stdev);
+            c1[j] = st.gaussian(3 * uint64_t(EOC_N) + 2 * uint64_t(j), 0u, p.bk_stdev) + (k < count ? uint32_t(msgs[k]) : 0u);
+        }
+        add_binary_product(ones, a, c0);
+        add_binary_product(ones, b, c1);
+    }
+}
+} // namespace eoc_host
+// ints = false: bits (+-2^29, eoc_encrypt_bits' encoding); true: eoc_encrypt_ints' encoding at p in {2, 4, 8}.  Everything is
+// checked before anything is written.
+static int pk_encrypt(const char *what, const void *pk, size_t pk_len, const uint8_t *enc_key, bool keyed, uint64_t enc_seed,
+                      uint64_t first_list, bool ints, int p, const uint8_t *values, size_t count, int32_t *lists)
+{
+    eoc_params prm;
+    std::vector<int32_t> ab;
+    if (!pk || !values || !lists || (keyed && !enc_key)) {
+        eoc_set_error("%s: null argument", what);
+        return EOC_ERR_ARG;
+    }
+    if (ints && !lut_p_ok(p)) {
+        eoc_set_error("%s: message space p = %d is not one of 2, 4, 8", what, p);
+        return EOC_ERR_ARG;
+    }
+    if (!eoc_host::parse_public_key_blob(pk, pk_len, &prm, &ab)) {
+        eoc_set_error("%s: not an EOCPK1 public key blob", what);
+        return EOC_ERR_ARG;
+    }
+    for (size_t i = 0; ints && i < count; i++)
+        if (values[i] >= p) {
+            eoc_set_error("%s: value %u at %zu is not below p = %d", what, unsigned(values[i]), i, p);
+            return EOC_ERR_ARG;
+        }
+    if (!count) return EOC_OK;
+    std::vector<int32_t> msgs(count);
+    const int32_t one8 = eoc_modswitch_to_torus32(1, 8);
+    for (size_t i = 0; i < count; i++) msgs[i] = ints ? int_phase(values[i], p) : (values[i] ? one8 : -one8);
+    eoc_host::compact_encrypt(prm, ab.data(), ab.data() + EOC_N, enc_key, enc_seed, first_list, msgs.data(), count, lists);
+    return EOC_OK;
+}
+extern "C" int eoc_pk_encrypt_bits(const void *pk, size_t pk_len, uint64_t enc_seed, uint64_t first_list, const uint8_t *bits,
+                                   size_t count, int32_t *lists)
+{
+    return pk_encrypt("eoc_pk_encrypt_bits", pk, pk_len, nullptr, false, enc_seed, first_list, false, 0, bits, count, lists);
+}
+extern "C" int eoc_pk_encrypt_bits_keyed(const void *pk, size_t pk_len, const uint8_t enc_key[32], uint64_t first_list,
+                                         const uint8_t *bits, size_t count, int32_t *lists)
+{
+    return pk_encrypt("eoc_pk_encrypt_bits_keyed", pk, pk_len, enc_key, true, 0, first_list, false, 0, bits, count, lists);
+}
+extern "C" int eoc_pk_encrypt_ints(const void *pk, size_t pk_len, uint64_t enc_seed, uint64_t first_list, int p,
+                                   const uint8_t *values, size_t count, int32_t *lists)
+{
+    return pk_encrypt("eoc_pk_encrypt_ints", pk, pk_len, nullptr, false, enc_seed, first_list, true, p, values, count, lists);
+}
+extern "C" int eoc_pk_encrypt_ints_keyed(const void *pk, size_t pk_len, const uint8_t enc_key[32], uint64_t first_list, int p,
+                                         const uint8_t *values, size_t count, int32_t *lists)
+{
+    return pk_encrypt("eoc_pk_encrypt_ints_keyed", pk, pk_len, enc_key, true, 0, first_list, true, p, values, count, lists);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -842,6 +944,23 @@ extern "C" int eoc_global_gate_batch_submit(int op, const uint8_t *ops, const in
     int rc = ensure_engine_locked();
     if (rc) return rc;
     return eoc_gate_batch_submit(op, ops, in0, in1, in2, out, count, ticket);
+}
+// compact lists -> LWE samples on the global context's engines (brought up behind the global key on first use; a cloud key
+// alone suffices)
+extern "C" int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *out)
+{
+    if (!lists || !out) {
+        eoc_set_error("eoc_compact_expand: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) {
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    }
+    return eoc_compact_expand_engines(lists, count, out);
 }
 extern "C" int eoc_global_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires,
                                       size_t instances)

@@ -58,6 +58,13 @@ void lwe_encrypt_secure(const eoc_secret_key *sk, const uint8_t enc_key[32], uin
 bool arm_secure_encryption_locked();
 void wipe_secret_key(eoc_secret_key *sk); // explicit_bzero over the master key and the key bits
 int ensure_engine_locked(); // caller holds ctx().mu
+// compact public-key encryption: the public key (A, B) of a secret key [N] each, and lists [ceil(count / N)][2][N]
+// of msgs[count] under it (enc_key != NULL: ChaCha20 streams under it, else the seeded test streams of enc_seed)
+void make_public_key(const eoc_secret_key *sk, int32_t *A, int32_t *B);
+void compact_encrypt(const eoc_params &p, const int32_t *A, const int32_t *B, const uint8_t *enc_key, uint64_t enc_seed,
+                     uint64_t first_list, const int32_t *msgs, size_t count, int32_t *lists);
+// an EOCPK1 blob of exactly `len` bytes -> its parameters and A | B (2N words); false for anything else
+bool parse_public_key_blob(const void *buf, size_t len, eoc_params *p, std::vector<int32_t> *ab);
 void drop_keys_locked();    // wipes and frees whichever key the context holds (caller holds ctx().mu)
 
 } // namespace eoc_host

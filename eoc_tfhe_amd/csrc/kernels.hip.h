@@ -1154,4 +1154,42 @@ __global__ __launch_bounds__(256) void k_keyswitch_generic(const GateDesc *__res
     }
 }
 
+// =================================================================================================
+// Compact public-key lists: sample extraction straight into the key switch's operand.
+// A list is one TLWE sample (c0, c1) [2][N]; slot j of it is the LWE sample under s' with
+//   a'_i = c0[j - i] (i <= j), -c0[N + j - i] (i > j),  b' = c1[j]      (the X^m a convention of the bootstrapping key)
+// This kernel does for such a sample what k_ks_init does for an extracted one: ubar[s][i] = a'_i + 2^(31 - t basebit) and
+// out[s] = (0, ..., 0, b'); the key switch then runs unchanged with its operand already in place.  A workgroup serves
+// kCompactSlotsPerWG consecutive slots of ONE list and stages the list's c0 (4 KiB) in LDS once for all of them; lane i of
+// a row reads c0[(j - i) mod N], consecutive lanes consecutive (descending) words: no bank conflict.
+// grid: x = ((first mod G) + S + G - 1) / G; block = 256.  Sample s is slot `first + s` of `lists` (counted from slot 0 of
+// list 0); workgroup w covers the G-aligned slots [G (first / G + w), + G), G divides N, and skips those outside the call.
+// =================================================================================================
+constexpr int kCompactSlotsPerWG = 16;
+__global__ __launch_bounds__(256) void k_compact_expand(const int32_t *__restrict__ lists, uint64_t first, uint32_t S,
+                                                        uint32_t *__restrict__ ubar, int32_t *__restrict__ out, int n,
+                                                        uint32_t prec_offset)
+{
+    static_assert(kN % kCompactSlotsPerWG == 0, "a workgroup's slots lie inside one list");
+    __shared__ int32_t s_c0[kN];
+    const uint64_t g0 = (first / kCompactSlotsPerWG + blockIdx.x) * kCompactSlotsPerWG;
+    const int32_t *list = lists + (g0 / kN) * (uint64_t)(2 * kN);
+    for (int k = threadIdx.x; k < kN; k += 256) s_c0[k] = list[k];
+    __syncthreads();
+    for (int q = 0; q < kCompactSlotsPerWG; q++) {
+        const uint64_t g = g0 + q;
+        if (g < first || g >= first + S) continue;
+        const uint32_t s = (uint32_t)(g - first);
+        const int j = (int)(g % kN);
+        uint32_t *row = ubar + (size_t)s * kN;
+        for (int i = threadIdx.x; i < kN; i += 256) {
+            const uint32_t v = (uint32_t)s_c0[(j - i) & (kN - 1)];
+            row[i] = (i <= j ? v : 0u - v) + prec_offset;
+        }
+        int32_t *o = out + (size_t)s * (n + 1);
+        for (int m = threadIdx.x; m < n; m += 256) o[m] = 0;
+        if (threadIdx.x == 0) o[n] = list[kN + j];
+    }
+}
+
 } // namespace eoc

@@ -121,6 +121,8 @@ const char *linear_op(const char *b64a, const char *b64b, int sign)
 const char kMagicSK[8] = {'E', 'O', 'C', 'S', 'K', '1', 0, 0};
 const char kMagicSK2[8] = {'E', 'O', 'C', 'S', 'K', '2', 0, 0};
 const char kMagicCK[8] = {'E', 'O', 'C', 'C', 'K', '1', 0, 0};
+// public key blob: "EOCPK1\0\0" | same params | A int32[N] | B int32[N]      (compact public-key encryption)
+const char kMagicPK[8] = {'E', 'O', 'C', 'P', 'K', '1', 0, 0};
 const size_t kParamBytes = 5 * 4 + 2 * 8;
 
 void put_params(const eoc_params &p, unsigned char *o)
@@ -249,6 +251,50 @@ extern "C" int eoc_cloud_key_blob_params(const void *buf, size_t len, eoc_params
     if (!buf || !p || len < 8 + kParamBytes) return EOC_ERR_ARG;
     const unsigned char *o = static_cast<const unsigned char *>(buf);
     if (memcmp(o, kMagicCK, 8) != 0 || !get_params(o + 8, *p)) return EOC_ERR_ARG;
+    return EOC_OK;
+}
+
+// ---- compact public-key encryption: the EOCPK1 blob ------------------------------------------------------------------------
+extern "C" size_t eoc_public_key_blob_bytes(const eoc_params *p) { return p ? 8 + kParamBytes + 2 * size_t(EOC_N) * 4 : 0; }
+
+extern "C" int eoc_public_key_export(const eoc_secret_key *sk, void *buf, size_t cap)
+{
+    if (!sk || !buf || cap < eoc_public_key_blob_bytes(&sk->p)) {
+        eoc_set_error("eoc_public_key_export: null argument or a buffer below eoc_public_key_blob_bytes");
+        return EOC_ERR_ARG;
+    }
+    std::vector<int32_t> ab(2 * EOC_N);
+    make_public_key(sk, ab.data(), ab.data() + EOC_N);
+    unsigned char *o = static_cast<unsigned char *>(buf);
+    memcpy(o, kMagicPK, 8);
+    put_params(sk->p, o + 8);
+    memcpy(o + 8 + kParamBytes, ab.data(), ab.size() * 4);
+    return EOC_OK;
+}
+
+namespace eoc_host {
+bool parse_public_key_blob(const void *buf, size_t len, eoc_params *p, std::vector<int32_t> *ab)
+{
+    const unsigned char *o = static_cast<const unsigned char *>(buf);
+    eoc_params q;
+    if (!buf || len < 8 + kParamBytes || memcmp(o, kMagicPK, 8) != 0 || !get_params(o + 8, q) ||
+        len != eoc_public_key_blob_bytes(&q))
+        return false;
+    if (p) *p = q;
+    if (ab) {
+        ab->resize(2 * EOC_N);
+        memcpy(ab->data(), o + 8 + kParamBytes, 2 * size_t(EOC_N) * 4);
+    }
+    return true;
+}
+} // namespace eoc_host
+
+extern "C" int eoc_public_key_blob_params(const void *buf, size_t len, eoc_params *p)
+{
+    if (!p || !parse_public_key_blob(buf, len, p, nullptr)) {
+        eoc_set_error("eoc_public_key_blob_params: not an EOCPK1 public key blob");
+        return EOC_ERR_ARG;
+    }
     return EOC_OK;
 }
 
@@ -419,6 +465,15 @@ extern "C" size_t eoc_global_cloud_key_export(void *buf, size_t cap)
     if (!cloud_blob_locked(c, blob)) return 0;
     memcpy(buf, blob.data(), need);
     return need;
+}
+extern "C" size_t eoc_global_public_key_export(void *buf, size_t cap)
+{
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (!c.sk) return 0; // the public key is made from the secret key: a cloud-key-only context has none
+    const size_t need = eoc_public_key_blob_bytes(&c.sk->p);
+    if (!buf || cap < need) return need;
+    return eoc_public_key_export(c.sk, buf, cap) == EOC_OK ? need : 0;
 }
 extern "C" int eoc_global_import_cloud_key_blob(const void *buf, size_t len)
 {

@@ -126,7 +126,8 @@ struct Slot {
     // persistent wire buffer of the circuit path
     int32_t *d_wires = nullptr;
     size_t cap_wire_ints = 0;
-    // persistent buffer of the table-lookup path: test polynomials | input rows | output rows
+    // persistent buffer of the table-lookup path (test polynomials | input rows | output rows) and of compact-list expansion
+    // (lists | output rows)
     int32_t *d_lut = nullptr;
     size_t cap_lut_ints = 0;
     uint64_t grows = 0; // buffer growths (0 in steady state)
@@ -416,6 +417,44 @@ int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in,
             eoc_set_error("hipMemcpy2DAsync failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
             rc = EOC_ERR_HIP;
         }
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(st); // no copy may outlive the call
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return EOC_OK;
+}
+
+// one device's block [lo, hi) of a compact-list expansion: lists [ceil(count / N)][2][N], out [count][stride] on the host.
+// Only the lists the block touches cross PCIe; the block's first sample sits at slot lo mod N of the first of them.
+int slot_compact_block(Slot &s, const int32_t *lists, int32_t *out, size_t lo, size_t hi, size_t stride_ints)
+{
+    const size_t blk = hi - lo;
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t l0 = lo / EOC_N, l1 = (hi - 1) / EOC_N + 1;
+    const size_t list_ints = (l1 - l0) * 2 * EOC_N, need = list_ints + blk * stride_ints;
+    if (need > s.cap_lut_ints) {
+        HIP_TRY(hipDeviceSynchronize());
+        hipFree(s.d_lut);
+        s.d_lut = nullptr;
+        s.cap_lut_ints = 0;
+        HIP_TRY(hipMalloc(&s.d_lut, need * 4));
+        s.cap_lut_ints = need;
+        s.grows++;
+    }
+    int32_t *d_lists = s.d_lut, *d_out = d_lists + list_ints;
+    hipStream_t st = s.st[0];
+    int rc = EOC_OK;
+    hipError_t e = hipMemcpyAsync(d_lists, lists + l0 * 2 * EOC_N, list_ints * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        rc = eoc_compact_expand_device_from(s.e, d_lists, lo - l0 * EOC_N, blk, d_out, st);
+        if (rc == EOC_OK) e = hipMemcpyAsync(out + lo * stride_ints, d_out, blk * stride_ints * 4, hipMemcpyDeviceToHost, st);
+    }
+    if (e != hipSuccess) {
+        eoc_set_error("hipMemcpyAsync failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+        rc = EOC_ERR_HIP;
     }
     if (rc) {
         (void)hipStreamSynchronize(st); // no copy may outlive the call
@@ -1111,6 +1150,24 @@ extern "C" int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, si
     const int32_t *tvp = tv.data();
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
         return slot_lut_block(G.slots[i], tvp, n_luts, in, out, count, lo, hi, stride, n_tables);
+    });
+}
+
+// eoc_compact_expand's engine half (host.cpp holds the global key's lock and has brought the engines up)
+int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_compact_expand: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        return EOC_ERR_NO_DEVICE;
+    }
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    const size_t stride = (size_t)G.p.n + 1;
+    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
+        return slot_compact_block(G.slots[i], lists, out, lo, hi, stride);
     });
 }
 

@@ -292,3 +292,52 @@ def lut_margin_sigma(params, lwe_key, tlwe_key, p, n_tables=1, inputs=1):
     OUTPUT noise of a many-LUT lookup is the gate bootstrap's: the grid only widens the rounding at the input."""
     v_out = predict(params, lwe_key, tlwe_key)["total_var"]
     return (1.0 / (4 * int(p))) / float(np.sqrt(inputs * v_out + modswitch_var(lwe_key, n_tables)))
+
+
+def _sig2(params):
+    """variance of one gaussian32 draw at bk_stdev, truncation toward zero included (as `predict` computes it)"""
+    u = 2.0**-32
+    sig = float(params.bk_stdev)
+    return sig * sig - sig * np.sqrt(2.0 / np.pi) * u + u * u / 3.0
+
+
+def pk_noise(pk, tlwe_key):
+    """e = B - A s' of a compact public key (PublicKey / its EOCPK1 blob, or an (A, B) pair), [N] torus units"""
+    if isinstance(pk, (bytes, bytearray)):
+        w = np.frombuffer(bytes(pk), np.int32)
+        A, B = w[-2 * N:-N], w[-N:]
+    elif hasattr(pk, "A"):
+        A, B = pk.A, pk.B
+    else:
+        A, B = pk
+    A = np.asarray(A, np.int64)
+    s1 = np.asarray(tlwe_key, np.int64)
+    # (A s')[j] = sum_m s'_m (X^m A)[j], (X^m A)[j] = A[j - m] (j >= m), -A[j - m + N] (j < m)
+    As = np.zeros(N, np.int64)
+    for m in np.flatnonzero(s1):
+        As += np.concatenate((-A[N - m:], A[:N - m]))
+    return _wrap32(np.asarray(B, np.int64) - As) / 2.0**32
+
+
+def compact_offset(tlwe_key, pk):
+    """mean error of slot j of a compact list under this public key, [N] torus units: u e with binary u of mean 1/2 gives
+    (1/2) (J e)[j], J = 1 + X + ... + X^(N-1), i.e. (1/2) (sum_{m <= j} e_m - sum_{m > j} e_m).  The lists' own e1, e2
+    have mean 0."""
+    e = pk_noise(pk, tlwe_key)
+    pre = np.cumsum(e)
+    return 0.5 * (2.0 * pre - pre[-1])
+
+
+def compact_var(params, tlwe_key, pk=None):
+    """variance (torus units) of the error of one extracted compact-list sample under s', around its slot's mean
+    (compact_offset), over the lists' randomness.  Error of slot j: (u e)[j] + e2[j] - (e1 s')[j].
+      u e     binary u (variance 1/4 per coefficient): ||e||^2 / 4 -- from the key's own e when `pk` is given, N sigma^2 / 4
+              (its expectation) otherwise
+      e2      sigma^2
+      e1 s'   |s'| sigma^2
+    sigma^2 is the truncation-corrected variance of gaussian32 at bk_stdev, as in `predict`.  The key switch adds
+    predict(...)['ks_var'] and ['ks_mean'] on top: the two sums are independent."""
+    s1 = np.asarray(tlwe_key, np.int64)
+    sig2 = _sig2(params)
+    ue = float((pk_noise(pk, tlwe_key) ** 2).sum()) / 4.0 if pk is not None else N * sig2 / 4.0
+    return ue + sig2 + float(s1.sum()) * sig2

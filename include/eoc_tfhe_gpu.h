@@ -356,6 +356,17 @@ int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n_luts, cons
  * Asynchronous on hip_stream.  EOC_ERR_ARG for a null pointer, T outside {2, 4, 8} or n_luts x T outside [1, 32 768]. */
 int eoc_lut_many_batch_device(eoc_engine *e, int n_tables, const int32_t *d_tv, size_t n_luts, const int32_t *d_in,
                               int32_t *d_out, size_t count, void *hip_stream);
+/* Compact public-key lists -> LWE samples (formats and security: "compact public-key encryption" below).
+ *   d_lists  DEVICE array [ceil(count / N)][2][N] int32 of lists (eoc_pk_encrypt_*): sample s is slot s mod N of list s / N
+ *   d_out    DEVICE array [count][n+1]: out[s] = lweKeySwitch(extract(list s / N, slot s mod N)) with the engine's KSK
+ * Extraction of slot j: a'_i = c0[j - i] (i <= j), -c0[N + j - i] (i > j), b' = c1[j] -- an LWE sample of dimension N under
+ * the TLWE key s', which the key-switch key takes to the LWE key.  Both steps are integer operations: the result equals the
+ * CPU composition (orc_keyswitch of the extracted sample) bit for bit.  One extraction kernel (k_compact_expand) writes the
+ * key switch's operand rows, then the key switch runs unchanged; calls run in slices of at most 2^20 samples.  Needs the KSK
+ * only (EOC_ERR_NO_KEY without one); stats: keyswitches += count.  Workspace and capture rules: those of eoc_engine_reserve,
+ * with max_jobs = min(count, 2^20) (no descriptor slot is used).  Asynchronous on hip_stream.  EOC_ERR_ARG for a null
+ * pointer; count 0 is a no-op. */
+int eoc_compact_expand_device(eoc_engine *e, const int32_t *d_lists, size_t count, int32_t *d_out, void *hip_stream);
 /* per-kernel timing with HIP events recorded on the launch stream.  kinds: [0] prepare,
  * [1] blind_rotate, [2] keyswitch.  eoc_engine_kernel_times synchronises the device. */
 int eoc_engine_set_profiling(eoc_engine *e, int on);
@@ -538,6 +549,53 @@ int importCloudKeyFromFile(const char *path);        /* 0 or -1 */
 size_t eoc_global_cloud_key_export(void *buf, size_t cap); /* bytes needed (0 without a key); fills buf when cap suffices */
 int eoc_global_import_cloud_key_blob(const void *buf, size_t len);
 int eoc_global_key_mode(void);                       /* 0 no key, 1 secret + cloud key, 2 cloud key only (server) */
+
+/* ------------------------------------------------------------------------------------------------
+ * compact public-key encryption: a third party encrypts with an 8 KiB public key into compact lists, a
+ * server turns them into ordinary gate / LUT inputs with the cloud key it already holds.
+ *   public key  pk = (A, B) in Z_2^32[X]/(X^N + 1), B = A s' + e: one bootstrapping-key row with message 0 under the TLWE
+ *               key s' -- A[j] = torus(j), e[j] = gaussian(N + 2j, 0, bk_stdev) from the secret key's own source (seeded
+ *               or ChaCha20) under stream tag 6 (PublicKey), index 0.  The same secret key always gives the same public key.
+ *               Blob "EOCPK1\0\0" | params (as EOCSK1 / EOCCK1) | A int32[N] | B int32[N], little-endian: 8 236 bytes.
+ *   list        list L of a call holds messages L N ... L N + N - 1 as one TLWE sample (c0, c1), [2][N] int32, c0 first:
+ *               u[i] = bit(i) (binary), e1[j] = gaussian(N + 2j), e2[j] = gaussian(3N + 2j), both bk_stdev, from the
+ *               encryptor's stream tag 7 (CompactEnc), index first_list + L;  c0 = u A + e1,  c1 = u B + e2 + M.
+ *               Slots past `count` in the last list encrypt 0.  8 KiB carry N = 1024 messages: 8 bytes per message against
+ *               4 (n + 1) for an LWE sample (250 x smaller on Set A, 315 x on Set B).  `lists` has room for ceil(count / N).
+ *   messages    bits at +-2^29 (eoc_encrypt_bits' encoding), integers m in Z_p at m 2^32 / (2p), p in {2, 4, 8}
+ *               (eoc_encrypt_ints' encoding).
+ *   expansion   eoc_compact_expand_device / eoc_compact_expand: slot j's extracted sample has phase M_j + u e + e2 - e1 s'
+ *               under s' (sigma ~2e-7 on Set A, ~1e-6 on Set B: eoc_tfhe_amd/noise.compact_var); after the key switch the
+ *               error is the key switch's (sigma ~0.0019 / ~0.0024), below a gate output's (~0.0042 / ~0.0035), so every
+ *               decision margin stated for gate outputs holds for expanded inputs.
+ *   randomness  eoc_pk_encrypt_bits / _ints with enc_seed: REPRODUCIBLE / TEST mode (splitmix64 streams, shared with the
+ *               oracle) -- NOT secure, as for eoc_encrypt_bits.  The _keyed forms: ChaCha20 streams under the caller's
+ *               256-bit enc_key.  NEVER encrypt two lists under one (key, list index) pair: they share u, e1 and e2, so
+ *               c1 - c1' = M - M' and the difference of the messages is in the clear.  The Python wrappers draw a fresh
+ *               key from the OS per call (and fail if none is available), so they cannot repeat a pair.
+ *   security    the public key and every list are ring-LWE samples in the bootstrapping key's ring (N = 1024, modulus 2^32)
+ *               with its noise (bk_stdev) and a binary secret (s' for the key, u for a list): they rest on the assumption
+ *               the published bootstrapping key already rests on, and nothing beyond it is claimed.
+ * Client side, CPU only, multithreaded over lists (eoc_host_threads).  EOC_ERR_ARG, with nothing written, for a null pointer,
+ * a blob that is not a whole EOCPK1 blob (wrong magic, truncated, an EOCCK1 or EOCSK* blob), p outside {2, 4, 8} or a
+ * value >= p; count 0 is a no-op. */
+size_t eoc_public_key_blob_bytes(const eoc_params *p);                            /* 8 236 for both default sets */
+int eoc_public_key_export(const eoc_secret_key *sk, void *buf, size_t cap);       /* EOC_ERR_ARG when cap is too small */
+int eoc_public_key_blob_params(const void *buf, size_t len, eoc_params *p);       /* a whole EOCPK1 blob, else EOC_ERR_ARG */
+int eoc_pk_encrypt_bits(const void *pk, size_t pk_len, uint64_t enc_seed, uint64_t first_list, const uint8_t *bits,
+                        size_t count, int32_t *lists);
+int eoc_pk_encrypt_bits_keyed(const void *pk, size_t pk_len, const uint8_t enc_key[32], uint64_t first_list,
+                              const uint8_t *bits, size_t count, int32_t *lists);
+int eoc_pk_encrypt_ints(const void *pk, size_t pk_len, uint64_t enc_seed, uint64_t first_list, int p, const uint8_t *values,
+                        size_t count, int32_t *lists);
+int eoc_pk_encrypt_ints_keyed(const void *pk, size_t pk_len, const uint8_t enc_key[32], uint64_t first_list, int p,
+                              const uint8_t *values, size_t count, int32_t *lists);
+/* lists [ceil(count / N)][2][N] -> out [count][n+1] on the global context (host buffers, synchronous): samples are cut into
+ * eoc_shard_range blocks, one per engine, and each engine receives only the lists its block touches.  The engines come up
+ * behind the global key on first use; the cloud key alone suffices (key mode 2).  EOC_ERR_ARG for a null pointer. */
+int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *out);
+/* EOCPK1 blob of the global secret key (key mode 1): bytes needed, 0 without a secret key; fills buf when cap suffices */
+size_t eoc_global_public_key_export(void *buf, size_t cap);
 
 #ifdef __cplusplus
 }
