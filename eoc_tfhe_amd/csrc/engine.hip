@@ -567,126 +567,165 @@ extern "C" int eoc_engine_cloud_key_device(eoc_engine *e, const void **d_bkfft, 
 // ---- launch helpers -------------------------------------------------------------------------
 typedef eoc_engine::Workspace WS;
 
+// What one blind rotation runs over; launch_blind_rotate refuses the combinations that mean nothing.
+struct BRWork {
+    uint32_t njobs = 0;
+    // kernel family: k_blind_rotate* (every job starts from the gate accumulator), *_tv (programmable bootstrapping: job j
+    // starts from test polynomial tv[j / tv_rows]), k_lut_many* (many-LUT bootstrapping: the same, and n_tables samples are
+    // extracted per job into the workspace's slot rows).  Same shapes and same segmentation for all three.
+    enum Seed { GATE, TV, MANY } seed = GATE;
+    const int32_t *tv = nullptr;
+    uint32_t tv_rows = 1, n_tables = 0;
+    // GATE / TV: the kernel's epilogue sets the key switch up (no k_ks_init), its prologue makes the rotation amounts too (no
+    // k_prepare), from the level's device descriptors `descs` (jobs are [gate][S]) or, single-gate level (KS_AND_PREP), from
+    // `inline_desc`, which travels as a kernel argument
+    enum Fold { NONE, KS, KS_AND_PREP } fold = NONE;
+    const GateDesc *descs = nullptr, *inline_desc = nullptr;
+    uint32_t S = 0;
+};
+
+// THE PLAN: the launches a blind rotation of `njobs_total` jobs is cut into -- a pure function of these integers.
 // One launch holds at most `br_slice` jobs (default: what is resident at once, four workgroups per CU): a launch in
 // which every workgroup is resident from the start runs with the wave-priority alternation and finishes all its
 // workgroups within half a per cent of each other (3.0 ms per 1024 jobs), while a launch of several rounds settles at
 // a 10 % lower rate (the arbiter's age bias), so wide levels are cut into back-to-back single-round launches.
-// tv != nullptr (programmable bootstrapping): every job starts from test polynomial tv[job / tv_rows] instead of the gate
-// accumulator, on the *_tv twin of the kernel the policy below picks (same shapes, same segmentation); n_tables > 0 (many-LUT
-// bootstrapping): on the k_lut_many* twin instead, which extracts n_tables samples per job into the workspace's slot rows
-static int launch_blind_rotate(eoc_engine *e, WS &W, uint32_t njobs_total, hipStream_t st,
-                               const GateDesc *fold_descs = nullptr, uint32_t fold_S = 0, const GateDesc *inline_desc = nullptr,
-                               bool fold_prep = true, const int32_t *tv = nullptr, uint32_t tv_rows = 1, uint32_t n_tables = 0)
+// Two kernel shapes (kernels.hip.h).  The pair kernel (one ciphertext = one wave pair) fills the chip with 4 x CUs
+// ciphertexts; the wide kernel (one ciphertext = one wave, gadget length 2 only) with 8 x CUs, and saves the partial-chain
+// exchange and its barriers.  A level wider than the pair kernel's resident set runs as full wide launches plus a
+// remainder: on the pair kernel when it fits its resident set (a half-empty wide launch has one wave per SIMD and runs
+// at 0.7 of the pair kernel's rate), on the wide kernel otherwise (tools/wide_sweep.py).
+struct BRSeg { uint32_t off, njobs; bool wide; };
+struct BRPlan {
+    std::vector<BRSeg> segs;
+    int parts; // consecutive launches (step ranges) per segment
+};
+static BRPlan plan_blind_rotate(uint32_t njobs_total, int num_cus, int l, int kpl, int n, int br_slice, int br_parts, int br_wide)
 {
-    SpanGuard span(e, st, KIND_BLIND_ROTATE);
-    // Two kernel shapes (kernels.hip.h).  The pair kernel (one ciphertext = one wave pair) fills the chip with 4 x CUs
-    // ciphertexts; the wide kernel (one ciphertext = one wave, gadget length 2 only) with 8 x CUs, and saves the partial-chain
-    // exchange and its barriers.  A level wider than the pair kernel's resident set runs as full wide launches plus a
-    // remainder: on the pair kernel when it fits its resident set (a half-empty wide launch has one wave per SIMD and runs
-    // at 0.7 of the pair kernel's rate), on the wide kernel otherwise (tools/wide_sweep.py).
-    const uint32_t resident_pair = 4u * (uint32_t)e->num_cus, resident_wide = 8u * (uint32_t)e->num_cus;
-    const bool can_wide = e->p.l == 2 && e->br_wide != 0;
-    const bool force_wide = can_wide && e->br_wide > 0;
-    struct Seg { uint32_t off, njobs; bool wide; };
-    std::vector<Seg> segs;
-    segs.reserve(njobs_total / resident_pair + 2);
-    const int auto_parts = e->kpl * 2 * kNH * 16 > 80 * 1024 ? 2 : 1;
-    const int parts = std::max(1, std::min(e->br_parts > 0 ? e->br_parts : auto_parts, e->p.n));
-    {
-        auto even = [&](uint32_t off, uint32_t total, uint32_t slice, bool wide) { // even slices: 1536 jobs as 768 + 768
-            if (parts > 1 && slice > 16u * (uint32_t)e->num_cus) slice = 16u * (uint32_t)e->num_cus; // acc_state capacity
-            const uint32_t nsl = (total + slice - 1) / slice;
-            slice = (total + nsl - 1) / nsl;
-            for (uint32_t o = 0; o < total; o += slice) segs.push_back({off + o, std::min(slice, total - o), wide});
-        };
-        if (e->br_slice != 0) // diagnostics: fixed slice (> 0) or one launch (< 0), one kernel shape
-            even(0, njobs_total, e->br_slice > 0 ? (uint32_t)e->br_slice : njobs_total, force_wide);
-        else if (force_wide)
-            even(0, njobs_total, resident_wide, true);
-        else if (!can_wide || njobs_total <= resident_pair)
-            even(0, njobs_total, resident_pair, false);
-        else {
-            const uint32_t full = njobs_total / resident_wide * resident_wide, rem = njobs_total - full;
-            if (full) even(0, full, resident_wide, true);
-            if (rem) even(full, rem, rem <= resident_pair ? resident_pair : resident_wide, rem > resident_pair);
-        }
+    const uint32_t resident_pair = 4u * (uint32_t)num_cus, resident_wide = 8u * (uint32_t)num_cus;
+    const bool can_wide = l == 2 && br_wide != 0;
+    const bool force_wide = can_wide && br_wide > 0;
+    const int auto_parts = kpl * 2 * kNH * 16 > 80 * 1024 ? 2 : 1;
+    BRPlan plan;
+    plan.parts = std::max(1, std::min(br_parts > 0 ? br_parts : auto_parts, n));
+    plan.segs.reserve(njobs_total / resident_pair + 2);
+    auto even = [&](uint32_t off, uint32_t total, uint32_t slice, bool wide) { // even slices: 1536 jobs as 768 + 768
+        if (plan.parts > 1 && slice > 16u * (uint32_t)num_cus) slice = 16u * (uint32_t)num_cus; // acc_state capacity
+        const uint32_t nsl = (total + slice - 1) / slice;
+        slice = (total + nsl - 1) / nsl;
+        for (uint32_t o = 0; o < total; o += slice) plan.segs.push_back({off + o, std::min(slice, total - o), wide});
+    };
+    if (br_slice != 0) // diagnostics: fixed slice (> 0) or one launch (< 0), one kernel shape
+        even(0, njobs_total, br_slice > 0 ? (uint32_t)br_slice : njobs_total, force_wide);
+    else if (force_wide)
+        even(0, njobs_total, resident_wide, true);
+    else if (!can_wide || njobs_total <= resident_pair)
+        even(0, njobs_total, resident_pair, false);
+    else {
+        const uint32_t full = njobs_total / resident_wide * resident_wide, rem = njobs_total - full;
+        if (full) even(0, full, resident_wide, true);
+        if (rem) even(full, rem, rem <= resident_pair ? resident_pair : resident_wide, rem > resident_pair);
     }
-    for (const Seg &sg : segs) {
-        const uint32_t off = sg.off, njobs = sg.njobs;
-        const bool wide = sg.wide;
-        const uint32_t resident = wide ? resident_wide : resident_pair;
-        for (int part = 0; part < parts; part++) {
-            BRArgs a{};
-            a.bkfft = e->bkfft;
-            a.bara = W.d_bara + (size_t)off * e->bara_stride;
-            a.u = W.d_u + (size_t)off * (kN + 1);
-            a.njobs = njobs;
-            a.n = e->p.n;
-            a.Bgbit = e->p.Bgbit;
-            a.bara_stride = e->bara_stride;
-            a.mu = (int32_t)(1u << 29);
-            a.stamps = e->d_stamps;
-            a.ks_descs = fold_descs;
-            a.prep = fold_descs != nullptr && fold_prep; // false: k_prepare wrote the rotation amounts (three-operand gates)
-            a.inline_desc = inline_desc != nullptr;
-            if (inline_desc) {
-                a.desc0 = *inline_desc;
-                a.ks_descs = reinterpret_cast<const GateDesc *>(W.d_descs); // non-null = fold; never dereferenced
-                a.prep = 1;
-            }
-            a.ubar = W.d_ubar;
-            a.ks_S = fold_S ? fold_S : 1;
-            a.ks_prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
-            a.job0 = off;
-            a.step_begin = (int)((long long)e->p.n * part / parts);
-            a.step_end = (int)((long long)e->p.n * (part + 1) / parts);
-            a.acc_state = W.d_acc_state;
-            // priority alternation pays only when every workgroup is resident from the start (four per CU)
-            a.prio_duty = (e->prio_duty_override != INT32_MIN) ? e->prio_duty_override
-                          : (njobs <= resident ? kPrioDuty : e->prio_multi);
-            dim3 grid(njobs), block(128);
-            // SABAR: the rotation amounts read back by scalar loads (EOC_TFHE_SCALAR_ABAR=1) instead of vector loads
-#define EOC_BR_LAUNCH(KERNEL_, MANY_, LDS_, ...)                                                                   \
-    do {                                                                                                          \
-        if (n_tables) {                                                                                           \
-            if (e->scalar_abar)                                                                                   \
-                hipLaunchKernelGGL((MANY_<__VA_ARGS__, true>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows, n_tables); \
-            else                                                                                                  \
-                hipLaunchKernelGGL((MANY_<__VA_ARGS__, false>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows, n_tables); \
-        } else if (tv) {                                                                                          \
-            if (e->scalar_abar)                                                                                   \
-                hipLaunchKernelGGL((KERNEL_##_tv<__VA_ARGS__, true>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows); \
-            else                                                                                                  \
-                hipLaunchKernelGGL((KERNEL_##_tv<__VA_ARGS__, false>), grid, block, LDS_, st, a, e->d_tw, e->d_twist, tv, tv_rows); \
-        } else if (e->scalar_abar) hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, true>), grid, block, LDS_, st, a, e->d_tw, e->d_twist);  \
-        else hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, false>), grid, block, LDS_, st, a, e->d_tw, e->d_twist);     \
-    } while (0)
-            if (wide) {
-                grid = dim3((njobs + kBRWideJobsPerWG - 1) / kBRWideJobsPerWG);
-                block = dim3(64 * kBRWideJobsPerWG);
-                if (e->p.Bgbit == 10) EOC_BR_LAUNCH(k_blind_rotate_wide, k_lut_many_wide, kBRWideLds, 10); // Set A
-                else EOC_BR_LAUNCH(k_blind_rotate_wide, k_lut_many_wide, kBRWideLds, 0);
-                e->br_wide_launches++;
-            } else if (e->p.l == 2 && e->p.Bgbit == 10) EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 2, 10); // Set A
-            else if (e->p.l == 3 && e->p.Bgbit == 7) EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 3, 7);     // Set B
-            else
-                switch (e->p.l) {
-                case 1: EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 1, 0); break;
-                case 2: EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 2, 0); break;
-                case 3: EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 3, 0); break;
-                case 4: EOC_BR_LAUNCH(k_blind_rotate, k_lut_many, kBRLds, 4, 0); break;
-                default: return EOC_ERR_ARG;
-                }
-#undef EOC_BR_LAUNCH
-            HIP_TRY(hipGetLastError());
+    return plan;
+}
+
+// THE ARGUMENTS of one launch: part `part` of `parts` of segment `sg`
+static BRArgs blind_rotate_args(const eoc_engine *e, const WS &W, const BRWork &w, const BRSeg &sg, int part, int parts)
+{
+    BRArgs a{};
+    a.bkfft = e->bkfft;
+    a.bara = W.d_bara + (size_t)sg.off * e->bara_stride;
+    a.u = W.d_u + (size_t)sg.off * (kN + 1);
+    a.njobs = sg.njobs;
+    a.n = e->p.n;
+    a.Bgbit = e->p.Bgbit;
+    a.bara_stride = e->bara_stride;
+    a.mu = (int32_t)(1u << 29);
+    a.stamps = e->d_stamps;
+    a.ks_descs = w.fold != BRWork::NONE ? w.descs : nullptr;
+    a.prep = w.fold == BRWork::KS_AND_PREP; // KS alone: k_prepare wrote the rotation amounts (three-operand gates)
+    a.inline_desc = w.inline_desc != nullptr;
+    if (w.inline_desc) {
+        a.desc0 = *w.inline_desc;
+        a.ks_descs = reinterpret_cast<const GateDesc *>(W.d_descs); // non-null = fold; never dereferenced
+    }
+    a.ubar = W.d_ubar;
+    a.ks_S = w.fold != BRWork::NONE ? w.S : 1;
+    a.ks_prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    a.job0 = sg.off;
+    a.step_begin = (int)((long long)e->p.n * part / parts);
+    a.step_end = (int)((long long)e->p.n * (part + 1) / parts);
+    a.acc_state = W.d_acc_state;
+    // priority alternation pays only when every workgroup is resident from the start (four per CU)
+    const uint32_t resident = (sg.wide ? 8u : 4u) * (uint32_t)e->num_cus;
+    a.prio_duty = (e->prio_duty_override != INT32_MIN) ? e->prio_duty_override
+                  : (sg.njobs <= resident ? kPrioDuty : e->prio_multi);
+    return a;
+}
+
+// THE KERNEL: the instance for (shape, gadget, family, read-back form).  Exactly these are instantiated: six pair and two
+// wide shapes, each as gate / _tv / many-LUT kernel, each with the rotation amounts read back by vector loads or
+// (sabar, EOC_TFHE_SCALAR_ABAR=1) by scalar loads.
+template <int L, int BGBIT> static const void *br_pair_kernel(BRWork::Seed seed, bool sabar)
+{
+    switch (seed) {
+    case BRWork::GATE: return sabar ? (const void *)&k_blind_rotate<L, BGBIT, true> : (const void *)&k_blind_rotate<L, BGBIT, false>;
+    case BRWork::TV: return sabar ? (const void *)&k_blind_rotate_tv<L, BGBIT, true> : (const void *)&k_blind_rotate_tv<L, BGBIT, false>;
+    default: return sabar ? (const void *)&k_lut_many<L, BGBIT, true> : (const void *)&k_lut_many<L, BGBIT, false>;
+    }
+}
+template <int BGBIT> static const void *br_wide_kernel(BRWork::Seed seed, bool sabar)
+{
+    switch (seed) {
+    case BRWork::GATE: return sabar ? (const void *)&k_blind_rotate_wide<BGBIT, true> : (const void *)&k_blind_rotate_wide<BGBIT, false>;
+    case BRWork::TV: return sabar ? (const void *)&k_blind_rotate_wide_tv<BGBIT, true> : (const void *)&k_blind_rotate_wide_tv<BGBIT, false>;
+    default: return sabar ? (const void *)&k_lut_many_wide<BGBIT, true> : (const void *)&k_lut_many_wide<BGBIT, false>;
+    }
+}
+struct BRKernel { const void *fn; dim3 grid, block; unsigned lds; }; // fn == nullptr: no kernel for this gadget length
+static BRKernel blind_rotate_kernel(bool wide, int l, int Bgbit, bool sabar, BRWork::Seed seed, uint32_t njobs)
+{
+    if (wide) {
+        const void *fn = Bgbit == 10 ? br_wide_kernel<10>(seed, sabar) : br_wide_kernel<0>(seed, sabar); // 10: Set A
+        return {fn, dim3((njobs + kBRWideJobsPerWG - 1) / kBRWideJobsPerWG), dim3(64 * kBRWideJobsPerWG), kBRWideLds};
+    }
+    const void *fn = nullptr;
+    if (l == 2 && Bgbit == 10) fn = br_pair_kernel<2, 10>(seed, sabar); // Set A
+    else if (l == 3 && Bgbit == 7) fn = br_pair_kernel<3, 7>(seed, sabar); // Set B
+    else if (l == 1) fn = br_pair_kernel<1, 0>(seed, sabar);
+    else if (l == 2) fn = br_pair_kernel<2, 0>(seed, sabar);
+    else if (l == 3) fn = br_pair_kernel<3, 0>(seed, sabar);
+    else if (l == 4) fn = br_pair_kernel<4, 0>(seed, sabar);
+    return {fn, dim3(njobs), dim3(128), kBRLds};
+}
+
+static int launch_blind_rotate(eoc_engine *e, WS &W, const BRWork &w, hipStream_t st)
+{
+    const bool folds = w.fold != BRWork::NONE;
+    if ((w.seed != BRWork::GATE && !w.tv) || (w.seed == BRWork::MANY && (folds || w.n_tables == 0)) ||
+        (folds && !w.inline_desc && (!w.descs || !w.S)) || (w.inline_desc && (w.fold != BRWork::KS_AND_PREP || !w.S))) {
+        eoc_set_error("internal: blind rotation of family %d with fold %d: a table family needs its test polynomials, the "
+                      "many-LUT kernel has no fold, a fold needs descriptors and their row count", (int)w.seed, (int)w.fold);
+        return EOC_ERR_STATE;
+    }
+    SpanGuard span(e, st, KIND_BLIND_ROTATE);
+    const BRPlan plan = plan_blind_rotate(w.njobs, e->num_cus, e->p.l, e->kpl, e->p.n, e->br_slice, e->br_parts, e->br_wide);
+    for (const BRSeg &sg : plan.segs) {
+        const BRKernel k = blind_rotate_kernel(sg.wide, e->p.l, e->p.Bgbit, e->scalar_abar, w.seed, sg.njobs);
+        if (!k.fn) return EOC_ERR_ARG;
+        for (int part = 0; part < plan.parts; part++) {
+            BRArgs a = blind_rotate_args(e, W, w, sg, part, plan.parts);
+            // the gate kernels take the first three arguments, the _tv kernels five, the many-LUT kernels all six
+            void *args[] = {&a, (void *)&e->d_tw, (void *)&e->d_twist, (void *)&w.tv, (void *)&w.tv_rows, (void *)&w.n_tables};
+            HIP_TRY(hipLaunchKernel(k.fn, k.grid, k.block, args, k.lds, st));
             e->br_launches++;
+            e->br_wide_launches += sg.wide;
         }
     }
     return EOC_OK;
 }
 
 static int launch_keyswitch(eoc_engine *e, WS &W, const GateDesc *d_descs, uint32_t ngates, uint32_t S, hipStream_t st,
-                            bool init_done = false, const GateDesc *inline_desc = nullptr)
+                            bool init_done, const GateDesc *inline_desc)
 {
     KSArgs a;
     a.inline_desc = inline_desc != nullptr;
@@ -798,6 +837,58 @@ static void ring_mark(WS &W, hipStream_t st)
     }
 }
 
+// Rotation amounts of gates [0, cnt) of `dd`, `rows` workspace rows each (S, or 2 S where a MUX is among them): k_prepare, or
+// -- theta > 0, many-LUT bootstrapping -- the mod switch onto the 2^theta-grid
+static void launch_prepare(eoc_engine *e, WS &W, const GateDesc *dd, uint32_t cnt, uint32_t rows, uint32_t S, int theta,
+                           hipStream_t st)
+{
+    const int n = e->p.n;
+    const dim3 grid(rows, (unsigned)((n + 1 + 255) / 256), cnt);
+    if (theta) hipLaunchKernelGGL(k_modswitch_coarse, grid, dim3(256), 0, st, dd, n, theta, W.d_bara, e->bara_stride);
+    else hipLaunchKernelGGL(k_prepare, grid, dim3(256), 0, st, dd, n, S, W.d_bara, e->bara_stride);
+}
+
+// One bootstrap level: descriptors -> rotation amounts -> ONE blind rotation -> key switch(es) -> stats.  The callers say
+// what differs; ring_mark stays with them, once per call, behind everything the call pushed (free gates included).
+struct DescRange { uint32_t first, count, S; bool mux; }; // descriptors [first, first + count) of the level, S rows each
+struct Level {
+    const GateDesc *descs = nullptr; // host side; pushed ahead of the kernels (none: br.inline_desc travels as an argument)
+    size_t ndescs = 0;
+    int theta = 0;                   // > 0: rotation amounts by k_modswitch_coarse(theta) instead of k_prepare
+    // one rotation-amount launch per range, inside ONE prepare span (skipped when the blind rotation's prologue makes them:
+    // br.fold == KS_AND_PREP), and one key switch per range (its set-up folded when br.fold != NONE)
+    const DescRange *prep = nullptr, *ks = nullptr;
+    size_t nprep = 0, nks = 0;
+    BRWork br;                       // br.descs is filled in here
+};
+static int run_bootstrap(eoc_engine *e, WS &W, const Level &lv, hipStream_t st)
+{
+    GateDesc *dd = nullptr;
+    int rc = lv.ndescs ? push_descs(W, lv.descs, lv.ndescs, st, &dd) : EOC_OK;
+    if (rc) return rc;
+    if (lv.br.fold != BRWork::KS_AND_PREP) {
+        SpanGuard span(e, st, KIND_PREPARE);
+        for (size_t k = 0; k < lv.nprep; k++) {
+            const DescRange &r = lv.prep[k];
+            launch_prepare(e, W, dd + r.first, r.count, r.S * (r.mux ? 2u : 1u), r.S, lv.theta, st);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    BRWork br = lv.br;
+    br.descs = dd;
+    rc = launch_blind_rotate(e, W, br, st);
+    if (rc) return rc;
+    for (size_t k = 0; k < lv.nks; k++) {
+        const DescRange &r = lv.ks[k];
+        rc = launch_keyswitch(e, W, dd ? dd + r.first : nullptr, r.count, r.S, st, br.fold != BRWork::NONE, br.inline_desc);
+        if (rc) return rc;
+        e->stats[2] += (uint64_t)r.count * r.S;
+    }
+    e->stats[0] += 1;
+    e->stats[1] += br.njobs;
+    return EOC_OK;
+}
+
 // One "level": a set of gates that all run over the same S instances.  descs are host-side and
 // carry device pointers; free gates and bootstrapped gates are separated here.
 static int run_level(eoc_engine *e, WS &W, std::vector<GateDesc> &boot, std::vector<GateDesc> &freeg, size_t S,
@@ -834,12 +925,6 @@ static int run_level(eoc_engine *e, WS &W, std::vector<GateDesc> &boot, std::vec
             return EOC_ERR_STATE;
         }
         const size_t cnt = g1 - g0;
-        // a level of ONE gate without MUX -- the plain eoc_gate_batch_device call -- sends its descriptor as a kernel
-        // argument: no copy into the descriptor ring precedes the two launches (and nothing is consumed from the ring)
-        const bool inline_one = cnt == 1 && !any_mux && !any_lin3 && !e->no_fold;
-        GateDesc *dd = nullptr;
-        int rc = inline_one ? EOC_OK : push_descs(W, boot.data() + g0, cnt, st, &dd);
-        if (rc) return rc;
         // without MUX every gate has S jobs (job = gate * S + instance): the blind rotation's prologue derives its own
         // rotation amounts from the operand rows (k_prepare folded away) and its epilogue sets the key switch up
         // (k_ks_init folded away) -- one launch per level besides the key switch; EOC_TFHE_NO_FOLD=1 keeps the separate
@@ -848,21 +933,22 @@ static int run_level(eoc_engine *e, WS &W, std::vector<GateDesc> &boot, std::vec
         // folded prologue stays the two-operand code it was -- but keep the folded key-switch set-up (every gate of the slice
         // has S jobs: job = gate * S + instance)
         const bool fold = !any_mux && !e->no_fold;
-        const bool fold_prep = fold && !any_lin3;
-        if (!fold_prep) {
-            dim3 grid((unsigned)(S * (any_mux ? 2 : 1)), (unsigned)((n + 1 + 255) / 256), (unsigned)cnt);
-            SpanGuard span(e, st, KIND_PREPARE);
-            hipLaunchKernelGGL(k_prepare, grid, dim3(256), 0, st, dd, n, (uint32_t)S, W.d_bara, e->bara_stride);
-            HIP_TRY(hipGetLastError());
+        const DescRange all{0, (uint32_t)cnt, (uint32_t)S, any_mux};
+        Level lv;
+        lv.prep = lv.ks = &all;
+        lv.nprep = lv.nks = 1;
+        lv.br.njobs = jobs;
+        lv.br.fold = !fold ? BRWork::NONE : (any_lin3 ? BRWork::KS : BRWork::KS_AND_PREP);
+        lv.br.S = (uint32_t)S;
+        // a level of ONE gate without MUX -- the plain eoc_gate_batch_device call -- sends its descriptor as a kernel
+        // argument: no copy into the descriptor ring precedes the two launches (and nothing is consumed from the ring)
+        if (cnt == 1 && lv.br.fold == BRWork::KS_AND_PREP) lv.br.inline_desc = boot.data() + g0;
+        else {
+            lv.descs = boot.data() + g0;
+            lv.ndescs = cnt;
         }
-        const GateDesc *one = inline_one ? boot.data() + g0 : nullptr;
-        rc = launch_blind_rotate(e, W, jobs, st, fold ? dd : nullptr, (uint32_t)S, one, fold_prep);
+        int rc = run_bootstrap(e, W, lv, st);
         if (rc) return rc;
-        rc = launch_keyswitch(e, W, dd, (uint32_t)cnt, (uint32_t)S, st, fold, one);
-        if (rc) return rc;
-        e->stats[0] += 1;
-        e->stats[1] += jobs;
-        e->stats[2] += S * cnt;
         g0 = g1;
     }
     ring_mark(W, st);
@@ -881,40 +967,29 @@ struct PoolItem {
 };
 static int run_pool(eoc_engine *e, WS &W, std::vector<PoolItem> &pool, hipStream_t st)
 {
-    const int n = e->p.n;
     size_t jobs = 0;
     std::vector<GateDesc> descs;
+    std::vector<DescRange> groups; // every group its own rotation-amount launch and its own key switch
     descs.reserve(pool.size());
+    groups.reserve(pool.size());
     for (PoolItem &it : pool) {
         it.d.job_base = (uint32_t)jobs;
         jobs += it.S * (it.d.op == OP_MUX ? 2 : 1);
+        groups.push_back({(uint32_t)descs.size(), 1, (uint32_t)it.S, it.d.op == OP_MUX});
         descs.push_back(it.d);
     }
     if (jobs > W.ws_jobs || jobs > 0xFFFFFFFFull) {
         eoc_set_error("internal: workspace too small for a pooled level (%zu jobs > %zu)", jobs, W.ws_jobs);
         return EOC_ERR_STATE;
     }
-    GateDesc *dd = nullptr;
-    int rc = push_descs(W, descs.data(), descs.size(), st, &dd);
+    Level lv;
+    lv.descs = descs.data();
+    lv.ndescs = descs.size();
+    lv.prep = lv.ks = groups.data();
+    lv.nprep = lv.nks = groups.size();
+    lv.br.njobs = (uint32_t)jobs;
+    int rc = run_bootstrap(e, W, lv, st);
     if (rc) return rc;
-    {
-        SpanGuard span(e, st, KIND_PREPARE);
-        for (size_t k = 0; k < pool.size(); k++) {
-            const size_t S = pool[k].S;
-            dim3 grid((unsigned)(S * (pool[k].d.op == OP_MUX ? 2 : 1)), (unsigned)((n + 1 + 255) / 256), 1);
-            hipLaunchKernelGGL(k_prepare, grid, dim3(256), 0, st, dd + k, n, (uint32_t)S, W.d_bara, e->bara_stride);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    rc = launch_blind_rotate(e, W, (uint32_t)jobs, st);
-    if (rc) return rc;
-    for (size_t k = 0; k < pool.size(); k++) {
-        rc = launch_keyswitch(e, W, dd + k, 1, (uint32_t)pool[k].S, st);
-        if (rc) return rc;
-        e->stats[2] += pool[k].S;
-    }
-    e->stats[0] += 1;
-    e->stats[1] += jobs;
     ring_mark(W, st);
     return EOC_OK;
 }
@@ -1012,7 +1087,8 @@ static int gate_batch_ws(eoc_engine *e, WS &W, int op, const uint8_t *ops, const
         sorted_ops.resize(count);
         for (size_t k = 0; k < count; k++) {
             size_t pos = bucket[ops[k]]++;
-            perm[pos] = (uint32_t)k | ((uint32_t)ops[k] << 28); // index | opcode: k_gather_rows masks, OP_MULTI reads the top
+            // index | opcode in the top four bits (k_gather_rows masks them, OP_MULTI rows -- opcodes 0..9 -- read them)
+            perm[pos] = (uint32_t)k | (ops[k] < OP_MUX ? (uint32_t)ops[k] << 28 : 0u);
             sorted_ops[pos] = ops[k];
         }
         int32_t *g0 = W.d_mixed, *g1 = g0 + count * stride, *g2 = g1 + count * stride, *go = g2 + count * stride;
@@ -1183,10 +1259,12 @@ extern "C" int eoc_blind_rotate_device(eoc_engine *e, const int32_t *d_t, int32_
     GateDesc d{OP_RAW, 0, d_t, nullptr, nullptr, nullptr}, *dd = nullptr;
     rc = push_descs(W, &d, 1, st, &dd);
     if (rc) return rc;
-    dim3 grid((unsigned)count, (unsigned)((e->p.n + 1 + 255) / 256), 1);
-    hipLaunchKernelGGL(k_prepare, grid, dim3(256), 0, st, dd, e->p.n, (uint32_t)count, W.d_bara, e->bara_stride);
+    // (no key switch, no statistics and no prepare span: not a level, so not run_bootstrap)
+    launch_prepare(e, W, dd, 1, (uint32_t)count, (uint32_t)count, 0, st);
     HIP_TRY(hipGetLastError());
-    rc = launch_blind_rotate(e, W, (uint32_t)count, st);
+    BRWork br;
+    br.njobs = (uint32_t)count;
+    rc = launch_blind_rotate(e, W, br, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(d_u, W.d_u, count * (kN + 1) * 4, hipMemcpyDeviceToDevice, st));
     ring_mark(W, st);
@@ -1209,7 +1287,7 @@ extern "C" int eoc_keyswitch_device(eoc_engine *e, const int32_t *d_u, int32_t *
     GateDesc d{OP_RAW, 0, nullptr, nullptr, nullptr, d_out}, *dd = nullptr;
     rc = push_descs(W, &d, 1, st, &dd);
     if (rc) return rc;
-    rc = launch_keyswitch(e, W, dd, 1, (uint32_t)count, st);
+    rc = launch_keyswitch(e, W, dd, 1, (uint32_t)count, st, false, nullptr);
     ring_mark(W, st);
     return rc;
 }
@@ -1261,10 +1339,57 @@ extern "C" int eoc_compact_expand_device(eoc_engine *e, const int32_t *d_lists, 
     return eoc_compact_expand_device_from(e, d_lists, 0, count, d_out, hip_stream);
 }
 
-// ---- programmable bootstrapping -------------------------------------------------------------
-// One level of n_luts x rows jobs, [table][row]: one OP_RAW descriptor per table (all read the same input rows, job_base =
-// table x rows, out = the table's output block) serves k_prepare, the blind rotation and the key switch.  Levels wider than
-// 2^20 jobs run in row slices, as circuit levels do.
+// ---- programmable bootstrapping ----------------------------------------
+// Table lookups, n_tables = 0: one level of n_luts x rows jobs, [table][row]: one OP_RAW descriptor per table (all read the
+// same input rows, job_base = table x rows, out = the table's output block) serves k_prepare, the blind rotation and the key
+// switch.  Many-LUT bootstrapping, n_tables = T: one level of n_luts x rows blind rotations, [polynomial][row], each extracting
+// T samples: the n_luts descriptors (no output) serve the coarse mod switch, n_luts x T more the key switch (job_base =
+// (g T + j) x rows, out = slot j's block of polynomial g).  Rows are sliced, as circuit levels are, so that the workspace
+// holds the extracted samples of a slice: at most 2^20.
+static int lut_levels(eoc_engine *e, const char *who, int n_tables, const int32_t *d_tv, size_t n_luts, const int32_t *d_in,
+                      int32_t *d_out, size_t count, hipStream_t st)
+{
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->bkfft || !e->ksk) {
+        eoc_set_error("%s: no cloud key loaded", who);
+        return EOC_ERR_NO_KEY;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    WS &W = e->ws;
+    const bool many = n_tables > 0;
+    const size_t stride = (size_t)e->p.n + 1, slots = n_luts * (many ? (size_t)n_tables : 1);
+    const size_t rows = std::min(count, std::max<size_t>(1, ((size_t)1 << 20) / slots));
+    std::vector<GateDesc> descs(many ? n_luts + slots : n_luts);
+    int rc = ensure_ws(e, W, slots * rows, descs.size(), 0, st);
+    if (rc) return rc;
+    for (size_t r0 = 0; r0 < count; r0 += rows) {
+        const size_t S = std::min(rows, count - r0);
+        for (size_t t = 0; t < n_luts; t++)
+            descs[t] = GateDesc{OP_RAW, (uint32_t)(t * S), d_in + r0 * stride, nullptr, nullptr,
+                                many ? nullptr : d_out + (t * count + r0) * stride};
+        for (size_t s = 0; many && s < slots; s++)
+            descs[n_luts + s] = GateDesc{OP_RAW, (uint32_t)(s * S), nullptr, nullptr, nullptr, d_out + (s * count + r0) * stride};
+        const DescRange tables{0, (uint32_t)n_luts, (uint32_t)S, false}, outs{(uint32_t)n_luts, (uint32_t)slots, (uint32_t)S, false};
+        Level lv;
+        lv.descs = descs.data();
+        lv.ndescs = descs.size();
+        lv.theta = n_tables == 2 ? 1 : (n_tables == 4 ? 2 : (n_tables == 8 ? 3 : 0));
+        lv.prep = &tables;
+        lv.ks = many ? &outs : &tables;
+        lv.nprep = lv.nks = 1;
+        lv.br.njobs = (uint32_t)(n_luts * S);
+        lv.br.seed = many ? BRWork::MANY : BRWork::TV;
+        lv.br.tv = d_tv;
+        lv.br.tv_rows = (uint32_t)S;
+        lv.br.n_tables = (uint32_t)n_tables;
+        rc = run_bootstrap(e, W, lv, st);
+        if (rc) return rc;
+    }
+    ring_mark(W, st);
+    return EOC_OK;
+}
+
 extern "C" int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n_luts, const int32_t *d_in, int32_t *d_out,
                                     size_t count, void *hip_stream)
 {
@@ -1272,51 +1397,9 @@ extern "C" int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n
         eoc_set_error("eoc_lut_batch_device: null argument or n_luts outside [1, %zu]", kMaxGatesPerLaunch);
         return EOC_ERR_ARG;
     }
-    if (!count) return EOC_OK;
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!e->bkfft || !e->ksk) {
-        eoc_set_error("eoc_lut_batch_device: no cloud key loaded");
-        return EOC_ERR_NO_KEY;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    WS &W = e->ws;
-    const int n = e->p.n;
-    const size_t stride = (size_t)n + 1;
-    const size_t rows = std::min(count, std::max<size_t>(1, ((size_t)1 << 20) / n_luts));
-    int rc = ensure_ws(e, W, n_luts * rows, n_luts, 0, st);
-    if (rc) return rc;
-    std::vector<GateDesc> descs(n_luts);
-    for (size_t r0 = 0; r0 < count; r0 += rows) {
-        const size_t S = std::min(rows, count - r0);
-        for (size_t t = 0; t < n_luts; t++)
-            descs[t] = GateDesc{OP_RAW, (uint32_t)(t * S), d_in + r0 * stride, nullptr, nullptr, d_out + (t * count + r0) * stride};
-        GateDesc *dd = nullptr;
-        rc = push_descs(W, descs.data(), n_luts, st, &dd);
-        if (rc) return rc;
-        {
-            SpanGuard span(e, st, KIND_PREPARE);
-            dim3 grid((unsigned)S, (unsigned)((n + 1 + 255) / 256), (unsigned)n_luts);
-            hipLaunchKernelGGL(k_prepare, grid, dim3(256), 0, st, dd, n, (uint32_t)S, W.d_bara, e->bara_stride);
-            HIP_TRY(hipGetLastError());
-        }
-        const uint32_t jobs = (uint32_t)(n_luts * S);
-        rc = launch_blind_rotate(e, W, jobs, st, nullptr, 0, nullptr, true, d_tv, (uint32_t)S);
-        if (rc) return rc;
-        rc = launch_keyswitch(e, W, dd, (uint32_t)n_luts, (uint32_t)S, st);
-        if (rc) return rc;
-        e->stats[0] += 1;
-        e->stats[1] += jobs;
-        e->stats[2] += jobs;
-    }
-    ring_mark(W, st);
-    return EOC_OK;
+    return lut_levels(e, "eoc_lut_batch_device", 0, d_tv, n_luts, d_in, d_out, count, (hipStream_t)hip_stream);
 }
 
-// ---- many-LUT bootstrapping ------------------------------------------------
-// One level of n_luts x rows blind rotations, [polynomial][row], each extracting T samples: n_luts OP_RAW descriptors
-// (job_base = g x rows) for the coarse mod switch, n_luts x T for the key switch (job_base = (g T + j) x rows, out = slot
-// j's block of polynomial g).  Rows are sliced so that the workspace holds the n_luts x T x rows extracted samples.
 extern "C" int eoc_lut_many_batch_device(eoc_engine *e, int n_tables, const int32_t *d_tv, size_t n_luts, const int32_t *d_in,
                                          int32_t *d_out, size_t count, void *hip_stream)
 {
@@ -1326,50 +1409,7 @@ extern "C" int eoc_lut_many_batch_device(eoc_engine *e, int n_tables, const int3
                       "outside [1, %zu]", n_tables, kMaxGatesPerLaunch);
         return EOC_ERR_ARG;
     }
-    if (!count) return EOC_OK;
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!e->bkfft || !e->ksk) {
-        eoc_set_error("eoc_lut_many_batch_device: no cloud key loaded");
-        return EOC_ERR_NO_KEY;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    WS &W = e->ws;
-    const int n = e->p.n;
-    const size_t stride = (size_t)n + 1, T = (size_t)n_tables, slots = n_luts * T;
-    const int theta = n_tables == 2 ? 1 : (n_tables == 4 ? 2 : 3);
-    const size_t rows = std::min(count, std::max<size_t>(1, ((size_t)1 << 20) / slots));
-    int rc = ensure_ws(e, W, slots * rows, n_luts + slots, 0, st);
-    if (rc) return rc;
-    std::vector<GateDesc> descs(n_luts + slots);
-    for (size_t r0 = 0; r0 < count; r0 += rows) {
-        const size_t S = std::min(rows, count - r0);
-        for (size_t g = 0; g < n_luts; g++) {
-            descs[g] = GateDesc{OP_RAW, (uint32_t)(g * S), d_in + r0 * stride, nullptr, nullptr, nullptr};
-            for (size_t j = 0; j < T; j++)
-                descs[n_luts + g * T + j] = GateDesc{OP_RAW, (uint32_t)((g * T + j) * S), nullptr, nullptr, nullptr,
-                                                     d_out + ((g * T + j) * count + r0) * stride};
-        }
-        GateDesc *dd = nullptr;
-        rc = push_descs(W, descs.data(), descs.size(), st, &dd);
-        if (rc) return rc;
-        {
-            SpanGuard span(e, st, KIND_PREPARE);
-            dim3 grid((unsigned)S, (unsigned)((n + 1 + 255) / 256), (unsigned)n_luts);
-            hipLaunchKernelGGL(k_modswitch_coarse, grid, dim3(256), 0, st, dd, n, theta, W.d_bara, e->bara_stride);
-            HIP_TRY(hipGetLastError());
-        }
-        const uint32_t jobs = (uint32_t)(n_luts * S);
-        rc = launch_blind_rotate(e, W, jobs, st, nullptr, 0, nullptr, true, d_tv, (uint32_t)S, (uint32_t)n_tables);
-        if (rc) return rc;
-        rc = launch_keyswitch(e, W, dd + n_luts, (uint32_t)slots, (uint32_t)S, st);
-        if (rc) return rc;
-        e->stats[0] += 1;
-        e->stats[1] += jobs;
-        e->stats[2] += slots * S;
-    }
-    ring_mark(W, st);
-    return EOC_OK;
+    return lut_levels(e, "eoc_lut_many_batch_device", n_tables, d_tv, n_luts, d_in, d_out, count, (hipStream_t)hip_stream);
 }
 
 extern "C" int eoc_engine_set_profiling(eoc_engine *e, int on)

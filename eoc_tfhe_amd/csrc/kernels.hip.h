@@ -493,6 +493,8 @@ __device__ __forceinline__ int gate_lin3(int op) { return op == OP_MAJ ? 1 : (op
 // opcode (the gather permutation: original index | op << 28).
 constexpr int OP_MULTI = 101;
 constexpr uint32_t kPermIndexMask = 0x0FFFFFFFu;
+// the opcode field above the mask is 4 bits wide: the host stores opcodes 0..9 there (the only ones OP_MULTI rows can have)
+static_assert(OP_MUX - 1 <= (~kPermIndexMask >> 28), "two-input opcodes must fit the permutation's opcode field");
 __device__ __forceinline__ int desc_op(const GateDesc &d, uint32_t inst)
 {
     return d.op == OP_MULTI ? (int)(reinterpret_cast<const uint32_t *>(d.in2)[inst] >> 28) : d.op;

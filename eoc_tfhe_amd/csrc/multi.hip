@@ -120,9 +120,9 @@ struct Slot {
     eoc_engine *e = nullptr;
     hipStream_t st[3] = {nullptr, nullptr, nullptr}; // [0] kernels, [1] H2D copies, [2] D2H copies
     std::vector<hipEvent_t> ev;                       // chunk hand-offs between the three (grown on demand, re-used)
-    // persistent buffers of the gate-batch path: 3 inputs + 1 output, `cap_rows` rows each
+    // persistent buffers of the gate-batch path: 3 inputs + 1 output, `cap_io_ints` ints each
     int32_t *d_io[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cap_rows = 0;
+    size_t cap_io_ints = 0;
     // persistent wire buffer of the circuit path
     int32_t *d_wires = nullptr;
     size_t cap_wire_ints = 0;
@@ -186,20 +186,32 @@ void *mapped_address(const void *p)
 }
 bool is_pinned(const void *p) { return !p || mapped_address(p) != nullptr; }
 
-int slot_reserve_rows(Slot &s, size_t rows, size_t stride_ints)
+// Grow the `nbuf` persistent device buffers `bufs` of slot `s` (device already selected) to `need` ints each.  The device is
+// synchronised first: nothing in flight may still use the buffers that are replaced.  Counted in eoc_host_path_buffer_grows.
+int slot_grow(Slot &s, int32_t **bufs, int nbuf, size_t *cap, size_t need)
 {
-    if (rows <= s.cap_rows) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
+    if (need <= *cap) return EOC_OK;
     HIP_TRY(hipDeviceSynchronize());
-    size_t cap = std::max<size_t>(rows, 1024);
-    for (int k = 0; k < 4; k++) {
-        hipFree(s.d_io[k]);
-        s.d_io[k] = nullptr;
+    for (int k = 0; k < nbuf; k++) {
+        hipFree(bufs[k]);
+        bufs[k] = nullptr;
     }
-    s.cap_rows = 0;
-    for (int k = 0; k < 4; k++) HIP_TRY(hipMalloc(&s.d_io[k], cap * stride_ints * 4));
-    s.cap_rows = cap;
+    *cap = 0;
+    for (int k = 0; k < nbuf; k++) HIP_TRY(hipMalloc(&bufs[k], need * 4));
+    *cap = need;
     s.grows++;
+    return EOC_OK;
+}
+
+// the common exit of the one-stream block functions: the stream is drained whatever `rc` is -- an error must not leave a
+// copy into (or out of) the caller's buffers in flight after the call has returned
+int slot_finish(hipStream_t st, int rc)
+{
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
     return EOC_OK;
 }
 
@@ -214,9 +226,9 @@ int slot_gate_block(Slot &s, int op, const uint8_t *ops, const int32_t *in0, con
                     int32_t *out, size_t count, size_t stride_ints)
 {
     if (!count) return EOC_OK;
-    int rc = slot_reserve_rows(s, count, stride_ints);
-    if (rc) return rc;
     HIP_TRY(hipSetDevice(s.device));
+    int rc = slot_grow(s, s.d_io, 4, &s.cap_io_ints, std::max<size_t>(count, 1024) * stride_ints);
+    if (rc) return rc;
     const int32_t *h[3] = {in0, in1, in2};
     const bool zero_copy = !getenv("EOC_TFHE_NO_ZERO_COPY");
     bool pin[3] = {false, false, false};
@@ -323,16 +335,8 @@ int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *
     const size_t blk = hi - lo;
     if (!blk) return EOC_OK;
     HIP_TRY(hipSetDevice(s.device));
-    const size_t need = n_wires * blk * stride_ints;
-    if (need > s.cap_wire_ints) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(s.d_wires);
-        s.d_wires = nullptr;
-        s.cap_wire_ints = 0;
-        HIP_TRY(hipMalloc(&s.d_wires, need * 4));
-        s.cap_wire_ints = need;
-        s.grows++;
-    }
+    int rc = slot_grow(s, &s.d_wires, 1, &s.cap_wire_ints, n_wires * blk * stride_ints);
+    if (rc) return rc;
     hipStream_t st = s.st[0];
     // Only the wires that matter cross PCIe: host -> device the wires some gate READS BEFORE any gate has written them
     // (the circuit's inputs), device -> host the wires some gate WRITES; a wire nobody touches keeps the caller's bytes
@@ -367,63 +371,39 @@ int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *
         }
         return EOC_OK;
     };
-    int rc = copy_runs(live_in, true);
+    rc = copy_runs(live_in, true);
     if (rc == EOC_OK) rc = eoc_circuit_run_device(s.e, gates, n_gates, s.d_wires, n_wires, blk, st);
     if (rc == EOC_OK) rc = copy_runs(written, false);
-    if (rc) {
-        (void)hipStreamSynchronize(st); // no copy may outlive the call
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return EOC_OK;
+    return slot_finish(st, rc);
 }
 
 // one device's block [lo, hi) of a table-lookup batch: in [count][stride], out [n_luts][count][stride] on the host; n_tables
 // > 0: many-LUT lookups (eoc_lut_many_batch_device), out [n_luts][n_tables][count][stride]
 int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in, int32_t *out, size_t count, size_t lo,
-                   size_t hi, size_t stride_ints, int n_tables = 0)
+                   size_t hi, size_t stride_ints, int n_tables)
 {
     const size_t blk = hi - lo;
     if (!blk) return EOC_OK;
     HIP_TRY(hipSetDevice(s.device));
     const size_t n_out = n_luts * (size_t)std::max(1, n_tables);
     const size_t tv_ints = n_luts * EOC_N, need = tv_ints + (1 + n_out) * blk * stride_ints;
-    if (need > s.cap_lut_ints) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(s.d_lut);
-        s.d_lut = nullptr;
-        s.cap_lut_ints = 0;
-        HIP_TRY(hipMalloc(&s.d_lut, need * 4));
-        s.cap_lut_ints = need;
-        s.grows++;
-    }
+    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    if (rc) return rc;
     int32_t *d_tv = s.d_lut, *d_in = d_tv + tv_ints, *d_out = d_in + blk * stride_ints;
     hipStream_t st = s.st[0];
     const size_t row_bytes = stride_ints * 4;
-    int rc = EOC_OK;
-    auto copies = [&]() -> int {
+    auto run = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_tv, tv, tv_ints * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_in, in + lo * stride_ints, blk * row_bytes, hipMemcpyHostToDevice, st));
+        int r = n_tables ? eoc_lut_many_batch_device(s.e, n_tables, d_tv, n_luts, d_in, d_out, blk, st)
+                         : eoc_lut_batch_device(s.e, d_tv, n_luts, d_in, d_out, blk, st);
+        if (r) return r;
+        // table t's block lands at rows [t count + lo, t count + hi) of the caller's array
+        HIP_TRY(hipMemcpy2DAsync(out + lo * stride_ints, count * row_bytes, d_out, blk * row_bytes, blk * row_bytes, n_out,
+                                 hipMemcpyDeviceToHost, st));
         return EOC_OK;
     };
-    rc = copies();
-    if (rc == EOC_OK)
-        rc = n_tables ? eoc_lut_many_batch_device(s.e, n_tables, d_tv, n_luts, d_in, d_out, blk, st)
-                      : eoc_lut_batch_device(s.e, d_tv, n_luts, d_in, d_out, blk, st);
-    if (rc == EOC_OK) { // table t's block lands at rows [t count + lo, t count + hi) of the caller's array
-        hipError_t e = hipMemcpy2DAsync(out + lo * stride_ints, count * row_bytes, d_out, blk * row_bytes, blk * row_bytes, n_out,
-                                        hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            eoc_set_error("hipMemcpy2DAsync failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-            rc = EOC_ERR_HIP;
-        }
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(st); // no copy may outlive the call
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return EOC_OK;
+    return slot_finish(st, run());
 }
 
 // one device's block [lo, hi) of a compact-list expansion: lists [ceil(count / N)][2][N], out [count][stride] on the host.
@@ -435,33 +415,18 @@ int slot_compact_block(Slot &s, const int32_t *lists, int32_t *out, size_t lo, s
     HIP_TRY(hipSetDevice(s.device));
     const size_t l0 = lo / EOC_N, l1 = (hi - 1) / EOC_N + 1;
     const size_t list_ints = (l1 - l0) * 2 * EOC_N, need = list_ints + blk * stride_ints;
-    if (need > s.cap_lut_ints) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(s.d_lut);
-        s.d_lut = nullptr;
-        s.cap_lut_ints = 0;
-        HIP_TRY(hipMalloc(&s.d_lut, need * 4));
-        s.cap_lut_ints = need;
-        s.grows++;
-    }
+    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    if (rc) return rc;
     int32_t *d_lists = s.d_lut, *d_out = d_lists + list_ints;
     hipStream_t st = s.st[0];
-    int rc = EOC_OK;
-    hipError_t e = hipMemcpyAsync(d_lists, lists + l0 * 2 * EOC_N, list_ints * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        rc = eoc_compact_expand_device_from(s.e, d_lists, lo - l0 * EOC_N, blk, d_out, st);
-        if (rc == EOC_OK) e = hipMemcpyAsync(out + lo * stride_ints, d_out, blk * stride_ints * 4, hipMemcpyDeviceToHost, st);
-    }
-    if (e != hipSuccess) {
-        eoc_set_error("hipMemcpyAsync failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-        rc = EOC_ERR_HIP;
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(st); // no copy may outlive the call
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return EOC_OK;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_lists, lists + l0 * 2 * EOC_N, list_ints * 4, hipMemcpyHostToDevice, st));
+        int r = eoc_compact_expand_device_from(s.e, d_lists, lo - l0 * EOC_N, blk, d_out, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(out + lo * stride_ints, d_out, blk * stride_ints * 4, hipMemcpyDeviceToHost, st));
+        return EOC_OK;
+    };
+    return slot_finish(st, run());
 }
 
 void destroy_slots_locked()
@@ -1093,54 +1058,31 @@ extern "C" int eoc_gate_batch(int op, const uint8_t *ops, const int32_t *in0, co
     });
 }
 
-extern "C" int eoc_lut_batch(int p, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out, size_t count)
+// eoc_lut_batch (n_tables = 0) and eoc_lut_many_batch (`many`): they differ in how table rows become a test polynomial
+static int lut_batch(const char *who, bool many, int p, int n_tables, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out,
+                     size_t count)
 {
     std::lock_guard<std::mutex> g(G.mu);
     if (G.slots.empty()) {
-        eoc_set_error("eoc_lut_batch: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        eoc_set_error("%s: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback", who);
         return EOC_ERR_NO_DEVICE;
     }
     if (!tables || !in || !out || n_luts == 0) {
-        eoc_set_error("eoc_lut_batch: null argument or no table");
+        eoc_set_error("%s: null argument or no table", who);
         return EOC_ERR_ARG;
     }
     std::vector<int32_t> tv(n_luts * EOC_N);
-    for (size_t t = 0; t < n_luts; t++)
-        if (eoc_lut_test_polynomial(p, tables + t * (size_t)p, tv.data() + t * EOC_N) != EOC_OK) {
-            eoc_set_error("eoc_lut_batch: message space p = %d is not one of 2, 4, 8", p);
+    for (size_t t = 0; t < n_luts; t++) {
+        int32_t *poly = tv.data() + t * EOC_N;
+        if (!many && eoc_lut_test_polynomial(p, tables + t * (size_t)p, poly) != EOC_OK) {
+            eoc_set_error("%s: message space p = %d is not one of 2, 4, 8", who, p);
             return EOC_ERR_ARG;
         }
-    if (!count) return EOC_OK;
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
-    const size_t stride = (size_t)G.p.n + 1;
-    const int32_t *tvp = tv.data();
-    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
-        return slot_lut_block(G.slots[i], tvp, n_luts, in, out, count, lo, hi, stride);
-    });
-}
-
-extern "C" int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out,
-                                  size_t count)
-{
-    std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_lut_many_batch: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
-    if (!tables || !in || !out || n_luts == 0) {
-        eoc_set_error("eoc_lut_many_batch: null argument or no table");
-        return EOC_ERR_ARG;
-    }
-    std::vector<int32_t> tv(n_luts * EOC_N);
-    for (size_t t = 0; t < n_luts; t++)
-        if (eoc_lut_many_test_polynomial(p, n_tables, tables + t * (size_t)n_tables * p, tv.data() + t * EOC_N) != EOC_OK) {
-            eoc_set_error("eoc_lut_many_batch: (p, n_tables) = (%d, %d) is not supported (p, T in {2, 4, 8}, p T <= 16)", p,
-                          n_tables);
+        if (many && eoc_lut_many_test_polynomial(p, n_tables, tables + t * (size_t)n_tables * p, poly) != EOC_OK) {
+            eoc_set_error("%s: (p, n_tables) = (%d, %d) is not supported (p, T in {2, 4, 8}, p T <= 16)", who, p, n_tables);
             return EOC_ERR_ARG;
         }
+    }
     if (!count) return EOC_OK;
     {
         int rc = drain_async_locked();
@@ -1151,6 +1093,15 @@ extern "C" int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, si
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
         return slot_lut_block(G.slots[i], tvp, n_luts, in, out, count, lo, hi, stride, n_tables);
     });
+}
+extern "C" int eoc_lut_batch(int p, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out, size_t count)
+{
+    return lut_batch("eoc_lut_batch", false, p, 0, tables, n_luts, in, out, count);
+}
+extern "C" int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out,
+                                  size_t count)
+{
+    return lut_batch("eoc_lut_many_batch", true, p, n_tables, tables, n_luts, in, out, count);
 }
 
 // eoc_compact_expand's engine half (host.cpp holds the global key's lock and has brought the engines up)

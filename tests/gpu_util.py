@@ -23,7 +23,7 @@ def sync():
 
 
 def br_segments(jobs, resident):
-    """first job of every launch segment a pair-kernel blind rotation of `jobs` is cut into (launch_blind_rotate): as few
+    """first job of every launch segment a pair-kernel blind rotation of `jobs` is cut into (plan_blind_rotate, the plan launch_blind_rotate runs): as few
     even slices as fit the resident set, e.g. 1 030 jobs at 1 024 -> 515 + 515.  Set B runs each segment as two launches."""
     nsl = -(-jobs // resident)
     return list(range(0, jobs, -(-jobs // nsl)))
