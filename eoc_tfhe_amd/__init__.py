@@ -167,6 +167,7 @@ def lib():
         "eoc_engine_workspace_grows": (u64, [vp]),
         "eoc_engine_blind_rotate_launches": (u64, [vp]),
         "eoc_engine_blind_rotate_wide_launches": (u64, [vp]),
+        "eoc_engine_keyswitch_mfma_launches": (u64, [vp]),
         "eoc_engine_resident_jobs": (C.c_size_t, [vp]),
         "eoc_engine_device": (C.c_int, [vp]),
         "eoc_engine_params": (PP, [vp]),
@@ -661,7 +662,8 @@ class Engine:
         _check(self.L.eoc_engine_stats(self.h, C.byref(out)), "eoc_engine_stats")
         return dict(batches=out[0], bootstraps=out[1], keyswitches=out[2],
                     br_launches=int(self.L.eoc_engine_blind_rotate_launches(self.h)),
-                    br_wide_launches=int(self.L.eoc_engine_blind_rotate_wide_launches(self.h)))
+                    br_wide_launches=int(self.L.eoc_engine_blind_rotate_wide_launches(self.h)),
+                    ks_mfma_launches=int(self.L.eoc_engine_keyswitch_mfma_launches(self.h)))
 
 
 def circuit_bootstraps(gates):

@@ -41,6 +41,10 @@ struct eoc_engine {
     bool own_keys = false;
     const double *bkfft = nullptr; // in use (owned or adopted)
     const int32_t *ksk = nullptr;
+    // the key-switch key once more, as signed byte limbs in k_keyswitch_mfma's operand order (kernels.hip.h): always the
+    // engine's own, derived from `ksk` whenever a key is installed, never on the launch path
+    void *d_ksl = nullptr;
+    bool ksl_ready = false;
     // workspace: device buffers AND a pinned host ring for the gate descriptors / opcode permutations that every launch
     // sends ahead of its kernels: nothing on the launch path reads pageable memory asynchronously, allocates or
     // synchronises once the workspace has its size (eoc_engine_reserve).  One set per engine: all kernels of an engine
@@ -79,10 +83,12 @@ struct eoc_engine {
     int br_wide = -1;                       // one-wave-per-ciphertext kernel: -1 = by launch width, 0 = never, 1 = whenever l = 2 (EOC_TFHE_BR_WIDE)
     int bara_stride = 0;
     bool ks_waves_ok = true;                // the > 64 KiB dynamic-LDS attribute of k_keyswitch_waves was granted
+    int ks_mfma = -1;                       // matrix-core key switch: -1 = by launch width, 0 = never, 1 = whenever basebit 2, t 8 (EOC_TFHE_KS_MFMA)
     uint64_t stats[3] = {0, 0, 0};
     uint64_t ws_grows = 0; // times a workspace had to grow inside a call (0 after eoc_engine_reserve)
     uint64_t br_launches = 0; // k_blind_rotate kernel launches (a wide level is several, a cut blind rotation too)
     uint64_t br_wide_launches = 0; // ... of which k_blind_rotate_wide
+    uint64_t ks_mfma_launches = 0; // k_keyswitch_mfma launches (key switches that ran on the matrix cores)
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
     struct Span { hipEvent_t a, b; int kind; };
@@ -250,6 +256,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
         if (const char *s = getenv("EOC_TFHE_SCALAR_ABAR")) e->scalar_abar = atoi(s) != 0;
         if (const char *s = getenv("EOC_TFHE_BR_PARTS")) e->br_parts = atoi(s);
         if (const char *s = getenv("EOC_TFHE_BR_WIDE")) e->br_wide = atoi(s);
+        if (const char *s = getenv("EOC_TFHE_KS_MFMA")) e->ks_mfma = atoi(s) != 0;
     }
     // the key-switch kernel uses > 64 KiB of dynamic LDS: raise the limit once, here, not on the launch path
     // (a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to k_keyswitch_generic: slow, exact)
@@ -295,6 +302,7 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
         hipFree(e->d_bkfft);
         hipFree(e->d_ksk);
     }
+    hipFree(e->d_ksl);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -499,6 +507,23 @@ static int build_cloud_key_images(eoc_engine *e, const int32_t *bk, const int32_
     return EOC_OK;
 }
 
+// The limb image of the key-switch key that has just been installed as e->ksk (basebit 2, t 8 only: the shapes
+// k_keyswitch_mfma serves).  The source image must be complete: the device is drained first (a borrowed or adopted image
+// may have been filled by a copy or a broadcast on any stream) and again behind the NULL-stream kernel, so that a
+// non-blocking caller stream cannot see a half-written image.  Allocated here, at key install, once per engine.
+static int install_ks_limbs(eoc_engine *e)
+{
+    e->ksl_ready = false;
+    if (e->p.ks_basebit != 2 || e->p.ks_t != 8 || e->ks_mfma == 0) return EOC_OK;
+    if (!e->d_ksl) HIP_TRY(hipMalloc(&e->d_ksl, ks_limb_bytes((int)e->n1p)));
+    HIP_TRY(hipDeviceSynchronize());
+    ks_limbs_launch(e->ksk, e->d_ksl, (int)e->n1p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    e->ksl_ready = true;
+    return EOC_OK;
+}
+
 extern "C" int eoc_engine_load_cloud_key(eoc_engine *e, const int32_t *bk, const int32_t *ksk)
 {
     if (!e || !bk || !ksk) return EOC_ERR_ARG;
@@ -513,7 +538,7 @@ extern "C" int eoc_engine_load_cloud_key(eoc_engine *e, const int32_t *bk, const
     if (rc) return rc;
     e->bkfft = e->d_bkfft;
     e->ksk = e->d_ksk;
-    return EOC_OK;
+    return install_ks_limbs(e);
 }
 
 // same, into caller-owned device buffers (which the engine then uses); lets the host keep the
@@ -528,16 +553,17 @@ extern "C" int eoc_engine_build_cloud_key_device(eoc_engine *e, const int32_t *b
     if (rc) return rc;
     e->bkfft = static_cast<const double *>(d_bkfft);
     e->ksk = static_cast<const int32_t *>(d_ksk);
-    return EOC_OK;
+    return install_ks_limbs(e);
 }
 
 extern "C" int eoc_engine_set_cloud_key_device(eoc_engine *e, const void *d_bkfft, const void *d_ksk)
 {
     if (!e || !d_bkfft || !d_ksk) return EOC_ERR_ARG;
     std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
     e->bkfft = static_cast<const double *>(d_bkfft);
     e->ksk = static_cast<const int32_t *>(d_ksk);
-    return EOC_OK;
+    return install_ks_limbs(e);
 }
 // take ownership of device images the engine's allocator produced (eoc_device_alloc): used for key replicas
 extern "C" int eoc_engine_adopt_cloud_key_device(eoc_engine *e, void *d_bkfft, void *d_ksk)
@@ -554,7 +580,7 @@ extern "C" int eoc_engine_adopt_cloud_key_device(eoc_engine *e, void *d_bkfft, v
     e->own_keys = true;
     e->bkfft = e->d_bkfft;
     e->ksk = e->d_ksk;
-    return EOC_OK;
+    return install_ks_limbs(e);
 }
 extern "C" int eoc_engine_cloud_key_device(eoc_engine *e, const void **d_bkfft, const void **d_ksk)
 {
@@ -724,6 +750,7 @@ static int launch_blind_rotate(eoc_engine *e, WS &W, const BRWork &w, hipStream_
     return EOC_OK;
 }
 
+constexpr uint32_t kKsMfmaMinS = 1;
 static int launch_keyswitch(eoc_engine *e, WS &W, const GateDesc *d_descs, uint32_t ngates, uint32_t S, hipStream_t st,
                             bool init_done, const GateDesc *inline_desc)
 {
@@ -758,7 +785,14 @@ static int launch_keyswitch(eoc_engine *e, WS &W, const GateDesc *d_descs, uint3
     // basebit 2, t 8 (both default sets): waves per workgroup x indices per wave chosen so that 1024 gates give every SIMD
     // its 3-4 waves: 4096 waves for n1p = 256 / 512 / 1024, 3072 (three 4-wave workgroups per CU) for n1p = 768
     const bool fast = bb == 2 && t == 8 && e->ks_waves_ok;
-    if (fast && ncb == 4) EOC_KS_LAUNCH(8, 8, 16);
+    // the matrix-core form from kKsMfmaMinS ciphertexts per gate group on (profiles/r08_ks_mfma_ab.txt: the sweep over S);
+    // EOC_TFHE_KS_MFMA = 0 | 1 forces either form.  The results are the same words either way.
+    const bool mfma = bb == 2 && t == 8 && e->ksl_ready && (e->ks_mfma == 1 || (e->ks_mfma < 0 && S >= kKsMfmaMinS));
+    if (mfma) {
+        ks_mfma_launch(ks_mfma_plan(S, (int)e->n1p), ngates, d_descs, a, e->d_ksl, st);
+        e->ks_mfma_launches++;
+    }
+    else if (fast && ncb == 4) EOC_KS_LAUNCH(8, 8, 16);
     else if (fast && ncb == 8) EOC_KS_LAUNCH(8, 8, 32);
     else if (fast && ncb == 12) EOC_KS_LAUNCH(8, 4, 64);
     else if (fast && ncb == 16) EOC_KS_LAUNCH(8, 8, 64);
@@ -1475,6 +1509,7 @@ extern "C" int eoc_engine_stats(eoc_engine *e, uint64_t out[3])
 extern "C" uint64_t eoc_engine_workspace_grows(eoc_engine *e) { return e ? e->ws_grows : 0; }
 extern "C" uint64_t eoc_engine_blind_rotate_launches(eoc_engine *e) { return e ? e->br_launches : 0; }
 extern "C" uint64_t eoc_engine_blind_rotate_wide_launches(eoc_engine *e) { return e ? e->br_wide_launches : 0; }
+extern "C" uint64_t eoc_engine_keyswitch_mfma_launches(eoc_engine *e) { return e ? e->ks_mfma_launches : 0; }
 extern "C" size_t eoc_engine_resident_jobs(eoc_engine *e)
 {
     if (!e) return 0;

@@ -903,6 +903,8 @@ __global__ __launch_bounds__(64 * kBRWideJobsPerWG, 2) void k_lut_many_wide(BRAr
 //   k_keyswitch_waves   basebit 2, even t: 64 ciphertexts per workgroup (one per lane), two digits per LDS look-up
 //                  through a table of row sums, partial sums of the i-slices through LDS and a few integer atomics
 //   k_keyswitch_generic any other (basebit, t): the plain one-thread-per-output-word form
+//   k_keyswitch_mfma    basebit 2, t 8 (both default sets; what launch_keyswitch takes): the same sum as four int8 matrix
+//                  products on the matrix cores, from the limb image k_ksk_limbs derives at key install
 // KSK device image: [N*t][base-1][n1p], rows padded with zeros to n1p (multiple of 256).
 // =================================================================================================
 constexpr int KS_GT = 64; // ciphertexts per workgroup (one per lane)
@@ -1154,6 +1156,191 @@ __global__ __launch_bounds__(256) void k_keyswitch_generic(const GateDesc *__res
         }
         o[m] = (int32_t)acc;
     }
+}
+
+// ---- k_keyswitch_mfma<NWV>: basebit 2, t 8 (both default sets) on the matrix cores --------------------------------
+// The key switch is the one dense contraction of the path:  out[c][col] = b[c] - sum_k OneHot[c][k] * KSK[k][col],
+// k = (i, j, d), an integer matrix product mod 2^32.  With every key word split into four signed byte limbs,
+//   l_0 = ((v + 128) & 255) - 128,  v <- (v - l_0) >> 8,  ...      v == l_0 + l_1 2^8 + l_2 2^16 + l_3 2^24  (mod 2^32),
+// it is four int8 products with int32 accumulators (at most kN t = 8192 terms of magnitude <= 128: |acc| <= 2^20), and
+//   out = b - (acc_0 + (acc_1 << 8) + (acc_2 << 16) + (acc_3 << 24))   in wrapping 32-bit arithmetic
+// equals the row sums of k_keyswitch_waves word for word: integers, so neither the order of the terms nor the way the
+// partial sums of the K-slices meet (integer atomics, as above) can change a bit.
+//   * K order: k = (i t + j) 4 + d with an all-zero d = 0 slot, so one (i, j) group is one dword of an operand fragment and
+//     one v_mfma_i32_32x32x32_i8 (K = 32) is exactly one index i.  Lane l = (h = l >> 5, r = l & 31) holds 16 bytes of A
+//     (row r) and of B (column r): its slot (h, byte 4 q + d) is digit j = 4 h + q, value d, in BOTH operands.  The
+//     instruction pairs A's and B's bytes of equal (h, byte), so the product does not depend on which k the hardware
+//     calls such a slot (tools/ubench_ks_mfma.hip compares every output word with k_keyswitch_waves).
+//   * A is never stored: a lane reads its ciphertext's operand word ubar[job][i] and forms the one-hot dword of digit j
+//     as 1 << (8 d), three vector instructions.
+//   * B is the limb image built by k_ksk_limbs at key install: [i][column tile of 32][limb][lane][16 B], so that a
+//     fragment is one 16-byte load per lane, 1 KiB contiguous per wave, and the 4 fragments (limbs) of a (tile, i) 4 KiB.
+//   * Workgroup = NWV waves stacked along M (64 ciphertexts each: 2 x 4 tiles of 32 x 32, A reused over the four limbs, B over
+//     the two row tiles) x one column tile x one slice of the indices i.  The B fragments of 4 indices (16 KiB) are staged
+//     per step through LDS (two buffers, one barrier per step; the global loads of step s + 1 fly during step s), each
+//     fragment feeding 2 NWV MFMAs.  The four limbs of a column sit at the same lane of four accumulator tiles (C/D: col =
+//     lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 h), so the recombination is in-lane.
+// grid: x = mtiles * (n1p / 32) * nsl, y = gates; block = 64 NWV.  nsl divides kN / 4.
+typedef int i16 __attribute__((ext_vector_type(16)));
+constexpr int KSM_KI = 4; // indices i per staged step (one 16-byte read of a ciphertext's operand row)
+
+template <int NWV>
+__global__ __launch_bounds__(64 * NWV, 2) void k_keyswitch_mfma(const GateDesc *__restrict__ descs, KSArgs A,
+                                                                 const i4 *__restrict__ limbs, int nsl)
+{
+    constexpr int MT = 64 * NWV;                 // ciphertexts per workgroup
+    constexpr int CHUNKS = KSM_KI * 4;           // 1 KiB fragments per step
+    constexpr int NLD = CHUNKS / NWV;            // ... of which each wave fetches this many
+    static_assert(CHUNKS % NWV == 0, "shape");
+    __shared__ i4 s_b[2][CHUNKS * 64];
+
+    const GateDesc d = A.inline_desc ? A.desc0 : descs[blockIdx.y];
+    const uint32_t ntiles = (A.S + MT - 1) / MT, nct = (uint32_t)A.n1p / 32u;
+    const uint32_t tile = blockIdx.x % ntiles, rest = blockIdx.x / ntiles;
+    const uint32_t ct = rest % nct, slice = rest / nct;
+    const int per = kN / nsl, nstage = per / KSM_KI;
+    const int ibeg = (int)slice * per;
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t row0 = tile * MT + (uint32_t)w * 64u;
+
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const u4 *ubp[2];
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+        const uint32_t s = row0 + 32u * m + r;
+        const uint32_t job = d.job_base + (s < A.S ? s : A.S - 1);
+        ubp[m] = reinterpret_cast<const u4 *>(A.ubar + (size_t)job * kN + ibeg);
+    }
+    // chunk c = ki * 4 + limb of step st: limbs[((ibeg + 4 st + ki) nct + ct) 256 + limb 64 + lane]
+    const i4 *bsrc = limbs + ((size_t)ibeg * nct + ct) * 256 + lane;
+    i4 stg[NLD];
+    auto stage_load = [&](int st) {
+#pragma unroll
+        for (int x = 0; x < NLD; x++) {
+            const int c = w + NWV * x;
+            stg[x] = bsrc[((size_t)(st * KSM_KI + (c >> 2)) * nct) * 256 + (c & 3) * 64];
+        }
+    };
+    auto stage_store = [&](int buf) {
+#pragma unroll
+        for (int x = 0; x < NLD; x++) s_b[buf][(w + NWV * x) * 64 + lane] = stg[x];
+    };
+
+    i16 acc[2][4];
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int q = 0; q < 16; q++) acc[m][k][q] = 0;
+
+    stage_load(0);
+    u4 ubc[2] = {ubp[0][0], ubp[1][0]};
+    stage_store(0);
+    stage_load(nstage > 1 ? 1 : 0);
+    __syncthreads();
+    const int sh0 = 27 - 8 * h; // digit j = 4 h + q sits at bits 31 - 2 j, 30 - 2 j: 8 d = (ub >> (27 - 2 j)) & 24
+#pragma unroll 1
+    for (int st = 0; st < nstage; st++) {
+        const int buf = st & 1;
+        const int stn = st + 1 < nstage ? st + 1 : st;
+        const u4 ubn[2] = {ubp[0][stn], ubp[1][stn]};
+#pragma unroll
+        for (int ki = 0; ki < KSM_KI; ki++) {
+            i4 b[4], a[2];
+#pragma unroll
+            for (int k = 0; k < 4; k++) b[k] = s_b[buf][(ki * 4 + k) * 64 + lane];
+#pragma unroll
+            for (int m = 0; m < 2; m++) {
+                const uint32_t ub = ubc[m][ki];
+#pragma unroll
+                for (int q = 0; q < 4; q++) a[m][q] = (int)(1u << ((ub >> (sh0 - 2 * q)) & 24u));
+            }
+#pragma unroll
+            for (int m = 0; m < 2; m++)
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    acc[m][k] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[m], b[k], acc[m][k], 0, 0, 0);
+        }
+        // unconditional (the last steps re-load the last one and store it where nobody reads): the number of loads in
+        // flight is then the same on every path and the waits stay counted instead of draining the fresh loads
+        stage_store(buf ^ 1); // (its readers of step st - 1 are behind the last barrier)
+        stage_load(st + 2 < nstage ? st + 2 : nstage - 1);
+        __syncthreads();
+        ubc[0] = ubn[0];
+        ubc[1] = ubn[1];
+    }
+
+    // out -= acc_0 + (acc_1 << 8) + (acc_2 << 16) + (acc_3 << 24); an atomic instruction covers two rows of 32 columns
+    const int col = (int)ct * 32 + r;
+    if (col <= A.n) {
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int q = 0; q < 16; q++) {
+                const uint32_t s = row0 + 32u * m + (uint32_t)((q & 3) + 8 * (q >> 2) + 4 * h);
+                const uint32_t v = (uint32_t)acc[m][0][q] + ((uint32_t)acc[m][1][q] << 8) + ((uint32_t)acc[m][2][q] << 16) +
+                                   ((uint32_t)acc[m][3][q] << 24);
+                if (v != 0 && s < A.S) atomicAdd(d.out + (size_t)s * (A.n + 1) + col, (int)(0u - v));
+            }
+    }
+}
+
+// The limb image of a [kN 8][3][n1p] key image (basebit 2, t 8): one thread per dword = one (i, j) group of one column
+// and limb, bytes d = 0 (zero), 1, 2, 3.  grid: kN * (n1p / 32) * 4 workgroups of 256 (one 1 KiB fragment each)
+__global__ __launch_bounds__(256) void k_ksk_limbs(const int32_t *__restrict__ ksk, uint32_t *__restrict__ limbs, int n1p)
+{
+    const uint32_t nct = (uint32_t)n1p / 32u;
+    const uint32_t limb = blockIdx.x & 3u, ct = (blockIdx.x >> 2) % nct, i = (blockIdx.x >> 2) / nct;
+    const int q = threadIdx.x & 3, lane = threadIdx.x >> 2, r = lane & 31, h = lane >> 5;
+    const int j = 4 * h + q;
+    const int32_t *row = ksk + ((size_t)i * 8 + j) * 3 * n1p + ct * 32 + r;
+    uint32_t o = 0;
+#pragma unroll
+    for (int dg = 1; dg <= 3; dg++) {
+        int32_t v = row[(size_t)(dg - 1) * n1p];
+        int32_t l = 0;
+        for (uint32_t k = 0; k <= limb; k++) {
+            l = (int32_t)(((uint32_t)v + 128u) & 255u) - 128;
+            v = (int32_t)((uint32_t)v - (uint32_t)l) >> 8;
+        }
+        o |= ((uint32_t)l & 255u) << (8 * dg);
+    }
+    limbs[(size_t)blockIdx.x * 256 + threadIdx.x] = o;
+}
+
+static inline size_t ks_limb_bytes(int n1p) { return (size_t)kN * (size_t)(n1p / 32) * 4096; }
+static inline void ks_limbs_launch(const int32_t *ksk, void *limbs, int n1p, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_ksk_limbs, dim3((unsigned)(kN * (n1p / 32) * 4)), dim3(256), 0, st, ksk,
+                       static_cast<uint32_t *>(limbs), n1p);
+}
+
+// Waves per workgroup and K-slices of a k_keyswitch_mfma launch over `S` ciphertexts per gate: enough slices that one gate
+// group gives every SIMD its two waves (2048 waves), at least 8 staged steps per slice.
+struct KSMPlan {
+    int nwv, nsl;
+    unsigned gx;
+};
+static inline KSMPlan ks_mfma_plan(uint32_t S, int n1p)
+{
+    KSMPlan p;
+    p.nwv = 4;
+    const unsigned ntiles = (S + 64 * p.nwv - 1) / (64 * p.nwv), nct = (unsigned)n1p / 32u;
+    p.nsl = 1;
+    while (p.nsl < 32 && ntiles * nct * p.nsl * p.nwv < 2048u) p.nsl *= 2;
+    p.gx = ntiles * nct * (unsigned)p.nsl;
+    return p;
+}
+static inline void ks_mfma_launch(const KSMPlan &pl, uint32_t ngates, const GateDesc *descs, const KSArgs &a,
+                                  const void *limbs, hipStream_t st)
+{
+    const i4 *lp = static_cast<const i4 *>(limbs);
+    if (pl.nwv == 8)
+        hipLaunchKernelGGL(k_keyswitch_mfma<8>, dim3(pl.gx, ngates), dim3(512), 0, st, descs, a, lp, pl.nsl);
+    else
+        hipLaunchKernelGGL(k_keyswitch_mfma<4>, dim3(pl.gx, ngates), dim3(256), 0, st, descs, a, lp, pl.nsl);
 }
 
 // =================================================================================================

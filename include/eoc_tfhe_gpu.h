@@ -191,7 +191,9 @@ int eoc_engine_load_cloud_key(eoc_engine *e, const int32_t *bk, const int32_t *k
 int eoc_engine_build_cloud_key_device(eoc_engine *e, const int32_t *bk, const int32_t *ksk,
                                       void *d_bkfft, void *d_ksk);
 /* adopt caller-owned device images (e.g. buffers filled by an RCCL broadcast); not freed by the
- * engine; must stay valid while the engine uses them */
+ * engine; must stay valid while the engine uses them.  The images must be COMPLETE when they are installed (here and in
+ * eoc_engine_adopt_cloud_key_device): the engine derives its own int8-limb image of the key-switch key from d_ksk in this
+ * call (it drains the device first) and does not look at d_ksk's later changes until a key is installed again. */
 int eoc_engine_set_cloud_key_device(eoc_engine *e, const void *d_bkfft, const void *d_ksk);
 /* take OWNERSHIP of device images allocated with eoc_device_alloc on this engine (key replicas filled by a
  * broadcast or a peer copy); the engine frees them */
@@ -233,6 +235,9 @@ uint64_t eoc_engine_blind_rotate_launches(eoc_engine *e);
  * runs as full wide launches of 8 x CUs (2 048) and a remainder, which runs wide when it exceeds 4 x CUs and on the pair
  * kernel otherwise; a level of at most 4 x CUs runs on the pair kernel */
 uint64_t eoc_engine_blind_rotate_wide_launches(eoc_engine *e);
+/* key-switch launches that ran on the matrix cores (k_keyswitch_mfma: basebit 2, t 8, i.e. both default sets; exact int8-limb
+ * products, the same words as the look-up kernel -- tests/test_gpu_ks_mfma.py).  EOC_TFHE_KS_MFMA=0|1 forces either form. */
+uint64_t eoc_engine_keyswitch_mfma_launches(eoc_engine *e);
 /* blind rotations that fill the device in ONE launch: 8 x compute units where the one-wave-per-ciphertext kernel applies
  * (gadget length 2), 4 x otherwise.  A host that cuts a long job into pieces should cut at multiples of this (the
  * host-buffer batch path does). */
