@@ -1,6 +1,7 @@
 // Body of k_blind_rotate / k_blind_rotate_tv / k_lut_many (kernels.hip.h), included into each.  In scope: template
 // parameters L, BGBIT, SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test polynomials, used
-// when TV); constexpr bool MANY; n_tables (interleaved tables per test polynomial, extracted when MANY).
+// when TV); constexpr bool MANY; n_tables (interleaved tables per test polynomial, extracted when MANY); constexpr bool
+// TLDS (gadget length 2 in its earlier form: tables read from LDS in the step loop, whole key rows requested per step).
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     d2 *s_tw = reinterpret_cast<d2 *>(smem);
     d2 *s_twist = s_tw + kTwEntries;
@@ -19,7 +20,10 @@
     typedef const __attribute__((address_space(4))) uint32_t *cu32p;
     unsigned long long bara_addr = (unsigned long long)(uintptr_t)(A.bara + (size_t)job * A.bara_stride);
 
-    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128);
+    // gadget length 2 keeps every loop-invariant table value in registers (below) and needs no table in LDS; TLDS selects
+    // the earlier form, which reads three of the five sets from LDS in every step (EOC_TFHE_BR_TABLES_LDS=1)
+    constexpr bool kResAll = L == 2 && !TLDS;
+    if constexpr (!kResAll) load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128);
     if (A.prep && A.step_begin == 0) { // folded k_prepare: this workgroup's row of rotation amounts
         const uint32_t gjob = A.job0 + job, g = gjob / A.ks_S;
         prepare_row(A.inline_desc ? A.desc0 : A.ks_descs[g], gjob - g * A.ks_S, A.n, A.bara + (size_t)job * A.bara_stride, tid, 128);
@@ -93,10 +97,20 @@
     // gadget length 2 has registers to spare: the forward transform's last four twiddles stay resident
     constexpr bool kResT2 = L == 2;
     d2 res_t2[4];
-    if constexpr (kResT2) tw_load(res_t2, s_tw + kTwF2 + lane, 64);
+    if constexpr (kResAll) tw_load(res_t2, g_tw + kTwF2 + lane, 64);
+    else if constexpr (kResT2) tw_load(res_t2, s_tw + kTwF2 + lane, 64);
     constexpr bool kResT1 = L == 2; // ... and the inverse transform's first table pass
     d2 res_t1[4];
-    if constexpr (kResT1) tw_load(res_t1, s_tw + kTwI1 + (lane & 7), 8);
+    if constexpr (kResAll) tw_load(res_t1, g_tw + kTwI1 + (lane & 7), 8);
+    else if constexpr (kResT1) tw_load(res_t1, s_tw + kTwI1 + (lane & 7), 8);
+    // kResAll: the forward pair's first table pass, the inverse's last one and the eight un-twist factors as well
+    d2 res_f1[4], res_i0[4], ut[8];
+    if constexpr (kResAll) {
+        tw_load(res_f1, g_tw + kTwF1 + (lane >> 3), 8);
+        tw_load(res_i0, g_tw + kTwI0 + lane, 64);
+#pragma unroll
+        for (int r = 0; r < 8; r++) ut[r] = g_twist[lane + 64 * r];
+    }
     int abar_next = load_abar(A.step_begin);
     for (int i = A.step_begin; i < A.step_end; i++) {
         EOC_STAMP(15);
@@ -137,7 +151,6 @@
             for (int r = 0; r < 8; r++)
                 b[r] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(bk_rsrc, lane * 16, (int)(row_off + r * 1024), 0));
         };
-        d2 ra[8], rb[8];
         uint32_t dlo[8], dhi[8];
         {
             const int s = abar & 63;
@@ -192,50 +205,112 @@
         // forward transforms of the l digits (two at a time, skewed on the one scratch; an odd last one alone) and
         // the chain for the partner's output polynomial.  The spectra stay in registers for the own chain below.
         d2 xs[L][8], S[8];
-#pragma unroll
-        for (int p0 = 0; p0 + 1 < L; p0 += 2) {
-            load_row(p0 + 1, 1 - h, ra);
-            load_row(p0 + 2, 1 - h, rb);
-            make_x0(p0 + 1, xs[p0]);
+        if constexpr (kResAll) {
+            // The key rows are streamed through the two chains bin block by bin block (block b < 8: rows (p = 1, 2) of the
+            // partner's output polynomial at bins r = b; b >= 8: the own ones at r = b - 8), kRowAhead blocks requested ahead
+            // of the one in use, so that no whole row is ever live next to both spectra and the resident tables.  Per bin
+            // the terms arrive in the canonical order and in mac's nesting.  The scheduling barriers pin the requests: the
+            // scheduler otherwise hoists all of them to the top.
+            constexpr int kRowAhead = 3;
+            const uint32_t step_off = (uint32_t)((((size_t)i * KPL + h * L) * 2) * kNH * 16);
+            d2 q[16][2];
+            auto issue = [&](int b) __attribute__((always_inline)) {
+                const uint32_t off = step_off + (uint32_t)((b < 8 ? 1 - h : h) * kNH * 16 + (b & 7) * 1024);
+                q[b][0] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(bk_rsrc, lane * 16, (int)off, 0));
+                q[b][1] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(bk_rsrc, lane * 16, (int)(off + 2 * kNH * 16), 0));
+            };
+            auto mac1 = [](d2 x, d2 b, d2 a) __attribute__((always_inline)) {
+                d2 o;
+                o.x = EOC_FMA(-x.y, b.y, EOC_FMA(x.x, b.x, a.x));
+                o.y = EOC_FMA(x.y, b.x, EOC_FMA(x.x, b.y, a.y));
+                return o;
+            };
+            make_x0(1, xs[0]);
             EOC_STAMP(1);
-            fft_fwd_rest_x2(xs[p0], xs[p0 + 1], [&]() __attribute__((always_inline)) { make_x0(p0 + 2, xs[p0 + 1]); },
-                            s_tw, scr, lane, kResT2 ? &res_t2 : nullptr);
-            EOC_STAMP(2);
-            mac(p0 == 0, xs[p0], ra, S);
-            mac(false, xs[p0 + 1], rb, S);
-            EOC_STAMP(3);
-        }
-        if constexpr ((L & 1) != 0) {
-            load_row(L, 1 - h, ra);
-            make_x0(L, xs[L - 1]);
-            EOC_STAMP(1);
-            fft_fwd_rest(xs[L - 1], s_tw, scr, lane);
-            EOC_STAMP(2);
-            mac(L == 1, xs[L - 1], ra, S);
-            EOC_STAMP(3);
-        }
-        // own rows: the first two are requested before the exchange (requesting the first one a register pass
-        // earlier into a third buffer, or the second one only after the exchange, changes nothing: measured)
-        load_row(1, h, ra);
-        if constexpr (L >= 2) load_row(2, h, rb);
+            fft_fwd_rest_x2(xs[0], xs[1], [&]() __attribute__((always_inline)) { make_x0(2, xs[1]); }, s_tw, scr, lane, &res_t2,
+                            &res_f1, [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int r = 0; r < 8; r++) scr[r * 64 + lane] = S[r];
-        EOC_STAMP(4);
-        __syncthreads();
-        EOC_STAMP(5);
+                                for (int b = 0; b < kRowAhead; b++) issue(b);
+                            });
+            EOC_STAMP(2);
+            EOC_SB();
 #pragma unroll
-        for (int r = 0; r < 8; r++) S[r] = scr_partner[r * 64 + lane]; // the chain of the other input polynomial
-        mac(false, xs[0], ra, S);
-        if constexpr (L >= 3) load_row(3, h, ra);
-        if constexpr (L >= 2) mac(false, xs[1], rb, S);
-        if constexpr (L >= 4) load_row(4, h, rb);
-        if constexpr (L >= 3) mac(false, xs[2], ra, S);
-        if constexpr (L >= 4) mac(false, xs[3], rb, S);
-        EOC_STAMP(6);
-        __syncthreads(); // the partner has read this wave's scratch before the inverse transform overwrites it
-        EOC_STAMP(7);
-        d2 ut[8];
-        fft_inv_wave(S, ut, s_tw, s_twist, scr, lane, kResT1 ? &res_t1 : nullptr);
+            for (int r = 0; r < 8; r++) { // the partner's chain: each bin block leaves for the scratch as it completes
+                d2 s;
+                s.x = EOC_FMA(-xs[0][r].y, q[r][0].y, xs[0][r].x * q[r][0].x);
+                s.y = EOC_FMA(xs[0][r].y, q[r][0].x, xs[0][r].x * q[r][0].y);
+                s = mac1(xs[1][r], q[r][1], s);
+                scr[r * 64 + lane] = s;
+                EOC_SB();
+                issue(r + kRowAhead); // from r = 8 - kRowAhead on: own rows, in flight across the barrier
+                EOC_SB();
+            }
+            EOC_STAMP(4);
+            __syncthreads();
+            EOC_STAMP(5);
+            constexpr int kChainAhead = 2; // blocks of the partner's chain read ahead of the one in use
+#pragma unroll
+            for (int r = 0; r < kChainAhead; r++) S[r] = scr_partner[r * 64 + lane];
+            EOC_SB();
+#pragma unroll
+            for (int r = 0; r < 8; r++) { // the chain of the other input polynomial, continued with the own digits
+                S[r] = mac1(xs[0][r], q[8 + r][0], S[r]);
+                S[r] = mac1(xs[1][r], q[8 + r][1], S[r]);
+                EOC_SB();
+                if (r + kChainAhead < 8) S[r + kChainAhead] = scr_partner[(r + kChainAhead) * 64 + lane];
+                if (8 + r + kRowAhead < 16) issue(8 + r + kRowAhead);
+                EOC_SB();
+            }
+            EOC_STAMP(6);
+            __syncthreads(); // the partner has read this wave's scratch before the inverse transform overwrites it
+            EOC_STAMP(7);
+            fft_inv_wave<true>(S, ut, s_tw, s_twist, scr, lane, &res_t1, &res_i0);
+        } else {
+            d2 ra[8], rb[8];
+#pragma unroll
+            for (int p0 = 0; p0 + 1 < L; p0 += 2) {
+                load_row(p0 + 1, 1 - h, ra);
+                load_row(p0 + 2, 1 - h, rb);
+                make_x0(p0 + 1, xs[p0]);
+                EOC_STAMP(1);
+                fft_fwd_rest_x2(xs[p0], xs[p0 + 1], [&]() __attribute__((always_inline)) { make_x0(p0 + 2, xs[p0 + 1]); },
+                                s_tw, scr, lane, kResT2 ? &res_t2 : nullptr);
+                EOC_STAMP(2);
+                mac(p0 == 0, xs[p0], ra, S);
+                mac(false, xs[p0 + 1], rb, S);
+                EOC_STAMP(3);
+            }
+            if constexpr ((L & 1) != 0) {
+                load_row(L, 1 - h, ra);
+                make_x0(L, xs[L - 1]);
+                EOC_STAMP(1);
+                fft_fwd_rest(xs[L - 1], s_tw, scr, lane);
+                EOC_STAMP(2);
+                mac(L == 1, xs[L - 1], ra, S);
+                EOC_STAMP(3);
+            }
+            // own rows: the first two are requested before the exchange (requesting the first one a register pass
+            // earlier into a third buffer, or the second one only after the exchange, changes nothing: measured)
+            load_row(1, h, ra);
+            if constexpr (L >= 2) load_row(2, h, rb);
+#pragma unroll
+            for (int r = 0; r < 8; r++) scr[r * 64 + lane] = S[r];
+            EOC_STAMP(4);
+            __syncthreads();
+            EOC_STAMP(5);
+#pragma unroll
+            for (int r = 0; r < 8; r++) S[r] = scr_partner[r * 64 + lane]; // the chain of the other input polynomial
+            mac(false, xs[0], ra, S);
+            if constexpr (L >= 3) load_row(3, h, ra);
+            if constexpr (L >= 2) mac(false, xs[1], rb, S);
+            if constexpr (L >= 4) load_row(4, h, rb);
+            if constexpr (L >= 3) mac(false, xs[2], ra, S);
+            if constexpr (L >= 4) mac(false, xs[3], rb, S);
+            EOC_STAMP(6);
+            __syncthreads(); // the partner has read this wave's scratch before the inverse transform overwrites it
+            EOC_STAMP(7);
+            fft_inv_wave(S, ut, s_tw, s_twist, scr, lane, kResT1 ? &res_t1 : nullptr);
+        }
         EOC_STAMP(8);
 #pragma unroll
         for (int r = 0; r < 8; r++) {

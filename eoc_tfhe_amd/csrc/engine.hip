@@ -83,6 +83,7 @@ struct eoc_engine {
     int br_wide = -1;                       // one-wave-per-ciphertext kernel: -1 = by launch width, 0 = never, 1 = whenever l = 2 (EOC_TFHE_BR_WIDE)
     int bara_stride = 0;
     bool ks_waves_ok = true;                // the > 64 KiB dynamic-LDS attribute of k_keyswitch_waves was granted
+    bool br_tables_lds = false;             // EOC_TFHE_BR_TABLES_LDS: gadget length 2 on the pair kernels' earlier form (tables read from LDS in the step loop)
     int ks_mfma = -1;                       // matrix-core key switch: -1 = by launch width, 0 = never, 1 = whenever basebit 2, t 8 (EOC_TFHE_KS_MFMA)
     uint64_t stats[3] = {0, 0, 0};
     uint64_t ws_grows = 0; // times a workspace had to grow inside a call (0 after eoc_engine_reserve)
@@ -257,6 +258,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
         if (const char *s = getenv("EOC_TFHE_BR_PARTS")) e->br_parts = atoi(s);
         if (const char *s = getenv("EOC_TFHE_BR_WIDE")) e->br_wide = atoi(s);
         if (const char *s = getenv("EOC_TFHE_KS_MFMA")) e->ks_mfma = atoi(s) != 0;
+        if (const char *s = getenv("EOC_TFHE_BR_TABLES_LDS")) e->br_tables_lds = atoi(s) != 0;
     }
     // the key-switch kernel uses > 64 KiB of dynamic LDS: raise the limit once, here, not on the launch path
     // (a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to k_keyswitch_generic: slow, exact)
@@ -690,13 +692,22 @@ static BRArgs blind_rotate_args(const eoc_engine *e, const WS &W, const BRWork &
 
 // THE KERNEL: the instance for (shape, gadget, family, read-back form).  Exactly these are instantiated: six pair and two
 // wide shapes, each as gate / _tv / many-LUT kernel, each with the rotation amounts read back by vector loads or
-// (sabar, EOC_TFHE_SCALAR_ABAR=1) by scalar loads.
+// (sabar, EOC_TFHE_SCALAR_ABAR=1) by scalar loads; and the two pair shapes of gadget length 2 a second time in their
+// earlier form (tables_lds, EOC_TFHE_BR_TABLES_LDS=1: kernels.hip.h, k_br_lds*).
 template <int L, int BGBIT> static const void *br_pair_kernel(BRWork::Seed seed, bool sabar)
 {
     switch (seed) {
     case BRWork::GATE: return sabar ? (const void *)&k_blind_rotate<L, BGBIT, true> : (const void *)&k_blind_rotate<L, BGBIT, false>;
     case BRWork::TV: return sabar ? (const void *)&k_blind_rotate_tv<L, BGBIT, true> : (const void *)&k_blind_rotate_tv<L, BGBIT, false>;
     default: return sabar ? (const void *)&k_lut_many<L, BGBIT, true> : (const void *)&k_lut_many<L, BGBIT, false>;
+    }
+}
+template <int L, int BGBIT> static const void *br_pair_lds_kernel(BRWork::Seed seed, bool sabar)
+{
+    switch (seed) {
+    case BRWork::GATE: return sabar ? (const void *)&k_br_lds<L, BGBIT, true> : (const void *)&k_br_lds<L, BGBIT, false>;
+    case BRWork::TV: return sabar ? (const void *)&k_br_lds_tv<L, BGBIT, true> : (const void *)&k_br_lds_tv<L, BGBIT, false>;
+    default: return sabar ? (const void *)&k_br_lds_many<L, BGBIT, true> : (const void *)&k_br_lds_many<L, BGBIT, false>;
     }
 }
 template <int BGBIT> static const void *br_wide_kernel(BRWork::Seed seed, bool sabar)
@@ -708,14 +719,15 @@ template <int BGBIT> static const void *br_wide_kernel(BRWork::Seed seed, bool s
     }
 }
 struct BRKernel { const void *fn; dim3 grid, block; unsigned lds; }; // fn == nullptr: no kernel for this gadget length
-static BRKernel blind_rotate_kernel(bool wide, int l, int Bgbit, bool sabar, BRWork::Seed seed, uint32_t njobs)
+static BRKernel blind_rotate_kernel(bool wide, int l, int Bgbit, bool sabar, bool tables_lds, BRWork::Seed seed, uint32_t njobs)
 {
     if (wide) {
         const void *fn = Bgbit == 10 ? br_wide_kernel<10>(seed, sabar) : br_wide_kernel<0>(seed, sabar); // 10: Set A
         return {fn, dim3((njobs + kBRWideJobsPerWG - 1) / kBRWideJobsPerWG), dim3(64 * kBRWideJobsPerWG), kBRWideLds};
     }
     const void *fn = nullptr;
-    if (l == 2 && Bgbit == 10) fn = br_pair_kernel<2, 10>(seed, sabar); // Set A
+    if (l == 2 && tables_lds) fn = Bgbit == 10 ? br_pair_lds_kernel<2, 10>(seed, sabar) : br_pair_lds_kernel<2, 0>(seed, sabar);
+    else if (l == 2 && Bgbit == 10) fn = br_pair_kernel<2, 10>(seed, sabar); // Set A
     else if (l == 3 && Bgbit == 7) fn = br_pair_kernel<3, 7>(seed, sabar); // Set B
     else if (l == 1) fn = br_pair_kernel<1, 0>(seed, sabar);
     else if (l == 2) fn = br_pair_kernel<2, 0>(seed, sabar);
@@ -736,7 +748,7 @@ static int launch_blind_rotate(eoc_engine *e, WS &W, const BRWork &w, hipStream_
     SpanGuard span(e, st, KIND_BLIND_ROTATE);
     const BRPlan plan = plan_blind_rotate(w.njobs, e->num_cus, e->p.l, e->kpl, e->p.n, e->br_slice, e->br_parts, e->br_wide);
     for (const BRSeg &sg : plan.segs) {
-        const BRKernel k = blind_rotate_kernel(sg.wide, e->p.l, e->p.Bgbit, e->scalar_abar, w.seed, sg.njobs);
+        const BRKernel k = blind_rotate_kernel(sg.wide, e->p.l, e->p.Bgbit, e->scalar_abar, e->br_tables_lds, w.seed, sg.njobs);
         if (!k.fn) return EOC_ERR_ARG;
         for (int part = 0; part < plan.parts; part++) {
             BRArgs a = blind_rotate_args(e, W, w, sg, part, plan.parts);

@@ -225,20 +225,32 @@ __device__ __forceinline__ void fft_fwd_rest(d2 (&x)[8], const d2 *tw, d2 *scr, 
 #define EOC_M_VALU 0x002
 #define EOC_M_DSR 0x100
 #define EOC_M_DSW 0x200
-// T2 != nullptr: the last pass's four twiddles are resident in registers (loop-invariant, kept by the caller)
-template <class MakeB>
+// T2 != nullptr: the last pass's four twiddles are resident in registers (loop-invariant, kept by the caller);
+// T1 != nullptr: the first table pass's too, and the pair then reads no table at all.
+// before_last() runs between the last transpose and b's last register pass, pinned there: the caller's first key-row
+// requests, which then fly under that pass
+struct FwdNoHook {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <class MakeB, class BeforeLast = FwdNoHook>
 __device__ __forceinline__ void fft_fwd_rest_x2(d2 (&xa)[8], d2 (&xb)[8], MakeB make_b, const d2 *tw, d2 *scr, int lane,
-                                                const d2 (*T2)[4] = nullptr)
+                                                const d2 (*T2)[4] = nullptr, const d2 (*T1)[4] = nullptr,
+                                                BeforeLast before_last = BeforeLast())
 {
     d2 t1[4], t2[4];
     EOC_SB();
     // region B: first pass of b, a's stores spread through it; then a's reads
-    tw_load(t1, tw + kTwF1 + (lane >> 3), 8);
+    if (T1) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) t1[k] = (*T1)[k];
+    } else {
+        tw_load(t1, tw + kTwF1 + (lane >> 3), 8);
+    }
     wave_lds_fence();
     t01_write(xa, scr, lane);
     make_b();
     t01_read(xa, scr, lane);
-    EOC_SGB(EOC_M_DSR, 4);
+    if (!T1) EOC_SGB(EOC_M_DSR, 4);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         EOC_SGB(EOC_M_DSW, 1);
@@ -291,6 +303,10 @@ __device__ __forceinline__ void fft_fwd_rest_x2(d2 (&xa)[8], d2 (&xb)[8], MakeB 
     EOC_SGB(EOC_M_DSR, 8);
     EOC_SGB(EOC_M_VALU, 40);
     EOC_SB();
+    if constexpr (!std::is_same<BeforeLast, FwdNoHook>::value) {
+        before_last();
+        EOC_SB();
+    }
     fwd_pass12(xb, t2);
 }
 
@@ -344,8 +360,11 @@ __device__ __forceinline__ void t10_read(d2 (&x)[8], const d2 *scr, int lane)
 // under the first transpose, so that no table read sits between a transpose read and its use.  The eight stores of each
 // transpose leave in the order the last stage of the register pass completes its butterflies -- (0,4) (1,5) (2,6) (3,7) --
 // and are spread through that stage (sched_group_barrier), as the forward pair does
+// T1 != nullptr: the first table pass's four twiddles are resident in registers.  RESIDENT: so are the last pass's (*T0)
+// and the eight un-twist factors, which `ut` then already holds, and the transform reads no table at all
+template <bool RESIDENT = false>
 __device__ __forceinline__ void fft_inv_wave(d2 (&x)[8], d2 (&ut)[8], const d2 *tw, const d2 *s_twist, d2 *scr, int lane,
-                                             const d2 (*T1)[4] = nullptr)
+                                             const d2 (*T1)[4] = nullptr, const d2 (*T0)[4] = nullptr)
 {
     d2 t1[4], t0[4];
     EOC_SB();
@@ -369,9 +388,14 @@ __device__ __forceinline__ void fft_inv_wave(d2 (&x)[8], d2 (&ut)[8], const d2 *
     EOC_SGB(EOC_M_VALU, 4);  EOC_SGB(EOC_M_DSW, 2);              // (2,6): w = conj(i)
     EOC_SGB(EOC_M_VALU, 6);  EOC_SGB(EOC_M_DSW, 2);              // (3,7)
     EOC_SGB(EOC_M_DSR, 8);
-    tw_load(t0, tw + kTwI0 + lane, 64);
+    if constexpr (RESIDENT) {
 #pragma unroll
-    for (int r = 0; r < 8; r++) ut[r] = s_twist[lane + 64 * r];
+        for (int k = 0; k < 4; k++) t0[k] = (*T0)[k];
+    } else {
+        tw_load(t0, tw + kTwI0 + lane, 64);
+#pragma unroll
+        for (int r = 0; r < 8; r++) ut[r] = s_twist[lane + 64 * r];
+    }
     wave_lds_fence();
     EOC_SB();
     inv_pass10(x, t1);
@@ -698,7 +722,8 @@ struct BRArgs {
     int32_t *acc_state;         // [jobs][2][N], only used when the range is a proper part of [0, n)
 };
 
-// LDS: the two tables + one 9 KB scratch per wave.  The accumulator lives in registers (racc[16]); the scratch holds it
+// LDS: the two tables (not loaded by the gadget-length-2 instances, which keep their values in registers; the layout and
+// the four workgroups per CU are the same for all) + one 9 KB scratch per wave.  The accumulator lives in registers (racc[16]); the scratch holds it
 // as a signed 2N-periodic image ext[k] = ACC[k], ext[k + N] = -ACC[k] (8 KB) only for the sample extraction after the
 // last step, which reads it by index.
 // (X^abar - 1) * ACC without an accumulator image: coefficient lane + 64 r of ACC lives in racc[r];
@@ -729,8 +754,11 @@ constexpr int kAbarLds = 2048;                                  // one job's rot
 constexpr int kBRLds = (kTwEntries + kNH + 2 * kScr) * 16 + kAbarLds; // 37 632 bytes: four workgroups per CU
 
 // BGBIT > 0: gadget base known at compile time (digit extraction becomes one bit-field extract); 0: run time.
-// Register budget (hipcc 7.2, -Rpass-analysis=kernel-resource-usage): <2,10> 250 VGPRs, <3,7> 256, <1> 162, <2> 254, <3> 256,
-// none of them spills.  Gadget length 4 (no default parameter set uses it) is a SLOW CORRECTNESS PATH: four live spectra
+// Register budget (hipcc 7.2, -Rpass-analysis=kernel-resource-usage): <2,10> 252 VGPRs, <3,7> 256, <1> 162, <2> 256, <3> 256,
+// none of them spills.  Gadget length 2 holds ALL loop-invariant table values in registers (96: four twiddle sets and the
+// eight un-twist factors) and reads no table in the step loop; what pays for them is that no whole key row is ever live
+// there: the rows are streamed through the chains bin block by bin block, three blocks (24 registers) ahead, and the
+// partner's chain leaves for the scratch block by block (blind_rotate_pair.inc).  Its earlier form is k_br_lds* below.  Gadget length 4 (no default parameter set uses it) is a SLOW CORRECTNESS PATH: four live spectra
 // exceed the 256 registers of a wave at two waves per SIMD, its kernel spills (324 VGPRs to scratch) and runs several
 // times slower per transform; it is bit-exact (tests/test_gpu_parity.py) and nothing else is claimed for it.
 
@@ -743,7 +771,7 @@ template <int L, int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(128, 2) void k_blind_rotate(BRArgs A, const d2 *__restrict__ g_tw,
                                                          const d2 *__restrict__ g_twist)
 {
-    constexpr bool TV = false, MANY = false;
+    constexpr bool TV = false, MANY = false, TLDS = false;
     const int32_t *const tv = nullptr;
     const uint32_t tv_rows = 1, n_tables = 1;
 #include "blind_rotate_pair.inc"
@@ -755,7 +783,7 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_tv(BRArgs A, const d2 *
                                                             const d2 *__restrict__ g_twist, const int32_t *__restrict__ tv,
                                                             uint32_t tv_rows)
 {
-    constexpr bool TV = true, MANY = false;
+    constexpr bool TV = true, MANY = false, TLDS = false;
     const uint32_t n_tables = 1;
 #include "blind_rotate_pair.inc"
 }
@@ -768,7 +796,35 @@ template <int L, int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(128, 2) void k_lut_many(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist,
                                                      const int32_t *__restrict__ tv, uint32_t tv_rows, uint32_t n_tables)
 {
-    constexpr bool TV = true, MANY = true;
+    constexpr bool TV = true, MANY = true, TLDS = false;
+#include "blind_rotate_pair.inc"
+}
+
+// The three families once more for gadget length 2 in their EARLIER form (TLDS: three of the five loop-invariant table
+// sets are read from LDS in every step, whole key rows are requested at the top of the step), kept for comparisons inside
+// one build: EOC_TFHE_BR_TABLES_LDS=1 selects them.  The names avoid "k_blind_rotate" and "k_lut_many": the ISA tests
+// count the kernels of those names.
+template <int L, int BGBIT = 0, bool SABAR = false>
+__global__ __launch_bounds__(128, 2) void k_br_lds(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist)
+{
+    constexpr bool TV = false, MANY = false, TLDS = true;
+    const int32_t *const tv = nullptr;
+    const uint32_t tv_rows = 1, n_tables = 1;
+#include "blind_rotate_pair.inc"
+}
+template <int L, int BGBIT = 0, bool SABAR = false>
+__global__ __launch_bounds__(128, 2) void k_br_lds_tv(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist,
+                                                      const int32_t *__restrict__ tv, uint32_t tv_rows)
+{
+    constexpr bool TV = true, MANY = false, TLDS = true;
+    const uint32_t n_tables = 1;
+#include "blind_rotate_pair.inc"
+}
+template <int L, int BGBIT = 0, bool SABAR = false>
+__global__ __launch_bounds__(128, 2) void k_br_lds_many(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist,
+                                                        const int32_t *__restrict__ tv, uint32_t tv_rows, uint32_t n_tables)
+{
+    constexpr bool TV = true, MANY = true, TLDS = true;
 #include "blind_rotate_pair.inc"
 }
 
