@@ -41,6 +41,19 @@ class Gate(C.Structure):
                 ("out", C.c_int32)]
 
 
+class INode(C.Structure):
+    """eoc_inode: a node of an integer netlist (include/eoc_tfhe_gpu.h)."""
+    _fields_ = [("n_tables", C.c_int32), ("out", C.c_int32), ("tv", C.c_int32), ("n_terms", C.c_int32),
+                ("in_", C.c_int32 * 4), ("w", C.c_int32 * 4), ("cst", C.c_int32)]
+
+
+def _inode_array(nodes):
+    arr = (INode * max(1, len(nodes)))()
+    for k, q in enumerate(nodes):
+        C.memmove(C.byref(arr[k]), C.byref(q), C.sizeof(INode))
+    return arr
+
+
 _lib = None
 
 
@@ -140,6 +153,9 @@ def lib():
         "eoc_lut_many_test_polynomial": (C.c_int, [C.c_int, C.c_int, vp, vp]),
         "eoc_lut_many_batch_device": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, sz, vp]),
         "eoc_lut_many_batch": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp, sz]),
+        "eoc_int_netlist_levels": (C.c_int64, [vp, sz, sz, sz, vp, vp]),
+        "eoc_int_circuit_run_device": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, sz, vp]),
+        "eoc_int_circuit_run": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, sz, sz]),
         "eoc_global_encrypt_ints": (C.c_int, [C.c_int, vp, sz, vp]),
         "eoc_global_decrypt_ints": (C.c_int, [C.c_int, vp, sz, vp]),
         "eoc_engine_stats": (C.c_int, [vp, C.POINTER(u64 * 3)]),
@@ -647,6 +663,13 @@ class Engine:
         _check(self.L.eoc_lut_many_batch_device(self.h, int(n_tables), d_tv, n_luts, d_in, d_out, count, stream),
                "eoc_lut_many_batch_device")
 
+    def int_circuit_run_device(self, nodes, d_tv, n_tv, d_wires, n_wires, instances, stream=None):
+        """Integer circuit (eoc_int_circuit_run_device): nodes = list of INode (IntCircuit.nodes()), d_tv
+        [n_tv][N] test polynomials, d_wires [n_wires][instances][n+1]; one blind rotation per (level, T) group of nodes."""
+        arr = _inode_array(nodes)
+        _check(self.L.eoc_int_circuit_run_device(self.h, C.addressof(arr), len(nodes), d_tv, n_tv, d_wires, n_wires,
+                                                 instances, stream), "eoc_int_circuit_run_device")
+
     def compact_expand_device(self, d_lists, count, d_out, stream=None):
         """Compact lists -> LWE samples (eoc_compact_expand_device): d_lists [ceil(count / N)][2][N] (PublicKey.encrypt_*),
         d_out [count][n+1]; slot extraction and the key switch, with the key-switch key alone"""
@@ -694,6 +717,19 @@ def netlist_levels(gates):
     if n < 0:
         raise EocError(f"eoc_netlist_levels failed ({n})")
     return list(lev[:len(gates)]), int(n), int(depth.value)
+
+
+def int_netlist_levels(nodes, n_wires, n_tv):
+    """eoc_int_netlist_levels: (level of every node, number of bootstrap levels, blind rotations per instance).  A free
+    node's level is the one in whose pre-pass it runs.  Raises EocError for a malformed netlist."""
+    arr = _inode_array(nodes)
+    lev = (C.c_int32 * max(1, len(nodes)))()
+    boots = C.c_int64(0)
+    n = lib().eoc_int_netlist_levels(C.addressof(arr), len(nodes), int(n_wires), int(n_tv), C.addressof(lev), C.addressof(boots))
+    if n < 0:
+        msg = lib().eoc_last_error()
+        raise EocError(f"eoc_int_netlist_levels failed ({n}): {msg.decode() if msg else ''}")
+    return list(lev[:len(nodes)]), int(n), int(boots.value)
 
 
 def netlist_cost(gates, instances, resident_jobs=0):
@@ -874,6 +910,24 @@ def lut_many_batch(p, tables, cts):
     _check(lib().eoc_lut_many_batch(int(p), T, tables.ctypes.data, n_luts, cts.ctypes.data, out.ctypes.data, cts.shape[0]),
            "eoc_lut_many_batch")
     return out
+
+
+def int_circuit_run(nodes, tables, wires, instances=None):
+    """eoc_int_circuit_run on the global context: nodes = list of INode, tables = one entry per test polynomial, each
+    [T][p] (or [p] for one table) of Torus32 output values, wires [n_wires][instances][n+1] with the input wires' rows filled
+    in.  Returns the array with every written wire's rows filled in (a copy when `wires` is not contiguous int32)."""
+    wires = np.ascontiguousarray(wires, np.int32)
+    if wires.ndim != 3:
+        raise EocError("int_circuit_run: wires is a 3-d array [n_wires][instances][n+1]")
+    entries = [np.atleast_2d(np.asarray(t, np.int32)) for t in tables]
+    flat = np.ascontiguousarray(np.concatenate([t.ravel() for t in entries]) if entries else np.zeros(1, np.int32), np.int32)
+    ps = np.array([t.shape[1] for t in entries] or [0], np.int32)
+    Ts = np.array([t.shape[0] for t in entries] or [0], np.int32)
+    arr = _inode_array(nodes)
+    _check(lib().eoc_int_circuit_run(C.addressof(arr), len(nodes), flat.ctypes.data, ps.ctypes.data, Ts.ctypes.data,
+                                     len(entries), wires.ctypes.data, wires.shape[0],
+                                     wires.shape[1] if instances is None else int(instances)), "eoc_int_circuit_run")
+    return wires
 
 
 def compact_expand(lists, count=None):
@@ -1269,3 +1323,6 @@ class Circuit:
             global_circuit_run(gates, wires, instances)
         return Tfhe._strings([wires[w] for w in outs]) if instances == 1 else [wires[w] for w in outs]
 
+
+
+from .int_circuits import IntCircuit, bit_function2, radix_add, radix_less_than  # noqa: E402,F401

@@ -81,6 +81,7 @@ struct eoc_engine {
     bool no_pool = false;                   // EOC_TFHE_NO_POOL: every opcode run of a mixed batch is a level of its own
     int br_parts = 0;                       // consecutive launches per blind rotation (EOC_TFHE_BR_PARTS); 0 = by key-row size
     int br_wide = -1;                       // one-wave-per-ciphertext kernel: -1 = by launch width, 0 = never, 1 = whenever l = 2 (EOC_TFHE_BR_WIDE)
+    int int_slice_rows = 0;                 // EOC_TFHE_INT_SLICE_ROWS: at most this many rows per slice of an integer circuit (diagnostics; 0 = the 2^20-sample rule alone)
     int bara_stride = 0;
     bool ks_waves_ok = true;                // the > 64 KiB dynamic-LDS attribute of k_keyswitch_waves was granted
     bool br_tables_lds = false;             // EOC_TFHE_BR_TABLES_LDS: gadget length 2 on the pair kernels' earlier form (tables read from LDS in the step loop)
@@ -259,6 +260,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
         if (const char *s = getenv("EOC_TFHE_BR_WIDE")) e->br_wide = atoi(s);
         if (const char *s = getenv("EOC_TFHE_KS_MFMA")) e->ks_mfma = atoi(s) != 0;
         if (const char *s = getenv("EOC_TFHE_BR_TABLES_LDS")) e->br_tables_lds = atoi(s) != 0;
+        if (const char *s = getenv("EOC_TFHE_INT_SLICE_ROWS")) e->int_slice_rows = atoi(s);
     }
     // the key-switch kernel uses > 64 KiB of dynamic LDS: raise the limit once, here, not on the launch path
     // (a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to k_keyswitch_generic: slow, exact)
@@ -894,6 +896,33 @@ static void launch_prepare(eoc_engine *e, WS &W, const GateDesc *dd, uint32_t cn
     else hipLaunchKernelGGL(k_prepare, grid, dim3(256), 0, st, dd, n, S, W.d_bara, e->bara_stride);
 }
 
+// Integer circuits: LinDesc arrays travel in the descriptor ring, two slots each (same pinned copy, same wrap rules)
+static int push_lin_descs(WS &W, const LinDesc *src, size_t count, hipStream_t st, LinDesc **d_out)
+{
+    GateDesc *dd = nullptr;
+    int rc = push_descs(W, reinterpret_cast<const GateDesc *>(src), 2 * count, st, &dd);
+    *d_out = reinterpret_cast<LinDesc *>(dd);
+    return rc;
+}
+// the linear stages of `cnt` nodes over `rows` rows: rotation amounts (boot) or the free nodes' output rows
+static void launch_lin(eoc_engine *e, WS &W, const LinDesc *dd, uint32_t cnt, uint32_t rows, int terms, bool boot, hipStream_t st)
+{
+    const int n = e->p.n;
+    const dim3 grid(rows, (unsigned)((n + 1 + 255) / 256), cnt);
+#define EOC_LIN_LAUNCH(MAXT)                                                                                         \
+    do {                                                                                                             \
+        if (boot) hipLaunchKernelGGL((k_lin_modswitch<MAXT, true>), grid, dim3(256), 0, st, dd, n, W.d_bara, e->bara_stride);  \
+        else hipLaunchKernelGGL((k_lin_modswitch<MAXT, false>), grid, dim3(256), 0, st, dd, n, W.d_bara, e->bara_stride);      \
+    } while (0)
+    switch (terms) {
+    case 1: EOC_LIN_LAUNCH(1); break;
+    case 2: EOC_LIN_LAUNCH(2); break;
+    case 3: EOC_LIN_LAUNCH(3); break;
+    default: EOC_LIN_LAUNCH(4); break;
+    }
+#undef EOC_LIN_LAUNCH
+}
+
 // One bootstrap level: descriptors -> rotation amounts -> ONE blind rotation -> key switch(es) -> stats.  The callers say
 // what differs; ring_mark stays with them, once per call, behind everything the call pushed (free gates included).
 struct DescRange { uint32_t first, count, S; bool mux; }; // descriptors [first, first + count) of the level, S rows each
@@ -905,15 +934,32 @@ struct Level {
     // br.fold == KS_AND_PREP), and one key switch per range (its set-up folded when br.fold != NONE)
     const DescRange *prep = nullptr, *ks = nullptr;
     size_t nprep = 0, nks = 0;
+    // integer circuits: the rotation amounts come from the nodes' own linear stages (k_lin_modswitch over these host-side
+    // descriptors, pushed with the level's; lin_terms = the largest term count among them), not from `prep`
+    const LinDesc *lin = nullptr;
+    size_t nlin = 0;
+    int lin_terms = 1;
     BRWork br;                       // br.descs is filled in here
 };
 static int run_bootstrap(eoc_engine *e, WS &W, const Level &lv, hipStream_t st)
 {
     GateDesc *dd = nullptr;
-    int rc = lv.ndescs ? push_descs(W, lv.descs, lv.ndescs, st, &dd) : EOC_OK;
+    const LinDesc *dlin = nullptr;
+    int rc = EOC_OK;
+    if (lv.nlin) {
+        // ONE push, the LinDesc array first (8-byte alignment) and the level's descriptors behind it: a second push could wrap
+        // the ring and land on the first before the kernel that reads it is launched
+        std::vector<GateDesc> both(2 * lv.nlin + lv.ndescs);
+        memcpy(both.data(), lv.lin, lv.nlin * sizeof(LinDesc));
+        if (lv.ndescs) memcpy(both.data() + 2 * lv.nlin, lv.descs, lv.ndescs * sizeof(GateDesc));
+        rc = push_descs(W, both.data(), both.size(), st, &dd);
+        dlin = reinterpret_cast<const LinDesc *>(dd);
+        dd += 2 * lv.nlin;
+    } else if (lv.ndescs) rc = push_descs(W, lv.descs, lv.ndescs, st, &dd);
     if (rc) return rc;
     if (lv.br.fold != BRWork::KS_AND_PREP) {
         SpanGuard span(e, st, KIND_PREPARE);
+        if (lv.nlin) launch_lin(e, W, dlin, (uint32_t)lv.nlin, lv.br.tv_rows, lv.lin_terms, true, st);
         for (size_t k = 0; k < lv.nprep; k++) {
             const DescRange &r = lv.prep[k];
             launch_prepare(e, W, dd + r.first, r.count, r.S * (r.mux ? 2u : 1u), r.S, lv.theta, st);
@@ -1456,6 +1502,162 @@ extern "C" int eoc_lut_many_batch_device(eoc_engine *e, int n_tables, const int3
         return EOC_ERR_ARG;
     }
     return lut_levels(e, "eoc_lut_many_batch_device", n_tables, d_tv, n_luts, d_in, d_out, count, (hipStream_t)hip_stream);
+}
+
+// ---- integer circuits ------------------------------------------------------
+// Netlists of linear stages and table lookups.  Per slice of rows and per level: the level's free nodes (k_lin_modswitch,
+// one launch; a free node that reads a free node of the same pre-pass waits for a launch of its own), then per group of
+// nodes with equal T one Level: the nodes' linear stages and mod switch (k_lin_modswitch), ONE blind rotation over nodes x
+// rows (node g of the group = polynomial g of the staged array, tv_rows = S) and one key switch over the group's outputs.
+// A group of more than 32 768 outputs (a grid dimension) runs as several.
+extern "C" int eoc_int_circuit_run_device(eoc_engine *e, const eoc_inode *nodes, size_t n_nodes, const int32_t *d_tv, size_t n_tv,
+                                          int32_t *d_wires, size_t n_wires, size_t instances, void *hip_stream)
+try {
+    if (!e || !d_wires || (!nodes && n_nodes)) {
+        eoc_set_error("eoc_int_circuit_run_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    std::vector<int32_t> level(n_nodes, 0);
+    int64_t n_boot = 0;
+    // without polynomials (d_tv == NULL) every tv index is out of range: only free nodes pass
+    const int64_t nlev64 = eoc_int_netlist_levels(nodes, n_nodes, n_wires, d_tv ? n_tv : 0, level.data(), &n_boot);
+    if (nlev64 < 0) return (int)nlev64;
+    if (!n_nodes || !instances) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->bkfft || !e->ksk) {
+        eoc_set_error("eoc_int_circuit_run_device: no cloud key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    WS &W = e->ws;
+    const int nlev = (int)nlev64;
+    const size_t stride = (size_t)e->p.n + 1, wstride = instances * stride;
+    // free nodes per (pre-pass, rank inside it), bootstrapped nodes per (level, theta); polynomials staged in that order
+    struct Group { std::vector<uint32_t> nodes; size_t staged = 0; };
+    std::vector<std::vector<std::vector<uint32_t>>> freen(nlev + 2);
+    std::vector<Group> groups((size_t)(nlev + 1) * 4);
+    std::vector<int32_t> free_rank(n_wires, 0), free_level(n_wires, 0);
+    size_t total_slots = 0, max_slots = 0;
+    for (size_t k = 0; k < n_nodes; k++) {
+        const eoc_inode &q = nodes[k];
+        if (q.n_tables) {
+            const int theta = q.n_tables == 1 ? 0 : (q.n_tables == 2 ? 1 : (q.n_tables == 4 ? 2 : 3));
+            groups[(size_t)level[k] * 4 + theta].nodes.push_back((uint32_t)k);
+            total_slots += (size_t)q.n_tables;
+            continue;
+        }
+        int32_t rank = 0;
+        for (int a = 0; a < q.n_terms; a++)
+            if (free_level[q.in[a]] == level[k]) rank = std::max(rank, free_rank[q.in[a]]);
+        free_level[q.out] = level[k];
+        free_rank[q.out] = rank + 1;
+        auto &pre = freen[level[k]];
+        if (pre.size() <= (size_t)rank) pre.resize(rank + 1);
+        pre[rank].push_back((uint32_t)k);
+    }
+    std::vector<int32_t> tv_idx;
+    tv_idx.reserve((size_t)n_boot);
+    for (int lv = 1; lv <= nlev; lv++)
+        for (int theta = 0; theta < 4; theta++) {
+            Group &G = groups[(size_t)lv * 4 + theta];
+            G.staged = tv_idx.size();
+            for (uint32_t k : G.nodes) tv_idx.push_back(nodes[k].tv);
+            max_slots = std::max(max_slots, std::min(G.nodes.size() << theta, kMaxGatesPerLaunch));
+        }
+    // rows per slice: a group holds at most 2^20 extracted samples (the rule of lut_levels)
+    size_t rows = std::min(instances, std::max<size_t>(1, ((size_t)1 << 20) / std::max<size_t>(1, max_slots)));
+    if (e->int_slice_rows > 0) rows = std::min(rows, (size_t)e->int_slice_rows);
+    const size_t idx_slots = (tv_idx.size() * 4 + sizeof(GateDesc) - 1) / sizeof(GateDesc);
+    const size_t stage_rows = (tv_idx.size() * (size_t)kN + 4 * stride - 1) / (4 * stride);
+    int rc = ensure_ws(e, W, max_slots * rows, 2 * n_nodes + total_slots + idx_slots + 64, stage_rows, st);
+    if (rc) return rc;
+    int32_t *staged = W.d_mixed;
+    if (!tv_idx.empty()) {
+        std::vector<GateDesc> raw(idx_slots);
+        memcpy(raw.data(), tv_idx.data(), tv_idx.size() * 4);
+        GateDesc *d_idx = nullptr;
+        rc = push_descs(W, raw.data(), idx_slots, st, &d_idx);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_tv_gather, dim3((unsigned)tv_idx.size()), dim3(256), 0, st, d_tv,
+                           reinterpret_cast<const int32_t *>(d_idx), staged);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<LinDesc> lin;
+    std::vector<GateDesc> outs;
+    auto lin_desc = [&](const eoc_inode &q, size_t r0, uint32_t job_base, int theta, bool boot) {
+        LinDesc d{};
+        for (int a = 0; a < EOC_INODE_MAX_TERMS; a++) {
+            const int src = a < q.n_terms ? a : 0; // unused slots repeat term 0 with weight 0: never loaded
+            d.in[a] = d_wires + (size_t)q.in[src] * wstride + r0 * stride;
+            d.w[a] = a < q.n_terms ? q.w[a] : 0;
+        }
+        d.cst = q.cst;
+        d.job_base = job_base;
+        d.out = boot ? nullptr : d_wires + (size_t)q.out * wstride + r0 * stride;
+        d.theta = theta;
+        d.n_terms = q.n_terms;
+        return d;
+    };
+    for (size_t r0 = 0; r0 < instances; r0 += rows) {
+        const size_t S = std::min(rows, instances - r0);
+        for (int lv = 1; lv <= nlev + 1; lv++) {
+            for (const auto &pass : freen[lv])
+                for (size_t g0 = 0; g0 < pass.size(); g0 += kMaxGatesPerLaunch) {
+                    const size_t cnt = std::min(kMaxGatesPerLaunch, pass.size() - g0);
+                    int terms = 1;
+                    lin.clear();
+                    for (size_t i = 0; i < cnt; i++) {
+                        const eoc_inode &q = nodes[pass[g0 + i]];
+                        terms = std::max(terms, (int)q.n_terms);
+                        lin.push_back(lin_desc(q, r0, 0, 0, false));
+                    }
+                    LinDesc *dlin = nullptr;
+                    rc = push_lin_descs(W, lin.data(), cnt, st, &dlin);
+                    if (rc) return rc;
+                    launch_lin(e, W, dlin, (uint32_t)cnt, (uint32_t)S, terms, false, st);
+                    HIP_TRY(hipGetLastError());
+                }
+            for (int theta = 0; lv <= nlev && theta < 4; theta++) {
+                const Group &G = groups[(size_t)lv * 4 + theta];
+                const size_t T = (size_t)1 << theta, per = kMaxGatesPerLaunch >> theta;
+                for (size_t g0 = 0; g0 < G.nodes.size(); g0 += per) {
+                    const size_t cnt = std::min(per, G.nodes.size() - g0);
+                    lin.clear();
+                    outs.clear();
+                    Level L;
+                    for (size_t i = 0; i < cnt; i++) {
+                        const eoc_inode &q = nodes[G.nodes[g0 + i]];
+                        L.lin_terms = std::max(L.lin_terms, (int)q.n_terms);
+                        lin.push_back(lin_desc(q, r0, (uint32_t)(i * S), theta, true));
+                        for (size_t j = 0; j < T; j++)
+                            outs.push_back(GateDesc{OP_RAW, (uint32_t)((i * T + j) * S), nullptr, nullptr, nullptr,
+                                                    d_wires + ((size_t)q.out + j) * wstride + r0 * stride});
+                    }
+                    const DescRange slots{0, (uint32_t)(cnt * T), (uint32_t)S, false};
+                    L.lin = lin.data();
+                    L.nlin = cnt;
+                    L.descs = outs.data();
+                    L.ndescs = outs.size();
+                    L.theta = theta;
+                    L.ks = &slots;
+                    L.nks = 1;
+                    L.br.njobs = (uint32_t)(cnt * S);
+                    L.br.seed = theta ? BRWork::MANY : BRWork::TV;
+                    L.br.tv = staged + (G.staged + g0) * (size_t)kN;
+                    L.br.tv_rows = (uint32_t)S;
+                    L.br.n_tables = theta ? (uint32_t)T : 0;
+                    rc = run_bootstrap(e, W, L, st);
+                    if (rc) return rc;
+                }
+            }
+        }
+        ring_mark(W, st);
+    }
+    return EOC_OK;
+} catch (...) {
+    eoc_set_error("eoc_int_circuit_run_device: out of memory");
+    return EOC_ERR_ALLOC;
 }
 
 extern "C" int eoc_engine_set_profiling(eoc_engine *e, int on)

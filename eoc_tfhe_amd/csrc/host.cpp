@@ -1598,3 +1598,75 @@ try {
 } catch (...) {
     return EOC_ERR_ALLOC;
 }
+
+// ---- integer netlists ------------------------------------------------------
+// avail[wire] = the bootstrap level whose end makes the wire's value exist (inputs: 0; a free node's output: that of its
+// deepest operand).  A bootstrapped node sits at 1 + its deepest operand; a free node is given the level in whose pre-pass it
+// runs, 1 + its deepest operand, and costs none.
+extern "C" int64_t eoc_int_netlist_levels(const eoc_inode *nodes, size_t n_nodes, size_t n_wires, size_t n_tv,
+                                          int32_t *level_of, int64_t *bootstraps)
+try {
+    if (!nodes && n_nodes) {
+        eoc_set_error("eoc_int_netlist_levels: null netlist");
+        return EOC_ERR_ARG;
+    }
+    std::vector<int64_t> writer(n_wires, -1);
+    for (size_t k = 0; k < n_nodes; k++) {
+        const eoc_inode &q = nodes[k];
+        const int T = q.n_tables;
+        if (!(T == 0 || T == 1 || T == 2 || T == 4 || T == 8) || q.n_terms < 1 || q.n_terms > EOC_INODE_MAX_TERMS) {
+            eoc_set_error("eoc_int_netlist_levels: node %zu: n_tables = %d not one of 0, 1, 2, 4, 8 or n_terms = %d outside [1, %d]",
+                          k, T, q.n_terms, EOC_INODE_MAX_TERMS);
+            return EOC_ERR_ARG;
+        }
+        const size_t outs = T ? (size_t)T : 1;
+        if (q.out < 0 || (size_t)q.out >= n_wires || outs > n_wires - (size_t)q.out) {
+            eoc_set_error("eoc_int_netlist_levels: node %zu: output wires %d .. %zu outside [0, %zu)", k, q.out,
+                          (size_t)q.out + outs - 1, n_wires);
+            return EOC_ERR_ARG;
+        }
+        if (T && (q.tv < 0 || (size_t)q.tv >= n_tv)) {
+            eoc_set_error("eoc_int_netlist_levels: node %zu: test polynomial %d outside [0, %zu)", k, q.tv, n_tv);
+            return EOC_ERR_ARG;
+        }
+        for (int a = 0; a < q.n_terms; a++)
+            if (q.in[a] < 0 || (size_t)q.in[a] >= n_wires) {
+                eoc_set_error("eoc_int_netlist_levels: node %zu: input wire %d outside [0, %zu)", k, q.in[a], n_wires);
+                return EOC_ERR_ARG;
+            }
+        for (size_t j = 0; j < outs; j++) {
+            if (writer[q.out + j] >= 0) {
+                eoc_set_error("eoc_int_netlist_levels: wire %zu is written by nodes %lld and %zu", (size_t)q.out + j,
+                              (long long)writer[q.out + j], k);
+                return EOC_ERR_ARG;
+            }
+            writer[q.out + j] = (int64_t)k;
+        }
+    }
+    std::vector<int32_t> avail(n_wires, 0);
+    int32_t nlev = 0;
+    int64_t boots = 0;
+    for (size_t k = 0; k < n_nodes; k++) {
+        const eoc_inode &q = nodes[k];
+        int32_t deepest = 0;
+        for (int a = 0; a < q.n_terms; a++) {
+            if (writer[q.in[a]] >= (int64_t)k) {
+                eoc_set_error("eoc_int_netlist_levels: node %zu reads wire %d, which node %lld writes: not topologically ordered",
+                              k, q.in[a], (long long)writer[q.in[a]]);
+                return EOC_ERR_ARG;
+            }
+            deepest = std::max(deepest, avail[q.in[a]]);
+        }
+        if (level_of) level_of[k] = deepest + 1;
+        if (q.n_tables) {
+            for (int j = 0; j < q.n_tables; j++) avail[q.out + j] = deepest + 1;
+            nlev = std::max(nlev, deepest + 1);
+            boots++;
+        } else avail[q.out] = deepest;
+    }
+    if (bootstraps) *bootstraps = boots;
+    return nlev;
+} catch (...) {
+    eoc_set_error("eoc_int_netlist_levels: out of memory");
+    return EOC_ERR_ALLOC;
+}

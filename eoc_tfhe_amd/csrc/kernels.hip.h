@@ -588,6 +588,56 @@ __global__ __launch_bounds__(256) void k_modswitch_coarse(const GateDesc *__rest
     bara[(size_t)(d.job_base + s) * bara_stride + m] = (uint16_t)((((t + (1u << (20 + theta))) >> (21 + theta)) << theta) & 2047u);
 }
 
+// Integer circuits: the linear stage of a netlist node, t = sum_k w[k] in[k][s] + (0, ..., 0, cst) in wrapping
+// int32, over up to four operand rows -- GateDesc has no room for weights and keeps its 40 bytes, so the nodes travel as
+// descriptors of their own (two GateDesc slots of the descriptor ring each).  BOOT: the mod switch onto the 2^theta-grid
+// behind it (k_modswitch_coarse's rounding; theta = 0 is k_prepare's) -> the node's rows of rotation amounts; otherwise a
+// free node, out[s] = t.  MAXT = the largest term count among the launch's nodes: the operand loop is unrolled to it and a
+// node issues one load per term it has (the count is uniform over the workgroup).  Kernels of their own: k_prepare and
+// k_modswitch_coarse run in shipped paths and stay as they are.  grid: x = rows, y = ceil((n+1)/256), z = nodes
+struct LinDesc {
+    const int32_t *in[4]; // operand rows (row 0 of the launch's slice)
+    int32_t w[4];
+    int32_t cst;          // Torus32, added to word n (b)
+    uint32_t job_base;    // BOOT: first blind-rotate job of the node (jobs are [node][row])
+    int32_t *out;         // free node: output rows
+    int32_t theta;        // BOOT: T = 2^theta tables
+    int32_t n_terms;      // 1 .. 4
+    int32_t pad[2];
+};
+static_assert(sizeof(LinDesc) == 2 * sizeof(GateDesc), "a LinDesc takes two slots of the descriptor ring");
+template <int MAXT, bool BOOT>
+__global__ __launch_bounds__(256) void k_lin_modswitch(const LinDesc *__restrict__ descs, int n, uint16_t *__restrict__ bara,
+                                                       int bara_stride)
+{
+    const LinDesc &d = descs[blockIdx.z];
+    const uint32_t s = blockIdx.x;
+    const int m = blockIdx.y * 256 + threadIdx.x;
+    if (m > n) return;
+    const size_t off = (size_t)s * (n + 1) + m;
+    const int nt = d.n_terms;
+    uint32_t t = (uint32_t)d.w[0] * (uint32_t)d.in[0][off];
+#pragma unroll
+    for (int k = 1; k < MAXT; k++)
+        if (k < nt) t += (uint32_t)d.w[k] * (uint32_t)d.in[k][off];
+    if (m == n) t += (uint32_t)d.cst;
+    if constexpr (BOOT) {
+        const int theta = d.theta;
+        bara[(size_t)(d.job_base + s) * bara_stride + m] = (uint16_t)((((t + (1u << (20 + theta))) >> (21 + theta)) << theta) & 2047u);
+    } else d.out[off] = (int32_t)t;
+}
+
+// The _tv and many-LUT kernels map job j to polynomial (job0 + j) / rows of ONE contiguous array: the polynomials of an
+// integer circuit's nodes are copied into level order, once per call.  grid: x = nodes; idx[node] = row of `tv`
+__global__ __launch_bounds__(256) void k_tv_gather(const int32_t *__restrict__ tv, const int32_t *__restrict__ idx,
+                                                   int32_t *__restrict__ staged)
+{
+    const int32_t *src = tv + (size_t)idx[blockIdx.x] * kN;
+    int32_t *dst = staged + (size_t)blockIdx.x * kN;
+#pragma unroll
+    for (int j = 0; j < kN / 256; j++) dst[threadIdx.x + 256 * j] = src[threadIdx.x + 256 * j];
+}
+
 // The folded prologue writes the job's row of rotation amounts with vector stores; the step loop reads it back.
 // SHIPPED FORM (SABAR = false): behind the workgroup barrier the row is copied ONCE into LDS (vector loads: writer and
 // reader share the CU's vector L1 and the barrier carries a workgroup-scope release / acquire -- inside the formal memory

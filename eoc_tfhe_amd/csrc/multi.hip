@@ -406,6 +406,33 @@ int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in,
     return slot_finish(st, run());
 }
 
+// one device's block [lo, hi) of an integer circuit's instances: wires [n_wires][instances][stride] on the host, every wire's
+// rows of the block in, the netlist, every wire's rows out; tv = the nodes' test polynomials [n_tv][N] on the host
+int slot_int_block(Slot &s, const eoc_inode *nodes, size_t n_nodes, const int32_t *tv, size_t n_tv, int32_t *wires,
+                   size_t n_wires, size_t instances, size_t lo, size_t hi, size_t stride_ints)
+{
+    const size_t blk = hi - lo;
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t tv_ints = n_tv * EOC_N, need = tv_ints + n_wires * blk * stride_ints;
+    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    if (rc) return rc;
+    int32_t *d_tv = s.d_lut, *d_wires = d_tv + tv_ints;
+    hipStream_t st = s.st[0];
+    const size_t row_bytes = stride_ints * 4;
+    auto run = [&]() -> int {
+        if (tv_ints) HIP_TRY(hipMemcpyAsync(d_tv, tv, tv_ints * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(d_wires, blk * row_bytes, wires + lo * stride_ints, instances * row_bytes, blk * row_bytes,
+                                 n_wires, hipMemcpyHostToDevice, st));
+        int r = eoc_int_circuit_run_device(s.e, nodes, n_nodes, tv_ints ? d_tv : nullptr, n_tv, d_wires, n_wires, blk, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpy2DAsync(wires + lo * stride_ints, instances * row_bytes, d_wires, blk * row_bytes, blk * row_bytes,
+                                 n_wires, hipMemcpyDeviceToHost, st));
+        return EOC_OK;
+    };
+    return slot_finish(st, run());
+}
+
 // one device's block [lo, hi) of a compact-list expansion: lists [ceil(count / N)][2][N], out [count][stride] on the host.
 // Only the lists the block touches cross PCIe; the block's first sample sits at slot lo mod N of the first of them.
 int slot_compact_block(Slot &s, const int32_t *lists, int32_t *out, size_t lo, size_t hi, size_t stride_ints)
@@ -1102,6 +1129,55 @@ extern "C" int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, si
                                   size_t count)
 {
     return lut_batch("eoc_lut_many_batch", true, p, n_tables, tables, n_luts, in, out, count);
+}
+
+extern "C" int eoc_int_circuit_run(const eoc_inode *nodes, size_t n_nodes, const int32_t *tables, const int32_t *table_p,
+                                   const int32_t *table_T, size_t n_tv, int32_t *wires, size_t n_wires, size_t instances)
+try {
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_int_circuit_run: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        return EOC_ERR_NO_DEVICE;
+    }
+    if (!wires || (!nodes && n_nodes) || (n_tv && (!tables || !table_p || !table_T))) {
+        eoc_set_error("eoc_int_circuit_run: null argument");
+        return EOC_ERR_ARG;
+    }
+    // first: behind it every node's tv is an index into table_p / table_T
+    const int64_t nlev = eoc_int_netlist_levels(nodes, n_nodes, n_wires, n_tv, nullptr, nullptr);
+    if (nlev < 0) return (int)nlev;
+    std::vector<int32_t> tv(n_tv * EOC_N);
+    const int32_t *tab = tables;
+    for (size_t t = 0; t < n_tv; t++) {
+        const int p = table_p[t], T = table_T[t];
+        int32_t *poly = tv.data() + t * EOC_N;
+        const int rc = T == 1 ? eoc_lut_test_polynomial(p, tab, poly) : eoc_lut_many_test_polynomial(p, T, tab, poly);
+        if (rc != EOC_OK) {
+            eoc_set_error("eoc_int_circuit_run: table entry %zu: (p, T) = (%d, %d) is not supported (p in {2, 4, 8}, T in "
+                          "{1, 2, 4, 8}, p T <= 16)", t, p, T);
+            return EOC_ERR_ARG;
+        }
+        tab += (size_t)T * p;
+    }
+    for (size_t k = 0; k < n_nodes; k++)
+        if (nodes[k].n_tables && nodes[k].n_tables != table_T[nodes[k].tv]) {
+            eoc_set_error("eoc_int_circuit_run: node %zu has %d tables, its table entry %d has %d", k, nodes[k].n_tables,
+                          nodes[k].tv, table_T[nodes[k].tv]);
+            return EOC_ERR_ARG;
+        }
+    if (!n_nodes || !instances) return EOC_OK;
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    const size_t stride = (size_t)G.p.n + 1;
+    const int32_t *tvp = tv.data();
+    return for_each_block(instances, [=](int i, size_t lo, size_t hi) {
+        return slot_int_block(G.slots[i], nodes, n_nodes, tvp, n_tv, wires, n_wires, instances, lo, hi, stride);
+    });
+} catch (...) {
+    eoc_set_error("eoc_int_circuit_run: out of memory");
+    return EOC_ERR_ALLOC;
 }
 
 // eoc_compact_expand's engine half (host.cpp holds the global key's lock and has brought the engines up)

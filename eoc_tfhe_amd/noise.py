@@ -294,6 +294,13 @@ def lut_margin_sigma(params, lwe_key, tlwe_key, p, n_tables=1, inputs=1):
     return (1.0 / (4 * int(p))) / float(np.sqrt(inputs * v_out + modswitch_var(lwe_key, n_tables)))
 
 
+def lut_margin_sigma_var(p, n_tables, input_var, lwe_key):
+    """the general form of lut_margin_sigma (integer circuits): 1/(4p) over sqrt(input_var + V_ms(T)), where
+    input_var is the variance (torus units) of the sample in front of the mod switch -- sum_k w_k^2 V(in_k) behind a linear
+    stage with weights w.  lut_margin_sigma(params, ..., p, T, inputs=k) = lut_margin_sigma_var(p, T, k V_out, lwe_key)."""
+    return (1.0 / (4 * int(p))) / float(np.sqrt(float(input_var) + modswitch_var(lwe_key, n_tables)))
+
+
 def _sig2(params):
     """variance of one gaussian32 draw at bk_stdev, truncation toward zero included (as `predict` computes it)"""
     u = 2.0**-32

@@ -361,6 +361,52 @@ int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n_luts, cons
  * Asynchronous on hip_stream.  EOC_ERR_ARG for a null pointer, T outside {2, 4, 8} or n_luts x T outside [1, 32 768]. */
 int eoc_lut_many_batch_device(eoc_engine *e, int n_tables, const int32_t *d_tv, size_t n_luts, const int32_t *d_in,
                               int32_t *d_out, size_t count, void *hip_stream);
+/* Integer circuits: netlists of linear stages and table lookups.  A node forms
+ *   t = sum_k w[k] wire[in[k]] + (0, ..., 0, cst)        wrapping int32, word by word over the n + 1 words of a sample
+ * and writes
+ *   n_tables == 0          out = t                                    a FREE node: no bootstrap
+ *   n_tables == 1          out = KeySwitch(BlindRotate(modswitch(t), tv))    what eoc_lut_batch_device gives for a row t
+ *   n_tables == T in 2,4,8 wires out .. out + T - 1 = the T outputs eoc_lut_many_batch_device gives for a row t (the mod
+ *                          switch rounds onto the T-grid; output j goes to wire out + j)
+ * The netlist is single-assignment and topologically ordered: every wire is written by at most one node, and a node reads
+ * only wires that no node writes (the circuit's inputs) or outputs of EARLIER nodes.  Wires are laid out
+ * [wire][instance][n+1], as in eoc_circuit_run_device.  Entries of in[] / w[] from n_terms on are ignored.
+ * Levels: a bootstrapped node sits one level above the deepest bootstrapped producer among its inputs (inputs: level 0); a
+ * free node costs no level: it runs in the pre-pass of the level after its deepest producer (level_of = that level, which
+ * is n_levels + 1 -- the last pre-pass -- when nothing bootstrapped follows it).
+ * Message ranges and noise are the caller's to track: eoc_tfhe_amd.IntCircuit.check does both. */
+#define EOC_INODE_MAX_TERMS 4
+typedef struct {
+    int32_t n_tables; /* 0: linear node, no bootstrap (free); 1: one table; 2, 4, 8: many-LUT, T outputs */
+    int32_t out;      /* output wire; a many-LUT node writes wires out .. out + T - 1 */
+    int32_t tv;       /* index of the node's test polynomial in d_tv[n_tv][N]; ignored when n_tables == 0 */
+    int32_t n_terms;  /* 1 .. EOC_INODE_MAX_TERMS */
+    int32_t in[EOC_INODE_MAX_TERMS];
+    int32_t w[EOC_INODE_MAX_TERMS];  /* integer weights */
+    int32_t cst;      /* Torus32 constant added to b */
+} eoc_inode;
+/* Host only, no GPU: validates the netlist and returns its number of bootstrap levels (>= 0).  level_of [n_nodes] and
+ * bootstraps may be NULL; *bootstraps = blind rotations per instance (one per node with n_tables >= 1).  EOC_ERR_ARG for a
+ * null netlist with n_nodes > 0, a wire or tv index out of range, n_terms outside [1, 4], n_tables not in {0, 1, 2, 4, 8},
+ * a many-LUT node whose out + T exceeds n_wires, a wire written twice, or a node that reads a wire written by itself or by
+ * a later node. */
+int64_t eoc_int_netlist_levels(const eoc_inode *nodes, size_t n_nodes, size_t n_wires, size_t n_tv, int32_t *level_of,
+                               int64_t *bootstraps);
+/* Runs the netlist over `instances` rows of every wire: d_tv DEVICE [n_tv][N] test polynomials (eoc_lut_test_polynomial
+ * for a node with one table, eoc_lut_many_test_polynomial for T tables), d_wires DEVICE [n_wires][instances][n+1].
+ * Per level and per slice of rows: one k_lin_modswitch launch for the level's free nodes, then per group of nodes with equal
+ * T one k_lin_modswitch launch (linear stage + mod switch onto the T-grid: the rotation amounts), ONE blind rotation over
+ * all of the group's nodes x rows through the gate levels' launch policy (k_blind_rotate_tv / k_lut_many families), and one
+ * key switch over the group's outputs.  Results equal eoc_lut_batch_device / eoc_lut_many_batch_device on rows t, bit for
+ * bit.  Stats: bootstraps += bootstrapped nodes x instances, keyswitches += their outputs x instances.
+ * Slices: a group holds at most 2^20 extracted samples (rows = min(instances, 2^20 / the widest group's outputs)).
+ * Workspace and capture rules: those of eoc_engine_reserve, with max_jobs = the widest group's outputs x rows of a slice,
+ * max_descs >= 2 (nodes + outputs) + 64 and max_mixed_rows >= bootstrapped nodes x N / (4 (n + 1)) + 1 (the nodes' test
+ * polynomials are gathered into level order once per call, in the mixed-batch area).
+ * Asynchronous on hip_stream.  EOC_ERR_ARG as eoc_int_netlist_levels and for a null pointer, before anything touches the
+ * device; EOC_ERR_NO_KEY without a cloud key; n_nodes = 0 or instances = 0 is a no-op. */
+int eoc_int_circuit_run_device(eoc_engine *e, const eoc_inode *nodes, size_t n_nodes, const int32_t *d_tv, size_t n_tv,
+                               int32_t *d_wires, size_t n_wires, size_t instances, void *hip_stream);
 /* Compact public-key lists -> LWE samples (formats and security: "compact public-key encryption" below).
  *   d_lists  DEVICE array [ceil(count / N)][2][N] int32 of lists (eoc_pk_encrypt_*): sample s is slot s mod N of list s / N
  *   d_out    DEVICE array [count][n+1]: out[s] = lweKeySwitch(extract(list s / N, slot s mod N)) with the engine's KSK
@@ -451,6 +497,15 @@ int eoc_lut_batch(int p, const int32_t *tables, size_t n_luts, const int32_t *in
  * pointer. */
 int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out,
                        size_t count);
+/* Integer circuit on the global context (host buffers, synchronous): the netlist of eoc_int_circuit_run_device with its
+ * tables as Torus32 output values.  Entry i of the n_tv entries has table_T[i] tables of table_p[i] values each, stored
+ * one entry after the other in `tables` ([T_0][p_0], then [T_1][p_1], ...); its polynomial is built on the host with
+ * eoc_lut_test_polynomial (T_i = 1) or eoc_lut_many_test_polynomial.  wires [n_wires][instances][n+1] in host memory: the
+ * input wires' rows are read, every written wire's rows are filled in.  Instances are cut into eoc_shard_range blocks,
+ * one per engine; the cloud key alone suffices.  EOC_ERR_ARG as eoc_int_netlist_levels, for an unsupported (p_i, T_i)
+ * and for a null pointer. */
+int eoc_int_circuit_run(const eoc_inode *nodes, size_t n_nodes, const int32_t *tables, const int32_t *table_p,
+                        const int32_t *table_T, size_t n_tv, int32_t *wires, size_t n_wires, size_t instances);
 
 /* ------------------------------------------------------------------------------------------------
  * string API (reference style; global key context)
