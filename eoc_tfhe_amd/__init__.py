@@ -253,6 +253,18 @@ def lib():
         "eoc_compact_expand_device": (C.c_int, [vp, vp, sz, vp, vp]),
         "eoc_compact_expand": (C.c_int, [vp, sz, vp]),
         "eoc_global_public_key_export": (sz, [vp, sz]),
+        # leveled operations: selectors, CMux, encrypted-index table reads
+        "eoc_tgsw_len": (sz, [PP]),
+        "eoc_tgsw_encrypt_bits": (C.c_int, [vp, u64, u64, vp, sz, vp]),
+        "eoc_tgsw_encrypt_bits_keyed": (C.c_int, [vp, vp, u64, vp, sz, vp]),
+        "eoc_global_tgsw_encrypt_bits": (C.c_int, [vp, sz, vp]),
+        "eoc_table_trivial": (C.c_int, [vp, sz, vp]),
+        "eoc_tgsw_fft_bytes": (sz, [PP]),
+        "eoc_tgsw_to_fft_device": (C.c_int, [vp, vp, sz, vp, vp]),
+        "eoc_cmux_device": (C.c_int, [vp, vp, vp, vp, vp, sz, vp]),
+        "eoc_table_read_device": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp]),
+        "eoc_engine_cmux_launches": (u64, [vp]),
+        "eoc_table_read": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -417,6 +429,35 @@ class SecretKey:
                                        out.ctypes.data), "eoc_encrypt_ints")
         return out
 
+    def encrypt_selector_bits(self, bits, enc_seed, first_idx=0):
+        """TGSW selectors of `bits` for Engine.cmux_device / table_read (eoc_tgsw_encrypt_bits): [len(bits)][2l][2][N] int32
+        in torus form, the shape of one bootstrapping-key block.  enc_seed an int: the reproducible test streams (enc_seed,
+        first_idx + s) -- NOT secure, refused for a secure-mode key.  enc_seed None: ChaCha20 streams under a fresh key from
+        the OS, drawn per call (a repeated (key, index) pair repeats mask and noise)."""
+        bits = np.ascontiguousarray(np.asarray(bits).ravel(), np.uint8)
+        p = self.params
+        out = np.empty((bits.size, 2 * p.l, 2, N), np.int32)
+        if enc_seed is not None:
+            _check(self.L.eoc_tgsw_encrypt_bits(self.h, int(enc_seed), int(first_idx), bits.ctypes.data, bits.size,
+                                                out.ctypes.data), "eoc_tgsw_encrypt_bits")
+            return out
+        if first_idx:
+            raise EocError("first_idx is a test-mode argument: secure encryption draws a fresh key per call")
+        key = np.frombuffer(os.urandom(32), np.uint8).copy()
+        try:
+            _check(self.L.eoc_tgsw_encrypt_bits_keyed(self.h, key.ctypes.data, 0, bits.ctypes.data, bits.size,
+                                                      out.ctypes.data), "eoc_tgsw_encrypt_bits_keyed")
+        finally:
+            key[:] = 0
+        return out
+
+    def encrypt_index(self, index, nbits, enc_seed, first_idx=0):
+        """The selectors of an encrypted table index: bits of `index` LSB first, [nbits][2l][2][N] (table_read's order)"""
+        index, nbits = int(index), int(nbits)
+        if index < 0 or index >> nbits:
+            raise EocError(f"encrypt_index: {index} does not fit {nbits} bits")
+        return self.encrypt_selector_bits([(index >> k) & 1 for k in range(nbits)], enc_seed, first_idx)
+
     def decrypt_ints(self, cts, p):
         """round(phase * 2p / 2^32) mod p (eoc_decrypt_ints)"""
         cts = np.ascontiguousarray(cts, np.int32).reshape(-1, self.n + 1)
@@ -491,6 +532,18 @@ class PublicKey:
         """small integers m < p, p in {2, 4, 8} (SecretKey.encrypt_ints' encoding) -> compact lists; randomness as
         encrypt_bits"""
         return self._encrypt(values, p, enc_seed, first_list)
+
+
+def trivial_table(messages):
+    """Public data as a table for table_read (eoc_table_trivial): Torus32 messages -> trivial TLWE lists [L][2][N], c0 = 0,
+    c1 = the messages, zero-padded to whole lists"""
+    messages = np.ascontiguousarray(np.asarray(messages).ravel(), np.int32)
+    out = np.empty((max(1, -(-messages.size // N)), 2, N), np.int32)
+    if messages.size == 0:
+        out[:] = 0
+        return out
+    _check(lib().eoc_table_trivial(messages.ctypes.data, messages.size, out.ctypes.data), "eoc_table_trivial")
+    return out
 
 
 def lut_test_polynomial(p, table):
@@ -675,6 +728,28 @@ class Engine:
         d_out [count][n+1]; slot extraction and the key switch, with the key-switch key alone"""
         _check(self.L.eoc_compact_expand_device(self.h, d_lists, count, d_out, stream), "eoc_compact_expand_device")
 
+    @property
+    def tgsw_fft_bytes(self):
+        """bytes of one converted selector (eoc_tgsw_fft_bytes): 64 KiB on Set A, 96 KiB on Set B"""
+        return self.L.eoc_tgsw_fft_bytes(C.byref(self.params))
+
+    def tgsw_to_fft_device(self, d_tgsw, count, d_fft, stream=None):
+        """Selectors in torus form [count][2l][2][N] -> the form the kernels multiply by, [count][2l][2][512] complex
+        (eoc_tgsw_to_fft_device; tgsw_fft_bytes each).  Needs no key."""
+        _check(self.L.eoc_tgsw_to_fft_device(self.h, d_tgsw, count, d_fft, stream), "eoc_tgsw_to_fft_device")
+
+    def cmux_device(self, d_sel_fft, d_in0, d_in1, d_out, count, stream=None):
+        """out[i] = in0[i] + C[i] (x) (in1[i] - in0[i]) on TLWE samples [count][2][N], one converted selector per item
+        (eoc_cmux_device): in1 where the bit is 1, in0 otherwise.  Needs no key."""
+        _check(self.L.eoc_cmux_device(self.h, d_sel_fft, d_in0, d_in1, d_out, count, stream), "eoc_cmux_device")
+
+    def table_read_device(self, d_table, log2_lists, log2_width, d_sel_fft, queries, d_out, stream=None):
+        """Entry idx_q of a table for each of `queries` encrypted indices (eoc_table_read_device): d_table [2^d][2][N], entries
+        of W = 2^log2_width slots, d_sel_fft [queries][10 - log2_width + d] converted selectors (index bits LSB first), d_out
+        [queries][W][n+1] -- ordinary gate / LUT inputs"""
+        _check(self.L.eoc_table_read_device(self.h, d_table, int(log2_lists), int(log2_width), d_sel_fft, queries, d_out,
+                                            stream), "eoc_table_read_device")
+
     def resident_jobs(self):
         """blind rotations that fill the device in one launch (8 x CUs where the one-wave-per-ciphertext kernel applies,
         4 x otherwise): cut long jobs at multiples of this"""
@@ -686,7 +761,8 @@ class Engine:
         return dict(batches=out[0], bootstraps=out[1], keyswitches=out[2],
                     br_launches=int(self.L.eoc_engine_blind_rotate_launches(self.h)),
                     br_wide_launches=int(self.L.eoc_engine_blind_rotate_wide_launches(self.h)),
-                    ks_mfma_launches=int(self.L.eoc_engine_keyswitch_mfma_launches(self.h)))
+                    ks_mfma_launches=int(self.L.eoc_engine_keyswitch_mfma_launches(self.h)),
+                    cmux_launches=int(self.L.eoc_engine_cmux_launches(self.h)))
 
 
 def circuit_bootstraps(gates):
@@ -946,6 +1022,33 @@ def compact_expand(lists, count=None):
             raise EocError("compact_expand: no key and no GPU engine on the global context")
         out = np.empty((count, lib().eoc_engine_params(e0).contents.n + 1), np.int32)
     _check(lib().eoc_compact_expand(lists.ctypes.data, count, out.ctypes.data), "eoc_compact_expand")
+    return out
+
+
+def table_read(table, log2_lists, log2_width, selectors):
+    """eoc_table_read on the global context (a cloud key alone suffices): table [2^log2_lists][2][N] (trivial_table or
+    PublicKey.encrypt_*), selectors [queries][10 - log2_width + log2_lists][2l][2][N] in torus form
+    (SecretKey.encrypt_index per query) -> [queries][2^log2_width][n+1] LWE samples"""
+    table = np.ascontiguousarray(table, np.int32)
+    d, lw = int(log2_lists), int(log2_width)
+    if table.ndim != 3 or table.shape[1:] != (2, N) or not 0 <= d <= 12 or table.shape[0] != 1 << d:
+        raise EocError(f"table_read: table must be [2^log2_lists][2][{N}] with log2_lists in [0, 12], got {table.shape}")
+    if not 0 <= lw <= 10:
+        raise EocError(f"table_read: log2_width = {lw} outside [0, 10]")
+    depth = d + 10 - lw
+    selectors = np.ascontiguousarray(selectors, np.int32)
+    if selectors.ndim != 5 or selectors.shape[1] != depth or selectors.shape[3:] != (2, N):
+        raise EocError(f"table_read: selectors must be [queries][{depth}][2l][2][{N}], got {selectors.shape}")
+    if lib().eoc_global_key_mode():
+        n = global_params().n
+    else:
+        e0 = lib().eoc_global_engine()
+        if not e0:
+            raise EocError("table_read: no key and no GPU engine on the global context")
+        n = lib().eoc_engine_params(e0).contents.n
+    out = np.empty((selectors.shape[0], 1 << lw, n + 1), np.int32)
+    _check(lib().eoc_table_read(table.ctypes.data, d, lw, selectors.ctypes.data, selectors.shape[0], out.ctypes.data),
+           "eoc_table_read")
     return out
 
 

@@ -25,3 +25,6 @@ int eoc_compact_expand_device_from(eoc_engine *e, const int32_t *d_lists, size_t
 // eoc_compact_expand's GPU half on the process-global engines (multi.hip): samples cut into eoc_shard_range blocks, one per
 // engine; the caller (host.cpp) has brought the engines up behind the global key
 int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out);
+// eoc_table_read's GPU half on the process-global engines (multi.hip): queries cut into eoc_shard_range blocks, one per engine
+int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries,
+                           int32_t *out);

@@ -91,6 +91,12 @@ struct eoc_engine {
     uint64_t br_launches = 0; // k_blind_rotate kernel launches (a wide level is several, a cut blind rotation too)
     uint64_t br_wide_launches = 0; // ... of which k_blind_rotate_wide
     uint64_t ks_mfma_launches = 0; // k_keyswitch_mfma launches (key switches that ran on the matrix cores)
+    // encrypted-index table reads: the two ping-pong buffers of the CMux tree, in TLWE samples, and the byte
+    // budget both together are held to (queries are sliced to fit; EOC_TFHE_TABLE_WS_BYTES, diagnostics)
+    int32_t *d_cmux[2] = {nullptr, nullptr};
+    size_t cmux_cap[2] = {0, 0};
+    size_t table_ws_bytes = (size_t)256 << 20;
+    uint64_t cmux_launches = 0; // k_cmux launches
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
     struct Span { hipEvent_t a, b; int kind; };
@@ -261,6 +267,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
         if (const char *s = getenv("EOC_TFHE_KS_MFMA")) e->ks_mfma = atoi(s) != 0;
         if (const char *s = getenv("EOC_TFHE_BR_TABLES_LDS")) e->br_tables_lds = atoi(s) != 0;
         if (const char *s = getenv("EOC_TFHE_INT_SLICE_ROWS")) e->int_slice_rows = atoi(s);
+        if (const char *s = getenv("EOC_TFHE_TABLE_WS_BYTES")) e->table_ws_bytes = (size_t)strtoull(s, nullptr, 10);
     }
     // the key-switch kernel uses > 64 KiB of dynamic LDS: raise the limit once, here, not on the launch path
     // (a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to k_keyswitch_generic: slow, exact)
@@ -274,6 +281,17 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
     EOC_KS_ATTR(8, 8, 64);
 #undef EOC_KS_ATTR
     if (!e->ks_waves_ok) (void)hipGetLastError();
+    // so does k_cmux (tables + four transpose scratches); a device that refuses it cannot run the leveled calls
+#define EOC_CMUX_ATTR(LL, BB) \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cmux<LL, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds)
+    EOC_CMUX_ATTR(2, 10);
+    EOC_CMUX_ATTR(3, 7);
+    EOC_CMUX_ATTR(1, 0);
+    EOC_CMUX_ATTR(2, 0);
+    EOC_CMUX_ATTR(3, 0);
+    EOC_CMUX_ATTR(4, 0);
+#undef EOC_CMUX_ATTR
+    (void)hipGetLastError();
     *out = e;
     return EOC_OK;
 }
@@ -307,6 +325,8 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
         hipFree(e->d_ksk);
     }
     hipFree(e->d_ksl);
+    hipFree(e->d_cmux[0]);
+    hipFree(e->d_cmux[1]);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -1431,6 +1451,188 @@ extern "C" int eoc_compact_expand_device(eoc_engine *e, const int32_t *d_lists, 
     return eoc_compact_expand_device_from(e, d_lists, 0, count, d_out, hip_stream);
 }
 
+// ---- leveled operations: selectors, CMux, encrypted-index table reads --------
+extern "C" size_t eoc_tgsw_fft_bytes(const eoc_params *p) { return p ? (size_t)2 * p->l * 2 * kNH * 16 : 0; }
+
+// torus-form selectors [count][2l][2][N] -> the layout the kernels multiply by, [count][2l][2][512] complex scaled by 2^-9:
+// the key-load transform (build_cloud_key_images), on the caller's stream.  No key is needed.
+extern "C" int eoc_tgsw_to_fft_device(eoc_engine *e, const int32_t *d_tgsw, size_t count, void *d_fft, void *hip_stream)
+{
+    if (!e || !d_tgsw || !d_fft) {
+        eoc_set_error("eoc_tgsw_to_fft_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    return launch_fft_fwd(e, d_tgsw, static_cast<double *>(d_fft), count * e->kpl * 2, 0x1p-9, (hipStream_t)hip_stream);
+}
+
+static int launch_cmux(eoc_engine *e, const CmuxArgs &a, uint32_t ny, hipStream_t st)
+{
+    const void *fn = nullptr;
+    const int l = e->p.l, bg = e->p.Bgbit;
+    if (l == 2 && bg == 10) fn = reinterpret_cast<const void *>(&k_cmux<2, 10>);
+    else if (l == 3 && bg == 7) fn = reinterpret_cast<const void *>(&k_cmux<3, 7>);
+    else if (l == 1) fn = reinterpret_cast<const void *>(&k_cmux<1, 0>);
+    else if (l == 2) fn = reinterpret_cast<const void *>(&k_cmux<2, 0>);
+    else if (l == 3) fn = reinterpret_cast<const void *>(&k_cmux<3, 0>);
+    else if (l == 4) fn = reinterpret_cast<const void *>(&k_cmux<4, 0>);
+    if (!fn) {
+        eoc_set_error("k_cmux: no kernel for gadget length %d", l);
+        return EOC_ERR_STATE;
+    }
+    CmuxArgs args = a;
+    args.Bgbit = bg;
+    const d2 *tw = e->d_tw, *twist = e->d_twist;
+    void *kargs[] = {&args, &tw, &twist};
+    SpanGuard span(e, st, KIND_BLIND_ROTATE);
+    HIP_TRY(hipLaunchKernel(fn, dim3((a.nx + kCmuxItemsPerWG - 1) / kCmuxItemsPerWG, ny), dim3(128 * kCmuxItemsPerWG), kargs,
+                            kCmuxLds, st));
+    e->cmux_launches++;
+    return EOC_OK;
+}
+
+extern "C" int eoc_cmux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in0, const int32_t *d_in1, int32_t *d_out,
+                               size_t count, void *hip_stream)
+{
+    if (!e || !d_sel_fft || !d_in0 || !d_in1 || !d_out) {
+        eoc_set_error("eoc_cmux_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t sel = (size_t)e->kpl * 2 * kNH, smp = (size_t)2 * kN;
+    constexpr size_t kSlice = (size_t)1 << 30; // items per launch (grid x)
+    for (size_t i0 = 0; i0 < count; i0 += kSlice) {
+        CmuxArgs a{};
+        a.sel = static_cast<const d2 *>(d_sel_fft) + i0 * sel;
+        a.in0 = d_in0 + i0 * smp;
+        a.in1 = d_in1 + i0 * smp;
+        a.out = d_out + i0 * smp;
+        a.sel_x = sel;
+        a.in0_x = a.in1_x = a.out_x = smp;
+        a.nx = (uint32_t)std::min(kSlice, count - i0);
+        a.rot = 0;
+        int rc = launch_cmux(e, a, 1, (hipStream_t)hip_stream);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+// the two ping-pong buffers, grown by the workspace's rule (ensure_ws): never under capture, the device drained first
+static int ensure_cmux_ws(eoc_engine *e, size_t s0, size_t s1, hipStream_t st)
+{
+    const size_t need[2] = {s0, s1};
+    if (need[0] <= e->cmux_cap[0] && need[1] <= e->cmux_cap[1]) return EOC_OK;
+    if (stream_is_capturing(st)) {
+        eoc_set_error("graph capture: the table-read workspace would have to grow (%zu > %zu or %zu > %zu samples); run one "
+                      "call of the captured shape before capturing", s0, e->cmux_cap[0], s1, e->cmux_cap[1]);
+        return EOC_ERR_STATE;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    for (int k = 0; k < 2; k++) {
+        if (need[k] <= e->cmux_cap[k]) continue;
+        hipFree(e->d_cmux[k]);
+        e->d_cmux[k] = nullptr;
+        e->cmux_cap[k] = 0;
+        HIP_TRY(hipMalloc(&e->d_cmux[k], need[k] * 2 * kN * sizeof(int32_t)));
+        e->cmux_cap[k] = need[k];
+        e->ws_grows++;
+    }
+    return EOC_OK;
+}
+
+extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
+                                     size_t queries, int32_t *d_out, void *hip_stream)
+{
+    if (!e || !d_table || !d_out || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10 ||
+        (!d_sel_fft && log2_lists + 10 - log2_width > 0)) {
+        eoc_set_error("eoc_table_read_device: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]",
+                      log2_lists, log2_width);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    const int d = log2_lists, r = 10 - log2_width, depth = d + r;
+    const size_t W = (size_t)1 << log2_width, smp = (size_t)2 * kN, sel = (size_t)e->kpl * 2 * kNH;
+    const size_t s0 = d >= 1 ? (size_t)1 << (d - 1) : 1, s1 = d >= 2 ? (size_t)1 << (d - 2) : 1; // samples per query
+    const size_t per_query = (s0 + s1) * smp * sizeof(int32_t);
+    if (depth > 0 && e->table_ws_bytes < per_query) {
+        eoc_set_error("eoc_table_read_device: one query at log2_lists = %d needs %zu bytes of workspace, the budget "
+                      "(EOC_TFHE_TABLE_WS_BYTES) is %zu", d, per_query, e->table_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    if (!e->ksk) {
+        eoc_set_error("eoc_table_read_device: no key-switch key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    if (!queries) return EOC_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    WS &Wk = e->ws;
+    // queries per slice: the byte budget of the tree's buffers, 2^20 extracted samples (lut_levels' rule), grid y
+    size_t qs = std::min<size_t>(queries, 32768);
+    if (depth > 0) qs = std::min(qs, e->table_ws_bytes / per_query);
+    qs = std::min(qs, std::max<size_t>(1, ((size_t)1 << 20) / W));
+    int rc = ensure_ws(e, Wk, qs * W, 0, 0, st);
+    if (rc) return rc;
+    if (depth > 0 && (rc = ensure_cmux_ws(e, qs * s0, qs * s1, st))) return rc;
+    const size_t stride = (size_t)e->p.n + 1;
+    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    for (size_t q0 = 0; q0 < queries; q0 += qs) {
+        const size_t Q = std::min(qs, queries - q0);
+        const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * depth * sel;
+        const int32_t *cur = d_table; // the TLWE samples the next launch reads: [Q][cur_y / smp] (cur_y = 0: shared)
+        size_t cur_y = 0;
+        int t = 0;
+        for (int v = 0; v < d; v++, t++) { // tree: nodes (2j, 2j + 1) -> j with bit r + v
+            CmuxArgs a{};
+            a.nx = (uint32_t)1 << (d - 1 - v);
+            a.sel = selq + (size_t)(r + v) * sel;
+            a.sel_x = 0;
+            a.sel_y = (size_t)depth * sel;
+            a.in0 = cur;
+            a.in1 = cur + smp;
+            a.in0_x = a.in1_x = 2 * smp;
+            a.in0_y = a.in1_y = cur_y;
+            a.out = e->d_cmux[t & 1];
+            a.out_x = smp;
+            a.out_y = (size_t)a.nx * smp;
+            a.rot = 0;
+            if ((rc = launch_cmux(e, a, (uint32_t)Q, st))) return rc;
+            cur = a.out;
+            cur_y = a.out_y;
+        }
+        for (int i = 0; i < r; i++, t++) { // rotations: X^(-W 2^i) under bit i brings slot W 2^i to slot 0
+            CmuxArgs a{};
+            a.nx = 1;
+            a.sel = selq + (size_t)i * sel;
+            a.sel_y = (size_t)depth * sel;
+            a.in0 = a.in1 = cur;
+            a.in0_y = a.in1_y = cur_y;
+            a.out = e->d_cmux[t & 1];
+            a.out_y = smp;
+            a.rot = 2 * kN - (int)(W << i);
+            if ((rc = launch_cmux(e, a, (uint32_t)Q, st))) return rc;
+            cur = a.out;
+            cur_y = a.out_y;
+        }
+        int32_t *o = d_out + q0 * W * stride;
+        {
+            SpanGuard span(e, st, KIND_PREPARE);
+            hipLaunchKernelGGL(k_tlwe_extract, dim3((unsigned)((W + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG), (unsigned)Q),
+                               dim3(256), 0, st, cur, cur_y, (uint32_t)W, Wk.d_ubar, o, e->p.n, prec_offset);
+            HIP_TRY(hipGetLastError());
+        }
+        const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
+        rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(Q * W), st, true, &gd);
+        if (rc) return rc;
+        e->stats[2] += Q * W;
+    }
+    return EOC_OK;
+}
+
 // ---- programmable bootstrapping ----------------------------------------
 // Table lookups, n_tables = 0: one level of n_luts x rows jobs, [table][row]: one OP_RAW descriptor per table (all read the
 // same input rows, job_base = table x rows, out = the table's output block) serves k_prepare, the blind rotation and the key
@@ -1724,6 +1926,7 @@ extern "C" uint64_t eoc_engine_workspace_grows(eoc_engine *e) { return e ? e->ws
 extern "C" uint64_t eoc_engine_blind_rotate_launches(eoc_engine *e) { return e ? e->br_launches : 0; }
 extern "C" uint64_t eoc_engine_blind_rotate_wide_launches(eoc_engine *e) { return e ? e->br_wide_launches : 0; }
 extern "C" uint64_t eoc_engine_keyswitch_mfma_launches(eoc_engine *e) { return e ? e->ks_mfma_launches : 0; }
+extern "C" uint64_t eoc_engine_cmux_launches(eoc_engine *e) { return e ? e->cmux_launches : 0; }
 extern "C" size_t eoc_engine_resident_jobs(eoc_engine *e)
 {
     if (!e) return 0;

@@ -167,7 +167,7 @@ extern "C" void eoc_dbg_chacha20_block(const uint8_t key[32], uint32_t counter, 
 namespace {
 
 struct Stream {
-    enum Tag : uint32_t { LweKey = 1, TlweKey = 2, Bk = 3, Ksk = 4, Enc = 5, PublicKey = 6, CompactEnc = 7 };
+    enum Tag : uint32_t { LweKey = 1, TlweKey = 2, Bk = 3, Ksk = 4, Enc = 5, PublicKey = 6, CompactEnc = 7, TgswEnc = 8 };
     bool secure = false;
     uint64_t key = 0;           // v1
     uint32_t sub[8];            // v2: this stream's ChaCha20 key
@@ -271,36 +271,100 @@ static void make_ksk(eoc_secret_key &k)
     }
 }
 
+// One TGSW row under the TLWE key whose ones sit at `ones`: a TLWE encryption of 0 at `stdev` from stream `st` (mask word j at
+// counter j, Gaussian j at N + 2j; b = e + s' a is a sum of signed rotations of a), plus, for bit 1, the gadget of row
+// (q, p) = (row / l, row % l + 1): 2^(32 - p Bgbit) on the constant coefficient of polynomial q.  row_out = a[N] | b[N].
+static void tgsw_row(const eoc_params &p, const std::vector<int> &ones, const Stream &st, int row, bool bit, int32_t *row_out)
+{
+    uint32_t *a = reinterpret_cast<uint32_t *>(row_out);
+    uint32_t *b = a + EOC_N;
+    for (int j = 0; j < EOC_N; j++) {
+        a[j] = st.torus(uint64_t(j));
+        b[j] = st.gaussian(uint64_t(EOC_N) + 2 * uint64_t(j), 0u, p.bk_stdev);
+    }
+    for (int m : ones) {
+        // X^m * a: coefficient j gets +a[j-m] (j >= m) or -a[j-m+N] (j < m)
+        const uint32_t *src = a + (EOC_N - m);
+        for (int j = 0; j < m; j++) b[j] -= src[j];
+        for (int j = m; j < EOC_N; j++) b[j] += a[j - m];
+    }
+    if (bit) { // gadget: 2^(32 - p*Bgbit) on polynomial q of row (q, p)
+        const int q = row / p.l, pp = row % p.l + 1;
+        (q ? b : a)[0] += 1u << (32 - pp * p.Bgbit);
+    }
+}
+static std::vector<int> tlwe_ones(const eoc_secret_key &k)
+{
+    std::vector<int> ones;
+    for (int m = 0; m < EOC_N; m++)
+        if (k.tlwe[m]) ones.push_back(m);
+    return ones;
+}
+
 static void make_bk(eoc_secret_key &k)
 {
     const eoc_params &p = k.p;
     const int kpl = 2 * p.l;
     k.bk.assign(eoc_bk_len(&p), 0);
-    // positions of the ones of the TLWE key: b = e + s*a is a sum of signed rotations of a
-    std::vector<int> ones;
-    for (int m = 0; m < EOC_N; m++)
-        if (k.tlwe[m]) ones.push_back(m);
+    const std::vector<int> ones = tlwe_ones(k);
 #pragma omp parallel for schedule(dynamic, 8) num_threads(usable_threads())
-    for (int ir = 0; ir < p.n * kpl; ir++) {
-        Stream st(k, Stream::Bk, uint64_t(ir));
-        uint32_t *a = reinterpret_cast<uint32_t *>(&k.bk[(size_t(ir) * 2) * EOC_N]);
-        uint32_t *b = a + EOC_N;
-        for (int j = 0; j < EOC_N; j++) {
-            a[j] = st.torus(uint64_t(j));
-            b[j] = st.gaussian(uint64_t(EOC_N) + 2 * uint64_t(j), 0u, p.bk_stdev);
-        }
-        for (int m : ones) {
-            // X^m * a: coefficient j gets +a[j-m] (j >= m) or -a[j-m+N] (j < m)
-            const uint32_t *src = a + (EOC_N - m);
-            for (int j = 0; j < m; j++) b[j] -= src[j];
-            for (int j = m; j < EOC_N; j++) b[j] += a[j - m];
-        }
-        const int i = ir / kpl, row = ir % kpl;
-        if (k.lwe[i]) { // gadget: s_i * 2^(32 - p*Bgbit) on polynomial q of row (q, p)
-            const int q = row / p.l, pp = row % p.l + 1;
-            (q ? b : a)[0] += 1u << (32 - pp * p.Bgbit);
+    for (int ir = 0; ir < p.n * kpl; ir++)
+        tgsw_row(p, ones, Stream(k, Stream::Bk, uint64_t(ir)), ir % kpl, k.lwe[ir / kpl] != 0, &k.bk[(size_t(ir) * 2) * EOC_N]);
+}
+
+// ---- selectors of an encrypted-index table read (include/eoc_tfhe_gpu.h) ------------------------------------
+extern "C" size_t eoc_tgsw_len(const eoc_params *p) { return p ? size_t(2) * p->l * 2 * EOC_N : 0; }
+// enc_key != NULL: ChaCha20 streams under it; else the seeded test streams of enc_seed
+static int tgsw_encrypt(const char *what, const eoc_secret_key *sk, const uint8_t *enc_key, bool keyed, uint64_t enc_seed,
+                        uint64_t first_idx, const uint8_t *bits, size_t count, int32_t *out)
+{
+    if (!sk || !bits || !out || (keyed && !enc_key)) {
+        eoc_set_error("%s: null argument", what);
+        return EOC_ERR_ARG;
+    }
+    if (!keyed && sk->secure) {
+        eoc_set_error("%s: a secure-mode key does not encrypt with the seeded test streams; use the _keyed form", what);
+        return EOC_ERR_STATE;
+    }
+    if (!count) return EOC_OK;
+    const eoc_params &p = sk->p;
+    const size_t kpl = size_t(2) * p.l, rows = count * kpl;
+    const std::vector<int> ones = tlwe_ones(*sk);
+#pragma omp parallel for schedule(dynamic, 4) num_threads(usable_threads()) if (rows >= 8)
+    for (size_t ir = 0; ir < rows; ir++) {
+        const size_t s = ir / kpl;
+        const uint64_t idx = (first_idx + s) * kpl + ir % kpl;
+        const Stream st = keyed ? Stream(enc_key, Stream::TgswEnc, idx) : Stream(enc_seed, Stream::TgswEnc, idx);
+        tgsw_row(p, ones, st, int(ir % kpl), bits[s] != 0, out + ir * 2 * EOC_N);
+    }
+    return EOC_OK;
+}
+extern "C" int eoc_tgsw_encrypt_bits(const eoc_secret_key *sk, uint64_t enc_seed, uint64_t first_idx, const uint8_t *bits,
+                                     size_t count, int32_t *out)
+{
+    return tgsw_encrypt("eoc_tgsw_encrypt_bits", sk, nullptr, false, enc_seed, first_idx, bits, count, out);
+}
+extern "C" int eoc_tgsw_encrypt_bits_keyed(const eoc_secret_key *sk, const uint8_t enc_key[32], uint64_t first_idx,
+                                           const uint8_t *bits, size_t count, int32_t *out)
+{
+    return tgsw_encrypt("eoc_tgsw_encrypt_bits_keyed", sk, enc_key, true, 0, first_idx, bits, count, out);
+}
+// public data as trivial TLWE lists: c0 = 0, c1 = the messages, zero-padded to whole lists
+extern "C" int eoc_table_trivial(const int32_t *messages, size_t count, int32_t *lists)
+{
+    if (!messages || !lists) {
+        eoc_set_error("eoc_table_trivial: null argument");
+        return EOC_ERR_ARG;
+    }
+    const size_t n_lists = (count + EOC_N - 1) / EOC_N;
+    for (size_t L = 0; L < n_lists; L++) {
+        int32_t *c0 = lists + L * 2 * EOC_N, *c1 = c0 + EOC_N;
+        for (size_t j = 0; j < size_t(EOC_N); j++) {
+            c0[j] = 0;
+            c1[j] = L * EOC_N + j < count ? messages[L * EOC_N + j] : 0;
         }
     }
+    return EOC_OK;
 }
 
 static int keygen_common(const eoc_params *p, uint64_t seed, const uint8_t *master, int with_cloud_key, eoc_secret_key **out)
@@ -885,6 +949,19 @@ extern "C" int eoc_global_encrypt_bits(const uint8_t *bits, size_t count, int32_
     c.enc_counter += count;
     return rc;
 }
+extern "C" int eoc_global_tgsw_encrypt_bits(const uint8_t *bits, size_t count, int32_t *out)
+{
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (!c.sk) {
+        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
+        return EOC_ERR_NO_KEY;
+    }
+    int rc = c.enc_secure ? eoc_tgsw_encrypt_bits_keyed(c.sk, c.enc_key, c.enc_counter, bits, count, out)
+                          : eoc_tgsw_encrypt_bits(c.sk, c.enc_seed, c.enc_counter, bits, count, out);
+    if (rc == EOC_OK) c.enc_counter += count;
+    return rc;
+}
 extern "C" int eoc_global_decrypt_bits(const int32_t *cts, size_t count, uint8_t *bits)
 {
     GlobalCtx &c = ctx();
@@ -961,6 +1038,26 @@ extern "C" int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *o
         if (rc) return rc;
     }
     return eoc_compact_expand_engines(lists, count, out);
+}
+// an encrypted-index table read on the global context's engines (brought up behind the global key on first use; a cloud key
+// alone suffices)
+extern "C" int eoc_table_read(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries,
+                              int32_t *out)
+{
+    const bool depth0 = log2_lists == 0 && log2_width == 10;
+    if (!table || !out || (!selectors && !depth0) || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10) {
+        eoc_set_error("eoc_table_read: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]",
+                      log2_lists, log2_width);
+        return EOC_ERR_ARG;
+    }
+    if (!queries) return EOC_OK;
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) {
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    }
+    return eoc_table_read_engines(table, log2_lists, log2_width, selectors, queries, out);
 }
 extern "C" int eoc_global_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires,
                                       size_t instances)

@@ -1487,4 +1487,178 @@ __global__ __launch_bounds__(256) void k_compact_expand(const int32_t *__restric
     }
 }
 
+// =================================================================================================
+// Leveled operations: the CMux of an encrypted-index table read.
+//   out = A + C (x) (X^rot B - A),  rot in [0, 2N)
+// A, B: TLWE samples [2][N] in global memory; C: a converted selector [2l][2][512] complex (one row block of the
+// bootstrapping key's FFT image, scaled by 2^-9).  The external product is the blind rotation's, in the canonical order
+// (oracle/tfhe_oracle.c): with A = B the item is one blind-rotation step with abar = rot, bit for bit.
+// Mapping: one wave PAIR per item, as k_blind_rotate -- wave h owns input polynomial h (difference, decomposition, the l
+// forward transforms) and output polynomial h (the chain the partner started, continued with the own digits, the inverse
+// transform, + A_h).  Wave h reads and writes polynomial h only.  kCmuxItemsPerWG pairs share one workgroup and its copy of
+// the twiddle tables; the pairs of a workgroup meet at the two exchange barriers (a pair past the end of the grid computes
+// the last item again and stores nothing, so every barrier is reached by all waves).  Nothing here is loop-invariant, so
+// the tables are read from LDS in every pass, as the pair kernel's gadget-length-3 instance does.
+// grid: x = ceil(nx / kCmuxItemsPerWG), y = ny; item (x, y) is addressed by strides in int32 (samples) / d2 (selectors).
+// =================================================================================================
+constexpr int kCmuxItemsPerWG = 2;
+constexpr int kCmuxLds = (kTwEntries + kNH + 2 * kCmuxItemsPerWG * kScr) * 16; // 53 760 bytes: two workgroups per CU
+
+struct CmuxArgs {
+    const d2 *sel;             // converted selectors
+    const int32_t *in0, *in1;  // A, B
+    int32_t *out;
+    size_t sel_x, sel_y;       // strides per item along x / y, in d2
+    size_t in0_x, in0_y, in1_x, in1_y, out_x, out_y; // ... in int32
+    uint32_t nx;               // items along x
+    int rot;                   // B is multiplied by X^rot
+    int Bgbit;
+};
+
+template <int L, int BGBIT = 0>
+__global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_cmux(CmuxArgs A, const d2 *__restrict__ g_tw,
+                                                                    const d2 *__restrict__ g_twist)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    d2 *s_tw = reinterpret_cast<d2 *>(smem);
+    d2 *s_twist = s_tw + kTwEntries;
+    d2 *s_scr_all = s_twist + kNH;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = wv & 1;
+    d2 *scr = s_scr_all + wv * kScr;
+    d2 *scr_partner = s_scr_all + (wv ^ 1) * kScr;
+    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128 * kCmuxItemsPerWG);
+
+    const uint32_t x_raw = blockIdx.x * kCmuxItemsPerWG + (uint32_t)(wv >> 1);
+    const bool live = x_raw < A.nx;
+    const size_t ix = live ? x_raw : A.nx - 1, iy = blockIdx.y;
+    const int32_t *pa = A.in0 + ix * A.in0_x + iy * A.in0_y + (size_t)h * kN;
+    const int32_t *pb = A.in1 + ix * A.in1_x + iy * A.in1_y + (size_t)h * kN;
+    const d2 *sel = A.sel + ix * A.sel_x + iy * A.sel_y;
+
+    const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
+    const uint32_t Bg = 1u << Bgbit, maskBg = Bg - 1, halfBg = Bg >> 1;
+    uint32_t offset = 0;
+#pragma unroll
+    for (int p = 1; p <= L; p++) offset += halfBg << (32 - p * Bgbit);
+    const double bias1 = 4503599627370496.0 + (double)halfBg, bias2 = 4503599627370496.0 + (double)Bg;
+
+    // offset + (X^rot B_h - A_h): coefficient lane + 64 r in dlo[r], lane + 64 r + 512 in dhi[r].  The rotation is index
+    // arithmetic on B's loads (X^N = -1: the upper half of the 2N-period is negated)
+    uint32_t dlo[8], dhi[8];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
+        const int idx = (j - A.rot) & (2 * kN - 1);
+        const uint32_t b = (uint32_t)pb[idx & (kN - 1)];
+        const uint32_t v = offset + ((idx & kN) ? 0u - b : b) - (uint32_t)pa[j];
+        if (r < 8) dlo[r] = v;
+        else dhi[r - 8] = v;
+    }
+    __syncthreads(); // the tables
+
+    // rows (h, p) of the selector for output polynomial c: 16 bytes per lane, 1 KiB contiguous per wave and instruction
+    auto load_row = [&](int p, int c, d2 (&b)[8]) __attribute__((always_inline)) {
+        const d2 *row = sel + ((size_t)(h * L + (p - 1)) * 2 + c) * kNH + lane;
+#pragma unroll
+        for (int r = 0; r < 8; r++) b[r] = row[r * 64];
+    };
+    auto make_x0 = [&](int p, d2 (&x)[8]) __attribute__((always_inline)) {
+        const int shift = 32 - p * Bgbit;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const uint32_t ua = (dlo[r] >> shift) & maskBg, ub = (dhi[r] >> shift) & maskBg;
+            const uint32_t up = (dlo[r + 4] >> shift) & maskBg, uq = (dhi[r + 4] >> shift) & maskBg;
+            const double a = __hiloint2double(0x43300000, (int)ua) - bias1;
+            const double b = __hiloint2double(0x43300000, (int)ub) - bias1;
+            const double dm = __hiloint2double(0x43300000, (int)(up - uq + Bg)) - bias2;
+            const double dp = __hiloint2double(0x43300000, (int)(up + uq)) - bias2;
+            fwd_stage0(x[r], x[r + 4], a, b, dm, dp);
+        }
+        fwd_pass0_tail(x);
+    };
+    auto mac = [&](bool first, const d2 (&x)[8], const d2 (&b)[8], d2 (&acc_)[8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            if (first) {
+                acc_[r].x = EOC_FMA(-x[r].y, b[r].y, x[r].x * b[r].x);
+                acc_[r].y = EOC_FMA(x[r].y, b[r].x, x[r].x * b[r].y);
+            } else {
+                acc_[r].x = EOC_FMA(-x[r].y, b[r].y, EOC_FMA(x[r].x, b[r].x, acc_[r].x));
+                acc_[r].y = EOC_FMA(x[r].y, b[r].x, EOC_FMA(x[r].x, b[r].y, acc_[r].y));
+            }
+        }
+    };
+    // forward transforms of the l digits (two at a time, skewed on the one scratch; an odd last one alone) and the chain
+    // for the partner's output polynomial; the spectra stay in registers for the own chain
+    d2 xs[L][8], S[8], ra[8], rb[8], ut[8];
+#pragma unroll
+    for (int p0 = 0; p0 + 1 < L; p0 += 2) {
+        load_row(p0 + 1, 1 - h, ra);
+        load_row(p0 + 2, 1 - h, rb);
+        make_x0(p0 + 1, xs[p0]);
+        fft_fwd_rest_x2(xs[p0], xs[p0 + 1], [&]() __attribute__((always_inline)) { make_x0(p0 + 2, xs[p0 + 1]); }, s_tw, scr,
+                        lane);
+        mac(p0 == 0, xs[p0], ra, S);
+        mac(false, xs[p0 + 1], rb, S);
+    }
+    if constexpr ((L & 1) != 0) {
+        load_row(L, 1 - h, ra);
+        make_x0(L, xs[L - 1]);
+        fft_fwd_rest(xs[L - 1], s_tw, scr, lane);
+        mac(L == 1, xs[L - 1], ra, S);
+    }
+    load_row(1, h, ra);
+    if constexpr (L >= 2) load_row(2, h, rb);
+#pragma unroll
+    for (int r = 0; r < 8; r++) scr[r * 64 + lane] = S[r];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 8; r++) S[r] = scr_partner[r * 64 + lane]; // the chain of the other input polynomial
+    mac(false, xs[0], ra, S);
+    if constexpr (L >= 3) load_row(3, h, ra);
+    if constexpr (L >= 2) mac(false, xs[1], rb, S);
+    if constexpr (L >= 4) load_row(4, h, rb);
+    if constexpr (L >= 3) mac(false, xs[2], ra, S);
+    if constexpr (L >= 4) mac(false, xs[3], rb, S);
+    __syncthreads(); // the partner has read this wave's scratch before the inverse transform overwrites it
+    fft_inv_wave(S, ut, s_tw, s_twist, scr, lane);
+    if (!live) return;
+    int32_t *po = A.out + ix * A.out_x + iy * A.out_y + (size_t)h * kN;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int j = lane + 64 * r;
+        const d2 y = cmulc(S[r], ut[r]); // 1/512 is in the selector's image
+        po[j] = (int32_t)((uint32_t)pa[j] + wrap_trunc(y.x));
+        po[j + kNH] = (int32_t)((uint32_t)pa[j + kNH] + wrap_trunc(y.y));
+    }
+}
+
+// k_compact_expand's sibling behind a table read: sample (q, w), w < W, is slot w of query q's TLWE sample
+// `lists + q * list_stride` and becomes key-switch operand row q W + w (ubar) and output row q W + w (0, ..., 0, b').  The
+// same staging of c0 in LDS and the same lane-contiguous stores.  grid: x = ceil(W / kCompactSlotsPerWG), y = queries
+__global__ __launch_bounds__(256) void k_tlwe_extract(const int32_t *__restrict__ lists, size_t list_stride, uint32_t W,
+                                                      uint32_t *__restrict__ ubar, int32_t *__restrict__ out, int n,
+                                                      uint32_t prec_offset)
+{
+    __shared__ int32_t s_c0[kN];
+    const int32_t *list = lists + (size_t)blockIdx.y * list_stride;
+    for (int k = threadIdx.x; k < kN; k += 256) s_c0[k] = list[k];
+    __syncthreads();
+    for (int q = 0; q < kCompactSlotsPerWG; q++) {
+        const uint32_t j = blockIdx.x * kCompactSlotsPerWG + q;
+        if (j >= W) break;
+        const size_t s = (size_t)blockIdx.y * W + j;
+        uint32_t *row = ubar + s * kN;
+        for (int i = threadIdx.x; i < kN; i += 256) {
+            const uint32_t v = (uint32_t)s_c0[((int)j - i) & (kN - 1)];
+            row[i] = (i <= (int)j ? v : 0u - v) + prec_offset;
+        }
+        int32_t *o = out + s * (n + 1);
+        for (int m = threadIdx.x; m < n; m += 256) o[m] = 0;
+        if (threadIdx.x == 0) o[n] = list[kN + j];
+    }
+}
+
 } // namespace eoc

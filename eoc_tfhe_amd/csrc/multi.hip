@@ -456,6 +456,37 @@ int slot_compact_block(Slot &s, const int32_t *lists, int32_t *out, size_t lo, s
     return slot_finish(st, run());
 }
 
+// one device's block [lo, hi) of the queries of an encrypted-index table read: the whole table and the block's
+// selectors in torus form in, converted on the device, out [queries][W][stride] on the host
+int slot_table_read_block(Slot &s, const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors,
+                          int32_t *out, size_t lo, size_t hi, size_t stride_ints)
+{
+    const size_t blk = hi - lo;
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t depth = (size_t)log2_lists + 10 - log2_width, W = (size_t)1 << log2_width;
+    const size_t tab_ints = ((size_t)2 * EOC_N) << log2_lists;
+    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth; // the converted form takes twice the ints
+    const size_t need = tab_ints + 3 * nsel * sel_ints + blk * W * stride_ints;
+    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    if (rc) return rc;
+    int32_t *d_tab = s.d_lut, *d_sel = d_tab + tab_ints, *d_fft = d_sel + nsel * sel_ints, *d_out = d_fft + 2 * nsel * sel_ints;
+    hipStream_t st = s.st[0];
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_tab, table, tab_ints * 4, hipMemcpyHostToDevice, st));
+        if (nsel) {
+            HIP_TRY(hipMemcpyAsync(d_sel, selectors + lo * depth * sel_ints, nsel * sel_ints * 4, hipMemcpyHostToDevice, st));
+            int r = eoc_tgsw_to_fft_device(s.e, d_sel, nsel, d_fft, st);
+            if (r) return r;
+        }
+        int r = eoc_table_read_device(s.e, d_tab, log2_lists, log2_width, d_fft, blk, d_out, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(out + lo * W * stride_ints, d_out, blk * W * stride_ints * 4, hipMemcpyDeviceToHost, st));
+        return EOC_OK;
+    };
+    return slot_finish(st, run());
+}
+
 void destroy_slots_locked()
 {
     for (auto &s : G.slots)
@@ -1195,6 +1226,25 @@ int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out)
     const size_t stride = (size_t)G.p.n + 1;
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
         return slot_compact_block(G.slots[i], lists, out, lo, hi, stride);
+    });
+}
+
+// eoc_table_read's engine half (host.cpp has checked the arguments, holds the global key's lock and has brought the engines up)
+int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries,
+                           int32_t *out)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_table_read: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        return EOC_ERR_NO_DEVICE;
+    }
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    const size_t stride = (size_t)G.p.n + 1;
+    return for_each_block(queries, [=](int i, size_t lo, size_t hi) {
+        return slot_table_read_block(G.slots[i], table, log2_lists, log2_width, selectors, out, lo, hi, stride);
     });
 }
 

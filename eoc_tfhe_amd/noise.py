@@ -348,3 +348,63 @@ def compact_var(params, tlwe_key, pk=None):
     sig2 = _sig2(params)
     ue = float((pk_noise(pk, tlwe_key) ** 2).sum()) / 4.0 if pk is not None else N * sig2 / 4.0
     return ue + sig2 + float(s1.sum()) * sig2
+
+
+# ---- leveled operations: CMux and encrypted-index table reads ------------------------------------------------
+def _Jv(tlwe_key):
+    """J * (1 - s') in Z[X]/(X^N + 1), J = 1 + X + ... + X^(N-1), as `predict` forms it: about 1 + |s'| - 2 (ones of s' up to j)"""
+    v = -np.asarray(tlwe_key, np.int64).astype(np.float64)
+    v[0] += 1.0
+    pre = np.cumsum(v)
+    return 2.0 * pre - pre[-1]
+
+
+def cmux_var(params, tlwe_key, bit=1):
+    """variance (torus units) one CMux  out = A + C (x) (B - A)  adds to every coefficient of the phase, for a fixed key, over
+    the selector's randomness and pseudo-random full-range inputs -- the two per-step terms of `predict`:
+      rows       2l N E[d^2] sigma_eff^2: the 2l TLWE-zero rows of the selector times the digits (E[d^2] = (Bg^2 + 2) / 12,
+                 sigma_eff^2 the truncation-corrected variance of gaussian32 at bk_stdev)
+      remainder  (1 + |s'|) q^2 / 12, q = Bg^-l: what the decomposition drops, low_b - low_a s' -- only where the bit is 1
+                 (a selector of 0 multiplies it by nothing)
+    This is the spread around the CMux's mean.  The mean is not zero where the bit is 1: see cmux_mean."""
+    l, Bgbit = int(params.l), int(params.Bgbit)
+    Bg = 1 << Bgbit
+    q = 2.0 ** (-l * Bgbit)
+    hw = int(np.asarray(tlwe_key, np.int64).sum())
+    return 2 * l * N * ((Bg * Bg + 2) / 12.0) * _sig2(params) + (1 if bit else 0) * (1 + hw) * q * q / 12.0
+
+
+def cmux_mean(params, tlwe_key, slot=0, bit=1):
+    """mean error (torus units) of coefficient `slot` behind one CMux whose bit is 1: the decomposition TRUNCATES, the dropped
+    parts low_x[j] are uniform on [0, q) with mean q/2, and the output loses low_b - low_a s': -(q/2) (J (1 - s'))[slot], the
+    polynomial whose coefficient 0 is the blind rotation's M_BR (`predict`).  About -(q/2) (1 + |s'|) at slot 0, falling
+    linearly to +(q/2) (|s'| - 1) at slot N - 1.  `slot` may be an array.  Zero where the bit is 0."""
+    q = 2.0 ** (-int(params.l) * int(params.Bgbit))
+    return -(q / 2) * _Jv(tlwe_key)[np.asarray(slot)] * (1 if bit else 0)
+
+
+def table_read_var(params, lwe_key, tlwe_key, depth, table_var=0.0, ksk=None):
+    """variance (torus units) of a table-read output (eoc_table_read_device) around its mean: table_var (0 for a trivial
+    table, compact_var for a public-key-encrypted one) + depth x cmux_var + the key switch's (`predict`; `ksk` as there)"""
+    return float(table_var) + int(depth) * cmux_var(params, tlwe_key) + predict(params, lwe_key, tlwe_key, ksk)["ks_var"]
+
+
+def table_read_slots(index, log2_lists, log2_width):
+    """the slot offsets at which the CMuxes of a read with index bit 1 leave their mean, for output slot 0: a tree level does
+    not move slots, rotation i (bit i set) moves slot W 2^i to 0.  Returns the list of slots, seen from output slot 0."""
+    d, r, W = int(log2_lists), 10 - int(log2_width), 1 << int(log2_width)
+    idx = int(index)
+    rot_bits = [i for i in range(r) if (idx >> i) & 1]
+    s = W * (idx & ((1 << r) - 1))
+    out = [s] * sum((idx >> (r + v)) & 1 for v in range(d))     # tree levels act on the slot the entry starts at
+    for k, i in enumerate(rot_bits):                             # behind rotation i the entry starts at the sum of the later ones
+        out.append(sum(W << j for j in rot_bits[k + 1:]))
+    return out
+
+
+def table_read_mean(params, tlwe_key, index, log2_lists, log2_width, w=0):
+    """mean error (torus units) of slot w of the read of entry `index`, before the key switch's own mean: the sum of cmux_mean
+    over the CMuxes whose bit is 1, each at the slot the entry occupied behind it.  Up to depth x (q/2) (1 + |s'|) in
+    magnitude: unlike a blind rotation's, these means are not spread by later rotations."""
+    slots = np.asarray(table_read_slots(index, log2_lists, log2_width), np.int64) + int(w)
+    return float(cmux_mean(params, tlwe_key, slots).sum()) if len(slots) else 0.0

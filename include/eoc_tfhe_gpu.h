@@ -657,6 +657,57 @@ int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *out);
 /* EOCPK1 blob of the global secret key (key mode 1): bytes needed, 0 without a secret key; fills buf when cap suffices */
 size_t eoc_global_public_key_export(void *buf, size_t cap);
 
+/* ------------------------------------------------------------------------------------------------
+ * leveled operations: TGSW selectors, CMux, and reading entry idx of a table when idx is encrypted.
+ *   selector    a TGSW sample of one bit in torus form, [2l][2][N] int32: the shape and convention of one bk[i] block --
+ *               2l TLWE encryptions of 0 under s' at bk_stdev, mask first; for bit 1, row (q, p) carries 2^(32 - p Bgbit) on
+ *               the constant coefficient of polynomial q.  32 KiB (Set A) / 48 KiB (Set B).  Row `row` of selector s uses
+ *               stream tag 8 (TgswEnc), index (first_idx + s) 2l + row, with make_bk's counters (mask word j at j, Gaussian
+ *               j at N + 2j).  eoc_tgsw_encrypt_bits is the REPRODUCIBLE / TEST mode and is refused (EOC_ERR_STATE) for a
+ *               secure-mode key; the _keyed form draws ChaCha20 streams under the caller's 256-bit key.  NEVER encrypt two
+ *               selectors under one (key, index) pair: they share masks and noise, and their difference is the gadget of
+ *               the bit difference in the clear.  The Python wrapper of the secure path draws a fresh key per call.
+ *   security    selectors are ring-LWE samples of the bootstrapping key's ring at its noise: the assumption the published
+ *               bootstrapping key already rests on.
+ *   table       TLWE samples [2^d][2][N] holding N slots each: compact lists (eoc_pk_encrypt_*), or public data as trivial
+ *               samples (eoc_table_trivial: c0 = 0, c1 = the messages; list L holds messages L N ... L N + N - 1).
+ *   device form eoc_tgsw_to_fft_device: the key-load transform; a converted selector is laid out like one row block of the
+ *               bootstrapping key's FFT image, [2l][2][512] complex f64 scaled by 2^-9 (eoc_tgsw_fft_bytes: 64 / 96 KiB).
+ *   CMux        eoc_cmux_device: out[i] = in0[i] + C[i] (x) (in1[i] - in0[i]) -- in1 if the bit is 1, in0 otherwise, plus
+ *               noise.cmux_var.  Needs no key.  `out` may not overlap the inputs.
+ *   read        eoc_table_read_device: W = 2^log2_width consecutive slots form an entry, the table has 2^(d + r) entries,
+ *               d = log2_lists in [0, 12], r = 10 - log2_width in [0, 10].  Index bits LSB first: bits 0 .. r-1 pick the entry
+ *               inside a list (slot offset W (idx mod 2^r)), bits r .. r+d-1 the list; d_sel_fft is [queries][r + d] converted
+ *               selectors in that order.  First the CMux tree over the lists (level v under bit r + v), then r rotations by
+ *               X^(-W 2^i) under bit i (ascending), then slots 0 .. W-1 are extracted and key-switched: d_out is
+ *               [queries][W][n+1], ordinary gate / LUT inputs whose error is below a gate output's (noise.table_read_var).
+ *               Only the key switch needs the cloud key (EOC_ERR_NO_KEY without one).  Workspace: two buffers of
+ *               queries 2^(d-1) and queries 2^(d-2) TLWE samples, grown by eoc_engine_reserve's rule (EOC_ERR_STATE under
+ *               capture); queries are sliced so that both stay within 256 MiB (EOC_TFHE_TABLE_WS_BYTES at engine creation
+ *               changes the budget and no result; a budget below one query's need is EOC_ERR_ARG) and a slice extracts at
+ *               most 2^20 samples.  Stats: keyswitches += queries W; eoc_engine_cmux_launches counts the k_cmux launches
+ *               (r + d per slice); eoc_engine_kernel_times books them under the blind rotation.
+ * EOC_ERR_ARG for a null pointer, log2_lists outside [0, 12] or log2_width outside [0, 10]; count / queries 0 is a no-op. */
+size_t eoc_tgsw_len(const eoc_params *p);      /* int32 count of one selector: 2l * 2 * N */
+int eoc_tgsw_encrypt_bits(const eoc_secret_key *sk, uint64_t enc_seed, uint64_t first_idx, const uint8_t *bits, size_t count,
+                          int32_t *out);
+int eoc_tgsw_encrypt_bits_keyed(const eoc_secret_key *sk, const uint8_t enc_key[32], uint64_t first_idx, const uint8_t *bits,
+                                size_t count, int32_t *out);
+/* on the global secret key, with its encryption randomness (eoc_global_encrypt_bits); EOC_ERR_NO_KEY on a cloud-key-only context */
+int eoc_global_tgsw_encrypt_bits(const uint8_t *bits, size_t count, int32_t *out);
+int eoc_table_trivial(const int32_t *messages, size_t count, int32_t *lists); /* lists [ceil(count / N)][2][N] */
+size_t eoc_tgsw_fft_bytes(const eoc_params *p);   /* 2l * 2 * 512 * 16 = eoc_bkfft_bytes(p) / n */
+int eoc_tgsw_to_fft_device(eoc_engine *e, const int32_t *d_tgsw, size_t count, void *d_fft, void *hip_stream);
+int eoc_cmux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in0, const int32_t *d_in1, int32_t *d_out,
+                    size_t count, void *hip_stream);
+int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
+                          size_t queries, int32_t *d_out, void *hip_stream);
+uint64_t eoc_engine_cmux_launches(eoc_engine *e);
+/* the read on the global context (host buffers, synchronous): table [2^d][2][N], selectors in TORUS form [queries][r + d][2l][2][N],
+ * out [queries][W][n+1].  Queries are cut into eoc_shard_range blocks, one per engine; every engine receives the whole table
+ * and converts its own selectors.  The cloud key alone suffices (key mode 2). */
+int eoc_table_read(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif
