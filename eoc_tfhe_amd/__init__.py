@@ -265,6 +265,23 @@ def lib():
         "eoc_table_read_device": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp]),
         "eoc_engine_cmux_launches": (u64, [vp]),
         "eoc_table_read": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp]),
+        # packing key switch: LWE samples -> compact lists
+        "eoc_packing_key_blob_bytes": (sz, [PP]),
+        "eoc_packing_key_export": (C.c_int, [vp, vp, sz]),
+        "eoc_packing_key_blob_params": (C.c_int, [vp, sz, PP]),
+        "eoc_engine_set_packing_key": (C.c_int, [vp, vp, sz]),
+        "eoc_pack_device": (C.c_int, [vp, vp, sz, vp, vp]),
+        "eoc_engine_pack_launches": (u64, [vp]),
+        "eoc_engine_packed_samples": (u64, [vp]),
+        "eoc_list_phases": (C.c_int, [vp, vp, sz, vp]),
+        "eoc_decrypt_list_bits": (C.c_int, [vp, vp, sz, vp]),
+        "eoc_decrypt_list_ints": (C.c_int, [vp, C.c_int, vp, sz, vp]),
+        "eoc_global_list_phases": (C.c_int, [vp, sz, vp]),
+        "eoc_global_decrypt_list_bits": (C.c_int, [vp, sz, vp]),
+        "eoc_global_decrypt_list_ints": (C.c_int, [C.c_int, vp, sz, vp]),
+        "eoc_global_packing_key_export": (sz, [vp, sz]),
+        "eoc_global_import_packing_key_blob": (C.c_int, [vp, sz]),
+        "eoc_pack": (C.c_int, [vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -393,6 +410,51 @@ class SecretKey:
         buf = (C.c_ubyte * need)()
         _check(self.L.eoc_public_key_export(self.h, buf, need), "eoc_public_key_export")
         return bytes(buf)
+
+    def packing_key_bytes(self):
+        """EOCPKS1 blob (params | t, basebit | rows [n][4][2][N]; 16.4 MB on Set A, 20.6 MB on Set B): the packing key of this
+        secret key, with which a server packs LWE samples into compact lists (Engine.load_packing_key)"""
+        need = self.L.eoc_packing_key_blob_bytes(C.byref(self.params))
+        buf = np.empty(need, np.uint8)
+        _check(self.L.eoc_packing_key_export(self.h, buf.ctypes.data, need), "eoc_packing_key_export")
+        return buf
+
+    @staticmethod
+    def _lists(lists):
+        lists = np.ascontiguousarray(lists, np.int32)
+        if lists.ndim == 2:
+            lists = lists[None]
+        if lists.ndim != 3 or lists.shape[1:] != (2, N):
+            raise EocError(f"lists must be [L][2][{N}], got {lists.shape}")
+        return lists
+
+    def list_phases(self, lists):
+        """phases c1 - c0 s' of every slot of compact lists [L][2][N] -> [L][N] int32 (eoc_list_phases)"""
+        lists = self._lists(lists)
+        out = np.empty((lists.shape[0], N), np.int32)
+        _check(self.L.eoc_list_phases(self.h, lists.ctypes.data, lists.shape[0], out.ctypes.data), "eoc_list_phases")
+        return out
+
+    def _decrypt_list(self, lists, count, p):
+        lists = self._lists(lists)
+        count = lists.shape[0] * N if count is None else int(count)
+        if count > lists.shape[0] * N:
+            raise EocError(f"{lists.shape[0]} lists hold at most {lists.shape[0] * N} messages, not {count}")
+        out = np.empty(count, np.uint8)
+        if p is None:
+            _check(self.L.eoc_decrypt_list_bits(self.h, lists.ctypes.data, count, out.ctypes.data), "eoc_decrypt_list_bits")
+        else:
+            _check(self.L.eoc_decrypt_list_ints(self.h, int(p), lists.ctypes.data, count, out.ctypes.data),
+                   "eoc_decrypt_list_ints")
+        return out
+
+    def decrypt_list_bits(self, lists, count=None):
+        """the first `count` slots of compact lists [L][2][N] as bits (phase > 0), count = L N unless given"""
+        return self._decrypt_list(lists, count, None)
+
+    def decrypt_list_ints(self, lists, p, count=None):
+        """the first `count` slots of compact lists as integers of Z_p (decrypt_ints' rule)"""
+        return self._decrypt_list(lists, count, p)
 
     def encrypt_bits(self, bits, enc_seed, first_idx=0):
         bits = np.ascontiguousarray(np.asarray(bits).ravel(), np.uint8)
@@ -750,6 +812,17 @@ class Engine:
         _check(self.L.eoc_table_read_device(self.h, d_table, int(log2_lists), int(log2_width), d_sel_fft, queries, d_out,
                                             stream), "eoc_table_read_device")
 
+    def load_packing_key(self, blob):
+        """Install an EOCPKS1 blob (SecretKey.packing_key_bytes) as this engine's packing key (eoc_engine_set_packing_key);
+        replaces an earlier one.  The blob's parameters must be the engine's."""
+        blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8)
+        _check(self.L.eoc_engine_set_packing_key(self.h, blob.ctypes.data, blob.size), "eoc_engine_set_packing_key")
+
+    def pack_device(self, d_in, count, d_lists, stream=None):
+        """LWE samples -> compact lists (eoc_pack_device): d_in [count][n+1], d_lists [ceil(count / N)][2][N]; sample i goes
+        to slot i mod N of list i / N.  Needs the packing key alone."""
+        _check(self.L.eoc_pack_device(self.h, d_in, count, d_lists, stream), "eoc_pack_device")
+
     def resident_jobs(self):
         """blind rotations that fill the device in one launch (8 x CUs where the one-wave-per-ciphertext kernel applies,
         4 x otherwise): cut long jobs at multiples of this"""
@@ -762,7 +835,9 @@ class Engine:
                     br_launches=int(self.L.eoc_engine_blind_rotate_launches(self.h)),
                     br_wide_launches=int(self.L.eoc_engine_blind_rotate_wide_launches(self.h)),
                     ks_mfma_launches=int(self.L.eoc_engine_keyswitch_mfma_launches(self.h)),
-                    cmux_launches=int(self.L.eoc_engine_cmux_launches(self.h)))
+                    cmux_launches=int(self.L.eoc_engine_cmux_launches(self.h)),
+                    pack_launches=int(self.L.eoc_engine_pack_launches(self.h)),
+                    packed_samples=int(self.L.eoc_engine_packed_samples(self.h)))
 
 
 def circuit_bootstraps(gates):
@@ -1050,6 +1125,23 @@ def table_read(table, log2_lists, log2_width, selectors):
     _check(lib().eoc_table_read(table.ctypes.data, d, lw, selectors.ctypes.data, selectors.shape[0], out.ctypes.data),
            "eoc_table_read")
     return out
+
+
+def pack(cts):
+    """eoc_pack on the global context (the packing key alone suffices: global_import_packing_key_blob): LWE samples
+    [count][n+1] -> compact lists [ceil(count / N)][2][N], sample i in slot i mod N of list i / N"""
+    cts = np.ascontiguousarray(cts, np.int32)
+    if cts.ndim != 2:
+        raise EocError(f"pack: samples must be [count][n+1], got {cts.shape}")
+    out = np.empty((max(1, -(-cts.shape[0] // N)), 2, N), np.int32)
+    _check(lib().eoc_pack(cts.ctypes.data, cts.shape[0], out.ctypes.data), "eoc_pack")
+    return out[:-(-cts.shape[0] // N)]
+
+
+def global_import_packing_key_blob(blob):
+    """Give the global context's engines an EOCPKS1 packing key (works behind a cloud key alone, key mode 2)"""
+    blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8)
+    _check(lib().eoc_global_import_packing_key_blob(blob.ctypes.data, blob.size), "eoc_global_import_packing_key_blob")
 
 
 def global_public_key_export():

@@ -28,3 +28,11 @@ int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out)
 // eoc_table_read's GPU half on the process-global engines (multi.hip): queries cut into eoc_shard_range blocks, one per engine
 int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries,
                            int32_t *out);
+// packing key switch: a whole EOCPKS1 blob with t = 4, basebit = 4 -> its parameters and the rows [n][4][2][N]
+// in torus form (a pointer into the blob); false for anything else (legacy.cpp)
+struct eoc_params;
+bool eoc_packing_key_blob_rows(const void *buf, size_t len, eoc_params *p, const int32_t **rows);
+// eoc_pack's GPU half on the process-global engines (multi.hip): WHOLE lists cut into eoc_shard_range blocks, one per engine
+int eoc_pack_engines(const int32_t *cts, size_t count, int32_t *lists);
+// the packing key on every process-global engine (multi.hip)
+int eoc_set_packing_key_engines(const void *blob, size_t len);

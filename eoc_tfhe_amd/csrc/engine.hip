@@ -97,6 +97,14 @@ struct eoc_engine {
     size_t cmux_cap[2] = {0, 0};
     size_t table_ws_bytes = (size_t)256 << 20;
     uint64_t cmux_launches = 0; // k_cmux launches
+    // packing key switch: the packing key's image [n][4][2][512] complex scaled by 2^-9 (the engine's own),
+    // the gathered mask columns [lists of a slice][n][N], and the byte budget that buffer is held to (lists are sliced to
+    // fit; EOC_TFHE_PACK_WS_BYTES, diagnostics)
+    d2 *d_pks = nullptr;
+    int32_t *d_pack_cols = nullptr;
+    size_t pack_cap = 0; // lists
+    size_t pack_ws_bytes = (size_t)256 << 20;
+    uint64_t pack_launches = 0, packed_samples = 0; // k_pack_rows launches; samples packed
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
     struct Span { hipEvent_t a, b; int kind; };
@@ -268,6 +276,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
         if (const char *s = getenv("EOC_TFHE_BR_TABLES_LDS")) e->br_tables_lds = atoi(s) != 0;
         if (const char *s = getenv("EOC_TFHE_INT_SLICE_ROWS")) e->int_slice_rows = atoi(s);
         if (const char *s = getenv("EOC_TFHE_TABLE_WS_BYTES")) e->table_ws_bytes = (size_t)strtoull(s, nullptr, 10);
+        if (const char *s = getenv("EOC_TFHE_PACK_WS_BYTES")) e->pack_ws_bytes = (size_t)strtoull(s, nullptr, 10);
     }
     // the key-switch kernel uses > 64 KiB of dynamic LDS: raise the limit once, here, not on the launch path
     // (a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to k_keyswitch_generic: slow, exact)
@@ -291,6 +300,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
     EOC_CMUX_ATTR(3, 0);
     EOC_CMUX_ATTR(4, 0);
 #undef EOC_CMUX_ATTR
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
     (void)hipGetLastError();
     *out = e;
     return EOC_OK;
@@ -327,6 +337,8 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
     hipFree(e->d_ksl);
     hipFree(e->d_cmux[0]);
     hipFree(e->d_cmux[1]);
+    hipFree(e->d_pks);
+    hipFree(e->d_pack_cols);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -1632,6 +1644,124 @@ extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int 
     }
     return EOC_OK;
 }
+
+// ---- packing key switch: LWE samples -> compact TLWE lists -------------------
+static_assert(kPackT == EOC_PACK_T && kPackBasebit == EOC_PACK_BASEBIT, "the kernels' decomposition is the format's");
+extern "C" int eoc_engine_set_packing_key(eoc_engine *e, const void *blob, size_t len)
+{
+    eoc_params bp;
+    const int32_t *rows = nullptr;
+    if (!e || !eoc_packing_key_blob_rows(blob, len, &bp, &rows)) {
+        eoc_set_error("eoc_engine_set_packing_key: null argument or not a whole EOCPKS1 blob (t = %d, basebit = %d)", kPackT,
+                      kPackBasebit);
+        return EOC_ERR_ARG;
+    }
+    const eoc_params &p = e->p;
+    if (bp.n != p.n || bp.l != p.l || bp.Bgbit != p.Bgbit || bp.ks_t != p.ks_t || bp.ks_basebit != p.ks_basebit ||
+        bp.ks_stdev != p.ks_stdev || bp.bk_stdev != p.bk_stdev) {
+        eoc_set_error("eoc_engine_set_packing_key: the blob's parameters (n = %d, l = %d) are not the engine's (n = %d, l = %d)",
+                      bp.n, bp.l, p.n, p.l);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t npoly = (size_t)p.n * kPackT * 2;
+    HIP_TRY(hipDeviceSynchronize()); // nothing in flight may still read the image that is about to be replaced
+    hipFree(e->d_pks);
+    e->d_pks = nullptr;
+    int32_t *d_rows = nullptr;
+    d2 *d_img = nullptr;
+    HIP_TRY(hipMalloc(&d_rows, npoly * kN * sizeof(int32_t)));
+    if (hipMalloc(&d_img, npoly * kNH * sizeof(d2)) != hipSuccess) {
+        hipFree(d_rows);
+        eoc_set_error("eoc_engine_set_packing_key: out of device memory");
+        return EOC_ERR_HIP;
+    }
+    int rc = EOC_OK;
+    if (hipMemcpy(d_rows, rows, npoly * kN * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = EOC_ERR_HIP;
+    // the key-load transform (build_cloud_key_images, eoc_tgsw_to_fft_device); NULL stream, drained below
+    if (!rc) rc = launch_fft_fwd(e, d_rows, reinterpret_cast<double *>(d_img), npoly, 0x1p-9, nullptr);
+    if (hipDeviceSynchronize() != hipSuccess && !rc) rc = EOC_ERR_HIP;
+    hipFree(d_rows);
+    if (rc) {
+        hipFree(d_img);
+        eoc_set_error("eoc_engine_set_packing_key: upload or conversion failed");
+        return rc;
+    }
+    e->d_pks = d_img;
+    return EOC_OK;
+}
+
+// the gathered mask columns, grown by the workspace's rule (ensure_ws): never under capture, the device drained first
+static int ensure_pack_ws(eoc_engine *e, size_t lists, hipStream_t st)
+{
+    if (lists <= e->pack_cap) return EOC_OK;
+    if (stream_is_capturing(st)) {
+        eoc_set_error("graph capture: the packing workspace would have to grow (%zu > %zu lists); run one call of the captured "
+                      "shape before capturing", lists, e->pack_cap);
+        return EOC_ERR_STATE;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    hipFree(e->d_pack_cols);
+    e->d_pack_cols = nullptr;
+    e->pack_cap = 0;
+    HIP_TRY(hipMalloc(&e->d_pack_cols, lists * (size_t)e->p.n * kN * sizeof(int32_t)));
+    e->pack_cap = lists;
+    e->ws_grows++;
+    return EOC_OK;
+}
+
+// k_pack_gather lays the mask columns out as polynomials and starts every list as (0, B); k_pack_rows subtracts the chunks.
+// All arguments travel as kernel arguments: no descriptor ring slot.  Lists are sliced by the byte budget of the columns.
+extern "C" int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count, int32_t *d_lists, void *hip_stream)
+{
+    if (!e || !d_in || !d_lists) {
+        eoc_set_error("eoc_pack_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->d_pks) {
+        eoc_set_error("eoc_pack_device: no packing key loaded (eoc_engine_set_packing_key)");
+        return EOC_ERR_NO_KEY;
+    }
+    if (!count) return EOC_OK;
+    const size_t n = (size_t)e->p.n, per_list = n * kN * sizeof(int32_t), n_lists = (count + kN - 1) / kN;
+    if (e->pack_ws_bytes < per_list) {
+        eoc_set_error("eoc_pack_device: one list needs %zu bytes of workspace, the budget (EOC_TFHE_PACK_WS_BYTES) is %zu",
+                      per_list, e->pack_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t ls = std::min({n_lists, e->pack_ws_bytes / per_list, (size_t)65535}); // grid z
+    int rc = ensure_pack_ws(e, ls, st);
+    if (rc) return rc;
+    const uint32_t nchunks = (uint32_t)((n + kPackChunk - 1) / kPackChunk);
+    for (size_t l0 = 0; l0 < n_lists; l0 += ls) {
+        const size_t L = std::min(ls, n_lists - l0), cnt = std::min(count - l0 * kN, L * kN);
+        const int32_t *in = d_in + l0 * kN * (n + 1);
+        int32_t *lists = d_lists + l0 * 2 * kN;
+        {
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            hipLaunchKernelGGL(k_pack_gather, dim3(kN / kPackTile, (unsigned)((n + 1 + kPackTile - 1) / kPackTile), (unsigned)L),
+                               dim3(256), 0, st, in, cnt, (int)n, e->d_pack_cols, lists);
+            HIP_TRY(hipGetLastError());
+        }
+        {
+            const uint32_t items = (uint32_t)(L * nchunks);
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            hipLaunchKernelGGL(k_pack_rows, dim3((items + kPackWavesPerWG - 1) / kPackWavesPerWG), dim3(64 * kPackWavesPerWG),
+                               kPackLds, st, (const int32_t *)e->d_pack_cols, (const d2 *)e->d_pks, lists, (int)n, nchunks, items,
+                               (const d2 *)e->d_tw, (const d2 *)e->d_twist);
+            HIP_TRY(hipGetLastError());
+        }
+        e->pack_launches++;
+    }
+    e->packed_samples += count;
+    return EOC_OK;
+}
+extern "C" uint64_t eoc_engine_pack_launches(eoc_engine *e) { return e ? e->pack_launches : 0; }
+extern "C" uint64_t eoc_engine_packed_samples(eoc_engine *e) { return e ? e->packed_samples : 0; }
 
 // ---- programmable bootstrapping ----------------------------------------
 // Table lookups, n_tables = 0: one level of n_luts x rows jobs, [table][row]: one OP_RAW descriptor per table (all read the

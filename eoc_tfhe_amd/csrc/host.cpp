@@ -167,7 +167,7 @@ extern "C" void eoc_dbg_chacha20_block(const uint8_t key[32], uint32_t counter, 
 namespace {
 
 struct Stream {
-    enum Tag : uint32_t { LweKey = 1, TlweKey = 2, Bk = 3, Ksk = 4, Enc = 5, PublicKey = 6, CompactEnc = 7, TgswEnc = 8 };
+    enum Tag : uint32_t { LweKey = 1, TlweKey = 2, Bk = 3, Ksk = 4, Enc = 5, PublicKey = 6, CompactEnc = 7, TgswEnc = 8, PackKsk = 9 };
     bool secure = false;
     uint64_t key = 0;           // v1
     uint32_t sub[8];            // v2: this stream's ChaCha20 key
@@ -365,6 +365,73 @@ extern "C" int eoc_table_trivial(const int32_t *messages, size_t count, int32_t 
         }
     }
     return EOC_OK;
+}
+
+// ---- packing key switch (include/eoc_tfhe_gpu.h) -------------------------------------------------------------
+namespace eoc_host {
+// Row (m, j), j = 1 .. 4: tgsw_row's TLWE encryption of 0 under s' (stream (key's source, PackKsk, 4 m + j - 1)) plus
+// s_m 2^(32 - 4j) on the constant coefficient of b.  rows [n][4][2][N]
+void make_packing_key(const eoc_secret_key *sk, int32_t *rows)
+{
+    const eoc_params &p = sk->p;
+    const std::vector<int> ones = tlwe_ones(*sk);
+    const int nrows = p.n * EOC_PACK_T;
+#pragma omp parallel for schedule(dynamic, 8) num_threads(usable_threads())
+    for (int ir = 0; ir < nrows; ir++) {
+        const int m = ir / EOC_PACK_T, j = ir % EOC_PACK_T + 1;
+        int32_t *row = rows + size_t(ir) * 2 * EOC_N;
+        tgsw_row(p, ones, Stream(*sk, Stream::PackKsk, uint64_t(ir)), 0, false, row);
+        if (sk->lwe[m]) row[EOC_N] = int32_t(uint32_t(row[EOC_N]) + (1u << (32 - EOC_PACK_BASEBIT * j)));
+    }
+}
+} // namespace eoc_host
+
+// phases of the slots of TLWE lists under s': c1 - c0 s' (a sum of signed rotations of c0)
+extern "C" int eoc_list_phases(const eoc_secret_key *sk, const int32_t *lists, size_t n_lists, int32_t *phases)
+{
+    if (!sk || !lists || !phases) {
+        eoc_set_error("eoc_list_phases: null argument");
+        return EOC_ERR_ARG;
+    }
+    const std::vector<int> ones = tlwe_ones(*sk);
+#pragma omp parallel for schedule(static) num_threads(usable_threads()) if (n_lists >= 2)
+    for (size_t L = 0; L < n_lists; L++) {
+        const uint32_t *c0 = reinterpret_cast<const uint32_t *>(lists + L * 2 * EOC_N), *c1 = c0 + EOC_N;
+        uint32_t *ph = reinterpret_cast<uint32_t *>(phases + L * EOC_N);
+        for (int j = 0; j < EOC_N; j++) ph[j] = c1[j];
+        for (int m : ones) {
+            const uint32_t *src = c0 + (EOC_N - m);
+            for (int j = 0; j < m; j++) ph[j] += src[j];
+            for (int j = m; j < EOC_N; j++) ph[j] -= c0[j - m];
+        }
+    }
+    return EOC_OK;
+}
+static int decrypt_list(const char *what, const eoc_secret_key *sk, int p, const int32_t *lists, size_t count, uint8_t *out)
+{
+    if (!sk || !lists || !out || (p && !(p == 2 || p == 4 || p == 8))) {
+        eoc_set_error("%s: null argument or a message space that is not one of 2, 4, 8", what);
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    const size_t n_lists = (count + EOC_N - 1) / EOC_N;
+    std::vector<int32_t> ph(n_lists * EOC_N);
+    int rc = eoc_list_phases(sk, lists, n_lists, ph.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < count; i++) {
+        if (!p) out[i] = ph[i] > 0;
+        else out[i] = (uint8_t)((((uint64_t)(uint32_t)ph[i] * (2u * (unsigned)p) + (1ull << 31)) >> 32) % (unsigned)p);
+    }
+    return EOC_OK;
+}
+extern "C" int eoc_decrypt_list_bits(const eoc_secret_key *sk, const int32_t *lists, size_t count, uint8_t *bits)
+{
+    return decrypt_list("eoc_decrypt_list_bits", sk, 0, lists, count, bits);
+}
+extern "C" int eoc_decrypt_list_ints(const eoc_secret_key *sk, int p, const int32_t *lists, size_t count, uint8_t *values)
+{
+    if (!p) p = -1;
+    return decrypt_list("eoc_decrypt_list_ints", sk, p, lists, count, values);
 }
 
 static int keygen_common(const eoc_params *p, uint64_t seed, const uint8_t *master, int with_cloud_key, eoc_secret_key **out)
@@ -1038,6 +1105,63 @@ extern "C" int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *o
         if (rc) return rc;
     }
     return eoc_compact_expand_engines(lists, count, out);
+}
+// ---- packing key switch on the global context ----
+static int global_list_call(const int32_t *lists, size_t count, void *out, int p, int what)
+{
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (!c.sk) {
+        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
+        return EOC_ERR_NO_KEY;
+    }
+    if (what == 0) return eoc_list_phases(c.sk, lists, count, static_cast<int32_t *>(out));
+    if (what == 1) return eoc_decrypt_list_bits(c.sk, lists, count, static_cast<uint8_t *>(out));
+    return eoc_decrypt_list_ints(c.sk, p, lists, count, static_cast<uint8_t *>(out));
+}
+extern "C" int eoc_global_list_phases(const int32_t *lists, size_t n_lists, int32_t *phases)
+{
+    return global_list_call(lists, n_lists, phases, 0, 0);
+}
+extern "C" int eoc_global_decrypt_list_bits(const int32_t *lists, size_t count, uint8_t *bits)
+{
+    return global_list_call(lists, count, bits, 0, 1);
+}
+extern "C" int eoc_global_decrypt_list_ints(int p, const int32_t *lists, size_t count, uint8_t *values)
+{
+    return global_list_call(lists, count, values, p, 2);
+}
+// the packing key of the global context's engines: works behind a cloud key alone (key mode 2); the blob's parameters must be
+// the context's
+extern "C" int eoc_global_import_packing_key_blob(const void *buf, size_t len)
+{
+    eoc_params bp;
+    if (eoc_packing_key_blob_params(buf, len, &bp) != EOC_OK) return EOC_ERR_ARG;
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) { // the engines come up behind the global key on first use; engines of eoc_gpu_init serve without one
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    } else if (eoc_gpu_engine_count() == 0) {
+        fprintf(stderr, "Public key not initialized. Generate the public key first.\n");
+        return EOC_ERR_NO_KEY;
+    }
+    return eoc_set_packing_key_engines(buf, len);
+}
+// LWE samples -> compact lists on the global context's engines: WHOLE lists are cut over the engines
+extern "C" int eoc_pack(const int32_t *cts, size_t count, int32_t *lists)
+{
+    if (!cts || !lists) {
+        eoc_set_error("eoc_pack: null argument");
+        return EOC_ERR_ARG;
+    }
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) {
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    }
+    return eoc_pack_engines(cts, count, lists);
 }
 // an encrypted-index table read on the global context's engines (brought up behind the global key on first use; a cloud key
 // alone suffices)

@@ -65,6 +65,8 @@ void compact_encrypt(const eoc_params &p, const int32_t *A, const int32_t *B, co
                      uint64_t first_list, const int32_t *msgs, size_t count, int32_t *lists);
 // an EOCPK1 blob of exactly `len` bytes -> its parameters and A | B (2N words); false for anything else
 bool parse_public_key_blob(const void *buf, size_t len, eoc_params *p, std::vector<int32_t> *ab);
+// packing key switch: the rows [n][4][2][N] of a secret key's packing key, in torus form
+void make_packing_key(const eoc_secret_key *sk, int32_t *rows);
 void drop_keys_locked();    // wipes and frees whichever key the context holds (caller holds ctx().mu)
 
 } // namespace eoc_host

@@ -1661,4 +1661,158 @@ __global__ __launch_bounds__(256) void k_tlwe_extract(const int32_t *__restrict_
     }
 }
 
+// =================================================================================================
+// Packing key switch: LWE samples (a_i, b_i) under the LWE key s -> compact TLWE lists under s'; sample i
+// goes to slot i mod N of list i / N.  With A_m(X) = sum_i a_{i,m} X^i and B(X) = sum_i b_i X^i a list is
+//   (0, B) - sum_m sum_{j = 1..4} D_{m,j}(X) Row(m, j),   Row(m, j) a TLWE encryption of s_m 2^(32 - 4j) under s',
+// D_{m,j} the j-th signed base-16 digit polynomial of A_m + 2^15 (a ROUNDING decomposition to 16 bits).
+// Format rule: the rows of 16 consecutive key indices (a chunk) are accumulated in the spectral domain, m ascending then j
+// ascending, per output polynomial; every chunk is inverse-transformed and converted once (|.| <= 64 * 8 * 1024 * 2^31 =
+// 2^50 < 2^51: wrap_trunc's contract holds unconditionally) and the int32 result is subtracted from the list.  Chunks
+// combine by integer addition, so their order -- and the atomics below -- cannot change a bit.
+// =================================================================================================
+constexpr int kPackT = 4, kPackBasebit = 4;   // decomposition of the packing key (part of the EOCPKS1 format)
+constexpr int kPackChunk = 16;                // key indices per inverse transform (part of the format)
+constexpr int kPackTile = 64;
+
+// The mask columns as polynomials: cols[list][m][i] = a_{list N + i, m} (0 past `count`), a 64 x 64 tile transpose through
+// LDS, both sides 256 contiguous bytes per wave and instruction; column n (the b_i) goes to c1 of the output list and c0 is
+// cleared: lists[list] = (0, B).  grid: x = N / 64 sample tiles, y = ceil((n + 1) / 64) column tiles, z = lists of the
+// slice; block = 256.  `in`, `lists` and `count` are those of the slice (sample 0 = slot 0 of list 0).
+__global__ __launch_bounds__(256) void k_pack_gather(const int32_t *__restrict__ in, size_t count, int n,
+                                                     int32_t *__restrict__ cols, int32_t *__restrict__ lists)
+{
+    __shared__ int32_t s_tile[kPackTile][kPackTile + 1];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int i0 = blockIdx.x * kPackTile, m0 = blockIdx.y * kPackTile;
+    const size_t list = blockIdx.z, s0 = list * kN + i0;
+    for (int r = ty; r < kPackTile; r += 4) {
+        const size_t s = s0 + r;
+        const int m = m0 + tx;
+        s_tile[r][tx] = (s < count && m <= n) ? in[s * ((size_t)n + 1) + m] : 0;
+    }
+    __syncthreads();
+    for (int r = ty; r < kPackTile; r += 4) {
+        const int m = m0 + r;
+        const int32_t v = s_tile[tx][r];
+        if (m < n) cols[(list * n + m) * kN + i0 + tx] = v;
+        else if (m == n) lists[list * 2 * kN + kN + i0 + tx] = v;
+    }
+    if (blockIdx.y == 0 && ty == 0) lists[list * 2 * kN + i0 + tx] = 0;
+}
+
+// One WAVE per (list, chunk): both spectral accumulators stay in registers (64 VGPRs), the four digit transforms of a key
+// index run two at a time through fft_fwd_rest_x2 on the wave's own scratch, and nothing is exchanged between waves: one
+// barrier (the tables), none in the row loop.  Key rows [n][4][2][512] complex (k_fft_fwd_polys at scale 2^-9, as the
+// selectors of k_cmux) are read 16 bytes per lane, 1 KiB per wave and instruction, and multiplied in bin block by bin
+// block as k_blind_rotate_wide does: whole rows held next to two accumulators and two transforms do not fit 256 registers.
+// The first row of a chunk starts both chains as a plain product (mac's nesting in k_cmux), so the first key index is
+// peeled off the loop.  Results leave as vector integer atomics of the negated words.
+// grid: x = ceil(items / 4), items = lists x chunks; block = 256.
+constexpr int kPackWavesPerWG = 4;
+constexpr int kPackLds = (kTwEntries + kNH + kPackWavesPerWG * kScr) * 16; // 53 760 bytes: two workgroups per CU
+
+__global__ __launch_bounds__(64 * kPackWavesPerWG, 2) void k_pack_rows(const int32_t *__restrict__ cols,
+                                                                       const d2 *__restrict__ key, int32_t *__restrict__ lists,
+                                                                       int n, uint32_t nchunks, uint32_t items,
+                                                                       const d2 *__restrict__ g_tw,
+                                                                       const d2 *__restrict__ g_twist)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    d2 *s_tw = reinterpret_cast<d2 *>(smem);
+    d2 *s_twist = s_tw + kTwEntries;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    d2 *scr = s_twist + kNH + wv * kScr;
+    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 64 * kPackWavesPerWG);
+    __syncthreads(); // the tables; the only barrier
+    const uint32_t item = blockIdx.x * kPackWavesPerWG + (uint32_t)wv;
+    if (item >= items) return;
+    const uint32_t list = item / nchunks, chunk = item - list * nchunks;
+    const int m_first = (int)chunk * kPackChunk, m_end = min(m_first + kPackChunk, n);
+
+    constexpr uint32_t Bg = 1u << kPackBasebit, maskBg = Bg - 1, halfBg = Bg >> 1;
+    uint32_t offset = 1u << (31 - kPackT * kPackBasebit); // the rounding term 2^15 ...
+#pragma unroll
+    for (int p = 1; p <= kPackT; p++) offset += halfBg << (32 - p * kPackBasebit); // ... and DecompH's offset
+    const double bias1 = 4503599627370496.0 + (double)halfBg, bias2 = 4503599627370496.0 + (double)Bg;
+
+    uint32_t dlo[8], dhi[8];
+    auto make_x0 = [&](int p, d2 (&x)[8]) __attribute__((always_inline)) {
+        const int shift = 32 - p * kPackBasebit;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const uint32_t ua = (dlo[r] >> shift) & maskBg, ub = (dhi[r] >> shift) & maskBg;
+            const uint32_t up = (dlo[r + 4] >> shift) & maskBg, uq = (dhi[r + 4] >> shift) & maskBg;
+            const double a = __hiloint2double(0x43300000, (int)ua) - bias1;
+            const double b = __hiloint2double(0x43300000, (int)ub) - bias1;
+            const double dm = __hiloint2double(0x43300000, (int)(up - uq + Bg)) - bias2;
+            const double dp = __hiloint2double(0x43300000, (int)(up + uq)) - bias2;
+            fwd_stage0(x[r], x[r + 4], a, b, dm, dp);
+        }
+        fwd_pass0_tail(x);
+    };
+    auto mul0 = [](d2 x, d2 b) __attribute__((always_inline)) {
+        d2 o;
+        o.x = EOC_FMA(-x.y, b.y, x.x * b.x);
+        o.y = EOC_FMA(x.y, b.x, x.x * b.y);
+        return o;
+    };
+    auto mac1 = [](d2 x, d2 b, d2 a) __attribute__((always_inline)) {
+        d2 o;
+        o.x = EOC_FMA(-x.y, b.y, EOC_FMA(x.x, b.x, a.x));
+        o.y = EOC_FMA(x.y, b.x, EOC_FMA(x.x, b.y, a.y));
+        return o;
+    };
+    d2 S0[8], S1[8];
+    auto key_index = [&](int m, auto first_tag) __attribute__((always_inline)) {
+        constexpr bool kFirst = decltype(first_tag)::value;
+        const int32_t *pa = cols + ((size_t)list * n + m) * kN;
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            dlo[r] = (uint32_t)pa[lane + 64 * r] + offset;
+            dhi[r] = (uint32_t)pa[lane + 64 * r + kNH] + offset;
+        }
+        const d2 *rows = key + (size_t)m * kPackT * 2 * kNH + lane; // Row(m, j) polynomial c at ((j - 1) * 2 + c) * 512
+        d2 xa[8], xb[8];
+#pragma unroll
+        for (int j0 = 1; j0 < kPackT; j0 += 2) {
+            make_x0(j0, xa);
+            fft_fwd_rest_x2(xa, xb, [&]() __attribute__((always_inline)) { make_x0(j0 + 1, xb); }, s_tw, scr, lane);
+            // both chains, bin block by bin block: row (m, j0), then row (m, j0 + 1)
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                const d2 a0 = rows[((j0 - 1) * 2 + 0) * kNH + r * 64], a1 = rows[((j0 - 1) * 2 + 1) * kNH + r * 64];
+                const d2 b0 = rows[(j0 * 2 + 0) * kNH + r * 64], b1 = rows[(j0 * 2 + 1) * kNH + r * 64];
+                const d2 s0 = (kFirst && j0 == 1) ? mul0(xa[r], a0) : mac1(xa[r], a0, S0[r]);
+                const d2 s1 = (kFirst && j0 == 1) ? mul0(xa[r], a1) : mac1(xa[r], a1, S1[r]);
+                S0[r] = mac1(xb[r], b0, s0);
+                S1[r] = mac1(xb[r], b1, s1);
+            }
+        }
+    };
+    key_index(m_first, std::true_type());
+#pragma unroll 1
+    for (int m = m_first + 1; m < m_end; m++) key_index(m, std::false_type());
+
+    int32_t *po = lists + (size_t)list * 2 * kN;
+    d2 ut[8];
+    fft_inv_wave(S0, ut, s_tw, s_twist, scr, lane);
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int j = lane + 64 * r;
+        const d2 y = cmulc(S0[r], ut[r]); // 1/512 is in the key image
+        atomicAdd(po + j, (int)(0u - wrap_trunc(y.x)));
+        atomicAdd(po + j + kNH, (int)(0u - wrap_trunc(y.y)));
+    }
+    fft_inv_wave(S1, ut, s_tw, s_twist, scr, lane);
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int j = lane + 64 * r;
+        const d2 y = cmulc(S1[r], ut[r]);
+        atomicAdd(po + kN + j, (int)(0u - wrap_trunc(y.x)));
+        atomicAdd(po + kN + j + kNH, (int)(0u - wrap_trunc(y.y)));
+    }
+}
+
 } // namespace eoc

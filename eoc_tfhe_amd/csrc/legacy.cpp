@@ -123,6 +123,8 @@ const char kMagicSK2[8] = {'E', 'O', 'C', 'S', 'K', '2', 0, 0};
 const char kMagicCK[8] = {'E', 'O', 'C', 'C', 'K', '1', 0, 0};
 // public key blob: "EOCPK1\0\0" | same params | A int32[N] | B int32[N]      (compact public-key encryption)
 const char kMagicPK[8] = {'E', 'O', 'C', 'P', 'K', '1', 0, 0};
+// packing key blob: "EOCPKS1\0" | same params | t_p, basebit_p (2 x i32; 4, 4) | rows int32[n][4][2][N]     
+const char kMagicPKS[8] = {'E', 'O', 'C', 'P', 'K', 'S', '1', 0};
 const size_t kParamBytes = 5 * 4 + 2 * 8;
 
 void put_params(const eoc_params &p, unsigned char *o)
@@ -296,6 +298,68 @@ extern "C" int eoc_public_key_blob_params(const void *buf, size_t len, eoc_param
         return EOC_ERR_ARG;
     }
     return EOC_OK;
+}
+
+// ---- packing key switch: the EOCPKS1 blob ------------------------------------------------------------------
+extern "C" size_t eoc_packing_key_blob_bytes(const eoc_params *p)
+{
+    return p ? 8 + kParamBytes + 8 + size_t(p->n) * EOC_PACK_T * 2 * EOC_N * 4 : 0;
+}
+
+extern "C" int eoc_packing_key_export(const eoc_secret_key *sk, void *buf, size_t cap)
+{
+    if (!sk || !buf || cap < eoc_packing_key_blob_bytes(&sk->p)) {
+        eoc_set_error("eoc_packing_key_export: null argument or a buffer below eoc_packing_key_blob_bytes");
+        return EOC_ERR_ARG;
+    }
+    unsigned char *o = static_cast<unsigned char *>(buf);
+    memcpy(o, kMagicPKS, 8);
+    put_params(sk->p, o + 8);
+    const int32_t tb[2] = {EOC_PACK_T, EOC_PACK_BASEBIT};
+    memcpy(o + 8 + kParamBytes, tb, 8);
+    // the rows are written through an aligned buffer: the header is 52 bytes
+    try {
+        std::vector<int32_t> rows(size_t(sk->p.n) * EOC_PACK_T * 2 * EOC_N);
+        make_packing_key(sk, rows.data());
+        memcpy(o + 8 + kParamBytes + 8, rows.data(), rows.size() * 4);
+    } catch (...) {
+        eoc_set_error("eoc_packing_key_export: out of memory");
+        return EOC_ERR_ALLOC;
+    }
+    return EOC_OK;
+}
+
+bool eoc_packing_key_blob_rows(const void *buf, size_t len, eoc_params *p, const int32_t **rows)
+{
+    const unsigned char *o = static_cast<const unsigned char *>(buf);
+    eoc_params q;
+    int32_t tb[2];
+    if (!buf || len < 8 + kParamBytes + 8 || memcmp(o, kMagicPKS, 8) != 0 || !get_params(o + 8, q)) return false;
+    memcpy(tb, o + 8 + kParamBytes, 8);
+    if (tb[0] != EOC_PACK_T || tb[1] != EOC_PACK_BASEBIT || len != eoc_packing_key_blob_bytes(&q)) return false;
+    if (p) *p = q;
+    if (rows) *rows = reinterpret_cast<const int32_t *>(o + 8 + kParamBytes + 8); // copied bytewise by the callers
+    return true;
+}
+
+extern "C" int eoc_packing_key_blob_params(const void *buf, size_t len, eoc_params *p)
+{
+    if (!p || !eoc_packing_key_blob_rows(buf, len, p, nullptr)) {
+        eoc_set_error("eoc_packing_key_blob_params: not a whole EOCPKS1 packing key blob (t = %d, basebit = %d)", EOC_PACK_T,
+                      EOC_PACK_BASEBIT);
+        return EOC_ERR_ARG;
+    }
+    return EOC_OK;
+}
+
+extern "C" size_t eoc_global_packing_key_export(void *buf, size_t cap)
+{
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (!c.sk) return 0;
+    const size_t need = eoc_packing_key_blob_bytes(&c.sk->p);
+    if (!buf || cap < need) return need;
+    return eoc_packing_key_export(c.sk, buf, cap) == EOC_OK ? need : 0;
 }
 
 extern "C" const char *exportSecretKey(void)

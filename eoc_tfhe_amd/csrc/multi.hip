@@ -487,6 +487,28 @@ int slot_table_read_block(Slot &s, const int32_t *table, int log2_lists, int log
     return slot_finish(st, run());
 }
 
+// one device's block of WHOLE lists [l_lo, l_hi) of a packing key switch: cts [count][stride] on the host,
+// lists [ceil(count / N)][2][N] out
+int slot_pack_block(Slot &s, const int32_t *cts, size_t count, int32_t *lists, size_t l_lo, size_t l_hi, size_t stride_ints)
+{
+    if (l_hi == l_lo) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t s_lo = l_lo * EOC_N, blk = std::min(count, l_hi * EOC_N) - s_lo;
+    const size_t in_ints = blk * stride_ints, out_ints = (l_hi - l_lo) * 2 * EOC_N;
+    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, in_ints + out_ints);
+    if (rc) return rc;
+    int32_t *d_in = s.d_lut, *d_out = d_in + in_ints;
+    hipStream_t st = s.st[0];
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_in, cts + s_lo * stride_ints, in_ints * 4, hipMemcpyHostToDevice, st));
+        int r = eoc_pack_device(s.e, d_in, blk, d_out, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(lists + l_lo * 2 * EOC_N, d_out, out_ints * 4, hipMemcpyDeviceToHost, st));
+        return EOC_OK;
+    };
+    return slot_finish(st, run());
+}
+
 void destroy_slots_locked()
 {
     for (auto &s : G.slots)
@@ -1226,6 +1248,46 @@ int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out)
     const size_t stride = (size_t)G.p.n + 1;
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
         return slot_compact_block(G.slots[i], lists, out, lo, hi, stride);
+    });
+}
+
+// eoc_global_import_packing_key_blob's engine half: every engine parses, converts and keeps its own image
+int eoc_set_packing_key_engines(const void *blob, size_t len)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_global_import_packing_key_blob: no GPU engine (eoc_gpu_init not called or failed)");
+        return EOC_ERR_NO_DEVICE;
+    }
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    for (auto &s : G.slots) {
+        int rc = eoc_engine_set_packing_key(s.e, blob, len);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+// eoc_pack's engine half (host.cpp holds the global key's lock and has brought the engines up): whole lists per engine
+int eoc_pack_engines(const int32_t *cts, size_t count, int32_t *lists)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_pack: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        return EOC_ERR_NO_DEVICE;
+    }
+    if (!count) { // the engines still answer for a missing key
+        return eoc_pack_device(G.slots[0].e, cts, 0, lists, nullptr);
+    }
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    const size_t stride = (size_t)G.p.n + 1, n_lists = (count + EOC_N - 1) / EOC_N;
+    return for_each_block(n_lists, [=](int i, size_t lo, size_t hi) {
+        return slot_pack_block(G.slots[i], cts, count, lists, lo, hi, stride);
     });
 }
 

@@ -408,3 +408,50 @@ def table_read_mean(params, tlwe_key, index, log2_lists, log2_width, w=0):
     magnitude: unlike a blind rotation's, these means are not spread by later rotations."""
     slots = np.asarray(table_read_slots(index, log2_lists, log2_width), np.int64) + int(w)
     return float(cmux_mean(params, tlwe_key, slots).sum()) if len(slots) else 0.0
+
+
+# ---- packing key switch: LWE samples into compact lists (DESIGN.md 13) ----------------------------------------------------------
+PACK_T, PACK_BASEBIT = 4, 4
+
+
+def pack_var(params, lwe_key, filled=N):
+    """variance (torus units) the packing key switch (eoc_pack_device) ADDS to the phase of every packed sample, for a fixed
+    key, over the packing key's randomness and pseudo-random full-range masks:
+      rows       n 4 filled E[d^2] sigma_eff^2: the n x 4 TLWE rows times the digit polynomials, which have `filled`
+                 non-zero coefficients (the occupied slots of the list); E[d^2] = (16^2 + 2) / 12, sigma_eff^2 the
+                 truncation-corrected variance of gaussian32 at bk_stdev, as in `predict`
+      rounding   |s| 2^-32 / 12: the mask words are rounded to 16 bits (uniform on [-2^-17, 2^-17)) where s_m = 1
+    The decomposition ROUNDS (the 2^15 of the key switch's precision offset), so unlike a CMux the operation leaves no mean:
+    pack_mean = 0."""
+    n = int(params.n)
+    hw = int(np.asarray(lwe_key, np.int64).sum())
+    Bg = 1 << PACK_BASEBIT
+    return n * PACK_T * int(filled) * ((Bg * Bg + 2) / 12.0) * _sig2(params) + hw * 2.0**-32 / 12.0
+
+
+def pack_mean(params=None, lwe_key=None, filled=N):
+    """mean (torus units) the packing key switch adds, over keys: 0 -- a rounding decomposition and zero-mean rows.  For ONE
+    key the slots carry the small fixed offsets of pack_offset, whose mean over keys is 0."""
+    return 0.0
+
+
+def pack_offset(row_phases, lwe_key, filled=N):
+    """what a FIXED packing key adds to slot i on average, [N] torus units (compact_offset's sibling; nothing fitted).  The
+    signed digits are uniform on [-8, 8): their mean is -1/2, not 0, on the `filled` occupied coefficients.  A list loses
+    sum D_{m,j} e_{m,j} (e the rows' noise), so slot i keeps (1/2) (P E)[i] with P = 1 + X + ... + X^(filled-1) and
+    E = sum_{m,j} e_{m,j}.  Over keys this has mean 0 and standard deviation (1/2) sqrt(4 n filled) sigma -- 5e-6 on Set A,
+    a twentieth of sqrt(pack_var) -- so it shows only in the mean of many thousand samples under one key.
+    row_phases: [n][4][N] int, the phases of the packing key's rows under s' (SecretKey.list_phases of the blob's rows)."""
+    ph = np.asarray(row_phases, np.int64).reshape(-1, PACK_T, N).copy()
+    s = np.asarray(lwe_key, np.int64)
+    for j in range(1, PACK_T + 1):
+        ph[:, j - 1, 0] -= s << (32 - PACK_BASEBIT * j)
+    E = (_wrap32(ph) / 2.0**32).sum(axis=(0, 1))
+    f = int(filled)
+    pre = np.concatenate(([0.0], np.cumsum(E)))                          # pre[k] = E[0] + ... + E[k-1]
+    i = np.arange(N)
+    lo = np.maximum(i - f + 1, 0)                                        # + E[lo .. i]
+    plus = pre[i + 1] - pre[lo]
+    a, b = np.minimum(i + 1 + N - f, N), N                               # - E[i - k + N] for i < k < filled
+    minus = np.where(f > i + 1, pre[b] - pre[np.maximum(a, i + 1)], 0.0)
+    return 0.5 * (plus - minus)

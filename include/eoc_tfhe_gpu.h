@@ -708,6 +708,64 @@ uint64_t eoc_engine_cmux_launches(eoc_engine *e);
  * and converts its own selectors.  The cloud key alone suffices (key mode 2). */
 int eoc_table_read(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries, int32_t *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * packing key switch: LWE samples under the LWE key s (gate or LUT outputs) -> compact TLWE lists under s',
+ * the layout of eoc_pk_encrypt_*, eoc_table_trivial and the table of eoc_table_read_device.  1 024 results leave in 8 KiB
+ * instead of 2 MB (Set A) / 2.5 MB (Set B), and a value the server computed can become a table.
+ *   packing key Row (m, j), m < n, j = 1 .. 4: a TLWE encryption under s' at bk_stdev of the constant polynomial
+ *               s_m 2^(32 - 4j) -- the mask and noise of one TGSW row with bit 0 (mask word k at counter k, Gaussian k at
+ *               N + 2k) from the secret key's own source under stream tag 9 (PackKsk), index 4 m + (j - 1), plus
+ *               2^(32 - 4j) on b[0] when s_m = 1.  The same secret key always gives the same packing key.  The decomposition
+ *               is FIXED at t = 4, basebit = 4 (EOC_PACK_T, EOC_PACK_BASEBIT: 16 bits of precision).
+ *               Blob "EOCPKS1\0" | params (as EOCCK1) | t, basebit (2 x i32) | rows int32[n][4][2][N], little-endian:
+ *               16.4 MB (Set A) / 20.6 MB (Set B).  A blob of its own: EOCCK1 and the cloud-key calls are unchanged.
+ *   operation   sample i goes to slot i mod N of list i / N; slots past `count` in the last list behave as samples (0, 0).
+ *               Per list, in wrapping 32-bit arithmetic: A_m(X) = sum_i a_{i,m} X^i, B(X) = sum_i b_i X^i,
+ *               out = (0, B) - sum_m sum_j D_{m,j}(X) Row(m, j), with digit d_j = ((x >> (32 - 4j)) & 15) - 8 of
+ *               x = a + 2^15 + sum_p 8 2^(32 - 4p): a ROUNDING decomposition (no mean is left).  The rows of 16 consecutive
+ *               key indices (a chunk; the last one is short) are accumulated in the spectral domain, m ascending then j
+ *               ascending, first term a product and every later one the two-FMA chain, inverse-transformed and converted
+ *               ONCE per chunk (|.| <= 2^50: exact conversion on every parameter set) and subtracted as int32; chunks
+ *               combine by integer addition, in any order.  The chunk is part of the format: eoc_pack_device equals the
+ *               CPU reference tests/c/pack_ref.c byte for byte.
+ *   noise       noise.pack_var: sigma ~9e-5 (Set A) / ~3e-4 (Set B) for a full list, far below a gate output's; mean 0.
+ *   security    the rows are ring-LWE samples of the bootstrapping key's ring under s' that encrypt bits of s: the
+ *               circular-security assumption the published key-switch and bootstrapping keys already make.
+ *   engine      eoc_engine_set_packing_key parses the blob, checks its parameters against the engine's, uploads and converts
+ *               the rows (the key-load transform, [n][4][2][512] complex f64 scaled by 2^-9: 32.8 / 41.3 MB, owned by the
+ *               engine) and replaces an earlier image.  eoc_pack_device: d_in DEVICE [count][n+1], d_lists DEVICE
+ *               [ceil(count / N)][2][N]; EOC_ERR_NO_KEY without a packing key, count 0 is a no-op.  Workspace: the mask
+ *               columns [lists][n][N] int32, grown by eoc_engine_reserve's rule (EOC_ERR_STATE under capture); lists are
+ *               sliced so that it stays within 256 MiB (EOC_TFHE_PACK_WS_BYTES at engine creation changes the budget and no
+ *               result; a budget below one list's need is EOC_ERR_ARG).  No descriptor slot is used.  Stats:
+ *               eoc_engine_pack_launches (one per slice), eoc_engine_packed_samples; eoc_engine_kernel_times books the
+ *               kernels under the key switch.  Asynchronous on hip_stream.
+ * Malformed, truncated or mismatched blobs (wrong magic, t or basebit other than 4, another parameter set than the
+ * engine's / the context's) are EOC_ERR_ARG. */
+#define EOC_PACK_T 4
+#define EOC_PACK_BASEBIT 4
+size_t eoc_packing_key_blob_bytes(const eoc_params *p);
+int eoc_packing_key_export(const eoc_secret_key *sk, void *buf, size_t cap);       /* EOC_ERR_ARG when cap is too small */
+int eoc_packing_key_blob_params(const void *buf, size_t len, eoc_params *p);       /* a whole EOCPKS1 blob, else EOC_ERR_ARG */
+int eoc_engine_set_packing_key(eoc_engine *e, const void *blob, size_t len);
+int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count, int32_t *d_lists, void *hip_stream);
+uint64_t eoc_engine_pack_launches(eoc_engine *e);
+uint64_t eoc_engine_packed_samples(eoc_engine *e);
+/* client side: the phases c1 - c0 s' of every slot, phases [n_lists][N]; the first `count` slots of lists
+ * [ceil(count / N)][2][N] as bits (phase > 0, eoc_decrypt_bits' rule) or as integers of Z_p (eoc_decrypt_ints' rule) */
+int eoc_list_phases(const eoc_secret_key *sk, const int32_t *lists, size_t n_lists, int32_t *phases);
+int eoc_decrypt_list_bits(const eoc_secret_key *sk, const int32_t *lists, size_t count, uint8_t *bits);
+int eoc_decrypt_list_ints(const eoc_secret_key *sk, int p, const int32_t *lists, size_t count, uint8_t *values);
+/* on the global context.  The three client calls and the export need the secret key (EOC_ERR_NO_KEY / 0 in key mode 2);
+ * eoc_global_import_packing_key_blob gives every engine of the context the packing key and works behind a cloud key alone
+ * (key mode 2); eoc_pack (host buffers, synchronous) cuts WHOLE lists into eoc_shard_range blocks, one per engine. */
+int eoc_global_list_phases(const int32_t *lists, size_t n_lists, int32_t *phases);
+int eoc_global_decrypt_list_bits(const int32_t *lists, size_t count, uint8_t *bits);
+int eoc_global_decrypt_list_ints(int p, const int32_t *lists, size_t count, uint8_t *values);
+size_t eoc_global_packing_key_export(void *buf, size_t cap); /* bytes needed (0 without a secret key); fills buf when cap suffices */
+int eoc_global_import_packing_key_blob(const void *buf, size_t len);
+int eoc_pack(const int32_t *cts, size_t count, int32_t *lists);
+
 #ifdef __cplusplus
 }
 #endif

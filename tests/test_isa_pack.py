@@ -1,0 +1,61 @@
+"""ISA guards of the packing kernels (hipcc cross-compiles gfx950 here; no GPU), from the code object's metadata alone:
+k_pack_rows fits the 256 registers of a wave at two waves per SIMD with no spill and no scratch, k_pack_gather is small, and
+the new names leave the kernel counts that tests/test_isa_lut.py and tests/test_isa_cmux.py rely on as they were."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.fixture(scope="module")
+def isa(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    out = tmp_path_factory.mktemp("isa_pack") / "engine.s"
+    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-w", "-S",
+                    "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "eoc_tfhe_amd", "csrc", "engine.hip")],
+                   check=True, cwd=str(out.parent))
+    return out.read_text()
+
+
+def kernel_meta(text):
+    meta = {}
+    for blk in text.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
+                      for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "sgpr_spill_count")}
+        meta[name]["agpr_count"] = int(re.match(r"\s*(\d+)", blk).group(1))
+    return meta
+
+
+def one(meta, name):
+    hits = [k for k in meta if name in k]
+    assert len(hits) == 1, hits
+    assert not any("blind_rotate" in k or "keyswitch_waves" in k for k in hits)
+    return meta[hits[0]]
+
+
+def test_pack_rows_fits_a_wave_without_spill_or_scratch(isa):
+    m = one(kernel_meta(isa), "k_pack_rows")
+    print("k_pack_rows", m)
+    assert m["vgpr_count"] + m["agpr_count"] <= 256, m          # two waves per SIMD
+    assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, m
+
+
+def test_pack_gather_is_small(isa):
+    m = one(kernel_meta(isa), "k_pack_gather")
+    print("k_pack_gather", m)
+    assert m["vgpr_count"] <= 32 and m["agpr_count"] == 0, m
+    assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, m
+
+
+def test_kernel_name_counts_are_unchanged(isa):
+    names = re.findall(r"^(_Z\S*k_blind_rotate\S*):", isa, flags=re.M)
+    assert len([k for k in names if "_tv" in k]) == len([k for k in names if "_tv" not in k]) == 16
+    assert len(re.findall(r"^(_Z\S*keyswitch_waves\S*):", isa, flags=re.M)) == 4
+    assert len([k for k in kernel_meta(isa) if "k_cmux" in k or "k_tlwe_extract" in k]) == 7
