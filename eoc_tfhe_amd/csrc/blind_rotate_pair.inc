@@ -2,6 +2,9 @@
 // parameters L, BGBIT, SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test polynomials, used
 // when TV); constexpr bool MANY; n_tables (interleaved tables per test polynomial, extracted when MANY); constexpr bool
 // TLDS (gadget length 2 in its earlier form: tables read from LDS in the step loop, whole key rows requested per step).
+// From kernels.hip.h: Gadget / digit_pass (the digit pass), cmul0 / cmac1 (the chains' arithmetic), rot_digits.  The step's
+// external product is written out here only for gadget length 2 (key rows streamed, the tuned part); every other
+// instance includes ext_product_pair.inc, the text k_cmux includes too.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     d2 *s_tw = reinterpret_cast<d2 *>(smem);
     d2 *s_twist = s_tw + kTwEntries;
@@ -75,16 +78,13 @@
     __syncthreads();
 
     const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
-    const uint32_t Bg = 1u << Bgbit, maskBg = Bg - 1, halfBg = Bg >> 1;
     uint32_t offset = 0;
 #pragma unroll
-    for (int p = 1; p <= L; p++) offset += halfBg << (32 - p * Bgbit);
+    for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
+    const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
     constexpr int KPL = 2 * L;
     const __amdgpu_buffer_rsrc_t bk_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(A.bkfft), 0, (int)((size_t)A.n * KPL * 2 * kNH * 16), 0x00020000);
-    // digits arrive biased, u = digit + Bg/2 in [0, Bg); as_double(2^52 | u) - (2^52 + Bg/2) is the digit, exactly;
-    // the stage-0 sums p - q and p + q are formed on the biased integers and converted the same way
-    const double bias1 = 4503599627370496.0 + (double)halfBg, bias2 = 4503599627370496.0 + (double)Bg;
 
 #ifdef EOC_STAMPS
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -175,41 +175,16 @@
             }
         }
         EOC_STAMP(0);
-        // digit p of the 16 coefficients of this lane, first pass of its forward transform (stages 0-2)
-        auto make_x0 = [&](int p, d2 (&x)[8]) __attribute__((always_inline)) {
-            const int shift = 32 - p * Bgbit;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const uint32_t ua = (dlo[r] >> shift) & maskBg, ub = (dhi[r] >> shift) & maskBg;
-                const uint32_t up = (dlo[r + 4] >> shift) & maskBg, uq = (dhi[r + 4] >> shift) & maskBg;
-                const double a = __hiloint2double(0x43300000, (int)ua) - bias1;
-                const double b = __hiloint2double(0x43300000, (int)ub) - bias1;
-                const double dm = __hiloint2double(0x43300000, (int)(up - uq + Bg)) - bias2;
-                const double dp = __hiloint2double(0x43300000, (int)(up + uq)) - bias2;
-                fwd_stage0(x[r], x[r + 4], a, b, dm, dp);
-            }
-            fwd_pass0_tail(x);
-        };
-        auto mac = [&](bool first, const d2 (&x)[8], const d2 (&b)[8], d2 (&acc_)[8]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                if (first) {
-                    acc_[r].x = EOC_FMA(-x[r].y, b[r].y, x[r].x * b[r].x);
-                    acc_[r].y = EOC_FMA(x[r].y, b[r].x, x[r].x * b[r].y);
-                } else {
-                    acc_[r].x = EOC_FMA(-x[r].y, b[r].y, EOC_FMA(x[r].x, b[r].x, acc_[r].x));
-                    acc_[r].y = EOC_FMA(x[r].y, b[r].x, EOC_FMA(x[r].x, b[r].y, acc_[r].y));
-                }
-            }
-        };
-        // forward transforms of the l digits (two at a time, skewed on the one scratch; an odd last one alone) and
-        // the chain for the partner's output polynomial.  The spectra stay in registers for the own chain below.
-        d2 xs[L][8], S[8];
+        // the external product: S = the spectrum-side update of ACC_h, before the un-twist
+        d2 S[8];
         if constexpr (kResAll) {
+            // the two forward transforms as one skewed pair; the spectra stay in registers for both chains
+            d2 xs[2][8];
+            auto make_x0 = [&](int p, d2 (&x)[8]) __attribute__((always_inline)) { digit_pass(dlo, dhi, gd.shift(p), gd, x); };
             // The key rows are streamed through the two chains bin block by bin block (block b < 8: rows (p = 1, 2) of the
             // partner's output polynomial at bins r = b; b >= 8: the own ones at r = b - 8), kRowAhead blocks requested ahead
             // of the one in use, so that no whole row is ever live next to both spectra and the resident tables.  Per bin
-            // the terms arrive in the canonical order and in mac's nesting.  The scheduling barriers pin the requests: the
+            // the terms arrive in the canonical order and in cmac1's nesting.  The scheduling barriers pin the requests: the
             // scheduler otherwise hoists all of them to the top.
             constexpr int kRowAhead = 3;
             const uint32_t step_off = (uint32_t)((((size_t)i * KPL + h * L) * 2) * kNH * 16);
@@ -218,12 +193,6 @@
                 const uint32_t off = step_off + (uint32_t)((b < 8 ? 1 - h : h) * kNH * 16 + (b & 7) * 1024);
                 q[b][0] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(bk_rsrc, lane * 16, (int)off, 0));
                 q[b][1] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(bk_rsrc, lane * 16, (int)(off + 2 * kNH * 16), 0));
-            };
-            auto mac1 = [](d2 x, d2 b, d2 a) __attribute__((always_inline)) {
-                d2 o;
-                o.x = EOC_FMA(-x.y, b.y, EOC_FMA(x.x, b.x, a.x));
-                o.y = EOC_FMA(x.y, b.x, EOC_FMA(x.x, b.y, a.y));
-                return o;
             };
             make_x0(1, xs[0]);
             EOC_STAMP(1);
@@ -236,11 +205,7 @@
             EOC_SB();
 #pragma unroll
             for (int r = 0; r < 8; r++) { // the partner's chain: each bin block leaves for the scratch as it completes
-                d2 s;
-                s.x = EOC_FMA(-xs[0][r].y, q[r][0].y, xs[0][r].x * q[r][0].x);
-                s.y = EOC_FMA(xs[0][r].y, q[r][0].x, xs[0][r].x * q[r][0].y);
-                s = mac1(xs[1][r], q[r][1], s);
-                scr[r * 64 + lane] = s;
+                scr[r * 64 + lane] = cmac1(xs[1][r], q[r][1], cmul0(xs[0][r], q[r][0]));
                 EOC_SB();
                 issue(r + kRowAhead); // from r = 8 - kRowAhead on: own rows, in flight across the barrier
                 EOC_SB();
@@ -254,8 +219,8 @@
             EOC_SB();
 #pragma unroll
             for (int r = 0; r < 8; r++) { // the chain of the other input polynomial, continued with the own digits
-                S[r] = mac1(xs[0][r], q[8 + r][0], S[r]);
-                S[r] = mac1(xs[1][r], q[8 + r][1], S[r]);
+                S[r] = cmac1(xs[0][r], q[8 + r][0], S[r]);
+                S[r] = cmac1(xs[1][r], q[8 + r][1], S[r]);
                 EOC_SB();
                 if (r + kChainAhead < 8) S[r + kChainAhead] = scr_partner[(r + kChainAhead) * 64 + lane];
                 if (8 + r + kRowAhead < 16) issue(8 + r + kRowAhead);
@@ -265,51 +230,11 @@
             __syncthreads(); // the partner has read this wave's scratch before the inverse transform overwrites it
             EOC_STAMP(7);
             fft_inv_wave<true>(S, ut, s_tw, s_twist, scr, lane, &res_t1, &res_i0);
-        } else {
-            d2 ra[8], rb[8];
-#pragma unroll
-            for (int p0 = 0; p0 + 1 < L; p0 += 2) {
-                load_row(p0 + 1, 1 - h, ra);
-                load_row(p0 + 2, 1 - h, rb);
-                make_x0(p0 + 1, xs[p0]);
-                EOC_STAMP(1);
-                fft_fwd_rest_x2(xs[p0], xs[p0 + 1], [&]() __attribute__((always_inline)) { make_x0(p0 + 2, xs[p0 + 1]); },
-                                s_tw, scr, lane, kResT2 ? &res_t2 : nullptr);
-                EOC_STAMP(2);
-                mac(p0 == 0, xs[p0], ra, S);
-                mac(false, xs[p0 + 1], rb, S);
-                EOC_STAMP(3);
-            }
-            if constexpr ((L & 1) != 0) {
-                load_row(L, 1 - h, ra);
-                make_x0(L, xs[L - 1]);
-                EOC_STAMP(1);
-                fft_fwd_rest(xs[L - 1], s_tw, scr, lane);
-                EOC_STAMP(2);
-                mac(L == 1, xs[L - 1], ra, S);
-                EOC_STAMP(3);
-            }
-            // own rows: the first two are requested before the exchange (requesting the first one a register pass
-            // earlier into a third buffer, or the second one only after the exchange, changes nothing: measured)
-            load_row(1, h, ra);
-            if constexpr (L >= 2) load_row(2, h, rb);
-#pragma unroll
-            for (int r = 0; r < 8; r++) scr[r * 64 + lane] = S[r];
-            EOC_STAMP(4);
-            __syncthreads();
-            EOC_STAMP(5);
-#pragma unroll
-            for (int r = 0; r < 8; r++) S[r] = scr_partner[r * 64 + lane]; // the chain of the other input polynomial
-            mac(false, xs[0], ra, S);
-            if constexpr (L >= 3) load_row(3, h, ra);
-            if constexpr (L >= 2) mac(false, xs[1], rb, S);
-            if constexpr (L >= 4) load_row(4, h, rb);
-            if constexpr (L >= 3) mac(false, xs[2], ra, S);
-            if constexpr (L >= 4) mac(false, xs[3], rb, S);
-            EOC_STAMP(6);
-            __syncthreads(); // the partner has read this wave's scratch before the inverse transform overwrites it
-            EOC_STAMP(7);
-            fft_inv_wave(S, ut, s_tw, s_twist, scr, lane, kResT1 ? &res_t1 : nullptr);
+        } else { // every other gadget length, and TLDS: whole key rows, the code k_cmux runs too
+            const d2 (*const xp_t2)[4] = kResT2 ? &res_t2 : nullptr, (*const xp_t1)[4] = kResT1 ? &res_t1 : nullptr;
+#define EOC_XP_STAMP(k) EOC_STAMP(k)
+#include "ext_product_pair.inc"
+#undef EOC_XP_STAMP
         }
         EOC_STAMP(8);
 #pragma unroll

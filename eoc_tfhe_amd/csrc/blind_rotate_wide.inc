@@ -1,6 +1,7 @@
 // Body of k_blind_rotate_wide / k_blind_rotate_wide_tv / k_lut_many_wide (kernels.hip.h), included into each.  In scope:
 // template parameters BGBIT, SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test
 // polynomials, used when TV); constexpr bool MANY; n_tables (tables per test polynomial, extracted when MANY).
+// From kernels.hip.h: Gadget / digit_pass (the digit pass), cmul0 / cmac1 (the chains' arithmetic), rot_digits.
     constexpr int L = 2, KPL = 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     d2 *s_tw = reinterpret_cast<d2 *>(smem);
@@ -68,13 +69,12 @@
     }
 
     const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
-    const uint32_t Bg = 1u << Bgbit, maskBg = Bg - 1, halfBg = Bg >> 1;
     uint32_t offset = 0;
 #pragma unroll
-    for (int p = 1; p <= L; p++) offset += halfBg << (32 - p * Bgbit);
+    for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
+    const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
     const __amdgpu_buffer_rsrc_t bk_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(A.bkfft), 0, (int)((size_t)A.n * KPL * 2 * kNH * 16), 0x00020000);
-    const double bias1 = 4503599627370496.0 + (double)halfBg, bias2 = 4503599627370496.0 + (double)Bg;
     const int prio_slot = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (3 << 11)); // HW_ID.WAVE_ID: slot on the SIMD
 
 #ifdef EOC_STAMPS
@@ -119,18 +119,7 @@
         }
         // digit p of the 16 coefficients of this lane (digit words d[0..7] = low half, d[8..15] = high half), first pass
         auto make_x0 = [&](const uint32_t (&d)[16], int p, d2 (&x)[8]) __attribute__((always_inline)) {
-            const int shift = 32 - p * Bgbit;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const uint32_t ua = (d[r] >> shift) & maskBg, ub = (d[8 + r] >> shift) & maskBg;
-                const uint32_t up = (d[r + 4] >> shift) & maskBg, uq = (d[12 + r] >> shift) & maskBg;
-                const double a = __hiloint2double(0x43300000, (int)ua) - bias1;
-                const double b = __hiloint2double(0x43300000, (int)ub) - bias1;
-                const double dm = __hiloint2double(0x43300000, (int)(up - uq + Bg)) - bias2;
-                const double dp = __hiloint2double(0x43300000, (int)(up + uq)) - bias2;
-                fwd_stage0(x[r], x[r + 4], a, b, dm, dp);
-            }
-            fwd_pass0_tail(x);
+            digit_pass(d, d + 8, gd.shift(p), gd, x);
         };
         EOC_STAMP(0);
         d2 xs0[2][8], xs1[2][8];
@@ -148,30 +137,18 @@
             const uint32_t off = step_off + (uint32_t)((((q * L) + (p - 1)) * 2 + c) * kNH * 16 + r * 1024);
             return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(bk_rsrc, lane * 16, (int)off, 0));
         };
-        auto mul0 = [](d2 x, d2 b) __attribute__((always_inline)) {
-            d2 o;
-            o.x = EOC_FMA(-x.y, b.y, x.x * b.x);
-            o.y = EOC_FMA(x.y, b.x, x.x * b.y);
-            return o;
-        };
-        auto mac1 = [](d2 x, d2 b, d2 a) __attribute__((always_inline)) {
-            d2 o;
-            o.x = EOC_FMA(-x.y, b.y, EOC_FMA(x.x, b.x, a.x));
-            o.y = EOC_FMA(x.y, b.x, EOC_FMA(x.x, b.y, a.y));
-            return o;
-        };
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const d2 b110 = ld(1, 1, 0, r), b120 = ld(1, 2, 0, r), b010 = ld(0, 1, 0, r), b020 = ld(0, 2, 0, r);
             const d2 b011 = ld(0, 1, 1, r), b021 = ld(0, 2, 1, r), b111 = ld(1, 1, 1, r), b121 = ld(1, 2, 1, r);
-            d2 a0 = mul0(xs1[0][r], b110);
-            a0 = mac1(xs1[1][r], b120, a0);
-            a0 = mac1(xs0[0][r], b010, a0);
-            a0 = mac1(xs0[1][r], b020, a0);
-            d2 a1 = mul0(xs0[0][r], b011);
-            a1 = mac1(xs0[1][r], b021, a1);
-            a1 = mac1(xs1[0][r], b111, a1);
-            a1 = mac1(xs1[1][r], b121, a1);
+            d2 a0 = cmul0(xs1[0][r], b110);
+            a0 = cmac1(xs1[1][r], b120, a0);
+            a0 = cmac1(xs0[0][r], b010, a0);
+            a0 = cmac1(xs0[1][r], b020, a0);
+            d2 a1 = cmul0(xs0[0][r], b011);
+            a1 = cmac1(xs0[1][r], b021, a1);
+            a1 = cmac1(xs1[0][r], b111, a1);
+            a1 = cmac1(xs1[1][r], b121, a1);
             S0[r] = a0;
             S1[r] = a1;
         }

@@ -151,6 +151,90 @@ __device__ __forceinline__ void fwd_pass0_tail(d2 (&x)[8])
     ct_w(x[4], x[5], w3);
     ct_iw(x[6], x[7], w3);
 }
+
+// ---- gadget decomposition and the external product's arithmetic: the ONE copy every kernel uses ---------------------
+// Constants of the signed decomposition into l digits of Bgbit bits.  The digit words carry an offset, Bg/2 at every
+// digit position, so digit p is a bit field of the word, biased: u = digit + Bg/2 in [0, Bg).
+// as_double(2^52 | u) - (2^52 + Bg/2) is the digit, exactly (bias1); the stage-0 sums p - q and p + q are formed on the
+// biased integers and converted the same way (bias2).
+// The offset itself is NOT here: each kernel sums it in three lines of its own text, from Bgbit alone, and builds its
+// Gadget behind that sum.  Measured with tools/isa_diff.py against the parent: with the sum inside make_gadget (as a loop
+// or loop-free), the step loop's entry test of k_blind_rotate_wide<10> came out inverted (4 changed lines) and
+// k_cmux<2,10> / <3,7> changed in 173 / 141 lines; with the sum in the kernels but behind make_gadget, the run-time-base
+// instances k_cmux<2,0> / <3,0> / <4,0> changed in 410-468 lines; as written now, every k_cmux, wide and gadget-length
+// 1, 3, 4 pair instance is byte-identical.  The cause was not established.
+template <int BGBIT> // > 0: the base is known at compile time (digit extraction becomes one bit-field extract); 0: run time
+struct Gadget {
+    int Bgbit;
+    uint32_t Bg, maskBg, halfBg;
+    double bias1, bias2;
+    __device__ __forceinline__ int shift(int p) const { return 32 - p * Bgbit; } // of digit p = 1..l in a digit word
+};
+template <int BGBIT>
+__device__ __forceinline__ Gadget<BGBIT> make_gadget(int Bgbit_rt)
+{
+    const int Bgbit = BGBIT > 0 ? BGBIT : Bgbit_rt;
+    Gadget<BGBIT> g;
+    g.Bgbit = Bgbit;
+    g.Bg = 1u << Bgbit;
+    g.maskBg = g.Bg - 1;
+    g.halfBg = g.Bg >> 1;
+    g.bias1 = 4503599627370496.0 + (double)g.halfBg;
+    g.bias2 = 4503599627370496.0 + (double)g.Bg;
+    return g;
+}
+// The digit pass: the digit at `shift` of the 16 coefficients of this lane (digit words lo[r]: coefficient lane + 64 r,
+// hi[r]: lane + 64 r + 512) and the first pass of its forward transform (stages 0-2).  EOC_GADGET_BG / _MASK: a
+// compile-time base is named as a constant, as a kernel's own text would name it, and a run-time one is read from the
+// struct at each use (measured: read from the struct, k_blind_rotate_wide<10> changed in 64 lines; copied into two
+// locals first, k_blind_rotate_wide<0> changed in 144 lines inside the step loop)
+#define EOC_GADGET_BG(g) (BGBIT > 0 ? 1u << BGBIT : (g).Bg)
+#define EOC_GADGET_MASK(g) (BGBIT > 0 ? (1u << BGBIT) - 1 : (g).maskBg)
+template <int BGBIT>
+__device__ __forceinline__ void digit_pass(const uint32_t *lo, const uint32_t *hi, int shift, const Gadget<BGBIT> &g,
+                                           d2 (&x)[8])
+{
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const uint32_t ua = (lo[r] >> shift) & EOC_GADGET_MASK(g), ub = (hi[r] >> shift) & EOC_GADGET_MASK(g);
+        const uint32_t up = (lo[r + 4] >> shift) & EOC_GADGET_MASK(g), uq = (hi[r + 4] >> shift) & EOC_GADGET_MASK(g);
+        const double a = __hiloint2double(0x43300000, (int)ua) - g.bias1;
+        const double b = __hiloint2double(0x43300000, (int)ub) - g.bias1;
+        const double dm = __hiloint2double(0x43300000, (int)(up - uq + EOC_GADGET_BG(g))) - g.bias2;
+        const double dp = __hiloint2double(0x43300000, (int)(up + uq)) - g.bias2;
+        fwd_stage0(x[r], x[r + 4], a, b, dm, dp);
+    }
+    fwd_pass0_tail(x);
+}
+#undef EOC_GADGET_BG
+#undef EOC_GADGET_MASK
+// The complex multiply-accumulate of the chains, in the canonical nesting (oracle/tfhe_oracle.c, compiled like this file
+// with -ffp-contract=off): the first term of a chain is a product, one multiplication and one fused multiply-add per
+// component (cmul0); every later term is two nested fused multiply-adds per component, the x.x product innermost (cmac1).
+// This nesting is the bit-parity contract with the oracle: change it here and there, or nowhere.
+__device__ __forceinline__ d2 cmul0(d2 x, d2 b)
+{
+    d2 o;
+    o.x = EOC_FMA(-x.y, b.y, x.x * b.x);
+    o.y = EOC_FMA(x.y, b.x, x.x * b.y);
+    return o;
+}
+__device__ __forceinline__ d2 cmac1(d2 x, d2 b, d2 acc)
+{
+    d2 o;
+    o.x = EOC_FMA(-x.y, b.y, EOC_FMA(x.x, b.x, acc.x));
+    o.y = EOC_FMA(x.y, b.x, EOC_FMA(x.x, b.y, acc.y));
+    return o;
+}
+__device__ __forceinline__ void cmac8(bool first, const d2 (&x)[8], const d2 (&b)[8], d2 (&acc)[8])
+{ // the eight bins of a lane; `first`: this term starts the chain (acc is not read)
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        if (first) acc[r] = cmul0(x[r], b[r]);
+        else acc[r] = cmac1(x[r], b[r], acc[r]);
+    }
+}
+
 // the four loaded twiddles of a table-driven pass; `stride` = 8 (pass 1, q = table + (lane >> 3)) or 64 (pass 2)
 __device__ __forceinline__ void tw_load(d2 (&t)[4], const d2 *q, int stride)
 {
@@ -813,8 +897,19 @@ constexpr int kBRLds = (kTwEntries + kNH + 2 * kScr) * 16 + kAbarLds; // 37 632 
 // times slower per transform; it is bit-exact (tests/test_gpu_parity.py) and nothing else is claimed for it.
 
 // Two kernel names share one body (blind_rotate_pair.inc, included into each so that it is compiled as the kernel's own
-// code: moved into a __device__ function the body compiles to different code, as a separate function is optimised before
-// it is inlined).  The body's constant TV selects the accumulator: false = the gate test vector (mu, ..., mu),
+// code).  What is known about sharing code between these kernels, measured with tools/isa_diff.py on the assembly of every
+// instance against the parent commit's:
+//   * the whole body moved into a __device__ function compiled to different code for the gate kernels; the L-generic
+//     external product as a force-inlined function template (row loader passed by value or by reference) changed
+//     k_blind_rotate<3,7> in 249 lines (SGPRs 89 -> 87), k_br_lds<2,10> in 57, k_cmux<2,10> in 950 and k_cmux<3,7> in 300.
+//     The same texts as includes (blind_rotate_pair.inc, blind_rotate_wide.inc, ext_product_pair.inc) change none of them;
+//   * the small force-inlined helpers Gadget, digit_pass, cmul0 / cmac1 / cmac8 leave every instance of a default
+//     parameter set byte-identical, provided a compile-time gadget base is named as a constant inside digit_pass
+//     (Gadget<BGBIT>), as the kernel's text named it: read from the struct, k_blind_rotate_wide<10> changed in 64 lines;
+//   * the measured exceptions: the rotation block (16 ds_bpermute + the 32-way rot_digits switch) as a function renames
+//     registers in k_blind_rotate<2,10> and changes the length of twenty other instances, and the three-line sum of the
+//     gadget offset as a helper inverts the step loop's entry test (see Gadget).  Both stay in the kernels' text.
+// The body's constant TV selects the accumulator: false = the gate test vector (mu, ..., mu),
 // true = a test polynomial per job.  The gate kernel's name, template arguments and argument list are what
 // tests/test_isa_guard.py and the profiles look up and what the shipped code was measured as: they do not change.
 template <int L, int BGBIT = 0, bool SABAR = false>
@@ -1491,8 +1586,9 @@ __global__ __launch_bounds__(256) void k_compact_expand(const int32_t *__restric
 // Leveled operations: the CMux of an encrypted-index table read.
 //   out = A + C (x) (X^rot B - A),  rot in [0, 2N)
 // A, B: TLWE samples [2][N] in global memory; C: a converted selector [2l][2][512] complex (one row block of the
-// bootstrapping key's FFT image, scaled by 2^-9).  The external product is the blind rotation's, in the canonical order
-// (oracle/tfhe_oracle.c): with A = B the item is one blind-rotation step with abar = rot, bit for bit.
+// bootstrapping key's FFT image, scaled by 2^-9).  The external product is the blind rotation's, the same text
+// (ext_product_pair.inc, in the canonical order of oracle/tfhe_oracle.c): with A = B the item is one blind-rotation step
+// with abar = rot, bit for bit, by construction.
 // Mapping: one wave PAIR per item, as k_blind_rotate -- wave h owns input polynomial h (difference, decomposition, the l
 // forward transforms) and output polynomial h (the chain the partner started, continued with the own digits, the inverse
 // transform, + A_h).  Wave h reads and writes polynomial h only.  kCmuxItemsPerWG pairs share one workgroup and its copy of
@@ -1538,11 +1634,10 @@ __global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_cmux(CmuxArgs A, c
     const d2 *sel = A.sel + ix * A.sel_x + iy * A.sel_y;
 
     const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
-    const uint32_t Bg = 1u << Bgbit, maskBg = Bg - 1, halfBg = Bg >> 1;
     uint32_t offset = 0;
 #pragma unroll
-    for (int p = 1; p <= L; p++) offset += halfBg << (32 - p * Bgbit);
-    const double bias1 = 4503599627370496.0 + (double)halfBg, bias2 = 4503599627370496.0 + (double)Bg;
+    for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
+    const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
 
     // offset + (X^rot B_h - A_h): coefficient lane + 64 r in dlo[r], lane + 64 r + 512 in dhi[r].  The rotation is index
     // arithmetic on B's loads (X^N = -1: the upper half of the 2N-period is negated)
@@ -1564,66 +1659,13 @@ __global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_cmux(CmuxArgs A, c
 #pragma unroll
         for (int r = 0; r < 8; r++) b[r] = row[r * 64];
     };
-    auto make_x0 = [&](int p, d2 (&x)[8]) __attribute__((always_inline)) {
-        const int shift = 32 - p * Bgbit;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const uint32_t ua = (dlo[r] >> shift) & maskBg, ub = (dhi[r] >> shift) & maskBg;
-            const uint32_t up = (dlo[r + 4] >> shift) & maskBg, uq = (dhi[r + 4] >> shift) & maskBg;
-            const double a = __hiloint2double(0x43300000, (int)ua) - bias1;
-            const double b = __hiloint2double(0x43300000, (int)ub) - bias1;
-            const double dm = __hiloint2double(0x43300000, (int)(up - uq + Bg)) - bias2;
-            const double dp = __hiloint2double(0x43300000, (int)(up + uq)) - bias2;
-            fwd_stage0(x[r], x[r + 4], a, b, dm, dp);
-        }
-        fwd_pass0_tail(x);
-    };
-    auto mac = [&](bool first, const d2 (&x)[8], const d2 (&b)[8], d2 (&acc_)[8]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            if (first) {
-                acc_[r].x = EOC_FMA(-x[r].y, b[r].y, x[r].x * b[r].x);
-                acc_[r].y = EOC_FMA(x[r].y, b[r].x, x[r].x * b[r].y);
-            } else {
-                acc_[r].x = EOC_FMA(-x[r].y, b[r].y, EOC_FMA(x[r].x, b[r].x, acc_[r].x));
-                acc_[r].y = EOC_FMA(x[r].y, b[r].x, EOC_FMA(x[r].x, b[r].y, acc_[r].y));
-            }
-        }
-    };
-    // forward transforms of the l digits (two at a time, skewed on the one scratch; an odd last one alone) and the chain
-    // for the partner's output polynomial; the spectra stay in registers for the own chain
-    d2 xs[L][8], S[8], ra[8], rb[8], ut[8];
-#pragma unroll
-    for (int p0 = 0; p0 + 1 < L; p0 += 2) {
-        load_row(p0 + 1, 1 - h, ra);
-        load_row(p0 + 2, 1 - h, rb);
-        make_x0(p0 + 1, xs[p0]);
-        fft_fwd_rest_x2(xs[p0], xs[p0 + 1], [&]() __attribute__((always_inline)) { make_x0(p0 + 2, xs[p0 + 1]); }, s_tw, scr,
-                        lane);
-        mac(p0 == 0, xs[p0], ra, S);
-        mac(false, xs[p0 + 1], rb, S);
+    d2 S[8], ut[8];
+    {
+        const d2 (*const xp_t2)[4] = nullptr, (*const xp_t1)[4] = nullptr; // nothing is loop-invariant here: tables from LDS
+#define EOC_XP_STAMP(k) do { } while (0)
+#include "ext_product_pair.inc"
+#undef EOC_XP_STAMP
     }
-    if constexpr ((L & 1) != 0) {
-        load_row(L, 1 - h, ra);
-        make_x0(L, xs[L - 1]);
-        fft_fwd_rest(xs[L - 1], s_tw, scr, lane);
-        mac(L == 1, xs[L - 1], ra, S);
-    }
-    load_row(1, h, ra);
-    if constexpr (L >= 2) load_row(2, h, rb);
-#pragma unroll
-    for (int r = 0; r < 8; r++) scr[r * 64 + lane] = S[r];
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 8; r++) S[r] = scr_partner[r * 64 + lane]; // the chain of the other input polynomial
-    mac(false, xs[0], ra, S);
-    if constexpr (L >= 3) load_row(3, h, ra);
-    if constexpr (L >= 2) mac(false, xs[1], rb, S);
-    if constexpr (L >= 4) load_row(4, h, rb);
-    if constexpr (L >= 3) mac(false, xs[2], ra, S);
-    if constexpr (L >= 4) mac(false, xs[3], rb, S);
-    __syncthreads(); // the partner has read this wave's scratch before the inverse transform overwrites it
-    fft_inv_wave(S, ut, s_tw, s_twist, scr, lane);
     if (!live) return;
     int32_t *po = A.out + ix * A.out_x + iy * A.out_y + (size_t)h * kN;
 #pragma unroll
@@ -1706,7 +1748,7 @@ __global__ __launch_bounds__(256) void k_pack_gather(const int32_t *__restrict__
 // barrier (the tables), none in the row loop.  Key rows [n][4][2][512] complex (k_fft_fwd_polys at scale 2^-9, as the
 // selectors of k_cmux) are read 16 bytes per lane, 1 KiB per wave and instruction, and multiplied in bin block by bin
 // block as k_blind_rotate_wide does: whole rows held next to two accumulators and two transforms do not fit 256 registers.
-// The first row of a chunk starts both chains as a plain product (mac's nesting in k_cmux), so the first key index is
+// The first row of a chunk starts both chains as a plain product (cmul0, as every chain), so the first key index is
 // peeled off the loop.  Results leave as vector integer atomics of the negated words.
 // grid: x = ceil(items / 4), items = lists x chunks; block = 256.
 constexpr int kPackWavesPerWG = 4;
@@ -1731,39 +1773,13 @@ __global__ __launch_bounds__(64 * kPackWavesPerWG, 2) void k_pack_rows(const int
     const uint32_t list = item / nchunks, chunk = item - list * nchunks;
     const int m_first = (int)chunk * kPackChunk, m_end = min(m_first + kPackChunk, n);
 
-    constexpr uint32_t Bg = 1u << kPackBasebit, maskBg = Bg - 1, halfBg = Bg >> 1;
+    const Gadget<kPackBasebit> gd = make_gadget<kPackBasebit>(0);
     uint32_t offset = 1u << (31 - kPackT * kPackBasebit); // the rounding term 2^15 ...
 #pragma unroll
-    for (int p = 1; p <= kPackT; p++) offset += halfBg << (32 - p * kPackBasebit); // ... and DecompH's offset
-    const double bias1 = 4503599627370496.0 + (double)halfBg, bias2 = 4503599627370496.0 + (double)Bg;
+    for (int p = 1; p <= kPackT; p++) offset += gd.halfBg << gd.shift(p); // ... and DecompH's offset
 
     uint32_t dlo[8], dhi[8];
-    auto make_x0 = [&](int p, d2 (&x)[8]) __attribute__((always_inline)) {
-        const int shift = 32 - p * kPackBasebit;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const uint32_t ua = (dlo[r] >> shift) & maskBg, ub = (dhi[r] >> shift) & maskBg;
-            const uint32_t up = (dlo[r + 4] >> shift) & maskBg, uq = (dhi[r + 4] >> shift) & maskBg;
-            const double a = __hiloint2double(0x43300000, (int)ua) - bias1;
-            const double b = __hiloint2double(0x43300000, (int)ub) - bias1;
-            const double dm = __hiloint2double(0x43300000, (int)(up - uq + Bg)) - bias2;
-            const double dp = __hiloint2double(0x43300000, (int)(up + uq)) - bias2;
-            fwd_stage0(x[r], x[r + 4], a, b, dm, dp);
-        }
-        fwd_pass0_tail(x);
-    };
-    auto mul0 = [](d2 x, d2 b) __attribute__((always_inline)) {
-        d2 o;
-        o.x = EOC_FMA(-x.y, b.y, x.x * b.x);
-        o.y = EOC_FMA(x.y, b.x, x.x * b.y);
-        return o;
-    };
-    auto mac1 = [](d2 x, d2 b, d2 a) __attribute__((always_inline)) {
-        d2 o;
-        o.x = EOC_FMA(-x.y, b.y, EOC_FMA(x.x, b.x, a.x));
-        o.y = EOC_FMA(x.y, b.x, EOC_FMA(x.x, b.y, a.y));
-        return o;
-    };
+    auto make_x0 = [&](int p, d2 (&x)[8]) __attribute__((always_inline)) { digit_pass(dlo, dhi, gd.shift(p), gd, x); };
     d2 S0[8], S1[8];
     auto key_index = [&](int m, auto first_tag) __attribute__((always_inline)) {
         constexpr bool kFirst = decltype(first_tag)::value;
@@ -1784,10 +1800,10 @@ __global__ __launch_bounds__(64 * kPackWavesPerWG, 2) void k_pack_rows(const int
             for (int r = 0; r < 8; r++) {
                 const d2 a0 = rows[((j0 - 1) * 2 + 0) * kNH + r * 64], a1 = rows[((j0 - 1) * 2 + 1) * kNH + r * 64];
                 const d2 b0 = rows[(j0 * 2 + 0) * kNH + r * 64], b1 = rows[(j0 * 2 + 1) * kNH + r * 64];
-                const d2 s0 = (kFirst && j0 == 1) ? mul0(xa[r], a0) : mac1(xa[r], a0, S0[r]);
-                const d2 s1 = (kFirst && j0 == 1) ? mul0(xa[r], a1) : mac1(xa[r], a1, S1[r]);
-                S0[r] = mac1(xb[r], b0, s0);
-                S1[r] = mac1(xb[r], b1, s1);
+                const d2 s0 = (kFirst && j0 == 1) ? cmul0(xa[r], a0) : cmac1(xa[r], a0, S0[r]);
+                const d2 s1 = (kFirst && j0 == 1) ? cmul0(xa[r], a1) : cmac1(xa[r], a1, S1[r]);
+                S0[r] = cmac1(xb[r], b0, s0);
+                S1[r] = cmac1(xb[r], b1, s1);
             }
         }
     };

@@ -3,22 +3,18 @@ against the oracle-stream restatement (tests/compact_oracle.py) bit for bit, the
 noise.compact_var, an oracle-composed expansion, the EOCPK1 blob and argument errors, the model's margin statement, and the
 new kernel's registers.  GPU side: tests/test_gpu_compact.py."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import compact_oracle as co
+import isa_lib
 import oracle_lib as ol
 from eoc_tfhe_amd import noise
 
 N = 1024
 EOC_ERR_ARG = -1
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 @pytest.fixture(scope="module")
@@ -227,19 +223,9 @@ def test_model_expanded_inputs_are_quieter_than_gate_outputs(eoc, pset):
     assert expanded < noise.predict(p, sk.lwe_key, sk.tlwe_key)["total_var"]     # also with the average-key key switch
 
 
-def test_isa_compact_expand_kernel_has_no_spill_no_scratch_vector_stores_only(tmp_path):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path / "engine.s"
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-w", "-S",
-                    "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "eoc_tfhe_amd", "csrc", "engine.hip")],
-                   check=True, cwd=str(tmp_path))
-    text = out.read_text()
-    meta = {}
-    for blk in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
-                      for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "sgpr_spill_count")}
+def test_isa_compact_expand_kernel_has_no_spill_no_scratch_vector_stores_only():
+    text = isa_lib.engine_isa()
+    meta = isa_lib.kernel_meta(text)
     hits = [k for k in meta if "k_compact_expand" in k]
     assert len(hits) == 1, hits
     m = meta[hits[0]]

@@ -6,41 +6,24 @@ not even copied into LDS: the kernel stores nothing 16 bytes wide to LDS ahead o
 table regions.  Nothing is spilled to make room for that.  The earlier form (k_br_lds*, EOC_TFHE_BR_TABLES_LDS=1) is
 compiled next to it and keeps its 72 reads: the difference, 16, is what SQ_INSTS_LDS per wave-step falls by.
 """
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from isa_lib import engine_isa, kernel_meta
+
 
 READS_RESIDENT = 56     # 6 transposes x 8 + the exchange's 8: all three remaining table sets are resident
 READS_TABLES_LDS = 72   # + forward pass 1 (4), inverse pass 0 (4), un-twist factors (8)
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("isa_br_resident") / "engine.s"
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-w", "-S",
-                    "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "eoc_tfhe_amd", "csrc", "engine.hip")],
-                   check=True, cwd=str(out.parent))
-    return out.read_text()
+def isa():
+    return engine_isa()
 
 
-def kernel_meta(text):
-    meta = {}
-    for blk in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
-                      for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "sgpr_spill_count")}
-    return meta
-
-
-def kernel_bodies(text):
+def kernel_text(text):
+    """raw text per kernel, labels and indentation kept (step_loop finds the loop by its labels), up to the last s_endpgm"""
     parts = re.split(r"^(_ZN3eoc\w+):[^\n]*$", text, flags=re.M)
     return {parts[i]: parts[i + 1][: parts[i + 1].rfind("s_endpgm")] for i in range(1, len(parts), 2)
             if "s_endpgm" in parts[i + 1]}
@@ -68,7 +51,7 @@ OLD = ("8k_br_ldsILi2E", "11k_br_lds_tvILi2E", "13k_br_lds_manyILi2E")
 
 
 def test_step_loop_of_gadget_length_2_reads_no_table(isa):
-    meta, bodies = kernel_meta(isa), kernel_bodies(isa)
+    meta, bodies = kernel_meta(isa), kernel_text(isa)
     seen = 0
     for fam in FAMILIES:
         for base in ("Li10E", "Li0E"):
@@ -97,7 +80,7 @@ def test_step_loop_of_gadget_length_2_reads_no_table(isa):
 
 
 def test_earlier_form_is_compiled_next_to_it(isa):
-    meta, bodies = kernel_meta(isa), kernel_bodies(isa)
+    meta, bodies = kernel_meta(isa), kernel_text(isa)
     for fam in OLD:
         for base in ("Li10E", "Li0E"):
             for form in ("Lb0EE", "Lb1EE"):

@@ -2,41 +2,16 @@
 instances ks_mfma_launch dispatches (4 waves per workgroup: the shipped plan; 8: the alternative tools/ubench_ks_mfma.hip measures), runs on v_mfma_i32_32x32x32_i8, keeps its 128 accumulator registers and everything else
 in the register file (no spill, no scratch) at two waves per SIMD, and the limb-image builder k_ksk_limbs exists.
 tests/test_isa_guard.py (unchanged) checks the whole library for the stores that must not be there."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from isa_lib import engine_isa, kernel_bodies, kernel_meta
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("isa_ks_mfma") / "engine.s"
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-w", "-S",
-                    "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "eoc_tfhe_amd", "csrc", "engine.hip")],
-                   check=True, cwd=str(out.parent))
-    return out.read_text()
-
-
-def kernel_meta(text):
-    meta = {}
-    for blk in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
-                      for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "sgpr_spill_count")}
-        meta[name]["agpr_count"] = int(re.match(r"\s*(\d+)", blk).group(1))
-    return meta
-
-
-def kernel_bodies(text):
-    parts = re.split(r"^(_ZN3eoc\w+):[^\n]*$", text, flags=re.M)
-    return {parts[i]: parts[i + 1][: parts[i + 1].find(".Lfunc_end")] for i in range(1, len(parts), 2)}
+def isa():
+    return engine_isa()
 
 
 def test_mfma_key_switch_exists_without_spill_or_scratch(isa):
@@ -47,7 +22,7 @@ def test_mfma_key_switch_exists_without_spill_or_scratch(isa):
         m = meta[name]
         assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (name, m)
         assert m["vgpr_count"] + m["agpr_count"] <= 256, (name, m)       # two waves per SIMD
-        code = [ln.strip() for ln in bodies[name].splitlines() if ln.strip() and not ln.strip().startswith((";", "."))]
+        code = bodies[name]
         mf = [ln for ln in code if ln.startswith("v_mfma_i32_")]
         assert mf and all(ln.startswith("v_mfma_i32_32x32x32_i8") for ln in mf), (name, mf[:2])
         assert len(mf) >= 32, (name, len(mf))                           # 4 indices x (2 row tiles x 4 limbs) per staged step

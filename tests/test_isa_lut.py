@@ -1,35 +1,16 @@
 """ISA guards of the programmable-bootstrapping kernels (hipcc cross-compiles gfx950 here; no GPU): the *_tv twins of the
 shipped blind-rotation kernels exist for Set A (pair and wide kernel) and Set B, in both forms of the rotation-amount
 read-back, and fit 256 VGPRs without scratch, like the kernels they share their body with (tests/test_isa_guard.py)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from isa_lib import engine_isa, kernel_meta
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("isa_lut") / "engine.s"
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-w", "-S",
-                    "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "eoc_tfhe_amd", "csrc", "engine.hip")],
-                   check=True, cwd=str(out.parent))
-    return out.read_text()
-
-
-def kernel_meta(text):
-    meta = {}
-    for blk in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
-                      for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "sgpr_spill_count")}
-    return meta
+def isa():
+    return engine_isa()
 
 
 def test_tv_kernels_fit_the_register_file_without_scratch(isa):

@@ -2,35 +2,16 @@
 shape the launch policy picks, in both forms of the rotation-amount read-back, with the register budgets of the _tv twins
 they share their body with, and their scalar read-back keeps the wait behind the scalar-cache invalidate
 (tests/test_isa_guard.py's memory-model check only looks at kernels named *blind_rotate*).  k_modswitch_coarse exists."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from isa_lib import engine_isa, kernel_meta
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("isa_lut_many") / "engine.s"
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-w", "-S",
-                    "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "eoc_tfhe_amd", "csrc", "engine.hip")],
-                   check=True, cwd=str(out.parent))
-    return out.read_text()
-
-
-def kernel_meta(text):
-    meta = {}
-    for blk in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
-                      for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "sgpr_spill_count")}
-    return meta
+def isa():
+    return engine_isa()
 
 
 PAIR = ["10k_lut_manyILi1ELi0E", "10k_lut_manyILi2ELi0E", "10k_lut_manyILi3ELi0E", "10k_lut_manyILi4ELi0E",

@@ -1,42 +1,22 @@
 """ISA guards of the packing kernels (hipcc cross-compiles gfx950 here; no GPU), from the code object's metadata alone:
 k_pack_rows fits the 256 registers of a wave at two waves per SIMD with no spill and no scratch, k_pack_gather is small, and
 the new names leave the kernel counts that tests/test_isa_lut.py and tests/test_isa_cmux.py rely on as they were."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from isa_lib import engine_isa, kernel_meta
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("isa_pack") / "engine.s"
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-w", "-S",
-                    "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "eoc_tfhe_amd", "csrc", "engine.hip")],
-                   check=True, cwd=str(out.parent))
-    return out.read_text()
-
-
-def kernel_meta(text):
-    meta = {}
-    for blk in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", blk).group(1))
-                      for k in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "sgpr_spill_count")}
-        meta[name]["agpr_count"] = int(re.match(r"\s*(\d+)", blk).group(1))
-    return meta
+def isa():
+    return engine_isa()
 
 
 def one(meta, name):
     hits = [k for k in meta if name in k]
     assert len(hits) == 1, hits
-    assert not any("blind_rotate" in k or "keyswitch_waves" in k for k in hits)
+    assert not any("blind_rotate" in k or "keyswitch_waves" in k for k in hits)   # the new names stay out of those counts
     return meta[hits[0]]
 
 
