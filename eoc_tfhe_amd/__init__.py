@@ -282,6 +282,12 @@ def lib():
         "eoc_global_packing_key_export": (sz, [vp, sz]),
         "eoc_global_import_packing_key_blob": (C.c_int, [vp, sz]),
         "eoc_pack": (C.c_int, [vp, sz, vp]),
+        # two-input table lookups
+        "eoc_lut2_test_polynomials": (C.c_int, [C.c_int, C.c_int, vp, vp]),
+        "eoc_lut_enc_batch_device": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, sz, vp]),
+        "eoc_tv_pack_device": (C.c_int, [vp, C.c_int, vp, sz, sz, vp, vp]),
+        "eoc_lut2_batch_device": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, sz, vp]),
+        "eoc_lut2_batch": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -634,6 +640,18 @@ def lut_many_test_polynomial(p, tables):
     return tv
 
 
+def lut2_test_polynomials(p, table, n_tables=1):
+    """Level-1 test polynomials [p / T][N] int32 of ONE two-input function (eoc_lut2_test_polynomials): table
+    [p][p] of Torus32 output values, table[x][y]; T = max(n_tables, 1) in {1, 2, 4, 8} divides p, p T <= 16 for T > 1.
+    Polynomial g holds the tables x -> F(x, y), y = g T .. g T + T - 1 (lut_many_test_polynomial's layout for T > 1)."""
+    table = np.ascontiguousarray(np.asarray(table, np.int64).astype(np.int32))
+    if table.shape != (int(p), int(p)):
+        raise EocError(f"lut2_test_polynomials: table must be [p][p], got {table.shape} for p = {p}")
+    T = max(int(n_tables), 1)
+    tv = np.empty((max(int(p) // T, 1), N), np.int32)
+    _check(lib().eoc_lut2_test_polynomials(int(p), int(n_tables), table.ctypes.data, tv.ctypes.data), "eoc_lut2_test_polynomials")
+    return tv
+
 
 class Engine:
     """One HIP engine (one GPU).  All array arguments are DEVICE pointers (ints) unless noted."""
@@ -822,6 +840,27 @@ class Engine:
         """LWE samples -> compact lists (eoc_pack_device): d_in [count][n+1], d_lists [ceil(count / N)][2][N]; sample i goes
         to slot i mod N of list i / N.  Needs the packing key alone."""
         _check(self.L.eoc_pack_device(self.h, d_in, count, d_lists, stream), "eoc_pack_device")
+
+    def lut_enc_batch_device(self, d_lists, n_groups, per_row, d_in, d_out, count, stream=None):
+        """Blind rotation from ENCRYPTED polynomials (eoc_lut_enc_batch_device): d_lists TLWE samples [..][2][N]
+        (pack_device / tv_pack_device outputs, PublicKey.encrypt_*, trivial_table), d_in [count][n+1], d_out
+        [n_groups][count][n+1].  Job (g, s) starts from list g (per_row false) or list g x count + s (per_row true), is rotated
+        by input row s, extracted and key-switched.  Needs the cloud key alone."""
+        _check(self.L.eoc_lut_enc_batch_device(self.h, d_lists, n_groups, 1 if per_row else 0, d_in, d_out, count, stream),
+               "eoc_lut_enc_batch_device")
+
+    def tv_pack_device(self, p, d_vals, n_funcs, count, d_lists, stream=None):
+        """LWE samples -> encrypted test polynomials (eoc_tv_pack_device): d_vals [n_funcs][p][count][n+1], d_lists
+        [n_funcs][count][2][N]; list (f, s) holds values 0 .. p - 1 of row s by lut_test_polynomial's rule.  Needs the packing
+        key."""
+        _check(self.L.eoc_tv_pack_device(self.h, int(p), d_vals, n_funcs, count, d_lists, stream), "eoc_tv_pack_device")
+
+    def lut2_batch_device(self, p, n_tables, d_tv0, n_funcs, d_x, d_y, d_out, count, stream=None):
+        """Two-input lookups F(x, y) (eoc_lut2_batch_device): d_tv0 [n_funcs][p / T][N] (lut2_test_polynomials
+        per function), d_x, d_y [count][n+1] at message space p, d_out [n_funcs][count][n+1].  Needs the cloud key and the
+        packing key."""
+        _check(self.L.eoc_lut2_batch_device(self.h, int(p), int(n_tables), d_tv0, n_funcs, d_x, d_y, d_out, count, stream),
+               "eoc_lut2_batch_device")
 
     def resident_jobs(self):
         """blind rotations that fill the device in one launch (8 x CUs where the one-wave-per-ciphertext kernel applies,
@@ -1060,6 +1099,25 @@ def lut_many_batch(p, tables, cts):
     out = np.empty((n_luts, T) + cts.shape, np.int32)
     _check(lib().eoc_lut_many_batch(int(p), T, tables.ctypes.data, n_luts, cts.ctypes.data, out.ctypes.data, cts.shape[0]),
            "eoc_lut_many_batch")
+    return out
+
+
+def lut2_batch(p, tables, x, y, n_tables=1):
+    """eoc_lut2_batch on the global context (cloud key + packing key: global_import_packing_key_blob): tables [p][p] or
+    [n_funcs][p][p] Torus32 output values, tables[f][x][y]; x, y [count][n+1] at message space p.  Returns
+    [n_funcs][count][n+1]."""
+    tables = np.asarray(tables, np.int64).astype(np.int32)
+    if tables.ndim == 2:
+        tables = tables[None]
+    tables = np.ascontiguousarray(tables)
+    if tables.ndim != 3 or tables.shape[1:] != (int(p), int(p)):
+        raise EocError(f"lut2_batch: tables must be [p][p] or [n_funcs][p][p], got {tables.shape} for p = {p}")
+    x, y = np.ascontiguousarray(x, np.int32), np.ascontiguousarray(y, np.int32)
+    if x.ndim != 2 or x.shape != y.shape:
+        raise EocError("lut2_batch: x and y are 2-d arrays [count][n+1] of one shape")
+    out = np.empty((tables.shape[0],) + x.shape, np.int32)
+    _check(lib().eoc_lut2_batch(int(p), int(n_tables), tables.ctypes.data, tables.shape[0], x.ctypes.data, y.ctypes.data,
+                                out.ctypes.data, x.shape[0]), "eoc_lut2_batch")
     return out
 
 

@@ -1,7 +1,8 @@
 // Body of k_blind_rotate / k_blind_rotate_tv / k_lut_many (kernels.hip.h), included into each.  In scope: template
 // parameters L, BGBIT, SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test polynomials, used
 // when TV); constexpr bool MANY; n_tables (interleaved tables per test polynomial, extracted when MANY); constexpr bool
-// TLDS (gadget length 2 in its earlier form: tables read from LDS in the step loop, whole key rows requested per step).
+// TLDS (gadget length 2 in its earlier form: tables read from LDS in the step loop, whole key rows requested per step);
+// constexpr bool ENC (with TV: tv holds TLWE lists [lists][2][N], wave h seeds ACC_h from polynomial h of the job's list).
 // From kernels.hip.h: Gadget / digit_pass (the digit pass), cmul0 / cmac1 (the chains' arithmetic), rot_digits.  The step's
 // external product is written out here only for gadget length 2 (key rows streamed, the tuned part); every other
 // instance includes ext_product_pair.inc, the text k_cmux includes too.
@@ -59,6 +60,7 @@
         const int rot = (2 * kN - barb) & (2 * kN - 1);
         const int32_t *st = A.acc_state + ((size_t)job * 2 + h) * kN;
         const int32_t *tvj = TV ? tv + (size_t)((A.job0 + job) / tv_rows) * kN : nullptr; // jobs are [table][row]
+        if constexpr (ENC) tvj = tv + ((size_t)((A.job0 + job) / tv_rows) * 2 + h) * kN; // an encrypted list: (c0, c1)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
@@ -70,7 +72,7 @@
             } else {
                 v = (idx & kN) ? -A.mu : A.mu;
             }
-            v = h ? v : 0;
+            if constexpr (!ENC) v = h ? v : 0;
             if (A.step_begin > 0) v = st[j]; // continue a blind rotation started by an earlier launch
             racc[r] = (uint32_t)v;
         }

@@ -1,6 +1,7 @@
 // Body of k_blind_rotate_wide / k_blind_rotate_wide_tv / k_lut_many_wide (kernels.hip.h), included into each.  In scope:
 // template parameters BGBIT, SABAR; kernel arguments A, g_tw, g_twist; constexpr bool TV; tv, tv_rows (the test
-// polynomials, used when TV); constexpr bool MANY; n_tables (tables per test polynomial, extracted when MANY).
+// polynomials, used when TV); constexpr bool MANY; n_tables (tables per test polynomial, extracted when MANY); constexpr
+// bool ENC (with TV: tv holds TLWE lists [lists][2][N] and the wave seeds both accumulators from the job's list).
 // From kernels.hip.h: Gadget / digit_pass (the digit pass), cmul0 / cmac1 (the chains' arithmetic), rot_digits.
     constexpr int L = 2, KPL = 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -48,12 +49,17 @@
         const int rot = (2 * kN - barb) & (2 * kN - 1);
         const int32_t *st = A.acc_state + (size_t)job * 2 * kN;
         const int32_t *tvj = TV ? tv + (size_t)((A.job0 + job) / tv_rows) * kN : nullptr; // jobs are [table][row]
+        if constexpr (ENC) tvj = tv + (size_t)((A.job0 + job) / tv_rows) * 2 * kN; // an encrypted list: (c0, c1)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
             const int idx = (j - rot) & (2 * kN - 1);
             int32_t v0 = 0, v1;
-            if constexpr (TV) {
+            if constexpr (ENC) {
+                const uint32_t c0 = (uint32_t)tvj[idx & (kN - 1)], c1 = (uint32_t)tvj[kN + (idx & (kN - 1))];
+                v0 = (int32_t)((idx & kN) ? 0u - c0 : c0);
+                v1 = (int32_t)((idx & kN) ? 0u - c1 : c1);
+            } else if constexpr (TV) {
                 const uint32_t c = (uint32_t)tvj[idx & (kN - 1)];
                 v1 = (int32_t)((idx & kN) ? 0u - c : c);
             } else {

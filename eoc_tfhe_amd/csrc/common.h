@@ -36,3 +36,7 @@ bool eoc_packing_key_blob_rows(const void *buf, size_t len, eoc_params *p, const
 int eoc_pack_engines(const int32_t *cts, size_t count, int32_t *lists);
 // the packing key on every process-global engine (multi.hip)
 int eoc_set_packing_key_engines(const void *blob, size_t len);
+// eoc_lut2_batch's GPU half on the process-global engines (multi.hip): rows cut into eoc_shard_range blocks, one
+// per engine
+int eoc_lut2_engines(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y, int32_t *out,
+                     size_t count);

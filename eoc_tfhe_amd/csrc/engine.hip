@@ -105,6 +105,9 @@ struct eoc_engine {
     size_t pack_cap = 0; // lists
     size_t pack_ws_bytes = (size_t)256 << 20;
     uint64_t pack_launches = 0, packed_samples = 0; // k_pack_rows launches; samples packed
+    // two-input lookups: the lists and the level-1 outputs of a slice of rows, one buffer
+    int32_t *d_lut2 = nullptr;
+    size_t lut2_cap = 0; // bytes
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
     struct Span { hipEvent_t a, b; int kind; };
@@ -339,6 +342,7 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
     hipFree(e->d_cmux[1]);
     hipFree(e->d_pks);
     hipFree(e->d_pack_cols);
+    hipFree(e->d_lut2);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -634,8 +638,9 @@ struct BRWork {
     uint32_t njobs = 0;
     // kernel family: k_blind_rotate* (every job starts from the gate accumulator), *_tv (programmable bootstrapping: job j
     // starts from test polynomial tv[j / tv_rows]), k_lut_many* (many-LUT bootstrapping: the same, and n_tables samples are
-    // extracted per job into the workspace's slot rows).  Same shapes and same segmentation for all three.
-    enum Seed { GATE, TV, MANY } seed = GATE;
+    // extracted per job into the workspace's slot rows), k_br_enc* (job j starts from the encrypted TLWE list tv[j / tv_rows],
+    // [lists][2][N]: DESIGN.md 14).  Same shapes and same segmentation for all four.
+    enum Seed { GATE, TV, MANY, ENC } seed = GATE;
     const int32_t *tv = nullptr;
     uint32_t tv_rows = 1, n_tables = 0;
     // GATE / TV: the kernel's epilogue sets the key switch up (no k_ks_init), its prologue makes the rotation amounts too (no
@@ -725,9 +730,10 @@ static BRArgs blind_rotate_args(const eoc_engine *e, const WS &W, const BRWork &
 }
 
 // THE KERNEL: the instance for (shape, gadget, family, read-back form).  Exactly these are instantiated: six pair and two
-// wide shapes, each as gate / _tv / many-LUT kernel, each with the rotation amounts read back by vector loads or
-// (sabar, EOC_TFHE_SCALAR_ABAR=1) by scalar loads; and the two pair shapes of gadget length 2 a second time in their
-// earlier form (tables_lds, EOC_TFHE_BR_TABLES_LDS=1: kernels.hip.h, k_br_lds*).
+// wide shapes, each as gate / _tv / many-LUT / encrypted-seed kernel, each with the rotation amounts read back by vector
+// loads or (sabar, EOC_TFHE_SCALAR_ABAR=1) by scalar loads; and the two pair shapes of gadget length 2 a second time in
+// their earlier form (tables_lds, EOC_TFHE_BR_TABLES_LDS=1: kernels.hip.h, k_br_lds*), for the first three families only:
+// the encrypted-seed family has no earlier-form twin and runs its shipped form under that knob too.
 template <int L, int BGBIT> static const void *br_pair_kernel(BRWork::Seed seed, bool sabar)
 {
     switch (seed) {
@@ -752,9 +758,17 @@ template <int BGBIT> static const void *br_wide_kernel(BRWork::Seed seed, bool s
     default: return sabar ? (const void *)&k_lut_many_wide<BGBIT, true> : (const void *)&k_lut_many_wide<BGBIT, false>;
     }
 }
+// the encrypted-seed family's instances (defined behind launch_lin: the device compiler emits kernels in the order of their
+// first use in this file, and the parent kernels keep their places, label numbers included, only if these come last)
+static const void *br_enc_kernel(bool wide, int l, int Bgbit, bool sabar);
 struct BRKernel { const void *fn; dim3 grid, block; unsigned lds; }; // fn == nullptr: no kernel for this gadget length
 static BRKernel blind_rotate_kernel(bool wide, int l, int Bgbit, bool sabar, bool tables_lds, BRWork::Seed seed, uint32_t njobs)
 {
+    if (seed == BRWork::ENC) {
+        const void *fn = br_enc_kernel(wide, l, Bgbit, sabar);
+        if (wide) return {fn, dim3((njobs + kBRWideJobsPerWG - 1) / kBRWideJobsPerWG), dim3(64 * kBRWideJobsPerWG), kBRWideLds};
+        return {fn, dim3(njobs), dim3(128), kBRLds};
+    }
     if (wide) {
         const void *fn = Bgbit == 10 ? br_wide_kernel<10>(seed, sabar) : br_wide_kernel<0>(seed, sabar); // 10: Set A
         return {fn, dim3((njobs + kBRWideJobsPerWG - 1) / kBRWideJobsPerWG), dim3(64 * kBRWideJobsPerWG), kBRWideLds};
@@ -786,7 +800,8 @@ static int launch_blind_rotate(eoc_engine *e, WS &W, const BRWork &w, hipStream_
         if (!k.fn) return EOC_ERR_ARG;
         for (int part = 0; part < plan.parts; part++) {
             BRArgs a = blind_rotate_args(e, W, w, sg, part, plan.parts);
-            // the gate kernels take the first three arguments, the _tv kernels five, the many-LUT kernels all six
+            // the gate kernels take the first three arguments, the _tv and encrypted-seed kernels five, the many-LUT kernels
+            // all six
             void *args[] = {&a, (void *)&e->d_tw, (void *)&e->d_twist, (void *)&w.tv, (void *)&w.tv_rows, (void *)&w.n_tables};
             HIP_TRY(hipLaunchKernel(k.fn, k.grid, k.block, args, k.lds, st));
             e->br_launches++;
@@ -954,6 +969,21 @@ static void launch_lin(eoc_engine *e, WS &W, const LinDesc *dd, uint32_t cnt, ui
     }
 #undef EOC_LIN_LAUNCH
 }
+
+// the shapes of blind_rotate_kernel() once more for the encrypted-seed family (no earlier-form twin)
+#define EOC_BR_ENC(KERNEL, ...) (sabar ? (const void *)&KERNEL<__VA_ARGS__, true> : (const void *)&KERNEL<__VA_ARGS__, false>)
+static const void *br_enc_kernel(bool wide, int l, int Bgbit, bool sabar)
+{
+    if (wide) return Bgbit == 10 ? EOC_BR_ENC(k_br_enc_wide, 10) : EOC_BR_ENC(k_br_enc_wide, 0);
+    if (l == 2 && Bgbit == 10) return EOC_BR_ENC(k_br_enc, 2, 10); // Set A
+    if (l == 3 && Bgbit == 7) return EOC_BR_ENC(k_br_enc, 3, 7);   // Set B
+    if (l == 1) return EOC_BR_ENC(k_br_enc, 1, 0);
+    if (l == 2) return EOC_BR_ENC(k_br_enc, 2, 0);
+    if (l == 3) return EOC_BR_ENC(k_br_enc, 3, 0);
+    if (l == 4) return EOC_BR_ENC(k_br_enc, 4, 0);
+    return nullptr;
+}
+#undef EOC_BR_ENC
 
 // One bootstrap level: descriptors -> rotation amounts -> ONE blind rotation -> key switch(es) -> stats.  The callers say
 // what differs; ring_mark stays with them, once per call, behind everything the call pushed (free gates included).
@@ -1711,6 +1741,20 @@ static int ensure_pack_ws(eoc_engine *e, size_t lists, hipStream_t st)
     return EOC_OK;
 }
 
+// k_pack_rows over the `L` lists whose columns a gather kernel has just laid out in d_pack_cols
+static int launch_pack_rows(eoc_engine *e, int32_t *lists, size_t L, hipStream_t st)
+{
+    const int n = e->p.n;
+    const uint32_t nchunks = (uint32_t)((n + kPackChunk - 1) / kPackChunk), items = (uint32_t)(L * nchunks);
+    SpanGuard span(e, st, KIND_KEYSWITCH);
+    hipLaunchKernelGGL(k_pack_rows, dim3((items + kPackWavesPerWG - 1) / kPackWavesPerWG), dim3(64 * kPackWavesPerWG), kPackLds, st,
+                       (const int32_t *)e->d_pack_cols, (const d2 *)e->d_pks, lists, n, nchunks, items, (const d2 *)e->d_tw,
+                       (const d2 *)e->d_twist);
+    HIP_TRY(hipGetLastError());
+    e->pack_launches++;
+    return EOC_OK;
+}
+
 // k_pack_gather lays the mask columns out as polynomials and starts every list as (0, B); k_pack_rows subtracts the chunks.
 // All arguments travel as kernel arguments: no descriptor ring slot.  Lists are sliced by the byte budget of the columns.
 extern "C" int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count, int32_t *d_lists, void *hip_stream)
@@ -1736,7 +1780,6 @@ extern "C" int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count,
     const size_t ls = std::min({n_lists, e->pack_ws_bytes / per_list, (size_t)65535}); // grid z
     int rc = ensure_pack_ws(e, ls, st);
     if (rc) return rc;
-    const uint32_t nchunks = (uint32_t)((n + kPackChunk - 1) / kPackChunk);
     for (size_t l0 = 0; l0 < n_lists; l0 += ls) {
         const size_t L = std::min(ls, n_lists - l0), cnt = std::min(count - l0 * kN, L * kN);
         const int32_t *in = d_in + l0 * kN * (n + 1);
@@ -1747,15 +1790,8 @@ extern "C" int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count,
                                dim3(256), 0, st, in, cnt, (int)n, e->d_pack_cols, lists);
             HIP_TRY(hipGetLastError());
         }
-        {
-            const uint32_t items = (uint32_t)(L * nchunks);
-            SpanGuard span(e, st, KIND_KEYSWITCH);
-            hipLaunchKernelGGL(k_pack_rows, dim3((items + kPackWavesPerWG - 1) / kPackWavesPerWG), dim3(64 * kPackWavesPerWG),
-                               kPackLds, st, (const int32_t *)e->d_pack_cols, (const d2 *)e->d_pks, lists, (int)n, nchunks, items,
-                               (const d2 *)e->d_tw, (const d2 *)e->d_twist);
-            HIP_TRY(hipGetLastError());
-        }
-        e->pack_launches++;
+        rc = launch_pack_rows(e, lists, L, st);
+        if (rc) return rc;
     }
     e->packed_samples += count;
     return EOC_OK;
@@ -1770,11 +1806,14 @@ extern "C" uint64_t eoc_engine_packed_samples(eoc_engine *e) { return e ? e->pac
 // T samples: the n_luts descriptors (no output) serve the coarse mod switch, n_luts x T more the key switch (job_base =
 // (g T + j) x rows, out = slot j's block of polynomial g).  Rows are sliced, as circuit levels are, so that the workspace
 // holds the extracted samples of a slice: at most 2^20.
-static int lut_levels(eoc_engine *e, const char *who, int n_tables, const int32_t *d_tv, size_t n_luts, const int32_t *d_in,
-                      int32_t *d_out, size_t count, hipStream_t st)
+// Encrypted seeds, enc = 1 | 2: d_tv holds TLWE lists [..][2][N] and the blind rotation is the k_br_enc family's;
+// 1 = one list per table (group), 2 = one list per job, list g x count + row.  A per-job level spans all groups only when one
+// slice holds every row (the kernel's list index is job / tv_rows); a sliced one runs group by group.  Table t's output block
+// starts at row t x out_rows of d_out (out_rows = count for the public calls).  The engine's lock is held by the caller.
+static int lut_levels_locked(eoc_engine *e, const char *who, int n_tables, int enc, const int32_t *d_tv, size_t n_luts,
+                             const int32_t *d_in, int32_t *d_out, size_t count, size_t out_rows, hipStream_t st)
 {
     if (!count) return EOC_OK;
-    std::lock_guard<std::mutex> g(e->mu);
     if (!e->bkfft || !e->ksk) {
         eoc_set_error("%s: no cloud key loaded", who);
         return EOC_ERR_NO_KEY;
@@ -1784,34 +1823,44 @@ static int lut_levels(eoc_engine *e, const char *who, int n_tables, const int32_
     const bool many = n_tables > 0;
     const size_t stride = (size_t)e->p.n + 1, slots = n_luts * (many ? (size_t)n_tables : 1);
     const size_t rows = std::min(count, std::max<size_t>(1, ((size_t)1 << 20) / slots));
-    std::vector<GateDesc> descs(many ? n_luts + slots : n_luts);
+    const size_t G = (enc == 2 && rows < count) ? 1 : n_luts; // tables per level
+    std::vector<GateDesc> descs(many ? n_luts + slots : G);
     int rc = ensure_ws(e, W, slots * rows, descs.size(), 0, st);
     if (rc) return rc;
-    for (size_t r0 = 0; r0 < count; r0 += rows) {
-        const size_t S = std::min(rows, count - r0);
-        for (size_t t = 0; t < n_luts; t++)
-            descs[t] = GateDesc{OP_RAW, (uint32_t)(t * S), d_in + r0 * stride, nullptr, nullptr,
-                                many ? nullptr : d_out + (t * count + r0) * stride};
-        for (size_t s = 0; many && s < slots; s++)
-            descs[n_luts + s] = GateDesc{OP_RAW, (uint32_t)(s * S), nullptr, nullptr, nullptr, d_out + (s * count + r0) * stride};
-        const DescRange tables{0, (uint32_t)n_luts, (uint32_t)S, false}, outs{(uint32_t)n_luts, (uint32_t)slots, (uint32_t)S, false};
-        Level lv;
-        lv.descs = descs.data();
-        lv.ndescs = descs.size();
-        lv.theta = n_tables == 2 ? 1 : (n_tables == 4 ? 2 : (n_tables == 8 ? 3 : 0));
-        lv.prep = &tables;
-        lv.ks = many ? &outs : &tables;
-        lv.nprep = lv.nks = 1;
-        lv.br.njobs = (uint32_t)(n_luts * S);
-        lv.br.seed = many ? BRWork::MANY : BRWork::TV;
-        lv.br.tv = d_tv;
-        lv.br.tv_rows = (uint32_t)S;
-        lv.br.n_tables = (uint32_t)n_tables;
-        rc = run_bootstrap(e, W, lv, st);
-        if (rc) return rc;
+    for (size_t g0 = 0; g0 < n_luts; g0 += G) {
+        for (size_t r0 = 0; r0 < count; r0 += rows) {
+            const size_t S = std::min(rows, count - r0);
+            for (size_t t = 0; t < G; t++)
+                descs[t] = GateDesc{OP_RAW, (uint32_t)(t * S), d_in + r0 * stride, nullptr, nullptr,
+                                    many ? nullptr : d_out + ((g0 + t) * out_rows + r0) * stride};
+            for (size_t s = 0; many && s < slots; s++)
+                descs[n_luts + s] = GateDesc{OP_RAW, (uint32_t)(s * S), nullptr, nullptr, nullptr, d_out + (s * out_rows + r0) * stride};
+            const DescRange tables{0, (uint32_t)G, (uint32_t)S, false}, outs{(uint32_t)n_luts, (uint32_t)slots, (uint32_t)S, false};
+            Level lv;
+            lv.descs = descs.data();
+            lv.ndescs = descs.size();
+            lv.theta = n_tables == 2 ? 1 : (n_tables == 4 ? 2 : (n_tables == 8 ? 3 : 0));
+            lv.prep = &tables;
+            lv.ks = many ? &outs : &tables;
+            lv.nprep = lv.nks = 1;
+            lv.br.njobs = (uint32_t)(G * S);
+            lv.br.seed = enc ? BRWork::ENC : (many ? BRWork::MANY : BRWork::TV);
+            lv.br.tv = enc == 2 ? d_tv + (g0 * count + r0) * 2 * kN : d_tv;
+            lv.br.tv_rows = enc == 2 ? 1u : (uint32_t)S;
+            lv.br.n_tables = (uint32_t)n_tables;
+            rc = run_bootstrap(e, W, lv, st);
+            if (rc) return rc;
+        }
     }
     ring_mark(W, st);
     return EOC_OK;
+}
+static int lut_levels(eoc_engine *e, const char *who, int n_tables, const int32_t *d_tv, size_t n_luts, const int32_t *d_in,
+                      int32_t *d_out, size_t count, hipStream_t st)
+{
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    return lut_levels_locked(e, who, n_tables, 0, d_tv, n_luts, d_in, d_out, count, count, st);
 }
 
 extern "C" int eoc_lut_batch_device(eoc_engine *e, const int32_t *d_tv, size_t n_luts, const int32_t *d_in, int32_t *d_out,
@@ -1834,6 +1883,133 @@ extern "C" int eoc_lut_many_batch_device(eoc_engine *e, int n_tables, const int3
         return EOC_ERR_ARG;
     }
     return lut_levels(e, "eoc_lut_many_batch_device", n_tables, d_tv, n_luts, d_in, d_out, count, (hipStream_t)hip_stream);
+}
+
+// ---- two-input table lookups --------------------------------------------------
+// Level 2 alone: n_groups x count blind rotations from encrypted lists, [group][row], job (g, s) rotated by input row s.
+extern "C" int eoc_lut_enc_batch_device(eoc_engine *e, const int32_t *d_lists, size_t n_groups, int per_row, const int32_t *d_in,
+                                        int32_t *d_out, size_t count, void *hip_stream)
+{
+    if (!e || !d_lists || !d_in || !d_out || n_groups == 0 || n_groups > kMaxGatesPerLaunch) {
+        eoc_set_error("eoc_lut_enc_batch_device: null argument or n_groups outside [1, %zu]", kMaxGatesPerLaunch);
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    return lut_levels_locked(e, "eoc_lut_enc_batch_device", 0, per_row ? 2 : 1, d_lists, n_groups, d_in, d_out, count, count,
+                             (hipStream_t)hip_stream);
+}
+
+// k_tvpack_cols + k_pack_rows over n_funcs x count lists, sliced by the column budget; the engine's lock is held by the caller
+static int tv_pack_locked(eoc_engine *e, const char *who, int p, const int32_t *d_vals, size_t n_funcs, size_t count,
+                          int32_t *d_lists, hipStream_t st)
+{
+    if (!e->d_pks) {
+        eoc_set_error("%s: no packing key loaded (eoc_engine_set_packing_key)", who);
+        return EOC_ERR_NO_KEY;
+    }
+    const size_t n = (size_t)e->p.n, per_list = n * kN * sizeof(int32_t), n_lists = n_funcs * count;
+    if (!n_lists) return EOC_OK;
+    if (e->pack_ws_bytes < per_list) {
+        eoc_set_error("%s: one list needs %zu bytes of workspace, the budget (EOC_TFHE_PACK_WS_BYTES) is %zu", who, per_list,
+                      e->pack_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t ls = std::min({n_lists, e->pack_ws_bytes / per_list, (size_t)65535}); // grid z
+    int rc = ensure_pack_ws(e, ls, st);
+    if (rc) return rc;
+    for (size_t l0 = 0; l0 < n_lists; l0 += ls) {
+        const size_t L = std::min(ls, n_lists - l0);
+        int32_t *lists = d_lists + l0 * 2 * kN;
+        {
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            const dim3 grid(kN / kPackTile, (unsigned)((n + 1 + kPackTile - 1) / kPackTile), (unsigned)L);
+            auto kfn = p == 2 ? k_tvpack_cols<2> : (p == 4 ? k_tvpack_cols<4> : k_tvpack_cols<8>);
+            hipLaunchKernelGGL(kfn, grid, dim3(256), 0, st, d_vals, (uint32_t)count, (uint32_t)l0, (int)n, e->d_pack_cols, lists);
+            HIP_TRY(hipGetLastError());
+        }
+        rc = launch_pack_rows(e, lists, L, st);
+        if (rc) return rc;
+    }
+    e->packed_samples += n_lists * (size_t)p; // the samples read, not the N slots they fill
+    return EOC_OK;
+}
+extern "C" int eoc_tv_pack_device(eoc_engine *e, int p, const int32_t *d_vals, size_t n_funcs, size_t count, int32_t *d_lists,
+                                  void *hip_stream)
+{
+    if (!e || !d_vals || !d_lists || !(p == 2 || p == 4 || p == 8) || n_funcs == 0 || n_funcs * (uint64_t)count > 0xffffffffull) {
+        eoc_set_error("eoc_tv_pack_device: null argument, p = %d not one of 2, 4, 8, no function, or more than 2^32 lists", p);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    return tv_pack_locked(e, "eoc_tv_pack_device", p, d_vals, n_funcs, count, d_lists, (hipStream_t)hip_stream);
+}
+
+// the level-1 outputs [n_funcs][p][rows][n+1] and the lists [n_funcs][rows][2][N] of a slice, grown by the workspace's rule
+static int ensure_lut2_ws(eoc_engine *e, size_t bytes, hipStream_t st)
+{
+    if (bytes <= e->lut2_cap) return EOC_OK;
+    if (stream_is_capturing(st)) {
+        eoc_set_error("graph capture: the two-input lookup workspace would have to grow (%zu > %zu bytes); run one call of the "
+                      "captured shape before capturing", bytes, e->lut2_cap);
+        return EOC_ERR_STATE;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    hipFree(e->d_lut2);
+    e->d_lut2 = nullptr;
+    e->lut2_cap = 0;
+    HIP_TRY(hipMalloc(&e->d_lut2, bytes));
+    e->lut2_cap = bytes;
+    e->ws_grows++;
+    return EOC_OK;
+}
+
+// F(x, y): level 1 (the existing _tv / many-LUT path) on x against the p tables x -> F(x, j), the pack of each row's p values
+// into one encrypted test polynomial, level 2 (k_br_enc*) on y from that polynomial.
+extern "C" int eoc_lut2_batch_device(eoc_engine *e, int p, int n_tables, const int32_t *d_tv0, size_t n_funcs, const int32_t *d_x,
+                                     const int32_t *d_y, int32_t *d_out, size_t count, void *hip_stream)
+{
+    const int T = n_tables > 1 ? n_tables : 1;
+    const bool p_ok = p == 2 || p == 4 || p == 8, t_ok = n_tables >= 0 && (T == 1 || T == 2 || T == 4 || T == 8);
+    if (!e || !d_tv0 || !d_x || !d_y || !d_out || !p_ok || !t_ok || p % T != 0 || (T > 1 && p * T > 16) || n_funcs == 0 ||
+        n_funcs > kMaxGatesPerLaunch / (size_t)(p_ok ? p : 1)) {
+        eoc_set_error("eoc_lut2_batch_device: null argument, (p, n_tables) = (%d, %d) not supported (p in {2, 4, 8}, T in {1, 2, 4, "
+                      "8}, T divides p, p T <= 16 for T > 1) or n_funcs x p outside [1, %zu]", p, n_tables, kMaxGatesPerLaunch);
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->bkfft || !e->ksk) {
+        eoc_set_error("eoc_lut2_batch_device: no cloud key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    if (!e->d_pks) {
+        eoc_set_error("eoc_lut2_batch_device: no packing key loaded (eoc_engine_set_packing_key)");
+        return EOC_ERR_NO_KEY;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t stride = (size_t)e->p.n + 1;
+    // per row: n_funcs x p level-1 outputs and n_funcs lists of 8 KiB; a slice holds at most 2^20 level-1 outputs (lut_levels'
+    // rule) and at most kLut2WsBytes of both
+    constexpr size_t kLut2WsBytes = (size_t)256 << 20;
+    const size_t row_vals = n_funcs * (size_t)p * stride * sizeof(int32_t), row_lists = n_funcs * 2 * kN * sizeof(int32_t);
+    const size_t rows = std::min({count, std::max<size_t>(1, ((size_t)1 << 20) / (n_funcs * (size_t)p)),
+                                  std::max<size_t>(1, kLut2WsBytes / (row_vals + row_lists))});
+    int rc = ensure_lut2_ws(e, rows * (row_vals + row_lists), st);
+    if (rc) return rc;
+    int32_t *d_lists = e->d_lut2, *d_vals = e->d_lut2 + rows * (row_lists / sizeof(int32_t));
+    for (size_t r0 = 0; r0 < count; r0 += rows) {
+        const size_t S = std::min(rows, count - r0);
+        rc = lut_levels_locked(e, "eoc_lut2_batch_device", T > 1 ? T : 0, 0, d_tv0, n_funcs * (size_t)(p / T), d_x + r0 * stride,
+                               d_vals, S, S, st);
+        if (!rc) rc = tv_pack_locked(e, "eoc_lut2_batch_device", p, d_vals, n_funcs, S, d_lists, st);
+        if (!rc) rc = lut_levels_locked(e, "eoc_lut2_batch_device", 0, 2, d_lists, n_funcs, d_y + r0 * stride, d_out + r0 * stride, S,
+                                        count, st);
+        if (rc) return rc;
+    }
+    return EOC_OK;
 }
 
 // ---- integer circuits ------------------------------------------------------

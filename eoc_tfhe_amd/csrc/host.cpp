@@ -631,6 +631,24 @@ extern "C" int eoc_lut_many_test_polynomial(int p, int n_tables, const int32_t *
     return EOC_OK;
 }
 
+// two-input lookups: the level-1 polynomials of ONE function, table[x p + y]; polynomial g holds the tables
+// x -> F(x, y) for y = g T .. g T + T - 1
+extern "C" int eoc_lut2_test_polynomials(int p, int n_tables, const int32_t *table, int32_t *tv)
+{
+    const int T = n_tables > 1 ? n_tables : 1;
+    const bool t_ok = n_tables >= 0 && (T == 1 || T == 2 || T == 4 || T == 8);
+    if (!table || !tv || !lut_p_ok(p) || !t_ok || p % T != 0 || (T > 1 && p * T > 16)) return EOC_ERR_ARG;
+    int32_t cols[8 * 8]; // [T][p]: table y of the polynomial as a function of x
+    for (int g = 0; g < p / T; g++) {
+        for (int j = 0; j < T; j++)
+            for (int x = 0; x < p; x++) cols[j * p + x] = table[x * p + g * T + j];
+        const int rc = T == 1 ? eoc_lut_test_polynomial(p, cols, tv + (size_t)g * EOC_N)
+                              : eoc_lut_many_test_polynomial(p, T, cols, tv + (size_t)g * EOC_N);
+        if (rc != EOC_OK) return rc;
+    }
+    return EOC_OK;
+}
+
 // ---- compact public-key encryption (include/eoc_tfhe_gpu.h) ---------------------------------------------
 // acc += u * P in Z_2^32[X]/(X^N + 1) for a binary u given by the positions of its ones: a sum of signed rotations of P
 static void add_binary_product(const std::vector<int> &ones, const uint32_t *P, uint32_t *acc)
@@ -1162,6 +1180,19 @@ extern "C" int eoc_pack(const int32_t *cts, size_t count, int32_t *lists)
         if (rc) return rc;
     }
     return eoc_pack_engines(cts, count, lists);
+}
+// two-input lookups on the global context's engines (brought up behind the global key on first use; a cloud key and an
+// imported packing key suffice: key mode 2)
+extern "C" int eoc_lut2_batch(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y,
+                              int32_t *out, size_t count)
+{
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) {
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    }
+    return eoc_lut2_engines(p, n_tables, tables, n_funcs, x, y, out, count);
 }
 // an encrypted-index table read on the global context's engines (brought up behind the global key on first use; a cloud key
 // alone suffices)

@@ -908,7 +908,12 @@ constexpr int kBRLds = (kTwEntries + kNH + 2 * kScr) * 16 + kAbarLds; // 37 632 
 //     (Gadget<BGBIT>), as the kernel's text named it: read from the struct, k_blind_rotate_wide<10> changed in 64 lines;
 //   * the measured exceptions: the rotation block (16 ds_bpermute + the 32-way rot_digits switch) as a function renames
 //     registers in k_blind_rotate<2,10> and changes the length of twenty other instances, and the three-line sum of the
-//     gadget offset as a helper inverts the step loop's entry test (see Gadget).  Both stay in the kernels' text.
+//     gadget offset as a helper inverts the step loop's entry test (see Gadget).  Both stay in the kernels' text;
+//   * the ORDER in which kernels are emitted is part of the assembly text (branch labels carry the function's number): plain
+//     kernels come first, in the order of their definitions, then the templates in the order of their first use in
+//     engine.hip.  A plain kernel added anywhere, or a template instance first used ahead of an existing one, renumbers the
+//     labels of everything behind it (same instructions, different text for tools/isa_diff.py): new kernels are templates
+//     whose first use lies behind every earlier one (k_br_enc*: engine.hip's br_enc_kernel; k_tvpack_cols: tv_pack_locked).
 // The body's constant TV selects the accumulator: false = the gate test vector (mu, ..., mu),
 // true = a test polynomial per job.  The gate kernel's name, template arguments and argument list are what
 // tests/test_isa_guard.py and the profiles look up and what the shipped code was measured as: they do not change.
@@ -916,7 +921,7 @@ template <int L, int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(128, 2) void k_blind_rotate(BRArgs A, const d2 *__restrict__ g_tw,
                                                          const d2 *__restrict__ g_twist)
 {
-    constexpr bool TV = false, MANY = false, TLDS = false;
+    constexpr bool TV = false, MANY = false, TLDS = false, ENC = false;
     const int32_t *const tv = nullptr;
     const uint32_t tv_rows = 1, n_tables = 1;
 #include "blind_rotate_pair.inc"
@@ -928,7 +933,7 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_tv(BRArgs A, const d2 *
                                                             const d2 *__restrict__ g_twist, const int32_t *__restrict__ tv,
                                                             uint32_t tv_rows)
 {
-    constexpr bool TV = true, MANY = false, TLDS = false;
+    constexpr bool TV = true, MANY = false, TLDS = false, ENC = false;
     const uint32_t n_tables = 1;
 #include "blind_rotate_pair.inc"
 }
@@ -941,7 +946,19 @@ template <int L, int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(128, 2) void k_lut_many(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist,
                                                      const int32_t *__restrict__ tv, uint32_t tv_rows, uint32_t n_tables)
 {
-    constexpr bool TV = true, MANY = true, TLDS = false;
+    constexpr bool TV = true, MANY = true, TLDS = false, ENC = false;
+#include "blind_rotate_pair.inc"
+}
+// Blind rotation from an ENCRYPTED polynomial: job j starts from ACC = X^(2N - barb) (c0, c1), (c0, c1) the
+// TLWE list tv[(job0 + j) / tv_rows] ([lists][2][N] int32, the layout of the packing key switch); wave h seeds polynomial
+// h.  Step loop and epilogue are the _tv kernel's.  The name avoids "k_blind_rotate" and "k_lut_many" (the ISA tests count
+// those); this family has no earlier-form twin.
+template <int L, int BGBIT = 0, bool SABAR = false>
+__global__ __launch_bounds__(128, 2) void k_br_enc(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist,
+                                                   const int32_t *__restrict__ tv, uint32_t tv_rows)
+{
+    constexpr bool TV = true, MANY = false, TLDS = false, ENC = true;
+    const uint32_t n_tables = 1;
 #include "blind_rotate_pair.inc"
 }
 
@@ -952,7 +969,7 @@ __global__ __launch_bounds__(128, 2) void k_lut_many(BRArgs A, const d2 *__restr
 template <int L, int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(128, 2) void k_br_lds(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist)
 {
-    constexpr bool TV = false, MANY = false, TLDS = true;
+    constexpr bool TV = false, MANY = false, TLDS = true, ENC = false;
     const int32_t *const tv = nullptr;
     const uint32_t tv_rows = 1, n_tables = 1;
 #include "blind_rotate_pair.inc"
@@ -961,7 +978,7 @@ template <int L, int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(128, 2) void k_br_lds_tv(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist,
                                                       const int32_t *__restrict__ tv, uint32_t tv_rows)
 {
-    constexpr bool TV = true, MANY = false, TLDS = true;
+    constexpr bool TV = true, MANY = false, TLDS = true, ENC = false;
     const uint32_t n_tables = 1;
 #include "blind_rotate_pair.inc"
 }
@@ -969,7 +986,7 @@ template <int L, int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(128, 2) void k_br_lds_many(BRArgs A, const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist,
                                                         const int32_t *__restrict__ tv, uint32_t tv_rows, uint32_t n_tables)
 {
-    constexpr bool TV = true, MANY = true, TLDS = true;
+    constexpr bool TV = true, MANY = true, TLDS = true, ENC = false;
 #include "blind_rotate_pair.inc"
 }
 
@@ -1072,7 +1089,7 @@ template <int BGBIT = 0, bool SABAR = false>
 __global__ __launch_bounds__(64 * kBRWideJobsPerWG, 2) void k_blind_rotate_wide(BRArgs A, const d2 *__restrict__ g_tw,
                                                               const d2 *__restrict__ g_twist)
 {
-    constexpr bool TV = false, MANY = false;
+    constexpr bool TV = false, MANY = false, ENC = false;
     const int32_t *const tv = nullptr;
     const uint32_t tv_rows = 1, n_tables = 1;
 #include "blind_rotate_wide.inc"
@@ -1082,7 +1099,7 @@ __global__ __launch_bounds__(64 * kBRWideJobsPerWG, 2) void k_blind_rotate_wide_
                                                                  const d2 *__restrict__ g_twist,
                                                                  const int32_t *__restrict__ tv, uint32_t tv_rows)
 {
-    constexpr bool TV = true, MANY = false;
+    constexpr bool TV = true, MANY = false, ENC = false;
     const uint32_t n_tables = 1;
 #include "blind_rotate_wide.inc"
 }
@@ -1093,7 +1110,17 @@ __global__ __launch_bounds__(64 * kBRWideJobsPerWG, 2) void k_lut_many_wide(BRAr
                                                                             const int32_t *__restrict__ tv, uint32_t tv_rows,
                                                                             uint32_t n_tables)
 {
-    constexpr bool TV = true, MANY = true;
+    constexpr bool TV = true, MANY = true, ENC = false;
+#include "blind_rotate_wide.inc"
+}
+// the wide twin of k_br_enc: the wave seeds both accumulators from the job's list
+template <int BGBIT = 0, bool SABAR = false>
+__global__ __launch_bounds__(64 * kBRWideJobsPerWG, 2) void k_br_enc_wide(BRArgs A, const d2 *__restrict__ g_tw,
+                                                                          const d2 *__restrict__ g_twist,
+                                                                          const int32_t *__restrict__ tv, uint32_t tv_rows)
+{
+    constexpr bool TV = true, MANY = false, ENC = true;
+    const uint32_t n_tables = 1;
 #include "blind_rotate_wide.inc"
 }
 
@@ -1829,6 +1856,40 @@ __global__ __launch_bounds__(64 * kPackWavesPerWG, 2) void k_pack_rows(const int
         atomicAdd(po + kN + j, (int)(0u - wrap_trunc(y.x)));
         atomicAdd(po + kN + j + kNH, (int)(0u - wrap_trunc(y.y)));
     }
+}
+
+// The same two outputs for a TEST-POLYNOMIAL list: list (f, s) holds the p values v_0 .. v_(p-1) of row s
+// of function f, in[((f p + j) rows + s)][n + 1], each over a window of N / p coefficients by the rule of
+// eoc_lut_test_polynomial: coefficient k < N - N / (2p) takes sample j(k) = floor((k p + N / 2) / N), the last N / (2p)
+// coefficients take sample 0 negated (word-wise).  The words are those of k_pack_gather on the N-row batch of repeated /
+// negated samples, which never exists in memory.  p in {2, 4, 8}: every window boundary is a multiple of 64, so a tile of 64
+// coefficients reads ONE sample: a wave loads 64 mask words (256 contiguous bytes) and stores, per key index, 64 copies of
+// one of them (256 contiguous bytes): no transpose, no LDS.  grid: x = N / 64 coefficient tiles, y = ceil((n + 1) / 64)
+// column tiles, z = lists of the slice (list = f rows + s - list0); block = 256 (wave w: columns w, w + 4, ...).  A template
+// over the message space p (defined and first used behind every other kernel: the device compiler emits kernels in that
+// order, and the earlier ones keep their label numbers).
+template <int p>
+__global__ __launch_bounds__(256) void k_tvpack_cols(const int32_t *__restrict__ in, uint32_t rows, uint32_t list0, int n,
+                                                     int32_t *__restrict__ cols, int32_t *__restrict__ lists)
+{
+    static_assert(p == 2 || p == 4 || p == 8, "window boundaries are multiples of the tile only for these");
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int i0 = blockIdx.x * kPackTile, m0 = blockIdx.y * kPackTile;
+    const size_t list = blockIdx.z;
+    const uint32_t gl = list0 + (uint32_t)list, f = gl / rows, s = gl - f * rows;
+    const bool neg = i0 >= kN - kN / (2 * p);
+    const int j = neg ? 0 : (i0 * p + kN / 2) / kN;
+    const int32_t *row = in + (((size_t)f * p + j) * rows + s) * ((size_t)n + 1);
+    const int m = m0 + tx;
+    const uint32_t w = m <= n ? (uint32_t)row[m] : 0u;
+    const int32_t mine = (int32_t)(neg ? 0u - w : w);
+    for (int r = ty; r < kPackTile; r += 4) {
+        const int mr = m0 + r;
+        const int32_t v = __shfl(mine, r, 64);
+        if (mr < n) cols[(list * n + mr) * kN + i0 + tx] = v;
+        else if (mr == n) lists[list * 2 * kN + kN + i0 + tx] = v;
+    }
+    if (blockIdx.y == 0 && ty == 0) lists[list * 2 * kN + i0 + tx] = 0;
 }
 
 } // namespace eoc

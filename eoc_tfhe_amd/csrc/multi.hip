@@ -406,6 +406,33 @@ int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in,
     return slot_finish(st, run());
 }
 
+// one device's block [lo, hi) of a two-input lookup batch: tv0 [n_funcs][p / T][N], x, y [count][stride] on the
+// host, out [n_funcs][count][stride]
+int slot_lut2_block(Slot &s, int p, int n_tables, const int32_t *tv0, size_t n_funcs, const int32_t *x, const int32_t *y,
+                    int32_t *out, size_t count, size_t lo, size_t hi, size_t stride_ints)
+{
+    const size_t blk = hi - lo;
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t tv_ints = n_funcs * (size_t)(p / std::max(1, n_tables)) * EOC_N, need = tv_ints + (2 + n_funcs) * blk * stride_ints;
+    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    if (rc) return rc;
+    int32_t *d_tv = s.d_lut, *d_x = d_tv + tv_ints, *d_y = d_x + blk * stride_ints, *d_out = d_y + blk * stride_ints;
+    hipStream_t st = s.st[0];
+    const size_t row_bytes = stride_ints * 4;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_tv, tv0, tv_ints * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_x, x + lo * stride_ints, blk * row_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_y, y + lo * stride_ints, blk * row_bytes, hipMemcpyHostToDevice, st));
+        int r = eoc_lut2_batch_device(s.e, p, n_tables, d_tv, n_funcs, d_x, d_y, d_out, blk, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpy2DAsync(out + lo * stride_ints, count * row_bytes, d_out, blk * row_bytes, blk * row_bytes, n_funcs,
+                                 hipMemcpyDeviceToHost, st));
+        return EOC_OK;
+    };
+    return slot_finish(st, run());
+}
+
 // one device's block [lo, hi) of an integer circuit's instances: wires [n_wires][instances][stride] on the host, every wire's
 // rows of the block in, the netlist, every wire's rows out; tv = the nodes' test polynomials [n_tv][N] on the host
 int slot_int_block(Slot &s, const eoc_inode *nodes, size_t n_nodes, const int32_t *tv, size_t n_tv, int32_t *wires,
@@ -1182,6 +1209,41 @@ extern "C" int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, si
                                   size_t count)
 {
     return lut_batch("eoc_lut_many_batch", true, p, n_tables, tables, n_luts, in, out, count);
+}
+
+// eoc_lut2_batch's engine half (host.cpp holds the global key's lock and has brought the engines up): tables
+// [n_funcs][p][p]; the level-1 polynomials are built on the host
+int eoc_lut2_engines(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y, int32_t *out,
+                     size_t count)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_lut2_batch: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        return EOC_ERR_NO_DEVICE;
+    }
+    if (!tables || !x || !y || !out || n_funcs == 0) {
+        eoc_set_error("eoc_lut2_batch: null argument or no function");
+        return EOC_ERR_ARG;
+    }
+    const int T = n_tables > 1 ? n_tables : 1;
+    const size_t per_func = (p > 0 && p <= 8 ? (size_t)(p / T) : 1) * EOC_N;
+    std::vector<int32_t> tv(n_funcs * per_func);
+    for (size_t f = 0; f < n_funcs; f++)
+        if (eoc_lut2_test_polynomials(p, n_tables, tables + f * (size_t)p * p, tv.data() + f * per_func) != EOC_OK) {
+            eoc_set_error("eoc_lut2_batch: (p, n_tables) = (%d, %d) is not supported (p in {2, 4, 8}, T in {1, 2, 4, 8}, T divides "
+                          "p, p T <= 16 for T > 1)", p, n_tables);
+            return EOC_ERR_ARG;
+        }
+    if (!count) return EOC_OK;
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    const size_t stride = (size_t)G.p.n + 1;
+    const int32_t *tvp = tv.data();
+    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
+        return slot_lut2_block(G.slots[i], p, n_tables, tvp, n_funcs, x, y, out, count, lo, hi, stride);
+    });
 }
 
 extern "C" int eoc_int_circuit_run(const eoc_inode *nodes, size_t n_nodes, const int32_t *tables, const int32_t *table_p,

@@ -455,3 +455,47 @@ def pack_offset(row_phases, lwe_key, filled=N):
     a, b = np.minimum(i + 1 + N - f, N), N                               # - E[i - k + N] for i < k < filled
     minus = np.where(f > i + 1, pre[b] - pre[np.maximum(a, i + 1)], 0.0)
     return 0.5 * (plus - minus)
+
+
+# ---- two-input table lookups: blind rotation from an encrypted polynomial ---------------------------------------
+def br_enc_var(params, lwe_key, tlwe_key):
+    """variance (torus units) a blind rotation ADDS when its accumulator starts from an ENCRYPTED TLWE sample (k_br_enc*):
+    the three terms of `predict` with step 0 a REGULAR step.  `predict` discounts step 0 because the gate accumulator
+    (0, X^-b tv) has an all-zero mask and a body of constant digits; an encrypted seed's mask is already pseudo-random, so
+      rows        n (1 - 1/2N) 2l N E[d^2] sigma_eff^2        every step counts whole (n_eff = n (1 - 1/2N): an amount of 0 adds nothing)
+      remainder   w (1 + |s'|) q^2 / 12                        w_eff = w: step 0 has a remainder too when s_0 = 1
+      truncation  (w - 1) (q/2)^2 G(s')                        the last active step is the constant br_mean, as in `predict`
+    Nothing fitted."""
+    n, l, Bgbit = int(params.n), int(params.l), int(params.Bgbit)
+    Bg = 1 << Bgbit
+    q = 2.0 ** (-l * Bgbit)
+    w = int(np.asarray(lwe_key, np.int64).sum())
+    hw = int(np.asarray(tlwe_key, np.int64).sum())
+    Jv = _Jv(tlwe_key)
+    rows = n * (1.0 - 1.0 / (2 * N)) * 2 * l * N * ((Bg * Bg + 2) / 12.0) * _sig2(params)
+    return rows + w * (1 + hw) * q * q / 12.0 + max(w - 1, 0) * (q / 2) ** 2 * float((Jv**2).mean())
+
+
+def lut2_var(params, lwe_key, tlwe_key, ksk=None):
+    """variance (torus units) of the error of a two-input lookup's output (eoc_lut2_batch_device) around lut2_mean, for a fixed
+    key: the level-1 output that sits in the packed polynomial (predict()['total_var']) + the packing key switch of a full
+    list (pack_var(params, lwe_key, N)) + a regular blind rotation (br_enc_var) + the key switch (predict()['ks_var'])."""
+    pr = predict(params, lwe_key, tlwe_key, ksk)
+    return pr["total_var"] + pack_var(params, lwe_key, N) + br_enc_var(params, lwe_key, tlwe_key) + pr["ks_var"]
+
+
+def lut2_mean(params, lwe_key, tlwe_key, ksk=None):
+    """mean error (torus units) of a two-input lookup's output: the level-1 output's total_mean + the level-2 blind rotation's
+    br_mean + its key switch's ks_mean; the pack's mean is 0"""
+    pr = predict(params, lwe_key, tlwe_key, ksk)
+    return pr["total_mean"] + pr["br_mean"] + pr["ks_mean"]
+
+
+def lut2_margin_sigma(p, n_tables, params, lwe_key, tlwe_key, x_var=None, y_var=None):
+    """(level-1 margin, level-2 margin) of a two-input lookup at message space p, in predicted standard deviations: level 1
+    mod-switches x on the grid of T = n_tables, level 2 mod-switches y on the grid of 1.  x_var / y_var: variance of the
+    samples in front of the call (None: a gate-bootstrap output, predict()['total_var'])."""
+    v_out = predict(params, lwe_key, tlwe_key)["total_var"]
+    vx = v_out if x_var is None else float(x_var)
+    vy = v_out if y_var is None else float(y_var)
+    return (lut_margin_sigma_var(p, max(int(n_tables), 1), vx, lwe_key), lut_margin_sigma_var(p, 1, vy, lwe_key))

@@ -766,6 +766,49 @@ size_t eoc_global_packing_key_export(void *buf, size_t cap); /* bytes needed (0 
 int eoc_global_import_packing_key_blob(const void *buf, size_t len);
 int eoc_pack(const int32_t *cts, size_t count, int32_t *lists);
 
+/* ---- two-input table lookups: blind rotation from an encrypted polynomial --------------------------------
+ * F(x, y) on Z_p x Z_p, p in {2, 4, 8}, by the tree method: level 1 bootstraps x against the p public tables x -> F(x, j)
+ * (T = max(n_tables, 1) tables per blind rotation), the packing key switch lays the p results v_0 .. v_(p-1) of a row out as
+ * ONE TLWE test polynomial by eoc_lut_test_polynomial's rule, and level 2 blind-rotates that ENCRYPTED polynomial by y,
+ * extracts and key-switches: v_y = F(x, y), with refreshed noise (noise.lut2_var).
+ *   eoc_lut2_test_polynomials   host: table [p][p] of Torus32 output values, table[x p + y]; writes tv [p / T][N], polynomial
+ *               g holding the tables y = g T .. g T + T - 1 as eoc_lut_many_test_polynomial (T > 1) or
+ *               eoc_lut_test_polynomial (T = 1) lays them out.  EOC_ERR_ARG for a null pointer, p outside {2, 4, 8}, T outside
+ *               {1, 2, 4, 8}, T not dividing p, or p T > 16 at T > 1.
+ *   eoc_lut_enc_batch_device    level 2 alone: d_lists DEVICE TLWE samples [..][2][N] (c0 first: eoc_pack_device,
+ *               eoc_pk_encrypt_*, eoc_table_trivial), d_in DEVICE [count][n+1], d_out DEVICE [n_groups][count][n+1].  Job
+ *               (g, s) starts from ACC = X^(-barb_s) (c0, c1) of list g (per_row == 0) or list g x count + s (per_row != 0)
+ *               and is rotated by input row s: k_prepare, ONE blind rotation of the k_br_enc / k_br_enc_wide family through
+ *               the gate levels' launch policy, the key switch.  Rows are sliced by eoc_lut_batch_device's 2^20 rule; the
+ *               cloud key alone suffices.  EOC_TFHE_BR_TABLES_LDS=1 does not apply: the family has no earlier-form twin.
+ *               Stats: bootstraps and keyswitches += n_groups x count.  EOC_ERR_ARG for a null pointer or n_groups outside
+ *               [1, 32 768].
+ *   eoc_tv_pack_device          d_vals DEVICE [n_funcs][p][count][n+1] (eoc_lut_batch_device's / eoc_lut_many_batch_device's
+ *               output order), d_lists DEVICE [n_funcs][count][2][N]: list (f, s) = the packing key switch of the N-row batch
+ *               in which coefficient k < N - N / (2p) holds sample v_j, j = (k p + N / 2) / N, and the last N / (2p)
+ *               coefficients hold -v_0 (word-wise) -- word for word what eoc_pack_device gives for that batch, which is never
+ *               materialised.  EOC_ERR_NO_KEY without a packing key; lists are sliced by eoc_pack_device's column budget.
+ *               eoc_engine_pack_launches counts one per slice, eoc_engine_packed_samples the n_funcs x count x p samples READ.
+ *   eoc_lut2_batch_device       d_tv0 DEVICE [n_funcs][p / T][N] (eoc_lut2_test_polynomials per function), d_x, d_y DEVICE
+ *               [count][n+1] at message space p, d_out DEVICE [n_funcs][count][n+1].  Rows are sliced so that the level-1
+ *               outputs (at most 2^20) and the lists (8 KiB each) of a slice fit 256 MiB; that buffer grows by
+ *               eoc_engine_reserve's rule (EOC_ERR_STATE under capture: run one call of the captured shape first).  Needs the
+ *               cloud key and the packing key (EOC_ERR_NO_KEY).  Stats: bootstraps += n_funcs x count x (p / T + 1),
+ *               keyswitches += n_funcs x count x (p + 1).  EOC_ERR_ARG as eoc_lut2_test_polynomials, for n_tables < 0 and for
+ *               n_funcs x p outside [1, 32 768].  count == 0 is a no-op.
+ *   eoc_lut2_batch              global context, host buffers, synchronous: tables [n_funcs][p][p] of Torus32 output values,
+ *               x, y [count][n+1], out [n_funcs][count][n+1]; rows are cut into eoc_shard_range blocks, one per engine.  Works
+ *               in key mode 2 once eoc_global_import_packing_key_blob has run; EOC_ERR_NO_KEY otherwise. */
+int eoc_lut2_test_polynomials(int p, int n_tables, const int32_t *table, int32_t *tv);
+int eoc_lut_enc_batch_device(eoc_engine *e, const int32_t *d_lists, size_t n_groups, int per_row, const int32_t *d_in,
+                             int32_t *d_out, size_t count, void *hip_stream);
+int eoc_tv_pack_device(eoc_engine *e, int p, const int32_t *d_vals, size_t n_funcs, size_t count, int32_t *d_lists,
+                       void *hip_stream);
+int eoc_lut2_batch_device(eoc_engine *e, int p, int n_tables, const int32_t *d_tv0, size_t n_funcs, const int32_t *d_x,
+                          const int32_t *d_y, int32_t *d_out, size_t count, void *hip_stream);
+int eoc_lut2_batch(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y, int32_t *out,
+                   size_t count);
+
 #ifdef __cplusplus
 }
 #endif
