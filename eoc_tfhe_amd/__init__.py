@@ -265,6 +265,11 @@ def lib():
         "eoc_table_read_device": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp]),
         "eoc_engine_cmux_launches": (u64, [vp]),
         "eoc_table_read": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp]),
+        # encrypted-index table updates
+        "eoc_demux_device": (C.c_int, [vp, vp, vp, vp, vp, sz, C.c_int, vp]),
+        "eoc_table_update_device": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
+        "eoc_engine_demux_launches": (u64, [vp]),
+        "eoc_table_update": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, sz]),
         # packing key switch: LWE samples -> compact lists
         "eoc_packing_key_blob_bytes": (sz, [PP]),
         "eoc_packing_key_export": (C.c_int, [vp, vp, sz]),
@@ -830,6 +835,20 @@ class Engine:
         _check(self.L.eoc_table_read_device(self.h, d_table, int(log2_lists), int(log2_width), d_sel_fft, queries, d_out,
                                             stream), "eoc_table_read_device")
 
+    def demux_device(self, d_sel_fft, d_in, d_out0, d_out1, count, accumulate=False, stream=None):
+        """E = C[i] (x) in[i]; out1[i] = E, out0[i] = in[i] - E on TLWE samples [count][2][N], one converted selector per item
+        (eoc_demux_device): in[i] goes to out1 where the bit is 1 and to out0 otherwise.  accumulate adds into the outputs
+        (integer atomics) instead of storing.  Needs no key."""
+        _check(self.L.eoc_demux_device(self.h, d_sel_fft, d_in, d_out0, d_out1, count, 1 if accumulate else 0, stream),
+               "eoc_demux_device")
+
+    def table_update_device(self, d_table, log2_lists, log2_width, d_sel_fft, d_vals, queries, stream=None):
+        """table[idx_q] += value_q in place for each of `queries` encrypted indices (eoc_table_update_device): d_table
+        [2^d][2][N], d_sel_fft as table_read_device's (None at d = 0, log2_width = 10), d_vals [queries][2][N] TLWE samples with
+        the entry's W messages in slots 0 .. W-1 and 0 elsewhere.  Needs no key."""
+        _check(self.L.eoc_table_update_device(self.h, d_table, int(log2_lists), int(log2_width), d_sel_fft, d_vals, queries,
+                                              stream), "eoc_table_update_device")
+
     def load_packing_key(self, blob):
         """Install an EOCPKS1 blob (SecretKey.packing_key_bytes) as this engine's packing key (eoc_engine_set_packing_key);
         replaces an earlier one.  The blob's parameters must be the engine's."""
@@ -875,6 +894,7 @@ class Engine:
                     br_wide_launches=int(self.L.eoc_engine_blind_rotate_wide_launches(self.h)),
                     ks_mfma_launches=int(self.L.eoc_engine_keyswitch_mfma_launches(self.h)),
                     cmux_launches=int(self.L.eoc_engine_cmux_launches(self.h)),
+                    demux_launches=int(self.L.eoc_engine_demux_launches(self.h)),
                     pack_launches=int(self.L.eoc_engine_pack_launches(self.h)),
                     packed_samples=int(self.L.eoc_engine_packed_samples(self.h)))
 
@@ -1183,6 +1203,31 @@ def table_read(table, log2_lists, log2_width, selectors):
     _check(lib().eoc_table_read(table.ctypes.data, d, lw, selectors.ctypes.data, selectors.shape[0], out.ctypes.data),
            "eoc_table_read")
     return out
+
+
+def table_update(table, log2_lists, log2_width, selectors, values):
+    """eoc_table_update on the global context (no key is used; a cloud key alone brings the engines up): returns the table
+    [2^log2_lists][2][N] with table[idx_q] += values[q] for every query.  selectors as table_read's (None or empty at
+    log2_lists = 0, log2_width = 10), values [queries][2][N] TLWE samples (pack of W samples, PublicKey.encrypt_*,
+    trivial_table) with the entry in slots 0 .. W-1 and 0 elsewhere"""
+    table = np.array(table, np.int32, order="C")                              # a copy: the C call updates in place
+    d, lw = int(log2_lists), int(log2_width)
+    if table.ndim != 3 or table.shape[1:] != (2, N) or not 0 <= d <= 12 or table.shape[0] != 1 << d:
+        raise EocError(f"table_update: table must be [2^log2_lists][2][{N}] with log2_lists in [0, 12], got {table.shape}")
+    if not 0 <= lw <= 10:
+        raise EocError(f"table_update: log2_width = {lw} outside [0, 10]")
+    depth = d + 10 - lw
+    values = np.ascontiguousarray(values, np.int32)
+    if values.ndim != 3 or values.shape[1:] != (2, N):
+        raise EocError(f"table_update: values must be [queries][2][{N}], got {values.shape}")
+    sel_ptr = None
+    if depth:
+        selectors = np.ascontiguousarray(selectors, np.int32)
+        if selectors.ndim != 5 or selectors.shape[:2] != (values.shape[0], depth) or selectors.shape[3:] != (2, N):
+            raise EocError(f"table_update: selectors must be [{values.shape[0]}][{depth}][2l][2][{N}], got {selectors.shape}")
+        sel_ptr = selectors.ctypes.data
+    _check(lib().eoc_table_update(table.ctypes.data, d, lw, sel_ptr, values.ctypes.data, values.shape[0]), "eoc_table_update")
+    return table
 
 
 def pack(cts):

@@ -28,6 +28,10 @@ int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out)
 // eoc_table_read's GPU half on the process-global engines (multi.hip): queries cut into eoc_shard_range blocks, one per engine
 int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries,
                            int32_t *out);
+// eoc_table_update's GPU half on the process-global engines (multi.hip): queries cut into eoc_shard_range blocks,
+// one zeroed delta table per engine, added into `table` on the host
+int eoc_table_update_engines(int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
+                             size_t queries);
 // packing key switch: a whole EOCPKS1 blob with t = 4, basebit = 4 -> its parameters and the rows [n][4][2][N]
 // in torus form (a pointer into the blob); false for anything else (legacy.cpp)
 struct eoc_params;

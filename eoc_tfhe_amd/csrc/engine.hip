@@ -97,6 +97,7 @@ struct eoc_engine {
     size_t cmux_cap[2] = {0, 0};
     size_t table_ws_bytes = (size_t)256 << 20;
     uint64_t cmux_launches = 0; // k_cmux launches
+    uint64_t demux_launches = 0; // k_demux launches
     // packing key switch: the packing key's image [n][4][2][512] complex scaled by 2^-9 (the engine's own),
     // the gathered mask columns [lists of a slice][n][N], and the byte budget that buffer is held to (lists are sliced to
     // fit; EOC_TFHE_PACK_WS_BYTES, diagnostics)
@@ -238,6 +239,7 @@ static int upload_tables(eoc_engine *e)
     return EOC_OK;
 }
 
+static void set_demux_attrs();
 extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **out)
 {
     if (!out || !valid_params(p)) {
@@ -304,6 +306,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
     EOC_CMUX_ATTR(4, 0);
 #undef EOC_CMUX_ATTR
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
+    set_demux_attrs(); // k_demux, k_cmux's LDS plan (defined behind every other kernel's first use: DESIGN.md 15)
     (void)hipGetLastError();
     *out = e;
     return EOC_OK;
@@ -2167,6 +2170,160 @@ try {
     eoc_set_error("eoc_int_circuit_run_device: out of memory");
     return EOC_ERR_ALLOC;
 }
+
+// ---- encrypted-index table updates: the demultiplexer and table[idx] += v ----
+// The kernels of this section are templates first named here, behind every other kernel of the file: the device compiler
+// emits kernels in the order of their first use, so the earlier ones keep their text instruction for instruction.
+static const void *demux_kernel(int l, int bg)
+{
+    if (l == 2 && bg == 10) return reinterpret_cast<const void *>(&k_demux<2, 10>);
+    if (l == 3 && bg == 7) return reinterpret_cast<const void *>(&k_demux<3, 7>);
+    if (l == 1) return reinterpret_cast<const void *>(&k_demux<1, 0>);
+    if (l == 2) return reinterpret_cast<const void *>(&k_demux<2, 0>);
+    if (l == 3) return reinterpret_cast<const void *>(&k_demux<3, 0>);
+    if (l == 4) return reinterpret_cast<const void *>(&k_demux<4, 0>);
+    return nullptr;
+}
+
+static void set_demux_attrs()
+{
+    static const int shapes[6][2] = {{2, 10}, {3, 7}, {1, 0}, {2, 0}, {3, 0}, {4, 0}};
+    for (const auto &s : shapes)
+        (void)hipFuncSetAttribute(demux_kernel(s[0], s[1]), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
+}
+
+static int launch_demux(eoc_engine *e, const DemuxArgs &a, uint32_t ny, hipStream_t st)
+{
+    const void *fn = demux_kernel(e->p.l, e->p.Bgbit);
+    if (!fn) {
+        eoc_set_error("k_demux: no kernel for gadget length %d", e->p.l);
+        return EOC_ERR_STATE;
+    }
+    DemuxArgs args = a;
+    args.Bgbit = e->p.Bgbit;
+    const d2 *tw = e->d_tw, *twist = e->d_twist;
+    void *kargs[] = {&args, &tw, &twist};
+    SpanGuard span(e, st, KIND_BLIND_ROTATE);
+    HIP_TRY(hipLaunchKernel(fn, dim3((a.nx + kCmuxItemsPerWG - 1) / kCmuxItemsPerWG, ny), dim3(128 * kCmuxItemsPerWG), kargs,
+                            kCmuxLds, st));
+    e->demux_launches++;
+    return EOC_OK;
+}
+
+extern "C" int eoc_demux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in, int32_t *d_out0, int32_t *d_out1,
+                                size_t count, int accumulate, void *hip_stream)
+{
+    if (!e || !d_sel_fft || !d_in || !d_out0 || !d_out1) {
+        eoc_set_error("eoc_demux_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t sel = (size_t)e->kpl * 2 * kNH, smp = (size_t)2 * kN;
+    constexpr size_t kSlice = (size_t)1 << 30; // items per launch (grid x)
+    for (size_t i0 = 0; i0 < count; i0 += kSlice) {
+        DemuxArgs a{};
+        a.sel = static_cast<const d2 *>(d_sel_fft) + i0 * sel;
+        a.in = d_in + i0 * smp;
+        a.out0 = d_out0 + i0 * smp;
+        a.out1 = d_out1 + i0 * smp;
+        a.sel_x = sel;
+        a.in_x = a.out_x = smp;
+        a.nx = (uint32_t)std::min(kSlice, count - i0);
+        a.accumulate = accumulate != 0;
+        int rc = launch_demux(e, a, 1, (hipStream_t)hip_stream);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+extern "C" int eoc_table_update_device(eoc_engine *e, int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
+                                       const int32_t *d_vals, size_t queries, void *hip_stream)
+{
+    if (!e || !d_table || !d_vals || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10 ||
+        (!d_sel_fft && log2_lists + 10 - log2_width > 0)) {
+        eoc_set_error("eoc_table_update_device: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside "
+                      "[0, 10]", log2_lists, log2_width);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    const int d = log2_lists, r = 10 - log2_width, depth = d + r;
+    const size_t W = (size_t)1 << log2_width, smp = (size_t)2 * kN, sel = (size_t)e->kpl * 2 * kNH;
+    // the read's two buffers: the storing stages leave 2^(d-1) and 2^(d-2) samples per query, the rotations one
+    const size_t s0 = d >= 1 ? (size_t)1 << (d - 1) : 1, s1 = d >= 2 ? (size_t)1 << (d - 2) : 1;
+    const size_t per_query = (s0 + s1) * smp * sizeof(int32_t);
+    if (depth > 0 && e->table_ws_bytes < per_query) {
+        eoc_set_error("eoc_table_update_device: one query at log2_lists = %d needs %zu bytes of workspace, the budget "
+                      "(EOC_TFHE_TABLE_WS_BYTES) is %zu", d, per_query, e->table_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    if (!queries) return EOC_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    size_t qs = std::min<size_t>(queries, 32768); // grid y
+    if (depth > 0) qs = std::min(qs, e->table_ws_bytes / per_query);
+    int rc;
+    if (depth > 0 && (rc = ensure_cmux_ws(e, qs * s0, qs * s1, st))) return rc;
+    for (size_t q0 = 0; q0 < queries; q0 += qs) {
+        const size_t Q = std::min(qs, queries - q0);
+        const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * depth * sel;
+        const int32_t *cur = d_vals + q0 * smp; // one sample per query until the tree starts
+        // rotations: X^(W 2^i) under bit i carries the value to slot W (idx mod 2^r).  Rotation i leaves its result in
+        // buffer (d - 1 + r - 1 - i) & 1, so the last one ends where the first storing stage does not write
+        for (int i = 0; i < r; i++) {
+            CmuxArgs a{};
+            a.nx = 1;
+            a.sel = selq + (size_t)i * sel;
+            a.sel_y = (size_t)depth * sel;
+            a.in0 = a.in1 = cur;
+            a.in0_y = a.in1_y = smp;
+            a.out = e->d_cmux[(d + r - i) & 1];
+            a.out_y = smp;
+            a.rot = (int)(W << i);
+            if ((rc = launch_cmux(e, a, (uint32_t)Q, st))) return rc;
+            cur = a.out;
+        }
+        if (d == 0) { // one list: the rotated value is the leaf
+            const bool vec = (((uintptr_t)cur | (uintptr_t)d_table) & 15) == 0;
+            SpanGuard span(e, st, KIND_BLIND_ROTATE);
+            if (vec) hipLaunchKernelGGL(k_sample_add<4>, dim3(2 * kN / (256 * 4), (unsigned)Q), dim3(256), 0, st, cur, d_table);
+            else hipLaunchKernelGGL(k_sample_add<1>, dim3(2 * kN / 256, (unsigned)Q), dim3(256), 0, st, cur, d_table);
+            HIP_TRY(hipGetLastError());
+            continue;
+        }
+        // tree: stage t under bit r + (d - 1 - t), parent j of 2^t -> children 2j (x - E) and 2j + 1 (E).  Stage t < d - 1
+        // stores [Q][2^(t+1)] samples into buffer (d - 2 - t) & 1 (the larger buffer takes the last storing stage); stage
+        // d - 1 accumulates its 2^d leaves into the table
+        size_t cur_y = smp;
+        for (int t = 0; t < d; t++) {
+            DemuxArgs a{};
+            a.nx = (uint32_t)1 << t;
+            a.sel = selq + (size_t)(r + d - 1 - t) * sel;
+            a.sel_x = 0;
+            a.sel_y = (size_t)depth * sel;
+            a.in = cur;
+            a.in_x = smp;
+            a.in_y = cur_y;
+            a.out_x = 2 * smp;
+            if (t == d - 1) {
+                a.out0 = d_table;
+                a.out_y = 0;
+                a.accumulate = 1;
+            } else {
+                a.out0 = e->d_cmux[(d - 2 - t) & 1];
+                a.out_y = (size_t)2 * a.nx * smp;
+                a.accumulate = 0;
+            }
+            a.out1 = a.out0 + smp;
+            if ((rc = launch_demux(e, a, (uint32_t)Q, st))) return rc;
+            cur = a.out0;
+            cur_y = a.out_y;
+        }
+    }
+    return EOC_OK;
+}
+extern "C" uint64_t eoc_engine_demux_launches(eoc_engine *e) { return e ? e->demux_launches : 0; }
 
 extern "C" int eoc_engine_set_profiling(eoc_engine *e, int on)
 {

@@ -1214,6 +1214,26 @@ extern "C" int eoc_table_read(const int32_t *table, int log2_lists, int log2_wid
     }
     return eoc_table_read_engines(table, log2_lists, log2_width, selectors, queries, out);
 }
+// an encrypted-index table update on the global context's engines: no key is used, the engines come up behind
+// the global key as for the read
+extern "C" int eoc_table_update(int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
+                                size_t queries)
+{
+    const bool depth0 = log2_lists == 0 && log2_width == 10;
+    if (!table || !values || (!selectors && !depth0) || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10) {
+        eoc_set_error("eoc_table_update: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]",
+                      log2_lists, log2_width);
+        return EOC_ERR_ARG;
+    }
+    if (!queries) return EOC_OK;
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) {
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    }
+    return eoc_table_update_engines(table, log2_lists, log2_width, selectors, values, queries);
+}
 extern "C" int eoc_global_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires,
                                       size_t instances)
 {

@@ -1892,4 +1892,126 @@ __global__ __launch_bounds__(256) void k_tvpack_cols(const int32_t *__restrict__
     if (blockIdx.y == 0 && ty == 0) lists[list * 2 * kN + i0 + tx] = 0;
 }
 
+// =================================================================================================
+// Encrypted-index table updates: the demultiplexer, a table read's CMux run backwards.
+//   E = C (x) x,  out1 = E,  out0 = x - E (word by word)
+// x: a TLWE sample [2][N]; C: a converted selector, as k_cmux's.  E is k_cmux's external product with in0 = 0, in1 = x,
+// rot = 0 before the add -- the same text (ext_product_pair.inc), so the two agree bit for bit by construction.  The mapping,
+// the LDS plan and the dead pair's rule are k_cmux's: wave h decomposes offset + x_h (no difference, no rotation), produces
+// E_h and writes polynomial h of BOTH children.  x is not held across the product: x - E is formed at store time from a
+// reload of x (8 KiB per item, L2-resident), which is what keeps the second output out of the register count.
+// accumulate = 0: plain stores (out0 / out1 may not overlap x).  accumulate = 1: vector integer atomicAdd into the
+// destination, lane-contiguous (256 bytes per wave and instruction) as k_pack_rows leaves its results: the last stage of an
+// update adds its leaves straight into the table, every word an integer sum, so colliding queries and any order of arrival
+// give the same words.
+// grid: x = ceil(nx / kCmuxItemsPerWG) parents, y = ny; item (x, y) by strides in int32 (samples) / d2 (selectors).  Templates
+// defined and first used behind every other kernel, as k_tvpack_cols: the earlier kernels keep their text.
+// =================================================================================================
+struct DemuxArgs {
+    const d2 *sel;            // converted selectors
+    const int32_t *in;        // x
+    int32_t *out0, *out1;     // x - E, E
+    size_t sel_x, sel_y;      // strides per item along x / y, in d2
+    size_t in_x, in_y, out_x, out_y; // ... in int32 (out0 and out1 share theirs)
+    uint32_t nx;              // items along x
+    int accumulate;           // 0: store, 1: atomicAdd
+    int Bgbit;
+};
+
+template <int L, int BGBIT = 0>
+__global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_demux(DemuxArgs A, const d2 *__restrict__ g_tw,
+                                                                     const d2 *__restrict__ g_twist)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    d2 *s_tw = reinterpret_cast<d2 *>(smem);
+    d2 *s_twist = s_tw + kTwEntries;
+    d2 *s_scr_all = s_twist + kNH;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = wv & 1;
+    d2 *scr = s_scr_all + wv * kScr;
+    d2 *scr_partner = s_scr_all + (wv ^ 1) * kScr;
+    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128 * kCmuxItemsPerWG);
+
+    const uint32_t x_raw = blockIdx.x * kCmuxItemsPerWG + (uint32_t)(wv >> 1);
+    const bool live = x_raw < A.nx;
+    const size_t ix = live ? x_raw : A.nx - 1, iy = blockIdx.y;
+    const int32_t *px = A.in + ix * A.in_x + iy * A.in_y + (size_t)h * kN;
+    const d2 *sel = A.sel + ix * A.sel_x + iy * A.sel_y;
+
+    const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
+    uint32_t offset = 0;
+#pragma unroll
+    for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
+    const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
+
+    // offset + x_h: coefficient lane + 64 r in dlo[r], lane + 64 r + 512 in dhi[r]
+    uint32_t dlo[8], dhi[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        dlo[r] = offset + (uint32_t)px[lane + 64 * r];
+        dhi[r] = offset + (uint32_t)px[lane + 64 * r + kNH];
+    }
+    __syncthreads(); // the tables
+
+    auto load_row = [&](int p, int c, d2 (&b)[8]) __attribute__((always_inline)) {
+        const d2 *row = sel + ((size_t)(h * L + (p - 1)) * 2 + c) * kNH + lane;
+#pragma unroll
+        for (int r = 0; r < 8; r++) b[r] = row[r * 64];
+    };
+    d2 S[8], ut[8];
+    {
+        const d2 (*const xp_t2)[4] = nullptr, (*const xp_t1)[4] = nullptr; // tables from LDS, as k_cmux
+#define EOC_XP_STAMP(k) do { } while (0)
+#include "ext_product_pair.inc"
+#undef EOC_XP_STAMP
+    }
+    if (!live) return;
+    const size_t oo = ix * A.out_x + iy * A.out_y + (size_t)h * kN;
+    int32_t *p0 = A.out0 + oo, *p1 = A.out1 + oo;
+    if (A.accumulate) {
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const int j = lane + 64 * r;
+            const d2 y = cmulc(S[r], ut[r]); // 1/512 is in the selector's image
+            const uint32_t e0 = wrap_trunc(y.x), e1 = wrap_trunc(y.y);
+            atomicAdd(p1 + j, (int)e0);
+            atomicAdd(p1 + j + kNH, (int)e1);
+            atomicAdd(p0 + j, (int)((uint32_t)px[j] - e0));
+            atomicAdd(p0 + j + kNH, (int)((uint32_t)px[j + kNH] - e1));
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const int j = lane + 64 * r;
+            const d2 y = cmulc(S[r], ut[r]);
+            const uint32_t e0 = wrap_trunc(y.x), e1 = wrap_trunc(y.y);
+            p1[j] = (int32_t)e0;
+            p1[j + kNH] = (int32_t)e1;
+            p0[j] = (int32_t)((uint32_t)px[j] - e0);
+            p0[j + kNH] = (int32_t)((uint32_t)px[j + kNH] - e1);
+        }
+    }
+}
+
+// table[0] += sample_q for q = 0 .. queries - 1: the update of a one-list table, where no demultiplexer runs (DESIGN.md
+// 15).  V = 4: one 16-byte load per lane (both pointers 16-byte aligned); V = 1: word loads.  Integer atomics either way:
+// queries meet on the one list.  grid: x = 2N / (256 V), y = queries; block = 256.
+template <int V>
+__global__ __launch_bounds__(256) void k_sample_add(const int32_t *__restrict__ in, int32_t *__restrict__ list)
+{
+    static_assert(V == 1 || V == 4, "a word or 16 bytes per lane");
+    const size_t k = ((size_t)blockIdx.x * 256 + threadIdx.x) * V;
+    const int32_t *src = in + (size_t)blockIdx.y * 2 * kN + k;
+    if constexpr (V == 4) {
+        const int4 v = *reinterpret_cast<const int4 *>(src);
+        atomicAdd(list + k, v.x);
+        atomicAdd(list + k + 1, v.y);
+        atomicAdd(list + k + 2, v.z);
+        atomicAdd(list + k + 3, v.w);
+    } else {
+        atomicAdd(list + k, src[0]);
+    }
+}
+
 } // namespace eoc

@@ -514,6 +514,39 @@ int slot_table_read_block(Slot &s, const int32_t *table, int log2_lists, int log
     return slot_finish(st, run());
 }
 
+// one device's block [lo, hi) of the queries of an encrypted-index table update: the block's selectors (torus
+// form, converted on the device) and values in; the block is accumulated into a zeroed table on the device, which comes back
+// as `delta` [2^d][2][N] for the host to add
+int slot_table_update_block(Slot &s, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
+                            int32_t *delta, size_t lo, size_t hi)
+{
+    const size_t blk = hi - lo;
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t depth = (size_t)log2_lists + 10 - log2_width, smp = (size_t)2 * EOC_N;
+    const size_t tab_ints = smp << log2_lists;
+    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth; // the converted form takes twice the ints
+    const size_t need = tab_ints + 3 * nsel * sel_ints + blk * smp;
+    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    if (rc) return rc;
+    int32_t *d_tab = s.d_lut, *d_sel = d_tab + tab_ints, *d_fft = d_sel + nsel * sel_ints, *d_vals = d_fft + 2 * nsel * sel_ints;
+    hipStream_t st = s.st[0];
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(d_tab, 0, tab_ints * 4, st));
+        HIP_TRY(hipMemcpyAsync(d_vals, values + lo * smp, blk * smp * 4, hipMemcpyHostToDevice, st));
+        if (nsel) {
+            HIP_TRY(hipMemcpyAsync(d_sel, selectors + lo * depth * sel_ints, nsel * sel_ints * 4, hipMemcpyHostToDevice, st));
+            int r = eoc_tgsw_to_fft_device(s.e, d_sel, nsel, d_fft, st);
+            if (r) return r;
+        }
+        int r = eoc_table_update_device(s.e, d_tab, log2_lists, log2_width, nsel ? d_fft : nullptr, d_vals, blk, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(delta, d_tab, tab_ints * 4, hipMemcpyDeviceToHost, st));
+        return EOC_OK;
+    };
+    return slot_finish(st, run());
+}
+
 // one device's block of WHOLE lists [l_lo, l_hi) of a packing key switch: cts [count][stride] on the host,
 // lists [ceil(count / N)][2][N] out
 int slot_pack_block(Slot &s, const int32_t *cts, size_t count, int32_t *lists, size_t l_lo, size_t l_hi, size_t stride_ints)
@@ -1370,6 +1403,39 @@ int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width,
     return for_each_block(queries, [=](int i, size_t lo, size_t hi) {
         return slot_table_read_block(G.slots[i], table, log2_lists, log2_width, selectors, out, lo, hi, stride);
     });
+}
+
+// eoc_table_update's engine half (host.cpp has checked the arguments, holds the global key's lock and has brought the engines up)
+int eoc_table_update_engines(int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
+                             size_t queries)
+try {
+    std::lock_guard<std::mutex> g(G.mu);
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_table_update: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
+        return EOC_ERR_NO_DEVICE;
+    }
+    {
+        int rc = drain_async_locked();
+        if (rc) return rc;
+    }
+    const size_t tab_ints = ((size_t)2 * EOC_N) << log2_lists;
+    std::vector<std::vector<int32_t>> deltas(G.slots.size());
+    for (size_t i = 0; i < deltas.size(); i++) {
+        size_t lo, hi;
+        shard_range(queries, (int)i, (int)deltas.size(), &lo, &hi);
+        if (hi > lo) deltas[i].assign(tab_ints, 0);
+    }
+    std::vector<int32_t> *dp = deltas.data();
+    int rc = for_each_block(queries, [=](int i, size_t lo, size_t hi) {
+        return slot_table_update_block(G.slots[i], log2_lists, log2_width, selectors, values, dp[i].data(), lo, hi);
+    });
+    if (rc) return rc; // the caller's table is untouched
+    for (const auto &dl : deltas)
+        for (size_t k = 0; k < dl.size(); k++) table[k] = (int32_t)((uint32_t)table[k] + (uint32_t)dl[k]);
+    return EOC_OK;
+} catch (...) {
+    eoc_set_error("eoc_table_update: out of memory");
+    return EOC_ERR_ALLOC;
 }
 
 extern "C" int eoc_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires, size_t instances)

@@ -410,6 +410,98 @@ def table_read_mean(params, tlwe_key, index, log2_lists, log2_width, w=0):
     return float(cmux_mean(params, tlwe_key, slots).sum()) if len(slots) else 0.0
 
 
+# ---- encrypted-index table updates: rotations and a demultiplexer tree -------------------------------------------
+# One update sends a value x through r rotations  x <- x + C_i (x) (X^(W 2^i) x - x)  and d demux stages  E = C (x) x,
+# child(2j + 1) = E, child(2j) = x - E.  With eps = phase(C (x) D) - bit phase(D) (mean cmux_mean, variance cmux_var(bit)):
+#   rotation, any bit     the error gains eps; a bit of 1 also moves what is there by W 2^i slots
+#   stage, bit 1          child 2j + 1 = x + eps        child 2j = -eps: an encryption of 0 whose error is eps NEGATED, and
+#                                                       whatever error x carried is gone with x
+#   stage, bit 0          child 2j + 1 = eps (rows only, mean 0; x's error is gone)        child 2j = x - eps
+# The models below assume a value with a pseudo-random mask (a packed or public-key list); for a trivial value the first
+# external product decomposes a sample without low parts and has neither remainder nor mean, so they bound it from above.
+def _update_bits(index, log2_lists, log2_width):
+    d, r = int(log2_lists), 10 - int(log2_width)
+    idx = int(index)
+    return d, r, 1 << int(log2_width), [(idx >> k) & 1 for k in range(r + d)]
+
+
+def table_update_var(params, tlwe_key, index, log2_lists, log2_width, lst=None, value_var=0.0):
+    """variance (torus units) ONE update (eoc_table_update_device) of entry `index` adds to a slot of list `lst`, around
+    table_update_mean.  lst None or the selected list (index >> r): value_var (the value's own noise: 0 for a trivial value,
+    compact_var / pack_var for a list) + cmux_var(bit) over the r + d external products -- every slot of that list, the entry's
+    and the others'.  Another list: only the external products between its branch point and the leaf count, and a stage
+    whose output does not contain its input (module comment) starts the sum afresh."""
+    d, r, W, bits = _update_bits(index, log2_lists, log2_width)
+    sel = int(index) >> r
+    lst = sel if lst is None else int(lst)
+    v = float(value_var) + sum(cmux_var(params, tlwe_key, b) for b in bits[:r])
+    for t in range(d):
+        b, g = bits[r + d - 1 - t], (lst >> (d - 1 - t)) & 1
+        keeps = g == b                      # child 2j + 1 under bit 1, child 2j under bit 0: the input + / - eps
+        v = (v if keeps else 0.0) + cmux_var(params, tlwe_key, b)
+    return v
+
+
+def table_update_mean(params, tlwe_key, index, log2_lists, log2_width, slot=None, lst=None):
+    """mean error (torus units) ONE update of entry `index` adds to slot `slot` (0 .. N-1, default the entry's first slot) of
+    list `lst` (default the selected one).  Rotation i with bit 1 leaves cmux_mean at every slot behind it, and the later
+    rotations with bit 1 carry it along (negated where it wraps past X^N = -1): seen from the final slot it sits at
+    slot - sum of the later shifts.  A stage under bit 1 leaves cmux_mean(slot) in child 2j + 1 and -cmux_mean(slot) in child
+    2j, whose other errors are gone; a stage under bit 0 has no mean and clears child 2j + 1.  Linear in the number of
+    updates of one list: the term that bounds how often a list can be updated before a refresh."""
+    d, r, W, bits = _update_bits(index, log2_lists, log2_width)
+    sel = int(index) >> r
+    lst = sel if lst is None else int(lst)
+    slot = W * (int(index) & ((1 << r) - 1)) if slot is None else int(slot)
+    m = 0.0
+    for i in range(r):
+        if not bits[i]:
+            continue
+        pos = (slot - sum((W << k) for k in range(i + 1, r) if bits[k])) % (2 * N)
+        m += float(cmux_mean(params, tlwe_key, pos % N)) * (-1.0 if pos >= N else 1.0)
+    here = float(cmux_mean(params, tlwe_key, slot))
+    for t in range(d):
+        b, g = bits[r + d - 1 - t], (lst >> (d - 1 - t)) & 1
+        if b:
+            m = m + here if g else -here
+        elif g:
+            m = 0.0
+    return m
+
+
+def table_update_budget(params, lwe_key, tlwe_key, p, log2_lists, log2_width, sigmas=6.0, value_var=0.0, table_var=0.0,
+                        ksk=None):
+    """how many updates a TABLE tolerates before a read of it no longer decodes with margin -- every update reaches every
+    list: the selected one gains the value and the most noise, the others an encryption of 0 with at most as much (the bound
+    below covers both, so U counts updates at any index): the largest U with
+        |mean| + sigmas sqrt(variance) <= 1 / (4p)        (half a step of the grid m / (2p) decrypt_ints rounds on)
+    for the worst index (every bit 1), where variance = table_var + U table_update_var + table_read_var(depth) and
+    |mean| = (U + 1) depth (q/2) (1 + |s'|) + |ks_mean|: every update and the read leave their largest mean at the slot.
+    0 if not even the read alone fits.  Computed from the model; nothing fitted."""
+    d, lw = int(log2_lists), int(log2_width)
+    depth = d + 10 - lw
+    worst = (1 << depth) - 1
+    hw = int(np.asarray(tlwe_key, np.int64).sum())
+    q = 2.0 ** (-int(params.l) * int(params.Bgbit))
+    m1 = depth * (q / 2) * (1 + hw)
+    v1 = table_update_var(params, tlwe_key, worst, d, lw, value_var=value_var)
+    pr = predict(params, lwe_key, tlwe_key, ksk)
+    v0 = float(table_var) + table_read_var(params, lwe_key, tlwe_key, depth, 0.0, ksk)
+    margin = 1.0 / (4 * int(p))
+
+    def fits(u):
+        return (u + 1) * m1 + abs(pr["ks_mean"]) + float(sigmas) * np.sqrt(v0 + u * v1) <= margin
+    if not fits(0):
+        return 0
+    lo, hi = 0, 1
+    while fits(hi) and hi < 1 << 40:
+        lo, hi = hi, hi * 2
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+    return lo
+
+
 # ---- packing key switch: LWE samples into compact lists (DESIGN.md 13) ----------------------------------------------------------
 PACK_T, PACK_BASEBIT = 4, 4
 

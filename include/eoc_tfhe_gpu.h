@@ -709,6 +709,37 @@ uint64_t eoc_engine_cmux_launches(eoc_engine *e);
 int eoc_table_read(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries, int32_t *out);
 
 /* ------------------------------------------------------------------------------------------------
+ * encrypted-index table updates: table[idx_q] += value_q under encrypted idx_q -- the read run backwards.
+ *   demux       eoc_demux_device: E = C[i] (x) in[i]; out1[i] = E, out0[i] = in[i] - E word by word: in[i] goes to out1 where
+ *               the bit is 1 and to out0 otherwise, the other child is an encryption of 0.  E is the CMux's external product
+ *               (in0 = 0, in1 = in[i]) bit for bit.  accumulate = 0 stores (the outputs may not overlap the input),
+ *               accumulate != 0 ADDS both children into out0 / out1 with integer atomics.  Needs no key.
+ *   update      eoc_table_update_device: the table [2^d][2][N] is updated IN PLACE; d, W = 2^log2_width, r = 10 - log2_width and
+ *               d_sel_fft [queries][r + d] are the read's, so one encrypted index serves a read and an update of the same
+ *               entry.  d_vals is [queries][2][N] TLWE samples under s' whose slots 0 .. W-1 carry the entry's W messages and
+ *               every other slot message 0 (a packed list of W samples, a public-key list, eoc_table_trivial); what the other
+ *               slots carry is added to the neighbouring entries of the selected list.  Per query: r rotations by X^(W 2^i)
+ *               under bit i ascending (k_cmux), then d demux stages, stage t under bit r + (d - 1 - t), parent j -> children
+ *               2j (x - E) and 2j + 1 (E); the last stage adds its 2^d leaves into the table.  Every word is a wrapping
+ *               integer sum: queries on one index, any slicing and any order give the same words.  d = r = 0 is a plain
+ *               wrapping add and takes d_sel_fft = NULL.  Needs no key.  Workspace, budget, slicing and their error codes
+ *               are the read's.  Stats: eoc_engine_demux_launches counts the k_demux launches (d per slice),
+ *               eoc_engine_cmux_launches advances by r per slice; eoc_engine_kernel_times books all of them under the blind
+ *               rotation.  Noise: noise.table_update_var / table_update_mean.
+ * EOC_ERR_ARG for a null pointer or a shape outside the read's ranges; count / queries 0 is a no-op. */
+int eoc_demux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in, int32_t *d_out0, int32_t *d_out1, size_t count,
+                     int accumulate, void *hip_stream);
+int eoc_table_update_device(eoc_engine *e, int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
+                            const int32_t *d_vals, size_t queries, void *hip_stream);
+uint64_t eoc_engine_demux_launches(eoc_engine *e);
+/* the update on the global context (host buffers, synchronous): table [2^d][2][N] updated in place, selectors in TORUS form
+ * [queries][r + d][2l][2][N], values [queries][2][N].  Queries are cut into eoc_shard_range blocks; every engine accumulates its
+ * block into a zeroed table of its own and the host adds those into `table` in wrapping arithmetic: any engine count gives the
+ * single-engine words.  The cloud key alone suffices (key mode 2). */
+int eoc_table_update(int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
+                     size_t queries);
+
+/* ------------------------------------------------------------------------------------------------
  * packing key switch: LWE samples under the LWE key s (gate or LUT outputs) -> compact TLWE lists under s',
  * the layout of eoc_pk_encrypt_*, eoc_table_trivial and the table of eoc_table_read_device.  1 024 results leave in 8 KiB
  * instead of 2 MB (Set A) / 2.5 MB (Set B), and a value the server computed can become a table.
