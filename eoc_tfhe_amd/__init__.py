@@ -293,6 +293,27 @@ def lib():
         "eoc_tv_pack_device": (C.c_int, [vp, C.c_int, vp, sz, sz, vp, vp]),
         "eoc_lut2_batch_device": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, sz, vp]),
         "eoc_lut2_batch": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp, vp, sz]),
+        # seeded ciphertexts, selectors and cloud key
+        "eoc_seeded_encrypt_bits": (C.c_int, [vp, vp, sz, vp, vp]),
+        "eoc_seeded_encrypt_ints": (C.c_int, [vp, C.c_int, vp, sz, vp, vp]),
+        "eoc_seeded_encrypt_bits_keyed": (C.c_int, [vp, vp, vp, u64, vp, sz, vp]),
+        "eoc_seeded_encrypt_ints_keyed": (C.c_int, [vp, vp, vp, u64, C.c_int, vp, sz, vp]),
+        "eoc_tgsw_seeded_encrypt_bits": (C.c_int, [vp, vp, sz, vp, vp]),
+        "eoc_tgsw_seeded_encrypt_bits_keyed": (C.c_int, [vp, vp, vp, u64, vp, sz, vp]),
+        "eoc_seeded_cloud_key_blob_bytes": (sz, [PP]),
+        "eoc_seeded_cloud_key_export": (C.c_int, [vp, vp, sz]),
+        "eoc_seeded_cloud_key_blob_params": (C.c_int, [vp, sz, PP]),
+        "eoc_seeded_expand_host": (C.c_int, [PP, vp, u64, vp, sz, vp]),
+        "eoc_tgsw_seeded_expand_host": (C.c_int, [PP, vp, u64, vp, sz, vp]),
+        "eoc_seeded_cloud_key_expand": (C.c_int, [vp, sz, vp, vp]),
+        "eoc_seeded_expand_device": (C.c_int, [vp, vp, u64, vp, sz, vp, vp]),
+        "eoc_tgsw_seeded_to_fft_device": (C.c_int, [vp, vp, u64, vp, sz, vp, vp]),
+        "eoc_engine_load_seeded_cloud_key": (C.c_int, [vp, vp, sz]),
+        "eoc_engine_create_from_seeded_cloud_key_blob": (C.c_int, [C.c_int, vp, sz, C.POINTER(vp)]),
+        "eoc_engine_seed_launches": (u64, [vp]),
+        "eoc_dbg_chacha20_blocks_device": (C.c_int, [vp, vp, u64, u64, sz, vp, vp]),
+        "eoc_seeded_expand": (C.c_int, [vp, u64, vp, sz, vp]),
+        "eoc_global_import_seeded_cloud_key_blob": (C.c_int, [vp, sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -341,6 +362,57 @@ def _np_view(ptr, count, dtype):
         return None
     buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
     return np.frombuffer(buf, dtype=dtype, count=count)
+
+
+def _key32(key, what):
+    k = np.frombuffer(bytes(key), np.uint8).copy() if key is not None else None
+    if k is None or k.size != 32:
+        raise EocError(f"{what} must be 32 bytes")
+    return k
+
+
+def _blob_u8(blob):
+    return np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8)
+
+
+def seeded_expand_host(params, seed, bodies, first_idx=0):
+    """Host twin of Engine.seeded_expand_device (eoc_seeded_expand_host): (seed, bodies [count]) -> samples [count][n+1]"""
+    s = _key32(seed, "seed")
+    bodies = np.ascontiguousarray(np.asarray(bodies).ravel(), np.int32)
+    out = np.empty((bodies.size, params.n + 1), np.int32)
+    _check(lib().eoc_seeded_expand_host(C.byref(params), s.ctypes.data, int(first_idx), bodies.ctypes.data, bodies.size,
+                                        out.ctypes.data), "eoc_seeded_expand_host")
+    return out
+
+
+def tgsw_seeded_expand_host(params, seed, bodies, first_idx=0):
+    """(seed, bodies [count][2l][N]) -> selectors in torus form [count][2l][2][N] (eoc_tgsw_seeded_expand_host)"""
+    s = _key32(seed, "seed")
+    bodies = np.ascontiguousarray(bodies, np.int32).reshape(-1, 2 * params.l, N)
+    out = np.empty((bodies.shape[0], 2 * params.l, 2, N), np.int32)
+    _check(lib().eoc_tgsw_seeded_expand_host(C.byref(params), s.ctypes.data, int(first_idx), bodies.ctypes.data,
+                                             bodies.shape[0], out.ctypes.data), "eoc_tgsw_seeded_expand_host")
+    return out
+
+
+def seeded_cloud_key_params(blob):
+    blob = _blob_u8(blob)
+    p = Params()
+    _check(lib().eoc_seeded_cloud_key_blob_params(blob.ctypes.data, blob.size, C.byref(p)), "eoc_seeded_cloud_key_blob_params")
+    return p
+
+
+def seeded_cloud_key_expand(blob):
+    """EOCCKS1 blob -> (bk [n][2l][2][N], ksk [N t (base - 1)][n+1]) in torus form, on the host: what Engine.load_cloud_key
+    and the oracle accept (eoc_seeded_cloud_key_expand)"""
+    blob = _blob_u8(blob)
+    p = seeded_cloud_key_params(blob)
+    L = lib()
+    bk = np.empty(L.eoc_bk_len(C.byref(p)), np.int32)
+    ksk = np.empty(L.eoc_ksk_len(C.byref(p)), np.int32)
+    _check(L.eoc_seeded_cloud_key_expand(blob.ctypes.data, blob.size, bk.ctypes.data, ksk.ctypes.data),
+           "eoc_seeded_cloud_key_expand")
+    return bk.reshape(p.n, 2 * p.l, 2, N), ksk.reshape(-1, p.n + 1)
 
 
 class SecretKey:
@@ -530,6 +602,66 @@ class SecretKey:
         if index < 0 or index >> nbits:
             raise EocError(f"encrypt_index: {index} does not fit {nbits} bits")
         return self.encrypt_selector_bits([(index >> k) & 1 for k in range(nbits)], enc_seed, first_idx)
+
+    # -- seeded forms: a public 32-byte mask seed and the bodies; the receiver regenerates the masks ----------
+    def _seeded_lwe(self, values, p, enc_key, mask_seed, first_idx):
+        values = np.ascontiguousarray(np.asarray(values).ravel(), np.uint8)
+        bodies = np.empty(values.size, np.int32)
+        if enc_key is None and mask_seed is None:       # secure: seed AND noise key fresh from the OS, per call
+            if first_idx:
+                raise EocError("first_idx is a test-mode argument: secure seeded encryption draws a fresh seed per call")
+            seed = np.zeros(32, np.uint8)
+            rc = (self.L.eoc_seeded_encrypt_bits(self.h, values.ctypes.data, values.size, seed.ctypes.data, bodies.ctypes.data)
+                  if p is None else
+                  self.L.eoc_seeded_encrypt_ints(self.h, int(p), values.ctypes.data, values.size, seed.ctypes.data,
+                                                 bodies.ctypes.data))
+            _check(rc, "eoc_seeded_encrypt")
+            return seed.tobytes(), bodies
+        k, s = _key32(enc_key, "enc_key"), _key32(mask_seed, "mask_seed")
+        rc = (self.L.eoc_seeded_encrypt_bits_keyed(self.h, k.ctypes.data, s.ctypes.data, int(first_idx), values.ctypes.data,
+                                                   values.size, bodies.ctypes.data) if p is None else
+              self.L.eoc_seeded_encrypt_ints_keyed(self.h, k.ctypes.data, s.ctypes.data, int(first_idx), int(p),
+                                                   values.ctypes.data, values.size, bodies.ctypes.data))
+        _check(rc, "eoc_seeded_encrypt_keyed")
+        return s.tobytes(), bodies
+
+    def encrypt_bits_seeded(self, bits, enc_key=None, mask_seed=None, first_idx=0):
+        """bits -> (seed, bodies): a 32-byte PUBLIC mask seed and one int32 body per bit; Engine.seeded_expand_device,
+        seeded_expand or seeded_expand_host turn them into encrypt_bits' samples [count][n+1].  By default the seed and the
+        noise key are drawn fresh from the OS per call.  enc_key / mask_seed (32 bytes each) and first_idx are the TEST-ONLY
+        keyed form: a (seed, index) pair must never mask two encryptions under one key."""
+        return self._seeded_lwe(bits, None, enc_key, mask_seed, first_idx)
+
+    def encrypt_ints_seeded(self, values, p, enc_key=None, mask_seed=None, first_idx=0):
+        """small integers m < p (encrypt_ints' encoding) -> (seed, bodies); randomness as encrypt_bits_seeded"""
+        return self._seeded_lwe(values, p, enc_key, mask_seed, first_idx)
+
+    def encrypt_selector_bits_seeded(self, bits, enc_key=None, mask_seed=None, first_idx=0):
+        """TGSW selectors of `bits` in seeded form -> (seed, bodies [len(bits)][2l][N]): half of encrypt_selector_bits'
+        size; Engine.tgsw_seeded_to_fft_device converts them for cmux_device / table_read_device, tgsw_seeded_expand_host
+        gives the torus form.  Randomness as encrypt_bits_seeded."""
+        bits = np.ascontiguousarray(np.asarray(bits).ravel(), np.uint8)
+        bodies = np.empty((bits.size, 2 * self.params.l, N), np.int32)
+        if enc_key is None and mask_seed is None:
+            if first_idx:
+                raise EocError("first_idx is a test-mode argument: secure seeded encryption draws a fresh seed per call")
+            seed = np.zeros(32, np.uint8)
+            _check(self.L.eoc_tgsw_seeded_encrypt_bits(self.h, bits.ctypes.data, bits.size, seed.ctypes.data, bodies.ctypes.data),
+                   "eoc_tgsw_seeded_encrypt_bits")
+            return seed.tobytes(), bodies
+        k, s = _key32(enc_key, "enc_key"), _key32(mask_seed, "mask_seed")
+        _check(self.L.eoc_tgsw_seeded_encrypt_bits_keyed(self.h, k.ctypes.data, s.ctypes.data, int(first_idx), bits.ctypes.data,
+                                                         bits.size, bodies.ctypes.data), "eoc_tgsw_seeded_encrypt_bits_keyed")
+        return s.tobytes(), bodies
+
+    def seeded_cloud_key_bytes(self):
+        """EOCCKS1 blob (params | seed | BK bodies | KSK bodies; 8.3 MB on Set A, 15.6 MB on Set B): a fresh, independent
+        encryption of this key's cloud key whose masks a server regenerates from the seed (Engine.from_seeded_cloud_key_blob,
+        global_import_seeded_cloud_key_blob, seeded_cloud_key_expand).  Deterministic: every export gives the same bytes."""
+        need = self.L.eoc_seeded_cloud_key_blob_bytes(C.byref(self.params))
+        buf = np.empty(need, np.uint8)
+        _check(self.L.eoc_seeded_cloud_key_export(self.h, buf.ctypes.data, need), "eoc_seeded_cloud_key_export")
+        return buf
 
     def decrypt_ints(self, cts, p):
         """round(phase * 2p / 2^32) mod p (eoc_decrypt_ints)"""
@@ -812,6 +944,44 @@ class Engine:
         """Compact lists -> LWE samples (eoc_compact_expand_device): d_lists [ceil(count / N)][2][N] (PublicKey.encrypt_*),
         d_out [count][n+1]; slot extraction and the key switch, with the key-switch key alone"""
         _check(self.L.eoc_compact_expand_device(self.h, d_lists, count, d_out, stream), "eoc_compact_expand_device")
+
+    # -- seeded forms (DESIGN.md 16) -----------------------------------------------------------
+    @classmethod
+    def from_seeded_cloud_key_blob(cls, blob, device=0):
+        """Server side: engine + key images from an EOCCKS1 blob alone; the masks are expanded on the GPU."""
+        blob = _blob_u8(blob)
+        self = cls.__new__(cls)
+        self.L = lib()
+        self.h = C.c_void_p()
+        self.params = seeded_cloud_key_params(blob)
+        _check(self.L.eoc_engine_create_from_seeded_cloud_key_blob(device, blob.ctypes.data, blob.size, C.byref(self.h)),
+               "eoc_engine_create_from_seeded_cloud_key_blob")
+        self.device = device
+        self.n = self.params.n
+        return self
+
+    def load_seeded_cloud_key(self, blob):
+        """EOCCKS1 blob -> device images: bodies uploaded, masks expanded on the GPU, then load_cloud_key's transform"""
+        blob = _blob_u8(blob)
+        _check(self.L.eoc_engine_load_seeded_cloud_key(self.h, blob.ctypes.data, blob.size), "eoc_engine_load_seeded_cloud_key")
+
+    def seeded_expand_device(self, seed, d_bodies, count, d_out, first_idx=0, stream=None):
+        """(seed, d_bodies [count]) -> d_out [count][n+1] (eoc_seeded_expand_device): SecretKey.encrypt_*_seeded's samples,
+        masks regenerated by k_seed_masks.  Needs no key; d_out must not overlap d_bodies."""
+        s = _key32(seed, "seed")
+        _check(self.L.eoc_seeded_expand_device(self.h, s.ctypes.data, int(first_idx), d_bodies, count, d_out, stream),
+               "eoc_seeded_expand_device")
+
+    def tgsw_seeded_to_fft_device(self, seed, d_bodies, count, d_fft, first_idx=0, stream=None):
+        """(seed, d_bodies [count][2l][N]) -> converted selectors d_fft (tgsw_fft_bytes each), byte for byte what
+        tgsw_to_fft_device gives for the host-expanded selectors (eoc_tgsw_seeded_to_fft_device)"""
+        s = _key32(seed, "seed")
+        _check(self.L.eoc_tgsw_seeded_to_fft_device(self.h, s.ctypes.data, int(first_idx), d_bodies, count, d_fft, stream),
+               "eoc_tgsw_seeded_to_fft_device")
+
+    @property
+    def seed_launches(self):
+        return self.L.eoc_engine_seed_launches(self.h)
 
     @property
     def tgsw_fft_bytes(self):
@@ -1281,6 +1451,31 @@ def global_import_cloud_key_blob(blob):
     """Server side: install an EOCCK1 blob (numpy uint8 / bytes) as the cloud-key-only global context."""
     blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, np.uint8)
     _check(lib().eoc_global_import_cloud_key_blob(blob.ctypes.data, blob.size), "eoc_global_import_cloud_key_blob")
+
+
+def global_import_seeded_cloud_key_blob(blob):
+    """Server side: install an EOCCKS1 blob as the cloud-key-only global context (key mode 2); every engine expands its own
+    copy of the key on its device"""
+    blob = _blob_u8(blob)
+    _check(lib().eoc_global_import_seeded_cloud_key_blob(blob.ctypes.data, blob.size), "eoc_global_import_seeded_cloud_key_blob")
+
+
+def seeded_expand(seed, bodies, first_idx=0):
+    """eoc_seeded_expand on the global context (no key is used): (seed, bodies [count]) -> [count][n+1] LWE samples, cut over
+    the engines"""
+    s = _key32(seed, "seed")
+    bodies = np.ascontiguousarray(np.asarray(bodies).ravel(), np.int32)
+    if lib().eoc_global_key_mode():
+        n = global_params().n
+    else:
+        e0 = lib().eoc_global_engine()
+        if not e0:
+            raise EocError("seeded_expand: no key and no GPU engine on the global context")
+        n = lib().eoc_engine_params(e0).contents.n
+    out = np.empty((bodies.size, n + 1), np.int32)
+    _check(lib().eoc_seeded_expand(s.ctypes.data, int(first_idx), bodies.ctypes.data, bodies.size, out.ctypes.data),
+           "eoc_seeded_expand")
+    return out
 
 
 def global_cloud_key_export():

@@ -36,6 +36,10 @@ int eoc_table_update_engines(int32_t *table, int log2_lists, int log2_width, con
 // in torus form (a pointer into the blob); false for anything else (legacy.cpp)
 struct eoc_params;
 bool eoc_packing_key_blob_rows(const void *buf, size_t len, eoc_params *p, const int32_t **rows);
+// seeded cloud key: a whole EOCCKS1 blob -> its parameters, the 32-byte mask seed and the two body arrays
+// (pointers into the blob: BK bodies [n][2l][N], KSK bodies [N t (base - 1)]); false for anything else (legacy.cpp)
+bool eoc_seeded_cloud_key_blob_parts(const void *buf, size_t len, eoc_params *p, const uint8_t **seed, const int32_t **bk_bodies,
+                                     const int32_t **ksk_bodies);
 // eoc_pack's GPU half on the process-global engines (multi.hip): WHOLE lists cut into eoc_shard_range blocks, one per engine
 int eoc_pack_engines(const int32_t *cts, size_t count, int32_t *lists);
 // the packing key on every process-global engine (multi.hip)

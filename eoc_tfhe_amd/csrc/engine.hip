@@ -109,6 +109,10 @@ struct eoc_engine {
     // two-input lookups: the lists and the level-1 outputs of a slice of rows, one buffer
     int32_t *d_lut2 = nullptr;
     size_t lut2_cap = 0; // bytes
+    // seeded selectors: the expanded torus-form rows [rows][2][N] in front of the key-load transform
+    int32_t *d_seed_stage = nullptr;
+    size_t seed_stage_cap = 0; // rows
+    uint64_t seed_launches = 0; // k_seed_masks launches
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
     struct Span { hipEvent_t a, b; int kind; };
@@ -346,6 +350,7 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
     hipFree(e->d_pks);
     hipFree(e->d_pack_cols);
     hipFree(e->d_lut2);
+    hipFree(e->d_seed_stage);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -2398,3 +2403,193 @@ extern "C" size_t eoc_engine_resident_jobs(eoc_engine *e)
 }
 extern "C" int eoc_engine_device(eoc_engine *e) { return e ? e->device : -1; }
 extern "C" const eoc_params *eoc_engine_params(eoc_engine *e) { return e ? &e->p : nullptr; }
+
+// ---- seeded ciphertexts, selectors and cloud key: masks expanded on the device ----------
+enum { TAG_SEED_LWE = 10, TAG_SEED_BK = 11, TAG_SEED_KSK = 12, TAG_SEED_TGSW = 13 }; // host.cpp, Stream::Tag
+
+// k_seed_masks over `rows` rows whose streams are (seed, tag, first_idx + r).  len = mask words per row; stride = words per
+// output row (SEED_LWE: len + 1, SEED_KSK: the padded stride, SEED_RING: 2 N).  Launches hold at most 2^24 rows.
+static int launch_seed_masks(eoc_engine *e, int mode, const uint8_t seed[32], uint32_t tag, uint64_t first_idx, size_t rows,
+                             uint32_t len, uint32_t stride, const int32_t *d_bodies, int32_t *d_out, hipStream_t st)
+{
+    const uint32_t istride = mode == SEED_RING ? (uint32_t)kN : stride;
+    if (len < 1 || len > (uint32_t)kN || istride > (uint32_t)kN || (mode != SEED_RING && len + 1 > istride) ||
+        (mode == SEED_KSK && stride % 4 != 0)) {
+        eoc_set_error("k_seed_masks: no launch for %u mask words in rows of %u words", len, istride);
+        return EOC_ERR_STATE;
+    }
+    if (mode != SEED_LWE && (((uintptr_t)d_out | (mode == SEED_RING ? (uintptr_t)d_bodies : 0)) & 15)) {
+        eoc_set_error("k_seed_masks: ring rows and key images are stored 16 bytes at a time; the buffers must be 16-byte aligned");
+        return EOC_ERR_ARG;
+    }
+    SeedArgs a{};
+    memcpy(a.seed, seed, 32);
+    a.tag = tag;
+    a.len = len;
+    a.stride = stride;
+    a.R = std::min<uint32_t>(kSeedMaxRows, (uint32_t)kSeedImgWords / istride);
+    const size_t body_words = mode == SEED_RING ? (size_t)kN : 1, out_words = mode == SEED_RING ? (size_t)2 * kN : stride;
+    constexpr size_t kSlice = (size_t)1 << 24;
+    for (size_t r0 = 0; r0 < rows; r0 += kSlice) {
+        a.rows = std::min(kSlice, rows - r0);
+        a.first_idx = first_idx + r0;
+        a.bodies = d_bodies + r0 * body_words;
+        a.out = d_out + r0 * out_words;
+        const dim3 grid((unsigned)((a.rows + a.R - 1) / a.R));
+        SpanGuard span(e, st, KIND_PREPARE);
+        if (mode == SEED_LWE) hipLaunchKernelGGL(k_seed_masks<SEED_LWE>, grid, dim3(256), 0, st, a);
+        else if (mode == SEED_KSK) hipLaunchKernelGGL(k_seed_masks<SEED_KSK>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_seed_masks<SEED_RING>, grid, dim3(256), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        e->seed_launches++;
+    }
+    return EOC_OK;
+}
+
+// bodies [count] + seed -> samples [count][n+1]: sample s has the mask stream (seed, SeedLwe, first_idx + s).  No key, no
+// workspace; asynchronous on the caller's stream.
+extern "C" int eoc_seeded_expand_device(eoc_engine *e, const uint8_t seed[32], uint64_t first_idx, const int32_t *d_bodies,
+                                        size_t count, int32_t *d_out, void *hip_stream)
+{
+    if (!e || !seed || !d_bodies || !d_out) {
+        eoc_set_error("eoc_seeded_expand_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    const size_t stride = (size_t)e->p.n + 1;
+    const uintptr_t b0 = (uintptr_t)d_bodies, b1 = b0 + count * 4, o0 = (uintptr_t)d_out, o1 = o0 + count * stride * 4;
+    if (b0 < o1 && o0 < b1) { // the kernel reads a workgroup's bodies while other workgroups store their rows
+        eoc_set_error("eoc_seeded_expand_device: d_out must not overlap d_bodies");
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    return launch_seed_masks(e, SEED_LWE, seed, TAG_SEED_LWE, first_idx, count, (uint32_t)e->p.n, (uint32_t)stride, d_bodies,
+                             d_out, (hipStream_t)hip_stream);
+}
+
+// the staging rows of the seeded selectors, grown by the workspace's rule (ensure_ws): never under capture, the device
+// drained first
+static int ensure_seed_stage(eoc_engine *e, size_t rows, hipStream_t st)
+{
+    if (rows <= e->seed_stage_cap) return EOC_OK;
+    if (stream_is_capturing(st)) {
+        eoc_set_error("graph capture: the seeded-selector staging buffer would have to grow (%zu > %zu rows); run one call of the "
+                      "captured shape before capturing", rows, e->seed_stage_cap);
+        return EOC_ERR_STATE;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    hipFree(e->d_seed_stage);
+    e->d_seed_stage = nullptr;
+    e->seed_stage_cap = 0;
+    HIP_TRY(hipMalloc(&e->d_seed_stage, rows * 2 * kN * sizeof(int32_t)));
+    e->seed_stage_cap = rows;
+    e->ws_grows++;
+    return EOC_OK;
+}
+
+// seeded selectors -> the converted form: bodies [count][2l][N] + seed -> torus-form rows in the staging buffer (row r of the
+// call has the mask stream (seed, SeedTgsw, first_idx 2l + r)), then the key-load transform of eoc_tgsw_to_fft_device.
+// Slices of at most 64 MiB of staging; all on the caller's stream.
+extern "C" int eoc_tgsw_seeded_to_fft_device(eoc_engine *e, const uint8_t seed[32], uint64_t first_idx, const int32_t *d_bodies,
+                                             size_t count, void *d_fft, void *hip_stream)
+{
+    if (!e || !seed || !d_bodies || !d_fft) {
+        eoc_set_error("eoc_tgsw_seeded_to_fft_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t kpl = (size_t)e->kpl;
+    const size_t slice = std::max<size_t>(1, ((size_t)64 << 20) / (kpl * 2 * kN * sizeof(int32_t))); // selectors
+    int rc = ensure_seed_stage(e, std::min(count, slice) * kpl, st);
+    if (rc) return rc;
+    for (size_t s0 = 0; s0 < count; s0 += slice) {
+        const size_t S = std::min(slice, count - s0), rows = S * kpl;
+        rc = launch_seed_masks(e, SEED_RING, seed, TAG_SEED_TGSW, (first_idx + s0) * kpl, rows, kN, 2 * kN,
+                               d_bodies + s0 * kpl * kN, e->d_seed_stage, st);
+        if (rc) return rc;
+        rc = launch_fft_fwd(e, e->d_seed_stage, static_cast<double *>(d_fft) + s0 * kpl * 2 * kNH * 2, rows * 2, 0x1p-9, st);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+// EOCCKS1 blob -> the engine's key images: the bodies are uploaded, the masks expanded on the device (the bootstrapping key
+// into the staging buffer build_cloud_key_images transforms, the key-switch key straight into the padded image), then the
+// same transform and the same limb image as eoc_engine_load_cloud_key.  NULL stream throughout, drained before any caller
+// stream can be handed an image.
+extern "C" int eoc_engine_load_seeded_cloud_key(eoc_engine *e, const void *blob, size_t len)
+{
+    eoc_params bp;
+    const uint8_t *seed = nullptr;
+    const int32_t *bkb = nullptr, *kskb = nullptr;
+    if (!e || !eoc_seeded_cloud_key_blob_parts(blob, len, &bp, &seed, &bkb, &kskb)) {
+        eoc_set_error("eoc_engine_load_seeded_cloud_key: null argument or not a whole EOCCKS1 blob");
+        return EOC_ERR_ARG;
+    }
+    const eoc_params &p = e->p;
+    if (bp.n != p.n || bp.l != p.l || bp.Bgbit != p.Bgbit || bp.ks_t != p.ks_t || bp.ks_basebit != p.ks_basebit) {
+        eoc_set_error("eoc_engine_load_seeded_cloud_key: the blob's parameters (n = %d, l = %d) are not the engine's (n = %d, "
+                      "l = %d)", bp.n, bp.l, p.n, p.l);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize()); // nothing in flight may still read the images that are about to be rewritten
+    if (!e->own_keys) {
+        HIP_TRY(hipMalloc(&e->d_bkfft, eoc_bkfft_bytes(&p)));
+        HIP_TRY(hipMalloc(&e->d_ksk, eoc_ksk_dev_bytes(&p)));
+        e->own_keys = true;
+    }
+    const size_t bk_rows = (size_t)p.n * e->kpl, ks_rows = (size_t)kN * p.ks_t * (((size_t)1 << p.ks_basebit) - 1);
+    int32_t *d_bodies = nullptr, *d_stage = nullptr;
+    HIP_TRY(hipMalloc(&d_bodies, std::max(bk_rows * kN, ks_rows) * sizeof(int32_t)));
+    if (hipMalloc(&d_stage, bk_rows * 2 * kN * sizeof(int32_t)) != hipSuccess) {
+        hipFree(d_bodies);
+        eoc_set_error("eoc_engine_load_seeded_cloud_key: out of device memory");
+        return EOC_ERR_HIP;
+    }
+    int rc = EOC_OK;
+    if (hipMemcpy(d_bodies, bkb, bk_rows * kN * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = EOC_ERR_HIP;
+    if (!rc) rc = launch_seed_masks(e, SEED_RING, seed, TAG_SEED_BK, 0, bk_rows, kN, 2 * kN, d_bodies, d_stage, nullptr);
+    // the key image carries the inverse transform's 1/512 (build_cloud_key_images)
+    if (!rc) rc = launch_fft_fwd(e, d_stage, e->d_bkfft, bk_rows * 2, 0x1p-9, nullptr);
+    if (hipDeviceSynchronize() != hipSuccess && !rc) rc = EOC_ERR_HIP; // the bodies are re-used below
+    if (!rc && hipMemcpy(d_bodies, kskb, ks_rows * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = EOC_ERR_HIP;
+    if (!rc) rc = launch_seed_masks(e, SEED_KSK, seed, TAG_SEED_KSK, 0, ks_rows, (uint32_t)p.n, (uint32_t)e->n1p, d_bodies, e->d_ksk,
+                                    nullptr);
+    if (hipDeviceSynchronize() != hipSuccess && !rc) rc = EOC_ERR_HIP;
+    hipFree(d_bodies);
+    hipFree(d_stage);
+    if (rc) {
+        if (rc == EOC_ERR_HIP) eoc_set_error("eoc_engine_load_seeded_cloud_key: upload or expansion failed");
+        return rc;
+    }
+    e->bkfft = e->d_bkfft;
+    e->ksk = e->d_ksk;
+    return install_ks_limbs(e);
+}
+extern "C" uint64_t eoc_engine_seed_launches(eoc_engine *e) { return e ? e->seed_launches : 0; }
+
+// the kernels' block function, all 16 words of n_blocks blocks ChaCha20(key, counter + i, nonce): known-answer tests
+extern "C" int eoc_dbg_chacha20_blocks_device(eoc_engine *e, const uint8_t key[32], uint64_t counter, uint64_t nonce,
+                                              size_t n_blocks, uint32_t *d_out, void *hip_stream)
+{
+    if (!e || !key || !d_out || ((uintptr_t)d_out & 15)) {
+        eoc_set_error("eoc_dbg_chacha20_blocks_device: null argument or an output that is not 16-byte aligned");
+        return EOC_ERR_ARG;
+    }
+    if (!n_blocks) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    SeedArgs a{};
+    memcpy(a.seed, key, 32);
+    a.rows = n_blocks;
+    hipLaunchKernelGGL(k_chacha20_blocks<16>, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, a,
+                       counter, nonce, d_out);
+    HIP_TRY(hipGetLastError());
+    return EOC_OK;
+}

@@ -167,7 +167,9 @@ extern "C" void eoc_dbg_chacha20_block(const uint8_t key[32], uint32_t counter, 
 namespace {
 
 struct Stream {
-    enum Tag : uint32_t { LweKey = 1, TlweKey = 2, Bk = 3, Ksk = 4, Enc = 5, PublicKey = 6, CompactEnc = 7, TgswEnc = 8, PackKsk = 9 };
+    enum Tag : uint32_t { LweKey = 1, TlweKey = 2, Bk = 3, Ksk = 4, Enc = 5, PublicKey = 6, CompactEnc = 7, TgswEnc = 8, PackKsk = 9,
+                          // seeded objects: masks under a PUBLIC seed, noise under the secret side's source
+                          SeedLwe = 10, SeedBk = 11, SeedKsk = 12, SeedTgsw = 13, SeedPub = 14 };
     bool secure = false;
     uint64_t key = 0;           // v1
     uint32_t sub[8];            // v2: this stream's ChaCha20 key
@@ -649,6 +651,253 @@ extern "C" int eoc_lut2_test_polynomials(int p, int n_tables, const int32_t *tab
     return EOC_OK;
 }
 
+// ---- seeded ciphertexts, selectors and cloud key (include/eoc_tfhe_gpu.h) --------------------------------
+// The mask of a seeded object is words 0 .. len-1 of the ChaCha20 stream (seed, tag, idx) under a PUBLIC 32-byte seed --
+// ChaCha20 also for test-mode keys --, so only the bodies travel.  The noise comes from a stream of the SECRET side (the
+// key's source, or the encryption key of the call) under the same tag and index, at the unseeded code's counters.
+namespace {
+void seed_mask_words(const uint8_t seed[32], Stream::Tag tag, uint64_t idx, int len, uint32_t *a)
+{
+    const Stream st(seed, tag, idx);
+    for (int j = 0; j < len; j++) a[j] = st.torus(uint64_t(j));
+}
+// b = gaussian(n; mu, sigma) of `noise` + <mask, s>
+uint32_t seeded_lwe_body(int n, const int32_t *s, const uint8_t seed[32], Stream::Tag tag, uint64_t idx, const Stream &noise,
+                         uint32_t mu, double sigma)
+{
+    const Stream mask(seed, tag, idx);
+    uint32_t b = noise.gaussian(uint64_t(n), mu, sigma);
+    for (int m = 0; m < n; m++) b += s[m] ? mask.torus(uint64_t(m)) : 0u;
+    return b;
+}
+// Body of a seeded TGSW row.  tgsw_row puts the gadget of rows q = 0 into a[0], which a seed cannot regenerate; here `a` is
+// the pure mask stream and b = e + s' (a - [q = 0] bit g) + [q = 1] bit g: tgsw_row run on a - [q = 0] bit g, so that the
+// expanded (a, b) has tgsw_row's phase and distribution and is an ordinary row.
+void seeded_tgsw_body(const eoc_params &p, const std::vector<int> &ones, const uint8_t seed[32], Stream::Tag tag, uint64_t idx,
+                      const Stream &noise, int row, bool bit, int32_t *body)
+{
+    uint32_t a[EOC_N];
+    uint32_t *b = reinterpret_cast<uint32_t *>(body);
+    seed_mask_words(seed, tag, idx, EOC_N, a);
+    const int q = row / p.l, pp = row % p.l + 1;
+    const uint32_t g = 1u << (32 - pp * p.Bgbit);
+    if (bit && q == 0) a[0] -= g;
+    for (int j = 0; j < EOC_N; j++) b[j] = noise.gaussian(uint64_t(EOC_N) + 2 * uint64_t(j), 0u, p.bk_stdev);
+    for (int m : ones) {
+        const uint32_t *src = a + (EOC_N - m);
+        for (int j = 0; j < m; j++) b[j] -= src[j];
+        for (int j = m; j < EOC_N; j++) b[j] += a[j - m];
+    }
+    if (bit && q == 1) b[0] += g;
+}
+// mu[count] -> bodies[count]: sample s has mask stream (mask_seed, SeedLwe, first_idx + s), noise stream (enc_key, SeedLwe, same)
+void seeded_lwe_encrypt(const eoc_secret_key *sk, const uint8_t enc_key[32], const uint8_t mask_seed[32], uint64_t first_idx,
+                        const std::vector<uint32_t> &mu, int32_t *bodies)
+{
+    const size_t count = mu.size();
+#pragma omp parallel for schedule(static) num_threads(usable_threads()) if (count >= 64)
+    for (size_t i = 0; i < count; i++)
+        bodies[i] = int32_t(seeded_lwe_body(sk->p.n, sk->lwe.data(), mask_seed, Stream::SeedLwe, first_idx + i,
+                                            Stream(enc_key, Stream::SeedLwe, first_idx + i), mu[i], sk->p.ks_stdev));
+}
+bool bit_messages(const uint8_t *bits, size_t count, std::vector<uint32_t> &mu)
+{
+    const uint32_t one8 = uint32_t(eoc_modswitch_to_torus32(1, 8));
+    mu.resize(count);
+    for (size_t i = 0; i < count; i++) mu[i] = bits[i] ? one8 : 0u - one8;
+    return true;
+}
+bool int_messages(int p, const uint8_t *values, size_t count, std::vector<uint32_t> &mu)
+{
+    if (!(p == 2 || p == 4 || p == 8)) return false;
+    mu.resize(count);
+    for (size_t i = 0; i < count; i++) {
+        if (values[i] >= p) return false;
+        mu[i] = uint32_t((uint64_t(values[i]) << 32) / (2u * unsigned(p)));
+    }
+    return true;
+}
+// the secure forms' randomness: a mask seed (returned to the caller, public) AND a noise key, both fresh from the OS per call,
+// so that no (seed, tag, idx) triple ever masks two encryptions
+bool draw_seed_and_key(const char *what, uint8_t seed[32], uint8_t enc_key[32])
+{
+    if (eoc_host::os_random(seed, 32) && eoc_host::os_random(enc_key, 32)) return true;
+    eoc_set_error("%s: no entropy source (getrandom and /dev/urandom both failed)", what);
+    return false;
+}
+void seeded_tgsw_encrypt(const eoc_secret_key *sk, const uint8_t enc_key[32], const uint8_t mask_seed[32], uint64_t first_idx,
+                         const uint8_t *bits, size_t count, int32_t *bodies)
+{
+    const eoc_params &p = sk->p;
+    const size_t kpl = size_t(2) * p.l, rows = count * kpl;
+    const std::vector<int> ones = tlwe_ones(*sk);
+#pragma omp parallel for schedule(dynamic, 4) num_threads(usable_threads()) if (rows >= 8)
+    for (size_t ir = 0; ir < rows; ir++) {
+        const size_t s = ir / kpl;
+        const uint64_t idx = (first_idx + s) * kpl + ir % kpl;
+        seeded_tgsw_body(p, ones, mask_seed, Stream::SeedTgsw, idx, Stream(enc_key, Stream::SeedTgsw, idx), int(ir % kpl),
+                         bits[s] != 0, bodies + ir * EOC_N);
+    }
+}
+} // namespace
+
+extern "C" int eoc_seeded_encrypt_bits_keyed(const eoc_secret_key *sk, const uint8_t enc_key[32], const uint8_t mask_seed[32],
+                                             uint64_t first_idx, const uint8_t *bits, size_t count, int32_t *bodies)
+{
+    std::vector<uint32_t> mu;
+    if (!sk || !enc_key || !mask_seed || !bits || !bodies || !bit_messages(bits, count, mu)) {
+        eoc_set_error("eoc_seeded_encrypt_bits_keyed: null argument");
+        return EOC_ERR_ARG;
+    }
+    seeded_lwe_encrypt(sk, enc_key, mask_seed, first_idx, mu, bodies);
+    return EOC_OK;
+}
+extern "C" int eoc_seeded_encrypt_ints_keyed(const eoc_secret_key *sk, const uint8_t enc_key[32], const uint8_t mask_seed[32],
+                                             uint64_t first_idx, int p, const uint8_t *values, size_t count, int32_t *bodies)
+{
+    std::vector<uint32_t> mu;
+    if (!sk || !enc_key || !mask_seed || !values || !bodies || !int_messages(p, values, count, mu)) {
+        eoc_set_error("eoc_seeded_encrypt_ints_keyed: null argument, p outside {2, 4, 8} or a value >= p");
+        return EOC_ERR_ARG;
+    }
+    seeded_lwe_encrypt(sk, enc_key, mask_seed, first_idx, mu, bodies);
+    return EOC_OK;
+}
+extern "C" int eoc_seeded_encrypt_bits(const eoc_secret_key *sk, const uint8_t *bits, size_t count, uint8_t seed_out[32],
+                                       int32_t *bodies)
+{
+    std::vector<uint32_t> mu;
+    if (!sk || !bits || !seed_out || !bodies || !bit_messages(bits, count, mu)) {
+        eoc_set_error("eoc_seeded_encrypt_bits: null argument");
+        return EOC_ERR_ARG;
+    }
+    uint8_t enc_key[32];
+    if (!draw_seed_and_key("eoc_seeded_encrypt_bits", seed_out, enc_key)) return EOC_ERR_STATE;
+    seeded_lwe_encrypt(sk, enc_key, seed_out, 0, mu, bodies);
+    explicit_bzero(enc_key, sizeof enc_key);
+    return EOC_OK;
+}
+extern "C" int eoc_seeded_encrypt_ints(const eoc_secret_key *sk, int p, const uint8_t *values, size_t count, uint8_t seed_out[32],
+                                       int32_t *bodies)
+{
+    std::vector<uint32_t> mu;
+    if (!sk || !values || !seed_out || !bodies || !int_messages(p, values, count, mu)) {
+        eoc_set_error("eoc_seeded_encrypt_ints: null argument, p outside {2, 4, 8} or a value >= p");
+        return EOC_ERR_ARG;
+    }
+    uint8_t enc_key[32];
+    if (!draw_seed_and_key("eoc_seeded_encrypt_ints", seed_out, enc_key)) return EOC_ERR_STATE;
+    seeded_lwe_encrypt(sk, enc_key, seed_out, 0, mu, bodies);
+    explicit_bzero(enc_key, sizeof enc_key);
+    return EOC_OK;
+}
+extern "C" int eoc_tgsw_seeded_encrypt_bits_keyed(const eoc_secret_key *sk, const uint8_t enc_key[32], const uint8_t mask_seed[32],
+                                                  uint64_t first_idx, const uint8_t *bits, size_t count, int32_t *bodies)
+{
+    if (!sk || !enc_key || !mask_seed || !bits || !bodies) {
+        eoc_set_error("eoc_tgsw_seeded_encrypt_bits_keyed: null argument");
+        return EOC_ERR_ARG;
+    }
+    seeded_tgsw_encrypt(sk, enc_key, mask_seed, first_idx, bits, count, bodies);
+    return EOC_OK;
+}
+extern "C" int eoc_tgsw_seeded_encrypt_bits(const eoc_secret_key *sk, const uint8_t *bits, size_t count, uint8_t seed_out[32],
+                                            int32_t *bodies)
+{
+    if (!sk || !bits || !seed_out || !bodies) {
+        eoc_set_error("eoc_tgsw_seeded_encrypt_bits: null argument");
+        return EOC_ERR_ARG;
+    }
+    uint8_t enc_key[32];
+    if (!draw_seed_and_key("eoc_tgsw_seeded_encrypt_bits", seed_out, enc_key)) return EOC_ERR_STATE;
+    seeded_tgsw_encrypt(sk, enc_key, seed_out, 0, bits, count, bodies);
+    explicit_bzero(enc_key, sizeof enc_key);
+    return EOC_OK;
+}
+// host twins of the device expansion: the reference of every GPU test, and the path of a consumer without a device
+extern "C" int eoc_seeded_expand_host(const eoc_params *p, const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies,
+                                      size_t count, int32_t *out)
+{
+    if (!p || !seed || !bodies || !out || p->n < 1 || p->n > 1023) {
+        eoc_set_error("eoc_seeded_expand_host: null argument or n outside [1, 1023]");
+        return EOC_ERR_ARG;
+    }
+    const size_t st = size_t(p->n) + 1;
+#pragma omp parallel for schedule(static) num_threads(usable_threads()) if (count >= 64)
+    for (size_t i = 0; i < count; i++) {
+        seed_mask_words(seed, Stream::SeedLwe, first_idx + i, p->n, reinterpret_cast<uint32_t *>(out + i * st));
+        out[i * st + p->n] = bodies[i];
+    }
+    return EOC_OK;
+}
+extern "C" int eoc_tgsw_seeded_expand_host(const eoc_params *p, const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies,
+                                           size_t count, int32_t *out)
+{
+    if (!p || !seed || !bodies || !out || p->l < 1 || p->l > 4) {
+        eoc_set_error("eoc_tgsw_seeded_expand_host: null argument or l outside [1, 4]");
+        return EOC_ERR_ARG;
+    }
+    const size_t kpl = size_t(2) * p->l, rows = count * kpl;
+#pragma omp parallel for schedule(static) num_threads(usable_threads()) if (rows >= 8)
+    for (size_t ir = 0; ir < rows; ir++) {
+        int32_t *row = out + ir * 2 * EOC_N;
+        seed_mask_words(seed, Stream::SeedTgsw, first_idx * kpl + ir, EOC_N, reinterpret_cast<uint32_t *>(row));
+        memcpy(row + EOC_N, bodies + ir * EOC_N, size_t(EOC_N) * 4);
+    }
+    return EOC_OK;
+}
+namespace eoc_host {
+// The seeded cloud key is a FRESH, INDEPENDENT encryption of the same key material, not the EOCCK1 key with its masks
+// swapped: row noise comes from streams (key's source, SeedBk / SeedKsk, row), never from tags Bk / Ksk -- with shared noise
+// b - b_seeded = s (a - a_seeded) is linear algebra for the key.  The mask seed is 32 bytes of the key's own source under tag
+// SeedPub (a PRF output: safe to publish, the same on every export), so that exporting twice yields the same bytes.
+void make_seeded_cloud_key(const eoc_secret_key *sk, uint8_t seed[32], int32_t *bk_bodies, int32_t *ksk_bodies)
+{
+    const eoc_secret_key &k = *sk;
+    const eoc_params &p = k.p;
+    {
+        const Stream pub(k, Stream::SeedPub, 0);
+        for (int w = 0; w < 4; w++) {
+            const uint64_t v = pub.u64(uint64_t(w));
+            memcpy(seed + 8 * w, &v, 8);
+        }
+    }
+    const int kpl = 2 * p.l;
+    const std::vector<int> ones = tlwe_ones(k);
+#pragma omp parallel for schedule(dynamic, 8) num_threads(usable_threads())
+    for (int ir = 0; ir < p.n * kpl; ir++)
+        seeded_tgsw_body(p, ones, seed, Stream::SeedBk, uint64_t(ir), Stream(k, Stream::SeedBk, uint64_t(ir)), ir % kpl,
+                         k.lwe[ir / kpl] != 0, bk_bodies + size_t(ir) * EOC_N);
+    const int n = p.n, t = p.ks_t, bb = p.ks_basebit, nd = (1 << bb) - 1;
+    const size_t rows = size_t(EOC_N) * t * nd;
+#pragma omp parallel for schedule(static) num_threads(usable_threads())
+    for (size_t r = 0; r < rows; r++) { // make_ksk's messages
+        const int d = int(r % nd) + 1, j = int((r / nd) % t), i = int(r / (size_t(nd) * t));
+        const uint32_t msg = k.tlwe[i] ? uint32_t(d) << (32 - (j + 1) * bb) : 0u;
+        ksk_bodies[r] = int32_t(seeded_lwe_body(n, k.lwe.data(), seed, Stream::SeedKsk, r, Stream(k, Stream::SeedKsk, r), msg,
+                                                p.ks_stdev));
+    }
+}
+// bodies + seed -> the torus-form arrays eoc_engine_load_cloud_key and the oracle accept
+void expand_seeded_cloud_key(const eoc_params &p, const uint8_t seed[32], const int32_t *bk_bodies, const int32_t *ksk_bodies,
+                             int32_t *bk, int32_t *ksk)
+{
+    const int nrows = p.n * 2 * p.l;
+#pragma omp parallel for schedule(static) num_threads(usable_threads())
+    for (int ir = 0; ir < nrows; ir++) {
+        int32_t *row = bk + size_t(ir) * 2 * EOC_N;
+        seed_mask_words(seed, Stream::SeedBk, uint64_t(ir), EOC_N, reinterpret_cast<uint32_t *>(row));
+        memcpy(row + EOC_N, bk_bodies + size_t(ir) * EOC_N, size_t(EOC_N) * 4);
+    }
+    const size_t rows = size_t(EOC_N) * p.ks_t * ((size_t(1) << p.ks_basebit) - 1), st = size_t(p.n) + 1;
+#pragma omp parallel for schedule(static) num_threads(usable_threads())
+    for (size_t r = 0; r < rows; r++) {
+        seed_mask_words(seed, Stream::SeedKsk, r, p.n, reinterpret_cast<uint32_t *>(ksk + r * st));
+        ksk[r * st + p.n] = ksk_bodies[r];
+    }
+}
+} // namespace eoc_host
+
 // ---- compact public-key encryption (include/eoc_tfhe_gpu.h) ---------------------------------------------
 // acc += u * P in Z_2^32[X]/(X^N + 1) for a binary u given by the positions of its ones: a sum of signed rotations of P
 static void add_binary_product(const std::vector<int> &ones, const uint32_t *P, uint32_t *acc)
@@ -854,7 +1103,9 @@ int ensure_engine_locked()
     if (c.engine_ready) return EOC_OK;
     // the cloud key of a full key set, or the imported one of a cloud-key-only (server) context
     const std::vector<int32_t> &bk = c.sk ? c.sk->bk : c.ck->bk, &ksk = c.sk ? c.sk->ksk : c.ck->ksk;
-    if (bk.empty() || ksk.empty()) return EOC_ERR_NO_KEY;
+    // a context imported as a seeded blob has no torus-form arrays: every engine expands its own copy
+    const bool seeded = !c.sk && c.ck && !c.ck->seeded.empty();
+    if (!seeded && (bk.empty() || ksk.empty())) return EOC_ERR_NO_KEY;
     if (!eoc_global_engine()) { // EOC_TFHE_DEVICES = "all" | "0,1,..." puts several GPUs behind the one global key
         int rc = eoc_gpu_init_from_env(p);
         if (rc) return rc;
@@ -873,7 +1124,13 @@ int ensure_engine_locked()
             return EOC_ERR_ARG;
         }
     }
-    int rc = eoc_upload_cloud_key_arrays(bk.data(), ksk.data());
+    int rc = EOC_OK;
+    if (seeded) {
+        for (int i = 0; i < eoc_gpu_engine_count() && !rc; i++)
+            rc = eoc_engine_load_seeded_cloud_key(eoc_global_engine_at(i), c.ck->seeded.data(), c.ck->seeded.size());
+    } else {
+        rc = eoc_upload_cloud_key_arrays(bk.data(), ksk.data());
+    }
     if (rc) return rc;
     c.engine_ready = true;
     return EOC_OK;
@@ -1123,6 +1380,56 @@ extern "C" int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *o
         if (rc) return rc;
     }
     return eoc_compact_expand_engines(lists, count, out);
+}
+// seeded samples -> LWE samples on the global context's engines: samples are cut into eoc_shard_range blocks,
+// one per engine; every block's upload and kernel are queued before the first result is collected.  No key is used: the
+// engines come up behind the global key when there is one, engines of eoc_gpu_init serve without
+extern "C" int eoc_seeded_expand(const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies, size_t count, int32_t *out)
+{
+    if (!seed || !bodies || !out) {
+        eoc_set_error("eoc_seeded_expand: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) {
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    }
+    const int world = eoc_gpu_engine_count();
+    if (world <= 0) {
+        eoc_set_error("eoc_seeded_expand: no engine (install a key or call eoc_gpu_init first)");
+        return EOC_ERR_STATE;
+    }
+    struct Block {
+        eoc_engine *e = nullptr;
+        void *d_bodies = nullptr, *d_out = nullptr;
+        size_t lo = 0, hi = 0;
+    };
+    std::vector<Block> blocks(world);
+    int rc = EOC_OK;
+    for (int r = 0; r < world && !rc; r++) {
+        Block &b = blocks[r];
+        eoc_shard_range(count, r, world, &b.lo, &b.hi);
+        if (b.lo == b.hi) continue;
+        b.e = eoc_global_engine_at(r);
+        const size_t S = b.hi - b.lo, st = size_t(eoc_engine_params(b.e)->n) + 1;
+        rc = eoc_device_alloc(b.e, S * 4, &b.d_bodies);
+        if (!rc) rc = eoc_device_alloc(b.e, S * st * 4, &b.d_out);
+        if (!rc) rc = eoc_host_to_device(b.e, b.d_bodies, bodies + b.lo, S * 4);
+        if (!rc) rc = eoc_seeded_expand_device(b.e, seed, first_idx + b.lo, static_cast<const int32_t *>(b.d_bodies), S,
+                                               static_cast<int32_t *>(b.d_out), nullptr);
+    }
+    for (Block &b : blocks) {
+        if (!b.e) continue;
+        const size_t st = size_t(eoc_engine_params(b.e)->n) + 1;
+        if (!rc) rc = eoc_device_to_host(b.e, out + b.lo * st, b.d_out, (b.hi - b.lo) * st * 4); // behind the NULL-stream kernel
+        else eoc_engine_synchronize(b.e);
+        if (b.d_bodies) eoc_device_free(b.e, b.d_bodies);
+        if (b.d_out) eoc_device_free(b.e, b.d_out);
+    }
+    return rc;
 }
 // ---- packing key switch on the global context ----
 static int global_list_call(const int32_t *lists, size_t count, void *out, int p, int what)

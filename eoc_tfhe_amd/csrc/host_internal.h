@@ -22,6 +22,9 @@ struct eoc_secret_key {
 struct eoc_cloud_key {
     eoc_params p;
     std::vector<int32_t> bk, ksk;
+    // imported as an EOCCKS1 blob: every engine expands its own copy on the device; bk / ksk stay empty until
+    // something asks for the torus form (eoc_global_cloud_key_export), which expands them on the host, once
+    std::vector<unsigned char> seeded;
 };
 
 namespace eoc_host {
@@ -67,6 +70,11 @@ void compact_encrypt(const eoc_params &p, const int32_t *A, const int32_t *B, co
 bool parse_public_key_blob(const void *buf, size_t len, eoc_params *p, std::vector<int32_t> *ab);
 // packing key switch: the rows [n][4][2][N] of a secret key's packing key, in torus form
 void make_packing_key(const eoc_secret_key *sk, int32_t *rows);
+// seeded cloud key: the public mask seed and the bodies of a FRESH encryption of sk's bootstrapping and
+// key-switch keys, bk_bodies [n][2l][N], ksk_bodies [N t (base - 1)]; and their expansion into the torus-form arrays
+void make_seeded_cloud_key(const eoc_secret_key *sk, uint8_t seed[32], int32_t *bk_bodies, int32_t *ksk_bodies);
+void expand_seeded_cloud_key(const eoc_params &p, const uint8_t seed[32], const int32_t *bk_bodies, const int32_t *ksk_bodies,
+                             int32_t *bk, int32_t *ksk);
 void drop_keys_locked();    // wipes and frees whichever key the context holds (caller holds ctx().mu)
 
 } // namespace eoc_host

@@ -2014,4 +2014,159 @@ __global__ __launch_bounds__(256) void k_sample_add(const int32_t *__restrict__ 
     }
 }
 
+// =================================================================================================
+// Seeded ciphertexts, selectors and cloud key: the masks of rows, regenerated from a public seed.
+// Row r of a call has the ChaCha20 stream (seed, tag, first_idx + r) of host.cpp's Stream: sub-key = words 0 .. 7 of block
+// ChaCha20(seed, counter tag << 32, nonce idx), mask word j = the ODD word 2 (j mod 8) + 1 of block ChaCha20(sub-key,
+// counter j / 8, nonce 0) (the high half of the stream's j-th 64-bit word): a block yields 8 mask words.  Integer ARX
+// only: 32-bit adds, xors and rotates (v_alignbit_b32), and the 64-bit block counter with its carry into the high word.
+// Mapping: a workgroup serves R consecutive rows (R = what fits the 32 KiB image, at most 32).  Lane r < R computes row r's
+// sub-key into LDS -- one block per row, against len / 8 data blocks --, then every lane computes whole blocks (item = row x
+// block, consecutive lanes consecutive blocks) and puts the 8 kept words into the LDS image of the rows; the image leaves with
+// lane-contiguous stores.  Three shapes:
+//   LWE   out [rows][len + 1], rows 4-byte aligned only (2 004-byte stride on Set A): mask in columns 0 .. len - 1, the body
+//         in column len.  The R rows of a workgroup are ONE contiguous span of the output: dword stores, consecutive lanes
+//         consecutive words.
+//   KSK   out [rows][stride], stride = eoc_ksk_row_stride (a multiple of 256 words): the engine's padded key-switch-key
+//         image, body in column len, zeros behind it (the whole row is written).  dwordx4 stores.
+//   RING  out [rows][2][N]: a = the stream's N words, b = the row's body [N], copied.  Rows are 16-byte aligned: dwordx4
+//         stores, 1 KiB contiguous per wave and instruction.
+// A partial last block (len mod 8 != 0) stores its leading words only.  No atomics, no buffer stores, no scratch: every
+// array below is indexed by unrolled constants.
+// grid: x = ceil(rows / R); block = 256.
+// =================================================================================================
+constexpr int kSeedImgWords = 8192; // the LDS image of a workgroup's rows
+constexpr int kSeedMaxRows = 32;
+enum { SEED_LWE = 0, SEED_KSK = 1, SEED_RING = 2 };
+
+struct SeedArgs {
+    uint32_t seed[8];
+    uint64_t first_idx; // stream index of row 0
+    uint64_t rows;
+    uint32_t tag;
+    uint32_t len;       // mask words per row
+    uint32_t R;         // rows per workgroup
+    uint32_t stride;    // words per output row (LWE: len + 1, KSK: the padded stride; RING: unused)
+    const int32_t *bodies; // LWE / KSK: [rows]; RING: [rows][N]
+    int32_t *out;
+};
+
+__device__ __forceinline__ uint32_t cc_rotl(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
+// the 20 rounds on x, in place
+__device__ __forceinline__ void chacha20_rounds(uint32_t (&x)[16])
+{
+#define EOC_CC_QR(a, b, c, d)                                                                   \
+    x[a] += x[b]; x[d] = cc_rotl(x[d] ^ x[a], 16); x[c] += x[d]; x[b] = cc_rotl(x[b] ^ x[c], 12); \
+    x[a] += x[b]; x[d] = cc_rotl(x[d] ^ x[a], 8);  x[c] += x[d]; x[b] = cc_rotl(x[b] ^ x[c], 7)
+#pragma unroll 1
+    for (int r = 0; r < 10; r++) {
+        EOC_CC_QR(0, 4, 8, 12); EOC_CC_QR(1, 5, 9, 13); EOC_CC_QR(2, 6, 10, 14); EOC_CC_QR(3, 7, 11, 15);
+        EOC_CC_QR(0, 5, 10, 15); EOC_CC_QR(1, 6, 11, 12); EOC_CC_QR(2, 7, 8, 13); EOC_CC_QR(3, 4, 9, 14);
+    }
+#undef EOC_CC_QR
+}
+// original ChaCha layout: constants | key | 64-bit block counter | 64-bit nonce (host.cpp, chacha20_block)
+__device__ __forceinline__ void chacha20_init(uint32_t (&x)[16], const uint32_t (&key)[8], uint64_t counter, uint64_t nonce)
+{
+    x[0] = 0x61707865u; x[1] = 0x3320646eu; x[2] = 0x79622d32u; x[3] = 0x6b206574u;
+#pragma unroll
+    for (int k = 0; k < 8; k++) x[4 + k] = key[k];
+    x[12] = (uint32_t)counter; x[13] = (uint32_t)(counter >> 32);
+    x[14] = (uint32_t)nonce; x[15] = (uint32_t)(nonce >> 32);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_seed_masks(SeedArgs A)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_img[kSeedImgWords];
+    __shared__ uint32_t s_sub[kSeedMaxRows][8];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t row0 = (uint64_t)blockIdx.x * A.R;
+    const uint64_t left = A.rows - row0;
+    const uint32_t R = left < A.R ? (uint32_t)left : A.R;
+    const uint32_t istride = MODE == SEED_RING ? (uint32_t)kN : A.stride;
+
+    if (tid < R) { // the row's sub-key: the tag sits in the high counter word, the stream index is the nonce
+        uint32_t x[16];
+        chacha20_init(x, A.seed, (uint64_t)A.tag << 32, A.first_idx + row0 + tid);
+        chacha20_rounds(x);
+        // the first half of the block: constants + x, then key words 0 .. 3 + x
+        s_sub[tid][0] = x[0] + 0x61707865u;
+        s_sub[tid][1] = x[1] + 0x3320646eu;
+        s_sub[tid][2] = x[2] + 0x79622d32u;
+        s_sub[tid][3] = x[3] + 0x6b206574u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) s_sub[tid][4 + k] = x[4 + k] + A.seed[k];
+    }
+    if (MODE != SEED_RING) { // body in column len; the key image's padding is zero
+        for (uint32_t r = tid; r < R; r += 256) s_img[r * istride + A.len] = (uint32_t)A.bodies[row0 + r];
+        if (MODE == SEED_KSK) {
+            const uint32_t pad = istride - A.len - 1;
+            for (uint32_t i = tid; i < R * pad; i += 256) s_img[(i / pad) * istride + A.len + 1 + i % pad] = 0u;
+        }
+    }
+    __syncthreads();
+
+    const uint32_t nb = (A.len + 7) / 8;
+    for (uint32_t it = tid; it < R * nb; it += 256) {
+        const uint32_t r = it / nb, b = it - r * nb;
+        uint32_t key[8], x[16];
+#pragma unroll
+        for (int k = 0; k < 8; k++) key[k] = s_sub[r][k];
+        chacha20_init(x, key, (uint64_t)b, 0);
+        chacha20_rounds(x);
+        // the odd words: 1, 3 are constants + x, 5 .. 11 key words + x, 13 the high counter word (0) + x, 15 the nonce (0) + x
+        const uint32_t w[8] = {x[1] + 0x3320646eu, x[3] + 0x6b206574u, x[5] + key[1], x[7] + key[3],
+                               x[9] + key[5],      x[11] + key[7],     x[13],         x[15]};
+        uint32_t *dst = s_img + r * istride + b * 8;
+        if (b * 8 + 8 <= A.len) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) dst[k] = w[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (b * 8 + k < A.len) dst[k] = w[k];
+        }
+    }
+    __syncthreads();
+
+    if (MODE == SEED_LWE) { // rows row0 .. row0 + R - 1 are one span of the output
+        int32_t *o = A.out + row0 * istride;
+        for (uint32_t i = tid; i < R * istride; i += 256) o[i] = (int32_t)s_img[i];
+    } else if (MODE == SEED_KSK) {
+        uint4 *o = reinterpret_cast<uint4 *>(A.out + row0 * istride);
+        const uint4 *img = reinterpret_cast<const uint4 *>(s_img);
+        for (uint32_t i = tid; i < R * (istride / 4); i += 256) o[i] = img[i];
+    } else {
+        const uint4 *img = reinterpret_cast<const uint4 *>(s_img);
+        for (uint32_t i = tid; i < R * (kN / 4); i += 256) {
+            const uint64_t row = row0 + (i >> 8);
+            const uint32_t c = i & 255;
+            uint4 *o = reinterpret_cast<uint4 *>(A.out + row * (2 * kN));
+            o[c] = img[i];
+            o[kN / 4 + c] = reinterpret_cast<const uint4 *>(A.bodies + row * kN)[c];
+        }
+    }
+}
+
+// block i of [n_blocks][16] = ChaCha20(key, counter + i, nonce): the block function above, all 16 words (known-answer tests).
+// A template, as k_seed_masks, so that the code object lists both behind every earlier kernel (labels of the earlier
+// kernels keep their numbers: tools/isa_diff.py compares them as text).
+template <int WORDS>
+__global__ __launch_bounds__(256) void k_chacha20_blocks(SeedArgs A, uint64_t counter, uint64_t nonce, uint32_t *__restrict__ out)
+{
+    static_assert(WORDS == 16, "whole blocks");
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.rows) return;
+    uint32_t x[16], s[16];
+    chacha20_init(x, A.seed, counter + i, nonce);
+#pragma unroll
+    for (int k = 0; k < 16; k++) s[k] = x[k];
+    chacha20_rounds(x);
+    uint4 *o = reinterpret_cast<uint4 *>(out + i * 16);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        o[k] = make_uint4(x[4 * k] + s[4 * k], x[4 * k + 1] + s[4 * k + 1], x[4 * k + 2] + s[4 * k + 2], x[4 * k + 3] + s[4 * k + 3]);
+}
+
 } // namespace eoc

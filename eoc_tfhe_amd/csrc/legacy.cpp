@@ -125,6 +125,9 @@ const char kMagicCK[8] = {'E', 'O', 'C', 'C', 'K', '1', 0, 0};
 const char kMagicPK[8] = {'E', 'O', 'C', 'P', 'K', '1', 0, 0};
 // packing key blob: "EOCPKS1\0" | same params | t_p, basebit_p (2 x i32; 4, 4) | rows int32[n][4][2][N]     
 const char kMagicPKS[8] = {'E', 'O', 'C', 'P', 'K', 'S', '1', 0};
+// seeded cloud key blob: "EOCCKS1\0" | same params | mask seed (32 bytes) | BK bodies int32[n][2l][N] |
+//                        KSK bodies int32[N t (base - 1)]                                                         
+const char kMagicCKS[8] = {'E', 'O', 'C', 'C', 'K', 'S', '1', 0};
 const size_t kParamBytes = 5 * 4 + 2 * 8;
 
 void put_params(const eoc_params &p, unsigned char *o)
@@ -362,6 +365,132 @@ extern "C" size_t eoc_global_packing_key_export(void *buf, size_t cap)
     return eoc_packing_key_export(c.sk, buf, cap) == EOC_OK ? need : 0;
 }
 
+// ---- seeded cloud key: the EOCCKS1 blob ---------------------------------------------------------------------
+namespace {
+size_t seeded_bk_words(const eoc_params &p) { return size_t(p.n) * 2 * p.l * EOC_N; }
+size_t seeded_ksk_words(const eoc_params &p) { return size_t(EOC_N) * p.ks_t * ((size_t(1) << p.ks_basebit) - 1); }
+const size_t kSeededHeader = 8 + kParamBytes + 32;
+} // namespace
+
+extern "C" size_t eoc_seeded_cloud_key_blob_bytes(const eoc_params *p)
+{
+    return p ? kSeededHeader + (seeded_bk_words(*p) + seeded_ksk_words(*p)) * 4 : 0;
+}
+
+// deterministic per secret key: the same key always exports the same bytes (host.cpp, make_seeded_cloud_key)
+extern "C" int eoc_seeded_cloud_key_export(const eoc_secret_key *sk, void *buf, size_t cap)
+{
+    if (!sk || !buf || cap < eoc_seeded_cloud_key_blob_bytes(&sk->p)) {
+        eoc_set_error("eoc_seeded_cloud_key_export: null argument or a buffer below eoc_seeded_cloud_key_blob_bytes");
+        return EOC_ERR_ARG;
+    }
+    unsigned char *o = static_cast<unsigned char *>(buf);
+    memcpy(o, kMagicCKS, 8);
+    put_params(sk->p, o + 8);
+    try { // the bodies are written through an aligned buffer: the header is 76 bytes
+        std::vector<int32_t> bodies(seeded_bk_words(sk->p) + seeded_ksk_words(sk->p));
+        uint8_t seed[32];
+        make_seeded_cloud_key(sk, seed, bodies.data(), bodies.data() + seeded_bk_words(sk->p));
+        memcpy(o + 8 + kParamBytes, seed, 32);
+        memcpy(o + kSeededHeader, bodies.data(), bodies.size() * 4);
+    } catch (...) {
+        eoc_set_error("eoc_seeded_cloud_key_export: out of memory");
+        return EOC_ERR_ALLOC;
+    }
+    return EOC_OK;
+}
+
+bool eoc_seeded_cloud_key_blob_parts(const void *buf, size_t len, eoc_params *p, const uint8_t **seed, const int32_t **bk_bodies,
+                                     const int32_t **ksk_bodies)
+{
+    const unsigned char *o = static_cast<const unsigned char *>(buf);
+    eoc_params q;
+    if (!buf || len < kSeededHeader || memcmp(o, kMagicCKS, 8) != 0 || !get_params(o + 8, q) ||
+        len != eoc_seeded_cloud_key_blob_bytes(&q))
+        return false;
+    if (p) *p = q;
+    if (seed) *seed = o + 8 + kParamBytes;
+    if (bk_bodies) *bk_bodies = reinterpret_cast<const int32_t *>(o + kSeededHeader); // copied bytewise by the callers
+    if (ksk_bodies) *ksk_bodies = reinterpret_cast<const int32_t *>(o + kSeededHeader + seeded_bk_words(q) * 4);
+    return true;
+}
+
+extern "C" int eoc_seeded_cloud_key_blob_params(const void *buf, size_t len, eoc_params *p)
+{
+    if (!p || !eoc_seeded_cloud_key_blob_parts(buf, len, p, nullptr, nullptr, nullptr)) {
+        eoc_set_error("eoc_seeded_cloud_key_blob_params: not a whole EOCCKS1 seeded cloud key blob");
+        return EOC_ERR_ARG;
+    }
+    return EOC_OK;
+}
+
+// blob -> torus-form bk [n][2l][2][N] and ksk [N t (base - 1)][n + 1] (eoc_bk_len / eoc_ksk_len words), on the host
+extern "C" int eoc_seeded_cloud_key_expand(const void *blob, size_t len, int32_t *bk, int32_t *ksk)
+{
+    eoc_params p;
+    const uint8_t *seed = nullptr;
+    const int32_t *bkb = nullptr, *kskb = nullptr;
+    if (!bk || !ksk || !eoc_seeded_cloud_key_blob_parts(blob, len, &p, &seed, &bkb, &kskb)) {
+        eoc_set_error("eoc_seeded_cloud_key_expand: null argument or not a whole EOCCKS1 blob");
+        return EOC_ERR_ARG;
+    }
+    try { // the bodies may sit at any byte offset of the caller's buffer: read them through aligned copies
+        std::vector<int32_t> bodies(seeded_bk_words(p) + seeded_ksk_words(p));
+        memcpy(bodies.data(), bkb, bodies.size() * 4);
+        expand_seeded_cloud_key(p, seed, bodies.data(), bodies.data() + seeded_bk_words(p), bk, ksk);
+    } catch (...) {
+        eoc_set_error("eoc_seeded_cloud_key_expand: out of memory");
+        return EOC_ERR_ALLOC;
+    }
+    return EOC_OK;
+}
+
+// server side: bring an engine up from a seeded cloud-key blob alone; the masks are expanded on the device
+extern "C" int eoc_engine_create_from_seeded_cloud_key_blob(int device, const void *buf, size_t len, eoc_engine **out)
+{
+    eoc_params p;
+    if (!out || !eoc_seeded_cloud_key_blob_parts(buf, len, &p, nullptr, nullptr, nullptr)) {
+        eoc_set_error("seeded cloud key blob: null argument or not a whole EOCCKS1 blob");
+        return EOC_ERR_ARG;
+    }
+    eoc_engine *e = nullptr;
+    int rc = eoc_engine_create(device, &p, &e);
+    if (rc) return rc;
+    rc = eoc_engine_load_seeded_cloud_key(e, buf, len);
+    if (rc) {
+        eoc_engine_destroy(e);
+        return rc;
+    }
+    *out = e;
+    return EOC_OK;
+}
+
+// a cloud-key-ONLY global context (key mode 2) from a seeded blob: the engines come up on the first gate call, each expanding
+// its own copy on the device (host.cpp, ensure_engine_locked)
+extern "C" int eoc_global_import_seeded_cloud_key_blob(const void *buf, size_t len)
+{
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.sk || c.ck) { // one key per process, as importCloudKey
+        std::cout << "Secret key is already generated for this instance..." << std::endl;
+        return EOC_ERR_ARG;
+    }
+    eoc_params p;
+    if (!eoc_seeded_cloud_key_blob_parts(buf, len, &p, nullptr, nullptr, nullptr)) {
+        eoc_set_error("eoc_global_import_seeded_cloud_key_blob: not a whole EOCCKS1 seeded cloud key blob");
+        return EOC_ERR_ARG;
+    }
+    eoc_cloud_key *ck = new eoc_cloud_key();
+    ck->p = p;
+    const unsigned char *o = static_cast<const unsigned char *>(buf);
+    ck->seeded.assign(o, o + len);
+    c.ck = ck;
+    c.enc_secure = false;
+    c.enc_seed = c.enc_counter = 0;
+    c.engine_ready = false;
+    return EOC_OK;
+}
+
 extern "C" const char *exportSecretKey(void)
 {
     GlobalCtx &c = ctx();
@@ -412,6 +541,14 @@ namespace {
 bool cloud_blob_locked(GlobalCtx &c, std::vector<unsigned char> &blob)
 {
     const eoc_params *p = c.params();
+    if (c.ck && c.ck->bk.empty() && !c.ck->seeded.empty()) { // imported as EOCCKS1: the torus form is made on demand, once
+        c.ck->bk.resize(eoc_bk_len(p));
+        c.ck->ksk.resize(eoc_ksk_len(p));
+        if (eoc_seeded_cloud_key_expand(c.ck->seeded.data(), c.ck->seeded.size(), c.ck->bk.data(), c.ck->ksk.data()) != EOC_OK) {
+            c.ck->bk.clear();
+            c.ck->ksk.clear();
+        }
+    }
     const std::vector<int32_t> *bk = c.sk ? &c.sk->bk : c.ck ? &c.ck->bk : nullptr;
     const std::vector<int32_t> *ksk = c.sk ? &c.sk->ksk : c.ck ? &c.ck->ksk : nullptr;
     if (!p || !bk || bk->empty() || ksk->empty()) {

@@ -840,6 +840,88 @@ int eoc_lut2_batch_device(eoc_engine *e, int p, int n_tables, const int32_t *d_t
 int eoc_lut2_batch(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y, int32_t *out,
                    size_t count);
 
+/* ---- seeded ciphertexts, selectors and cloud key: masks expanded on the GPU ---------------------------------
+ * Every LWE sample, TGSW row and key row is a uniform mask plus a body.  In the seeded forms the holder of the secret key
+ * sends the bodies and a PUBLIC 32-byte seed; the receiver regenerates the masks.  No key, no key switch, no extra noise.
+ *   mask streams the generator of the secure mode (ChaCha20, RFC 8439 block function) with the seed in the master key's
+ *               place: stream (seed, tag, idx) has the sub-key = first half of block ChaCha20(seed, counter tag << 32, nonce
+ *               idx); its word j is the HIGH half of the j-th 64-bit word of the blocks ChaCha20(sub-key, counter j / 8,
+ *               nonce 0) -- a block yields 8 mask words.  Tags: 10 LWE samples (idx = first_idx + s), 11 bootstrapping-key rows
+ *               (idx = row), 12 key-switch-key rows (idx = row), 13 selector rows (idx = (first_idx + s) 2l + row), 14 the
+ *               seed of a cloud key.  Masks are ChaCha20 also for test-mode keys.
+ *   noise       from the secret side, under the same tag and index and the unseeded code's counters: stream (enc_key, tag,
+ *               idx) for samples and selectors, stream (key's source, tag, row) for key rows.
+ *   LWE         sample s: a[m] = word m of stream (seed, 10, first_idx + s), b = gaussian(mu, ks_stdev) + <a, s>.  The wire
+ *               form is the seed once per batch and 4 bytes per sample (2 004 bytes unseeded on Set A).
+ *   selector    row (q, p) of selector s: a = the stream's N words, b = e + s' a - [q = 0] bit g_p s'(X) + [q = 1] bit g_p,
+ *               g_p = 2^(32 - p Bgbit): eoc_tgsw_encrypt_bits' row computed on a - [q = 0] bit g_p (its gadget on a[0] depends
+ *               on the bit and cannot come from a seed).  Same phase, same distribution; the expanded (a, b) is an ordinary
+ *               row.  Bodies [count][2l][N]: half of a selector.
+ *   cloud key   blob "EOCCKS1\0" | params (as EOCCK1) | seed[32] | BK bodies int32[n][2l][N] | KSK bodies
+ *               int32[N t (base - 1)], little-endian: 8.3 MB (Set A) / 15.6 MB (Set B) against 65.6 / 93.0 MB of EOCCK1.
+ *               It is a FRESH, INDEPENDENT encryption, not the EOCCK1 key with its masks swapped: the noise of its rows comes
+ *               from streams (key's source, 11 / 12, row), never from the streams of eoc_sk_bk / eoc_sk_ksk, and its seed is
+ *               32 bytes of the key's own source under tag 14 -- the export is deterministic: the same secret key always
+ *               gives the same bytes.  EOCCK1, eoc_cloud_key_export and the arrays of a secret key are unchanged.
+ * SECURITY, two rules.  (1) A (seed, tag, idx) triple must NEVER mask two different encryptions under one key: b1 - b2 would
+ * be the message difference in the clear.  eoc_seeded_encrypt_bits / _ints and eoc_tgsw_seeded_encrypt_bits draw the mask
+ * seed AND a noise key fresh from the OS per call, return the seed and take no first_idx (EOC_ERR_STATE without an entropy
+ * source).  The _keyed forms take both keys and first_idx explicitly and are TEST-ONLY: the caller answers for never
+ * repeating a triple and for an enc_key that is secret and unrelated to the seed.  (2) Two encryptions of one key under
+ * different masks must not share their noise: b - b' = s (a - a') is linear algebra for the key.  Hence the independent noise
+ * streams and the deterministic export above.
+ * Client side and host twins (CPU, multithreaded; EOC_ERR_ARG for a null pointer, p outside {2, 4, 8} or a value >= p):
+ *   eoc_seeded_expand_host       bodies[count] -> out[count][n+1]: what eoc_seeded_expand_device computes, word for word
+ *   eoc_tgsw_seeded_expand_host  bodies[count][2l][N] -> out[count][2l][2][N], eoc_tgsw_encrypt_bits' layout
+ *   eoc_seeded_cloud_key_expand  blob -> bk (eoc_bk_len words), ksk (eoc_ksk_len words): what eoc_engine_load_cloud_key and
+ *                                the oracle accept.  A blob that is not a whole EOCCKS1 blob (wrong magic, wrong length,
+ *                                invalid parameters) is EOC_ERR_ARG here and in every call that takes one.
+ * Engine (k_seed_masks; eoc_engine_seed_launches counts its launches, eoc_engine_kernel_times books it under prepare):
+ *   eoc_seeded_expand_device     d_bodies DEVICE [count], d_out DEVICE [count][n+1]; needs no key; asynchronous on hip_stream;
+ *                                count 0 is a no-op; EOC_ERR_ARG when d_out overlaps d_bodies.  No workspace is used.
+ *   eoc_tgsw_seeded_to_fft_device  d_bodies DEVICE [count][2l][N] (16-byte aligned) -> d_fft as eoc_tgsw_to_fft_device gives
+ *                                for the host-expanded selectors, byte for byte.  The expanded torus form goes through a
+ *                                staging buffer of at most 64 MiB that grows by eoc_engine_reserve's rule (EOC_ERR_STATE
+ *                                under capture: run one call of the captured shape first).
+ *   eoc_engine_load_seeded_cloud_key  uploads the bodies, expands on the device, transforms, installs the key-switch limbs:
+ *                                the images are byte-identical to eoc_engine_load_cloud_key's on the host-expanded arrays.
+ *                                Synchronous.  EOC_ERR_ARG when the blob's parameters are not the engine's.
+ *   eoc_dbg_chacha20_blocks_device  d_out DEVICE [n_blocks][16] words: block i = ChaCha20(key, counter + i, nonce) in the
+ *                                original layout (64-bit counter, 64-bit nonce), the kernels' block function.
+ * Global context: eoc_seeded_expand (host buffers, synchronous) cuts the samples into eoc_shard_range blocks, one per engine;
+ * eoc_global_import_seeded_cloud_key_blob installs a cloud-key-only context (key mode 2) whose engines each expand their own
+ * copy of the key (no broadcast); eoc_global_cloud_key_export then returns the EOCCK1 blob of the host-expanded arrays. */
+int eoc_seeded_encrypt_bits(const eoc_secret_key *sk, const uint8_t *bits, size_t count, uint8_t seed_out[32], int32_t *bodies);
+int eoc_seeded_encrypt_ints(const eoc_secret_key *sk, int p, const uint8_t *values, size_t count, uint8_t seed_out[32],
+                            int32_t *bodies);
+int eoc_seeded_encrypt_bits_keyed(const eoc_secret_key *sk, const uint8_t enc_key[32], const uint8_t mask_seed[32],
+                                  uint64_t first_idx, const uint8_t *bits, size_t count, int32_t *bodies);
+int eoc_seeded_encrypt_ints_keyed(const eoc_secret_key *sk, const uint8_t enc_key[32], const uint8_t mask_seed[32],
+                                  uint64_t first_idx, int p, const uint8_t *values, size_t count, int32_t *bodies);
+int eoc_tgsw_seeded_encrypt_bits(const eoc_secret_key *sk, const uint8_t *bits, size_t count, uint8_t seed_out[32],
+                                 int32_t *bodies);
+int eoc_tgsw_seeded_encrypt_bits_keyed(const eoc_secret_key *sk, const uint8_t enc_key[32], const uint8_t mask_seed[32],
+                                       uint64_t first_idx, const uint8_t *bits, size_t count, int32_t *bodies);
+size_t eoc_seeded_cloud_key_blob_bytes(const eoc_params *p);
+int eoc_seeded_cloud_key_export(const eoc_secret_key *sk, void *buf, size_t cap);   /* EOC_ERR_ARG when cap is too small */
+int eoc_seeded_cloud_key_blob_params(const void *buf, size_t len, eoc_params *p);   /* a whole EOCCKS1 blob, else EOC_ERR_ARG */
+int eoc_seeded_expand_host(const eoc_params *p, const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies, size_t count,
+                           int32_t *out);
+int eoc_tgsw_seeded_expand_host(const eoc_params *p, const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies,
+                                size_t count, int32_t *out);
+int eoc_seeded_cloud_key_expand(const void *blob, size_t len, int32_t *bk, int32_t *ksk);
+int eoc_seeded_expand_device(eoc_engine *e, const uint8_t seed[32], uint64_t first_idx, const int32_t *d_bodies, size_t count,
+                             int32_t *d_out, void *hip_stream);
+int eoc_tgsw_seeded_to_fft_device(eoc_engine *e, const uint8_t seed[32], uint64_t first_idx, const int32_t *d_bodies,
+                                  size_t count, void *d_fft, void *hip_stream);
+int eoc_engine_load_seeded_cloud_key(eoc_engine *e, const void *blob, size_t len);
+int eoc_engine_create_from_seeded_cloud_key_blob(int device, const void *blob, size_t len, eoc_engine **out);
+uint64_t eoc_engine_seed_launches(eoc_engine *e);
+int eoc_dbg_chacha20_blocks_device(eoc_engine *e, const uint8_t key[32], uint64_t counter, uint64_t nonce, size_t n_blocks,
+                                   uint32_t *d_out, void *hip_stream);
+int eoc_seeded_expand(const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies, size_t count, int32_t *out);
+int eoc_global_import_seeded_cloud_key_blob(const void *buf, size_t len);
+
 #ifdef __cplusplus
 }
 #endif
