@@ -29,6 +29,20 @@ using namespace eoc;
         }                                                                                   \
     } while (0)
 
+// The six pair shapes (gadget length l, Bgbit; Bgbit 0 = any, read at run time): the two default sets, then every length.
+// Every ladder over k_blind_rotate* / k_br_enc / k_cmux / k_demux and both attribute blocks are generated from this list, in
+// this order (the device compiler emits the instances in the order they are named: DESIGN.md 15).
+#define EOC_PAIR_SHAPES(X) X(2, 10) X(3, 7) X(1, 0) X(2, 0) X(3, 0) X(4, 0)
+// one rung: taken by the first shape of the list that fits gadget (l, bg), while `fn` is still unset
+#define EOC_IF_SHAPE(L, B, l, bg) if (!fn && (l) == L && (B == 0 || (bg) == B))
+
+// Grow-only device scratch, sized by a call's own arguments: grown by scratch_reserve alone, to exactly the bytes asked for
+struct Scratch {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int32_t *i32() const { return static_cast<int32_t *>(p); }
+};
+
 struct eoc_engine {
     int device = 0;
     eoc_params p{};
@@ -93,8 +107,7 @@ struct eoc_engine {
     uint64_t ks_mfma_launches = 0; // k_keyswitch_mfma launches (key switches that ran on the matrix cores)
     // encrypted-index table reads: the two ping-pong buffers of the CMux tree, in TLWE samples, and the byte
     // budget both together are held to (queries are sliced to fit; EOC_TFHE_TABLE_WS_BYTES, diagnostics)
-    int32_t *d_cmux[2] = {nullptr, nullptr};
-    size_t cmux_cap[2] = {0, 0};
+    Scratch cmux[2];
     size_t table_ws_bytes = (size_t)256 << 20;
     uint64_t cmux_launches = 0; // k_cmux launches
     uint64_t demux_launches = 0; // k_demux launches
@@ -102,16 +115,13 @@ struct eoc_engine {
     // the gathered mask columns [lists of a slice][n][N], and the byte budget that buffer is held to (lists are sliced to
     // fit; EOC_TFHE_PACK_WS_BYTES, diagnostics)
     d2 *d_pks = nullptr;
-    int32_t *d_pack_cols = nullptr;
-    size_t pack_cap = 0; // lists
+    Scratch pack_cols;
     size_t pack_ws_bytes = (size_t)256 << 20;
     uint64_t pack_launches = 0, packed_samples = 0; // k_pack_rows launches; samples packed
     // two-input lookups: the lists and the level-1 outputs of a slice of rows, one buffer
-    int32_t *d_lut2 = nullptr;
-    size_t lut2_cap = 0; // bytes
+    Scratch lut2;
     // seeded selectors: the expanded torus-form rows [rows][2][N] in front of the key-load transform
-    int32_t *d_seed_stage = nullptr;
-    size_t seed_stage_cap = 0; // rows
+    Scratch seed_stage;
     uint64_t seed_launches = 0; // k_seed_masks launches
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
@@ -301,13 +311,8 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
     if (!e->ks_waves_ok) (void)hipGetLastError();
     // so does k_cmux (tables + four transpose scratches); a device that refuses it cannot run the leveled calls
 #define EOC_CMUX_ATTR(LL, BB) \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cmux<LL, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds)
-    EOC_CMUX_ATTR(2, 10);
-    EOC_CMUX_ATTR(3, 7);
-    EOC_CMUX_ATTR(1, 0);
-    EOC_CMUX_ATTR(2, 0);
-    EOC_CMUX_ATTR(3, 0);
-    EOC_CMUX_ATTR(4, 0);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cmux<LL, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
+    EOC_PAIR_SHAPES(EOC_CMUX_ATTR)
 #undef EOC_CMUX_ATTR
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
     set_demux_attrs(); // k_demux, k_cmux's LDS plan (defined behind every other kernel's first use: DESIGN.md 15)
@@ -345,12 +350,8 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
         hipFree(e->d_ksk);
     }
     hipFree(e->d_ksl);
-    hipFree(e->d_cmux[0]);
-    hipFree(e->d_cmux[1]);
     hipFree(e->d_pks);
-    hipFree(e->d_pack_cols);
-    hipFree(e->d_lut2);
-    hipFree(e->d_seed_stage);
+    for (Scratch *s : {&e->cmux[0], &e->cmux[1], &e->pack_cols, &e->lut2, &e->seed_stage}) hipFree(s->p);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -442,6 +443,26 @@ static int ensure_ws(eoc_engine *e, eoc_engine::Workspace &W, size_t jobs, size_
     return EOC_OK;
 }
 
+// THE RULE of every Scratch: nothing to do when the buffer fits (no allocation, no synchronise in steady state); never
+// grown under capture (captured nodes may refer to the buffer, and nothing may be allocated while a stream captures); the
+// device drained before the buffer is replaced; one count in ws_grows per buffer that grew.  `what` names the buffer.
+static int scratch_reserve(eoc_engine *e, Scratch &s, size_t bytes, const char *what, hipStream_t st)
+{
+    if (bytes <= s.bytes) return EOC_OK;
+    if (stream_is_capturing(st)) {
+        eoc_set_error("graph capture: the %s would have to grow (%zu > %zu bytes); run one call of the captured shape before "
+                      "capturing", what, bytes, s.bytes);
+        return EOC_ERR_STATE;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    hipFree(s.p);
+    s = Scratch();
+    HIP_TRY(hipMalloc(&s.p, bytes));
+    s.bytes = bytes;
+    e->ws_grows++;
+    return EOC_OK;
+}
+
 extern "C" int eoc_engine_reserve(eoc_engine *e, size_t max_jobs, size_t max_descs, size_t max_mixed_rows)
 {
     if (!e) return EOC_ERR_ARG;
@@ -522,28 +543,57 @@ extern "C" int eoc_dbg_fft_inv_device(eoc_engine *e, const double *d_specs, int3
 }
 
 // ---- cloud key ------------------------------------------------------------------------------
+// A device temporary of the key loaders: move-only, freed on every exit path.  hipFree waits for the device, so a temporary
+// may go out of scope behind work that was queued on it.
+struct DevTmp {
+    void *p = nullptr;
+    DevTmp() = default;
+    DevTmp(DevTmp &&o) noexcept : p(o.release()) {}
+    DevTmp(const DevTmp &) = delete;
+    DevTmp &operator=(const DevTmp &) = delete;
+    ~DevTmp() { hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+    int32_t *i32() const { return static_cast<int32_t *>(p); }
+    void *release() { void *q = p; p = nullptr; return q; } // the buffer is the caller's from here on
+};
+
+// The key-load transform: `npoly` torus polynomials that are on the device -> their image; it carries the inverse transform's
+// 1/512 (exact power-of-two scaling).
+// NULL-stream audit: the rows came by a blocking hipMemcpy or by NULL-stream kernels (ordered with this one); the
+// transform runs on the NULL stream and is drained by the hipDeviceSynchronize that follows it, before any caller stream
+// (blocking or hipStreamNonBlocking) can be handed the image.
+static int key_image(eoc_engine *e, const int32_t *d_rows, void *d_img, size_t npoly)
+{
+    int rc = launch_fft_fwd(e, d_rows, static_cast<double *>(d_img), npoly, 0x1p-9, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return EOC_OK;
+}
+
+// The engine's own pair of cloud-key images: both installed or neither
+static int own_key_images(eoc_engine *e)
+{
+    if (e->own_keys) return EOC_OK;
+    DevTmp bk, ks;
+    HIP_TRY(bk.alloc(eoc_bkfft_bytes(&e->p)));
+    HIP_TRY(ks.alloc(eoc_ksk_dev_bytes(&e->p)));
+    e->d_bkfft = static_cast<double *>(bk.release());
+    e->d_ksk = static_cast<int32_t *>(ks.release());
+    e->own_keys = true;
+    return EOC_OK;
+}
+
 static int build_cloud_key_images(eoc_engine *e, const int32_t *bk, const int32_t *ksk, double *d_bkfft,
                                   int32_t *d_ksk)
 {
     const eoc_params &p = e->p;
     // BK: upload the torus form, transform on the GPU (tGswToFFTConvert)
     const size_t npoly = (size_t)p.n * e->kpl * 2;
-    int32_t *d_bk = nullptr;
-    HIP_TRY(hipMalloc(&d_bk, npoly * kN * 4));
-    if (hipMemcpy(d_bk, bk, npoly * kN * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(d_bk);
-        eoc_set_error("cloud key upload failed");
-        return EOC_ERR_HIP;
-    }
-    // the key image carries the inverse transform's 1/512 (exact power-of-two scaling)
-    // NULL-stream audit: the blocking hipMemcpy above has completed when it returns; the transform below
-    // runs on the NULL stream and is drained by the hipDeviceSynchronize that follows it, before any caller stream
-    // (blocking or hipStreamNonBlocking) can be handed the image.
-    int rc = launch_fft_fwd(e, d_bk, d_bkfft, npoly, 0x1p-9, nullptr);
-    hipError_t se = hipDeviceSynchronize();
-    hipFree(d_bk);
+    DevTmp d_bk;
+    HIP_TRY(d_bk.alloc(npoly * kN * 4));
+    HIP_TRY(hipMemcpy(d_bk.p, bk, npoly * kN * 4, hipMemcpyHostToDevice));
+    int rc = key_image(e, d_bk.i32(), d_bkfft, npoly);
     if (rc) return rc;
-    HIP_TRY(se);
     // KSK: [N*t*(base-1)][n+1]  ->  same rows padded with zeros to n1p
     const size_t rows = (size_t)kN * p.ks_t * (((size_t)1 << p.ks_basebit) - 1);
     // NULL-stream audit: fill and copy are both on the NULL stream (ordered among themselves), drained by the
@@ -577,12 +627,8 @@ extern "C" int eoc_engine_load_cloud_key(eoc_engine *e, const int32_t *bk, const
     if (!e || !bk || !ksk) return EOC_ERR_ARG;
     std::lock_guard<std::mutex> g(e->mu);
     HIP_TRY(hipSetDevice(e->device));
-    if (!e->own_keys) {
-        HIP_TRY(hipMalloc(&e->d_bkfft, eoc_bkfft_bytes(&e->p)));
-        HIP_TRY(hipMalloc(&e->d_ksk, eoc_ksk_dev_bytes(&e->p)));
-        e->own_keys = true;
-    }
-    int rc = build_cloud_key_images(e, bk, ksk, e->d_bkfft, e->d_ksk);
+    int rc = own_key_images(e);
+    if (!rc) rc = build_cloud_key_images(e, bk, ksk, e->d_bkfft, e->d_ksk);
     if (rc) return rc;
     e->bkfft = e->d_bkfft;
     e->ksk = e->d_ksk;
@@ -783,12 +829,9 @@ static BRKernel blind_rotate_kernel(bool wide, int l, int Bgbit, bool sabar, boo
     }
     const void *fn = nullptr;
     if (l == 2 && tables_lds) fn = Bgbit == 10 ? br_pair_lds_kernel<2, 10>(seed, sabar) : br_pair_lds_kernel<2, 0>(seed, sabar);
-    else if (l == 2 && Bgbit == 10) fn = br_pair_kernel<2, 10>(seed, sabar); // Set A
-    else if (l == 3 && Bgbit == 7) fn = br_pair_kernel<3, 7>(seed, sabar); // Set B
-    else if (l == 1) fn = br_pair_kernel<1, 0>(seed, sabar);
-    else if (l == 2) fn = br_pair_kernel<2, 0>(seed, sabar);
-    else if (l == 3) fn = br_pair_kernel<3, 0>(seed, sabar);
-    else if (l == 4) fn = br_pair_kernel<4, 0>(seed, sabar);
+#define EOC_BR_PAIR(L, B) EOC_IF_SHAPE(L, B, l, Bgbit) fn = br_pair_kernel<L, B>(seed, sabar);
+    EOC_PAIR_SHAPES(EOC_BR_PAIR)
+#undef EOC_BR_PAIR
     return {fn, dim3(njobs), dim3(128), kBRLds};
 }
 
@@ -983,13 +1026,11 @@ static void launch_lin(eoc_engine *e, WS &W, const LinDesc *dd, uint32_t cnt, ui
 static const void *br_enc_kernel(bool wide, int l, int Bgbit, bool sabar)
 {
     if (wide) return Bgbit == 10 ? EOC_BR_ENC(k_br_enc_wide, 10) : EOC_BR_ENC(k_br_enc_wide, 0);
-    if (l == 2 && Bgbit == 10) return EOC_BR_ENC(k_br_enc, 2, 10); // Set A
-    if (l == 3 && Bgbit == 7) return EOC_BR_ENC(k_br_enc, 3, 7);   // Set B
-    if (l == 1) return EOC_BR_ENC(k_br_enc, 1, 0);
-    if (l == 2) return EOC_BR_ENC(k_br_enc, 2, 0);
-    if (l == 3) return EOC_BR_ENC(k_br_enc, 3, 0);
-    if (l == 4) return EOC_BR_ENC(k_br_enc, 4, 0);
-    return nullptr;
+    const void *fn = nullptr;
+#define EOC_BR_ENC_PAIR(L, B) EOC_IF_SHAPE(L, B, l, Bgbit) fn = EOC_BR_ENC(k_br_enc, L, B);
+    EOC_PAIR_SHAPES(EOC_BR_ENC_PAIR)
+#undef EOC_BR_ENC_PAIR
+    return fn;
 }
 #undef EOC_BR_ENC
 
@@ -1522,12 +1563,9 @@ static int launch_cmux(eoc_engine *e, const CmuxArgs &a, uint32_t ny, hipStream_
 {
     const void *fn = nullptr;
     const int l = e->p.l, bg = e->p.Bgbit;
-    if (l == 2 && bg == 10) fn = reinterpret_cast<const void *>(&k_cmux<2, 10>);
-    else if (l == 3 && bg == 7) fn = reinterpret_cast<const void *>(&k_cmux<3, 7>);
-    else if (l == 1) fn = reinterpret_cast<const void *>(&k_cmux<1, 0>);
-    else if (l == 2) fn = reinterpret_cast<const void *>(&k_cmux<2, 0>);
-    else if (l == 3) fn = reinterpret_cast<const void *>(&k_cmux<3, 0>);
-    else if (l == 4) fn = reinterpret_cast<const void *>(&k_cmux<4, 0>);
+#define EOC_CMUX(L, B) EOC_IF_SHAPE(L, B, l, bg) fn = reinterpret_cast<const void *>(&k_cmux<L, B>);
+    EOC_PAIR_SHAPES(EOC_CMUX)
+#undef EOC_CMUX
     if (!fn) {
         eoc_set_error("k_cmux: no kernel for gadget length %d", l);
         return EOC_ERR_STATE;
@@ -1571,25 +1609,69 @@ extern "C" int eoc_cmux_device(eoc_engine *e, const void *d_sel_fft, const int32
     return EOC_OK;
 }
 
-// the two ping-pong buffers, grown by the workspace's rule (ensure_ws): never under capture, the device drained first
-static int ensure_cmux_ws(eoc_engine *e, size_t s0, size_t s1, hipStream_t st)
+// The walk over a table of 2^d lists of 2^(10 - r) slots that the encrypted-index read and update share: d tree stages and r
+// rotations per query, through two ping-pong buffers that hold 2^(d-1) and 2^(d-2) samples per query (the rotations one).
+// Queries are sliced so that both buffers together stay inside the byte budget (EOC_TFHE_TABLE_WS_BYTES) and a slice fits
+// grid y.
+struct TableWalk {
+    int d, r, depth;
+    size_t W, smp, sel; // slots per list; ints per TLWE sample and d2 per converted selector
+    size_t s0, s1;      // samples per query in buffer 0 and 1
+    size_t qs;          // queries per slice
+};
+// validation (messages under the caller's name `who`), the derived sizes, the budget check, queries per slice; ptrs_ok = the
+// caller's own pointers are there.  Reads nothing of the engine that changes after creation: called ahead of the lock.
+static int table_walk_plan(const eoc_engine *e, const char *who, bool ptrs_ok, int log2_lists, int log2_width, const void *d_sel_fft,
+                           size_t queries, TableWalk *tw)
 {
-    const size_t need[2] = {s0, s1};
-    if (need[0] <= e->cmux_cap[0] && need[1] <= e->cmux_cap[1]) return EOC_OK;
-    if (stream_is_capturing(st)) {
-        eoc_set_error("graph capture: the table-read workspace would have to grow (%zu > %zu or %zu > %zu samples); run one "
-                      "call of the captured shape before capturing", s0, e->cmux_cap[0], s1, e->cmux_cap[1]);
-        return EOC_ERR_STATE;
+    if (!e || !ptrs_ok || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10 ||
+        (!d_sel_fft && log2_lists + 10 - log2_width > 0)) {
+        eoc_set_error("%s: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]", who, log2_lists,
+                      log2_width);
+        return EOC_ERR_ARG;
     }
-    HIP_TRY(hipDeviceSynchronize());
-    for (int k = 0; k < 2; k++) {
-        if (need[k] <= e->cmux_cap[k]) continue;
-        hipFree(e->d_cmux[k]);
-        e->d_cmux[k] = nullptr;
-        e->cmux_cap[k] = 0;
-        HIP_TRY(hipMalloc(&e->d_cmux[k], need[k] * 2 * kN * sizeof(int32_t)));
-        e->cmux_cap[k] = need[k];
-        e->ws_grows++;
+    const int d = log2_lists, r = 10 - log2_width;
+    *tw = TableWalk{d, r, d + r, (size_t)1 << log2_width, (size_t)2 * kN, (size_t)e->kpl * 2 * kNH,
+                    d >= 1 ? (size_t)1 << (d - 1) : 1, d >= 2 ? (size_t)1 << (d - 2) : 1, 0};
+    const size_t per_query = (tw->s0 + tw->s1) * tw->smp * sizeof(int32_t);
+    if (tw->depth > 0 && e->table_ws_bytes < per_query) {
+        eoc_set_error("%s: one query at log2_lists = %d needs %zu bytes of workspace, the budget (EOC_TFHE_TABLE_WS_BYTES) is %zu",
+                      who, d, per_query, e->table_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    tw->qs = std::min<size_t>(queries, 32768); // grid y
+    if (tw->depth > 0) tw->qs = std::min(tw->qs, e->table_ws_bytes / per_query);
+    return EOC_OK;
+}
+// the two buffers of a slice, by the scratch rule
+static int table_walk_reserve(eoc_engine *e, const TableWalk &tw, hipStream_t st)
+{
+    if (tw.depth == 0) return EOC_OK;
+    const size_t per_sample = tw.qs * tw.smp * sizeof(int32_t);
+    int rc = scratch_reserve(e, e->cmux[0], tw.s0 * per_sample, "table workspace (buffer 0)", st);
+    if (!rc) rc = scratch_reserve(e, e->cmux[1], tw.s1 * per_sample, "table workspace (buffer 1)", st);
+    return rc;
+}
+// The r rotations of a slice of Q queries: the CMux under selector bit i picks its input or the input times X^(sign W 2^i).
+// Rotation 0 reads *cur, *cur_y ints between the queries' samples (0: one shared sample); rotation i leaves one sample per
+// query in buffer out_buf(tw, i); *cur and *cur_y follow the last output.
+static int table_walk_rotations(eoc_engine *e, const TableWalk &tw, const d2 *selq, int sign, const int32_t **cur, size_t *cur_y,
+                                int (*out_buf)(const TableWalk &, int), size_t Q, hipStream_t st)
+{
+    for (int i = 0; i < tw.r; i++) {
+        CmuxArgs a{};
+        a.nx = 1;
+        a.sel = selq + (size_t)i * tw.sel;
+        a.sel_y = (size_t)tw.depth * tw.sel;
+        a.in0 = a.in1 = *cur;
+        a.in0_y = a.in1_y = *cur_y;
+        a.out = e->cmux[out_buf(tw, i)].i32();
+        a.out_y = tw.smp;
+        a.rot = sign > 0 ? (int)(tw.W << i) : 2 * kN - (int)(tw.W << i);
+        int rc = launch_cmux(e, a, (uint32_t)Q, st);
+        if (rc) return rc;
+        *cur = a.out;
+        *cur_y = a.out_y;
     }
     return EOC_OK;
 }
@@ -1597,22 +1679,11 @@ static int ensure_cmux_ws(eoc_engine *e, size_t s0, size_t s1, hipStream_t st)
 extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
                                      size_t queries, int32_t *d_out, void *hip_stream)
 {
-    if (!e || !d_table || !d_out || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10 ||
-        (!d_sel_fft && log2_lists + 10 - log2_width > 0)) {
-        eoc_set_error("eoc_table_read_device: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]",
-                      log2_lists, log2_width);
-        return EOC_ERR_ARG;
-    }
+    TableWalk tw;
+    int rc = table_walk_plan(e, "eoc_table_read_device", d_table && d_out, log2_lists, log2_width, d_sel_fft, queries, &tw);
+    if (rc) return rc;
+    tw.qs = std::min(tw.qs, std::max<size_t>(1, ((size_t)1 << 20) / tw.W)); // 2^20 extracted samples a slice (lut_levels' rule)
     std::lock_guard<std::mutex> g(e->mu);
-    const int d = log2_lists, r = 10 - log2_width, depth = d + r;
-    const size_t W = (size_t)1 << log2_width, smp = (size_t)2 * kN, sel = (size_t)e->kpl * 2 * kNH;
-    const size_t s0 = d >= 1 ? (size_t)1 << (d - 1) : 1, s1 = d >= 2 ? (size_t)1 << (d - 2) : 1; // samples per query
-    const size_t per_query = (s0 + s1) * smp * sizeof(int32_t);
-    if (depth > 0 && e->table_ws_bytes < per_query) {
-        eoc_set_error("eoc_table_read_device: one query at log2_lists = %d needs %zu bytes of workspace, the budget "
-                      "(EOC_TFHE_TABLE_WS_BYTES) is %zu", d, per_query, e->table_ws_bytes);
-        return EOC_ERR_ARG;
-    }
     if (!e->ksk) {
         eoc_set_error("eoc_table_read_device: no key-switch key loaded");
         return EOC_ERR_NO_KEY;
@@ -1621,13 +1692,11 @@ extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int 
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
     WS &Wk = e->ws;
-    // queries per slice: the byte budget of the tree's buffers, 2^20 extracted samples (lut_levels' rule), grid y
-    size_t qs = std::min<size_t>(queries, 32768);
-    if (depth > 0) qs = std::min(qs, e->table_ws_bytes / per_query);
-    qs = std::min(qs, std::max<size_t>(1, ((size_t)1 << 20) / W));
-    int rc = ensure_ws(e, Wk, qs * W, 0, 0, st);
+    const int d = tw.d, r = tw.r, depth = tw.depth;
+    const size_t W = tw.W, smp = tw.smp, sel = tw.sel, qs = tw.qs;
+    rc = ensure_ws(e, Wk, qs * W, 0, 0, st);
+    if (!rc) rc = table_walk_reserve(e, tw, st);
     if (rc) return rc;
-    if (depth > 0 && (rc = ensure_cmux_ws(e, qs * s0, qs * s1, st))) return rc;
     const size_t stride = (size_t)e->p.n + 1;
     const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
     for (size_t q0 = 0; q0 < queries; q0 += qs) {
@@ -1646,7 +1715,7 @@ extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int 
             a.in1 = cur + smp;
             a.in0_x = a.in1_x = 2 * smp;
             a.in0_y = a.in1_y = cur_y;
-            a.out = e->d_cmux[t & 1];
+            a.out = e->cmux[t & 1].i32();
             a.out_x = smp;
             a.out_y = (size_t)a.nx * smp;
             a.rot = 0;
@@ -1654,20 +1723,9 @@ extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int 
             cur = a.out;
             cur_y = a.out_y;
         }
-        for (int i = 0; i < r; i++, t++) { // rotations: X^(-W 2^i) under bit i brings slot W 2^i to slot 0
-            CmuxArgs a{};
-            a.nx = 1;
-            a.sel = selq + (size_t)i * sel;
-            a.sel_y = (size_t)depth * sel;
-            a.in0 = a.in1 = cur;
-            a.in0_y = a.in1_y = cur_y;
-            a.out = e->d_cmux[t & 1];
-            a.out_y = smp;
-            a.rot = 2 * kN - (int)(W << i);
-            if ((rc = launch_cmux(e, a, (uint32_t)Q, st))) return rc;
-            cur = a.out;
-            cur_y = a.out_y;
-        }
+        // rotations: X^(-W 2^i) under bit i brings slot W 2^i to slot 0; launch t = d + i of the query writes buffer t & 1
+        rc = table_walk_rotations(e, tw, selq, -1, &cur, &cur_y, [](const TableWalk &w, int i) { return (w.d + i) & 1; }, Q, st);
+        if (rc) return rc;
         int32_t *o = d_out + q0 * W * stride;
         {
             SpanGuard span(e, st, KIND_PREPARE);
@@ -1707,56 +1765,25 @@ extern "C" int eoc_engine_set_packing_key(eoc_engine *e, const void *blob, size_
     HIP_TRY(hipDeviceSynchronize()); // nothing in flight may still read the image that is about to be replaced
     hipFree(e->d_pks);
     e->d_pks = nullptr;
-    int32_t *d_rows = nullptr;
-    d2 *d_img = nullptr;
-    HIP_TRY(hipMalloc(&d_rows, npoly * kN * sizeof(int32_t)));
-    if (hipMalloc(&d_img, npoly * kNH * sizeof(d2)) != hipSuccess) {
-        hipFree(d_rows);
-        eoc_set_error("eoc_engine_set_packing_key: out of device memory");
-        return EOC_ERR_HIP;
-    }
-    int rc = EOC_OK;
-    if (hipMemcpy(d_rows, rows, npoly * kN * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = EOC_ERR_HIP;
-    // the key-load transform (build_cloud_key_images, eoc_tgsw_to_fft_device); NULL stream, drained below
-    if (!rc) rc = launch_fft_fwd(e, d_rows, reinterpret_cast<double *>(d_img), npoly, 0x1p-9, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess && !rc) rc = EOC_ERR_HIP;
-    hipFree(d_rows);
-    if (rc) {
-        hipFree(d_img);
-        eoc_set_error("eoc_engine_set_packing_key: upload or conversion failed");
-        return rc;
-    }
-    e->d_pks = d_img;
+    DevTmp d_rows, d_img;
+    HIP_TRY(d_rows.alloc(npoly * kN * sizeof(int32_t)));
+    HIP_TRY(d_img.alloc(npoly * kNH * sizeof(d2)));
+    HIP_TRY(hipMemcpy(d_rows.p, rows, npoly * kN * sizeof(int32_t), hipMemcpyHostToDevice));
+    // the key-load transform (build_cloud_key_images, eoc_tgsw_to_fft_device); NULL stream, drained inside
+    int rc = key_image(e, d_rows.i32(), d_img.p, npoly);
+    if (rc) return rc;
+    e->d_pks = static_cast<d2 *>(d_img.release());
     return EOC_OK;
 }
 
-// the gathered mask columns, grown by the workspace's rule (ensure_ws): never under capture, the device drained first
-static int ensure_pack_ws(eoc_engine *e, size_t lists, hipStream_t st)
-{
-    if (lists <= e->pack_cap) return EOC_OK;
-    if (stream_is_capturing(st)) {
-        eoc_set_error("graph capture: the packing workspace would have to grow (%zu > %zu lists); run one call of the captured "
-                      "shape before capturing", lists, e->pack_cap);
-        return EOC_ERR_STATE;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    hipFree(e->d_pack_cols);
-    e->d_pack_cols = nullptr;
-    e->pack_cap = 0;
-    HIP_TRY(hipMalloc(&e->d_pack_cols, lists * (size_t)e->p.n * kN * sizeof(int32_t)));
-    e->pack_cap = lists;
-    e->ws_grows++;
-    return EOC_OK;
-}
-
-// k_pack_rows over the `L` lists whose columns a gather kernel has just laid out in d_pack_cols
+// k_pack_rows over the `L` lists whose columns a gather kernel has just laid out in pack_cols
 static int launch_pack_rows(eoc_engine *e, int32_t *lists, size_t L, hipStream_t st)
 {
     const int n = e->p.n;
     const uint32_t nchunks = (uint32_t)((n + kPackChunk - 1) / kPackChunk), items = (uint32_t)(L * nchunks);
     SpanGuard span(e, st, KIND_KEYSWITCH);
     hipLaunchKernelGGL(k_pack_rows, dim3((items + kPackWavesPerWG - 1) / kPackWavesPerWG), dim3(64 * kPackWavesPerWG), kPackLds, st,
-                       (const int32_t *)e->d_pack_cols, (const d2 *)e->d_pks, lists, n, nchunks, items, (const d2 *)e->d_tw,
+                       (const int32_t *)e->pack_cols.p, (const d2 *)e->d_pks, lists, n, nchunks, items, (const d2 *)e->d_tw,
                        (const d2 *)e->d_twist);
     HIP_TRY(hipGetLastError());
     e->pack_launches++;
@@ -1786,7 +1813,7 @@ extern "C" int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count,
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t ls = std::min({n_lists, e->pack_ws_bytes / per_list, (size_t)65535}); // grid z
-    int rc = ensure_pack_ws(e, ls, st);
+    int rc = scratch_reserve(e, e->pack_cols, ls * per_list, "packing columns", st);
     if (rc) return rc;
     for (size_t l0 = 0; l0 < n_lists; l0 += ls) {
         const size_t L = std::min(ls, n_lists - l0), cnt = std::min(count - l0 * kN, L * kN);
@@ -1795,7 +1822,7 @@ extern "C" int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count,
         {
             SpanGuard span(e, st, KIND_KEYSWITCH);
             hipLaunchKernelGGL(k_pack_gather, dim3(kN / kPackTile, (unsigned)((n + 1 + kPackTile - 1) / kPackTile), (unsigned)L),
-                               dim3(256), 0, st, in, cnt, (int)n, e->d_pack_cols, lists);
+                               dim3(256), 0, st, in, cnt, (int)n, e->pack_cols.i32(), lists);
             HIP_TRY(hipGetLastError());
         }
         rc = launch_pack_rows(e, lists, L, st);
@@ -1925,7 +1952,7 @@ static int tv_pack_locked(eoc_engine *e, const char *who, int p, const int32_t *
     }
     HIP_TRY(hipSetDevice(e->device));
     const size_t ls = std::min({n_lists, e->pack_ws_bytes / per_list, (size_t)65535}); // grid z
-    int rc = ensure_pack_ws(e, ls, st);
+    int rc = scratch_reserve(e, e->pack_cols, ls * per_list, "packing columns", st);
     if (rc) return rc;
     for (size_t l0 = 0; l0 < n_lists; l0 += ls) {
         const size_t L = std::min(ls, n_lists - l0);
@@ -1934,7 +1961,7 @@ static int tv_pack_locked(eoc_engine *e, const char *who, int p, const int32_t *
             SpanGuard span(e, st, KIND_KEYSWITCH);
             const dim3 grid(kN / kPackTile, (unsigned)((n + 1 + kPackTile - 1) / kPackTile), (unsigned)L);
             auto kfn = p == 2 ? k_tvpack_cols<2> : (p == 4 ? k_tvpack_cols<4> : k_tvpack_cols<8>);
-            hipLaunchKernelGGL(kfn, grid, dim3(256), 0, st, d_vals, (uint32_t)count, (uint32_t)l0, (int)n, e->d_pack_cols, lists);
+            hipLaunchKernelGGL(kfn, grid, dim3(256), 0, st, d_vals, (uint32_t)count, (uint32_t)l0, (int)n, e->pack_cols.i32(), lists);
             HIP_TRY(hipGetLastError());
         }
         rc = launch_pack_rows(e, lists, L, st);
@@ -1952,25 +1979,6 @@ extern "C" int eoc_tv_pack_device(eoc_engine *e, int p, const int32_t *d_vals, s
     }
     std::lock_guard<std::mutex> g(e->mu);
     return tv_pack_locked(e, "eoc_tv_pack_device", p, d_vals, n_funcs, count, d_lists, (hipStream_t)hip_stream);
-}
-
-// the level-1 outputs [n_funcs][p][rows][n+1] and the lists [n_funcs][rows][2][N] of a slice, grown by the workspace's rule
-static int ensure_lut2_ws(eoc_engine *e, size_t bytes, hipStream_t st)
-{
-    if (bytes <= e->lut2_cap) return EOC_OK;
-    if (stream_is_capturing(st)) {
-        eoc_set_error("graph capture: the two-input lookup workspace would have to grow (%zu > %zu bytes); run one call of the "
-                      "captured shape before capturing", bytes, e->lut2_cap);
-        return EOC_ERR_STATE;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    hipFree(e->d_lut2);
-    e->d_lut2 = nullptr;
-    e->lut2_cap = 0;
-    HIP_TRY(hipMalloc(&e->d_lut2, bytes));
-    e->lut2_cap = bytes;
-    e->ws_grows++;
-    return EOC_OK;
 }
 
 // F(x, y): level 1 (the existing _tv / many-LUT path) on x against the p tables x -> F(x, j), the pack of each row's p values
@@ -2005,9 +2013,10 @@ extern "C" int eoc_lut2_batch_device(eoc_engine *e, int p, int n_tables, const i
     const size_t row_vals = n_funcs * (size_t)p * stride * sizeof(int32_t), row_lists = n_funcs * 2 * kN * sizeof(int32_t);
     const size_t rows = std::min({count, std::max<size_t>(1, ((size_t)1 << 20) / (n_funcs * (size_t)p)),
                                   std::max<size_t>(1, kLut2WsBytes / (row_vals + row_lists))});
-    int rc = ensure_lut2_ws(e, rows * (row_vals + row_lists), st);
+    // one buffer: the lists [n_funcs][rows][2][N] of a slice, then its level-1 outputs [n_funcs][p][rows][n+1]
+    int rc = scratch_reserve(e, e->lut2, rows * (row_vals + row_lists), "two-input lookup workspace", st);
     if (rc) return rc;
-    int32_t *d_lists = e->d_lut2, *d_vals = e->d_lut2 + rows * (row_lists / sizeof(int32_t));
+    int32_t *d_lists = e->lut2.i32(), *d_vals = d_lists + rows * (row_lists / sizeof(int32_t));
     for (size_t r0 = 0; r0 < count; r0 += rows) {
         const size_t S = std::min(rows, count - r0);
         rc = lut_levels_locked(e, "eoc_lut2_batch_device", T > 1 ? T : 0, 0, d_tv0, n_funcs * (size_t)(p / T), d_x + r0 * stride,
@@ -2181,20 +2190,18 @@ try {
 // emits kernels in the order of their first use, so the earlier ones keep their text instruction for instruction.
 static const void *demux_kernel(int l, int bg)
 {
-    if (l == 2 && bg == 10) return reinterpret_cast<const void *>(&k_demux<2, 10>);
-    if (l == 3 && bg == 7) return reinterpret_cast<const void *>(&k_demux<3, 7>);
-    if (l == 1) return reinterpret_cast<const void *>(&k_demux<1, 0>);
-    if (l == 2) return reinterpret_cast<const void *>(&k_demux<2, 0>);
-    if (l == 3) return reinterpret_cast<const void *>(&k_demux<3, 0>);
-    if (l == 4) return reinterpret_cast<const void *>(&k_demux<4, 0>);
-    return nullptr;
+    const void *fn = nullptr;
+#define EOC_DEMUX(L, B) EOC_IF_SHAPE(L, B, l, bg) fn = reinterpret_cast<const void *>(&k_demux<L, B>);
+    EOC_PAIR_SHAPES(EOC_DEMUX)
+#undef EOC_DEMUX
+    return fn;
 }
 
 static void set_demux_attrs()
 {
-    static const int shapes[6][2] = {{2, 10}, {3, 7}, {1, 0}, {2, 0}, {3, 0}, {4, 0}};
-    for (const auto &s : shapes)
-        (void)hipFuncSetAttribute(demux_kernel(s[0], s[1]), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
+#define EOC_DEMUX_ATTR(L, B) (void)hipFuncSetAttribute(demux_kernel(L, B), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
+    EOC_PAIR_SHAPES(EOC_DEMUX_ATTR)
+#undef EOC_DEMUX_ATTR
 }
 
 static int launch_demux(eoc_engine *e, const DemuxArgs &a, uint32_t ny, hipStream_t st)
@@ -2246,49 +2253,27 @@ extern "C" int eoc_demux_device(eoc_engine *e, const void *d_sel_fft, const int3
 extern "C" int eoc_table_update_device(eoc_engine *e, int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
                                        const int32_t *d_vals, size_t queries, void *hip_stream)
 {
-    if (!e || !d_table || !d_vals || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10 ||
-        (!d_sel_fft && log2_lists + 10 - log2_width > 0)) {
-        eoc_set_error("eoc_table_update_device: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside "
-                      "[0, 10]", log2_lists, log2_width);
-        return EOC_ERR_ARG;
-    }
+    // the read's walk and its two buffers: the storing stages leave 2^(d-1) and 2^(d-2) samples per query, the rotations one
+    TableWalk tw;
+    int rc = table_walk_plan(e, "eoc_table_update_device", d_table && d_vals, log2_lists, log2_width, d_sel_fft, queries, &tw);
+    if (rc) return rc;
     std::lock_guard<std::mutex> g(e->mu);
-    const int d = log2_lists, r = 10 - log2_width, depth = d + r;
-    const size_t W = (size_t)1 << log2_width, smp = (size_t)2 * kN, sel = (size_t)e->kpl * 2 * kNH;
-    // the read's two buffers: the storing stages leave 2^(d-1) and 2^(d-2) samples per query, the rotations one
-    const size_t s0 = d >= 1 ? (size_t)1 << (d - 1) : 1, s1 = d >= 2 ? (size_t)1 << (d - 2) : 1;
-    const size_t per_query = (s0 + s1) * smp * sizeof(int32_t);
-    if (depth > 0 && e->table_ws_bytes < per_query) {
-        eoc_set_error("eoc_table_update_device: one query at log2_lists = %d needs %zu bytes of workspace, the budget "
-                      "(EOC_TFHE_TABLE_WS_BYTES) is %zu", d, per_query, e->table_ws_bytes);
-        return EOC_ERR_ARG;
-    }
     if (!queries) return EOC_OK;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    size_t qs = std::min<size_t>(queries, 32768); // grid y
-    if (depth > 0) qs = std::min(qs, e->table_ws_bytes / per_query);
-    int rc;
-    if (depth > 0 && (rc = ensure_cmux_ws(e, qs * s0, qs * s1, st))) return rc;
+    if ((rc = table_walk_reserve(e, tw, st))) return rc;
+    const int d = tw.d, r = tw.r, depth = tw.depth;
+    const size_t smp = tw.smp, sel = tw.sel, qs = tw.qs;
     for (size_t q0 = 0; q0 < queries; q0 += qs) {
         const size_t Q = std::min(qs, queries - q0);
         const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * depth * sel;
         const int32_t *cur = d_vals + q0 * smp; // one sample per query until the tree starts
+        size_t cur_y = smp;
         // rotations: X^(W 2^i) under bit i carries the value to slot W (idx mod 2^r).  Rotation i leaves its result in
         // buffer (d - 1 + r - 1 - i) & 1, so the last one ends where the first storing stage does not write
-        for (int i = 0; i < r; i++) {
-            CmuxArgs a{};
-            a.nx = 1;
-            a.sel = selq + (size_t)i * sel;
-            a.sel_y = (size_t)depth * sel;
-            a.in0 = a.in1 = cur;
-            a.in0_y = a.in1_y = smp;
-            a.out = e->d_cmux[(d + r - i) & 1];
-            a.out_y = smp;
-            a.rot = (int)(W << i);
-            if ((rc = launch_cmux(e, a, (uint32_t)Q, st))) return rc;
-            cur = a.out;
-        }
+        rc = table_walk_rotations(e, tw, selq, +1, &cur, &cur_y, [](const TableWalk &w, int i) { return (w.d + w.r - i) & 1; }, Q,
+                                  st);
+        if (rc) return rc;
         if (d == 0) { // one list: the rotated value is the leaf
             const bool vec = (((uintptr_t)cur | (uintptr_t)d_table) & 15) == 0;
             SpanGuard span(e, st, KIND_BLIND_ROTATE);
@@ -2300,7 +2285,6 @@ extern "C" int eoc_table_update_device(eoc_engine *e, int32_t *d_table, int log2
         // tree: stage t under bit r + (d - 1 - t), parent j of 2^t -> children 2j (x - E) and 2j + 1 (E).  Stage t < d - 1
         // stores [Q][2^(t+1)] samples into buffer (d - 2 - t) & 1 (the larger buffer takes the last storing stage); stage
         // d - 1 accumulates its 2^d leaves into the table
-        size_t cur_y = smp;
         for (int t = 0; t < d; t++) {
             DemuxArgs a{};
             a.nx = (uint32_t)1 << t;
@@ -2316,7 +2300,7 @@ extern "C" int eoc_table_update_device(eoc_engine *e, int32_t *d_table, int log2
                 a.out_y = 0;
                 a.accumulate = 1;
             } else {
-                a.out0 = e->d_cmux[(d - 2 - t) & 1];
+                a.out0 = e->cmux[(d - 2 - t) & 1].i32();
                 a.out_y = (size_t)2 * a.nx * smp;
                 a.accumulate = 0;
             }
@@ -2468,26 +2452,6 @@ extern "C" int eoc_seeded_expand_device(eoc_engine *e, const uint8_t seed[32], u
                              d_out, (hipStream_t)hip_stream);
 }
 
-// the staging rows of the seeded selectors, grown by the workspace's rule (ensure_ws): never under capture, the device
-// drained first
-static int ensure_seed_stage(eoc_engine *e, size_t rows, hipStream_t st)
-{
-    if (rows <= e->seed_stage_cap) return EOC_OK;
-    if (stream_is_capturing(st)) {
-        eoc_set_error("graph capture: the seeded-selector staging buffer would have to grow (%zu > %zu rows); run one call of the "
-                      "captured shape before capturing", rows, e->seed_stage_cap);
-        return EOC_ERR_STATE;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    hipFree(e->d_seed_stage);
-    e->d_seed_stage = nullptr;
-    e->seed_stage_cap = 0;
-    HIP_TRY(hipMalloc(&e->d_seed_stage, rows * 2 * kN * sizeof(int32_t)));
-    e->seed_stage_cap = rows;
-    e->ws_grows++;
-    return EOC_OK;
-}
-
 // seeded selectors -> the converted form: bodies [count][2l][N] + seed -> torus-form rows in the staging buffer (row r of the
 // call has the mask stream (seed, SeedTgsw, first_idx 2l + r)), then the key-load transform of eoc_tgsw_to_fft_device.
 // Slices of at most 64 MiB of staging; all on the caller's stream.
@@ -2504,14 +2468,15 @@ extern "C" int eoc_tgsw_seeded_to_fft_device(eoc_engine *e, const uint8_t seed[3
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t kpl = (size_t)e->kpl;
     const size_t slice = std::max<size_t>(1, ((size_t)64 << 20) / (kpl * 2 * kN * sizeof(int32_t))); // selectors
-    int rc = ensure_seed_stage(e, std::min(count, slice) * kpl, st);
+    int rc = scratch_reserve(e, e->seed_stage, std::min(count, slice) * kpl * 2 * kN * sizeof(int32_t),
+                             "seeded-selector staging rows", st);
     if (rc) return rc;
     for (size_t s0 = 0; s0 < count; s0 += slice) {
         const size_t S = std::min(slice, count - s0), rows = S * kpl;
         rc = launch_seed_masks(e, SEED_RING, seed, TAG_SEED_TGSW, (first_idx + s0) * kpl, rows, kN, 2 * kN,
-                               d_bodies + s0 * kpl * kN, e->d_seed_stage, st);
+                               d_bodies + s0 * kpl * kN, e->seed_stage.i32(), st);
         if (rc) return rc;
-        rc = launch_fft_fwd(e, e->d_seed_stage, static_cast<double *>(d_fft) + s0 * kpl * 2 * kNH * 2, rows * 2, 0x1p-9, st);
+        rc = launch_fft_fwd(e, e->seed_stage.i32(), static_cast<double *>(d_fft) + s0 * kpl * 2 * kNH * 2, rows * 2, 0x1p-9, st);
         if (rc) return rc;
     }
     return EOC_OK;
@@ -2539,35 +2504,21 @@ extern "C" int eoc_engine_load_seeded_cloud_key(eoc_engine *e, const void *blob,
     std::lock_guard<std::mutex> g(e->mu);
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize()); // nothing in flight may still read the images that are about to be rewritten
-    if (!e->own_keys) {
-        HIP_TRY(hipMalloc(&e->d_bkfft, eoc_bkfft_bytes(&p)));
-        HIP_TRY(hipMalloc(&e->d_ksk, eoc_ksk_dev_bytes(&p)));
-        e->own_keys = true;
-    }
+    int rc = own_key_images(e);
+    if (rc) return rc;
     const size_t bk_rows = (size_t)p.n * e->kpl, ks_rows = (size_t)kN * p.ks_t * (((size_t)1 << p.ks_basebit) - 1);
-    int32_t *d_bodies = nullptr, *d_stage = nullptr;
-    HIP_TRY(hipMalloc(&d_bodies, std::max(bk_rows * kN, ks_rows) * sizeof(int32_t)));
-    if (hipMalloc(&d_stage, bk_rows * 2 * kN * sizeof(int32_t)) != hipSuccess) {
-        hipFree(d_bodies);
-        eoc_set_error("eoc_engine_load_seeded_cloud_key: out of device memory");
-        return EOC_ERR_HIP;
-    }
-    int rc = EOC_OK;
-    if (hipMemcpy(d_bodies, bkb, bk_rows * kN * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = EOC_ERR_HIP;
-    if (!rc) rc = launch_seed_masks(e, SEED_RING, seed, TAG_SEED_BK, 0, bk_rows, kN, 2 * kN, d_bodies, d_stage, nullptr);
-    // the key image carries the inverse transform's 1/512 (build_cloud_key_images)
-    if (!rc) rc = launch_fft_fwd(e, d_stage, e->d_bkfft, bk_rows * 2, 0x1p-9, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess && !rc) rc = EOC_ERR_HIP; // the bodies are re-used below
-    if (!rc && hipMemcpy(d_bodies, kskb, ks_rows * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = EOC_ERR_HIP;
-    if (!rc) rc = launch_seed_masks(e, SEED_KSK, seed, TAG_SEED_KSK, 0, ks_rows, (uint32_t)p.n, (uint32_t)e->n1p, d_bodies, e->d_ksk,
-                                    nullptr);
-    if (hipDeviceSynchronize() != hipSuccess && !rc) rc = EOC_ERR_HIP;
-    hipFree(d_bodies);
-    hipFree(d_stage);
-    if (rc) {
-        if (rc == EOC_ERR_HIP) eoc_set_error("eoc_engine_load_seeded_cloud_key: upload or expansion failed");
-        return rc;
-    }
+    DevTmp d_bodies, d_stage;
+    HIP_TRY(d_bodies.alloc(std::max(bk_rows * kN, ks_rows) * sizeof(int32_t)));
+    HIP_TRY(d_stage.alloc(bk_rows * 2 * kN * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(d_bodies.p, bkb, bk_rows * kN * sizeof(int32_t), hipMemcpyHostToDevice));
+    rc = launch_seed_masks(e, SEED_RING, seed, TAG_SEED_BK, 0, bk_rows, kN, 2 * kN, d_bodies.i32(), d_stage.i32(), nullptr);
+    if (!rc) rc = key_image(e, d_stage.i32(), e->d_bkfft, bk_rows * 2); // drained: the bodies are re-used below
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(d_bodies.p, kskb, ks_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    rc = launch_seed_masks(e, SEED_KSK, seed, TAG_SEED_KSK, 0, ks_rows, (uint32_t)p.n, (uint32_t)e->n1p, d_bodies.i32(), e->d_ksk,
+                           nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
     e->bkfft = e->d_bkfft;
     e->ksk = e->d_ksk;
     return install_ks_limbs(e);

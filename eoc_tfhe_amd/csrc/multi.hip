@@ -31,15 +31,18 @@
 #include <thread>
 #include <vector>
 
-#define HIP_TRY(expr)                                                                       \
+// a failed HIP call leaves through drain(EOC_ERR_HIP): the pipelined paths drain their streams on the way out (an error
+// must not leave copies into or out of the caller's buffers in flight after the call has returned)
+#define HIP_TRY_ELSE(expr, drain)                                                           \
     do {                                                                                    \
         hipError_t _e = (expr);                                                             \
         if (_e != hipSuccess) {                                                             \
             eoc_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
                           __LINE__);                                                        \
-            return EOC_ERR_HIP;                                                             \
+            return drain(EOC_ERR_HIP);                                                      \
         }                                                                                   \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_ELSE(expr, )
 
 // result rows -> caller's pinned, device-mapped buffer (a kernel writes over PCIe at twice the rate of the copy
 // engine's 2 MB transfer and needs no separate queue hand-off)
@@ -123,18 +126,15 @@ struct Slot {
     // persistent buffers of the gate-batch path: 3 inputs + 1 output, `cap_io_ints` ints each
     int32_t *d_io[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t cap_io_ints = 0;
-    // persistent wire buffer of the circuit path
-    int32_t *d_wires = nullptr;
-    size_t cap_wire_ints = 0;
-    // persistent buffer of the table-lookup path (test polynomials | input rows | output rows) and of compact-list expansion
-    // (lists | output rows)
+    // persistent staging buffer of every other path, one call at a time (G.mu): carved by the call's Staging (the circuit
+    // path's wires; test polynomials | input rows | output rows of a table lookup; lists | output rows of an expansion; ...)
     int32_t *d_lut = nullptr;
     size_t cap_lut_ints = 0;
     uint64_t grows = 0; // buffer growths (0 in steady state)
     // asynchronous batch path (eoc_gate_batch_submit / _wait): two buffer sets, so that batch k + 1's operands arrive
     // while batch k computes and batch k's results leave under batch k + 1's kernels
     int32_t *d_as[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
-    size_t cap_async = 0;
+    size_t cap_async_ints = 0; // each
     hipEvent_t ev_as[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; // operands in, kernels done, results out
 };
 
@@ -203,6 +203,42 @@ int slot_grow(Slot &s, int32_t **bufs, int nbuf, size_t *cap, size_t need)
     return EOC_OK;
 }
 
+// The staging buffer's pieces, sized and carved by ONE statement each: take(p, ints) in buffer order, then commit() grows
+// s.d_lut to the sum and sets every p.  No second formula exists that could disagree with the carving.
+struct Staging {
+    enum { kMaxPieces = 4 };
+    int32_t **piece[kMaxPieces];
+    size_t off[kMaxPieces], ints = 0;
+    int n = 0;
+    Staging &take(int32_t *&p, size_t n_ints)
+    {
+        if (n < kMaxPieces) {
+            piece[n] = &p;
+            off[n] = ints;
+        }
+        n++;
+        ints += n_ints;
+        return *this;
+    }
+    int commit(Slot &s) // device already selected
+    {
+        if (n > kMaxPieces) {
+            eoc_set_error("internal: more than %d pieces in a staging buffer", (int)kMaxPieces);
+            return EOC_ERR_STATE;
+        }
+        int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, ints);
+        for (int k = 0; !rc && k < n; k++) *piece[k] = s.d_lut + off[k];
+        return rc;
+    }
+};
+
+// the three streams of the pipelined paths drained, whatever `code` is, which is handed back
+int drain_streams(Slot &s, int code)
+{
+    for (int k = 0; k < 3; k++) (void)hipStreamSynchronize(s.st[k]);
+    return code;
+}
+
 // the common exit of the one-stream block functions: the stream is drained whatever `rc` is -- an error must not leave a
 // copy into (or out of) the caller's buffers in flight after the call has returned
 int slot_finish(hipStream_t st, int rc)
@@ -260,42 +296,30 @@ int slot_gate_block(Slot &s, int op, const uint8_t *ops, const int32_t *in0, con
         }
         // An error anywhere in the pipeline must not leave copies into (or out of) the caller's buffers in flight after
         // the call has returned, nor kernels that still use d_io: every exit drains the three streams first.
-        auto drain = [&](int code) {
-            for (int k = 0; k < 3; k++) (void)hipStreamSynchronize(s.st[k]);
-            return code;
-        };
-#define PIPE_TRY(expr)                                                                                        \
-        do {                                                                                                  \
-            hipError_t _e = (expr);                                                                           \
-            if (_e != hipSuccess) {                                                                           \
-                eoc_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);    \
-                return drain(EOC_ERR_HIP);                                                                    \
-            }                                                                                                 \
-        } while (0)
+        auto drain = [&](int code) { return drain_streams(s, code); };
         for (size_t c = 0; c < nchunks; c++) { // operands of every chunk, queued back to back on the H2D stream
             size_t lo, hi;
             shard_range(count, (int)c, (int)nchunks, &lo, &hi);
             for (int k = 0; k < 3; k++)
                 if (h[k])
-                    PIPE_TRY(hipMemcpyAsync(s.d_io[k] + lo * stride_ints, h[k] + lo * stride_ints, (hi - lo) * row_bytes,
-                                            hipMemcpyHostToDevice, s.st[1]));
-            PIPE_TRY(hipEventRecord(s.ev[2 * c], s.st[1]));
+                    HIP_TRY_ELSE(hipMemcpyAsync(s.d_io[k] + lo * stride_ints, h[k] + lo * stride_ints, (hi - lo) * row_bytes,
+                                                hipMemcpyHostToDevice, s.st[1]), drain);
+            HIP_TRY_ELSE(hipEventRecord(s.ev[2 * c], s.st[1]), drain);
         }
         for (size_t c = 0; c < nchunks; c++) {
             size_t lo, hi;
             shard_range(count, (int)c, (int)nchunks, &lo, &hi);
             const size_t cnt = hi - lo;
-            PIPE_TRY(hipStreamWaitEvent(s.st[0], s.ev[2 * c], 0));
+            HIP_TRY_ELSE(hipStreamWaitEvent(s.st[0], s.ev[2 * c], 0), drain);
             rc = eoc_gate_batch_device(s.e, op, ops ? ops + lo : nullptr, h[0] ? s.d_io[0] + lo * stride_ints : nullptr,
                                        h[1] ? s.d_io[1] + lo * stride_ints : nullptr,
                                        h[2] ? s.d_io[2] + lo * stride_ints : nullptr, s.d_io[3] + lo * stride_ints, cnt, s.st[0]);
             if (rc) return drain(rc);
-            PIPE_TRY(hipEventRecord(s.ev[2 * c + 1], s.st[0]));
-            PIPE_TRY(hipStreamWaitEvent(s.st[2], s.ev[2 * c + 1], 0));
-            PIPE_TRY(hipMemcpyAsync(out + lo * stride_ints, s.d_io[3] + lo * stride_ints, cnt * row_bytes,
-                                    hipMemcpyDeviceToHost, s.st[2]));
+            HIP_TRY_ELSE(hipEventRecord(s.ev[2 * c + 1], s.st[0]), drain);
+            HIP_TRY_ELSE(hipStreamWaitEvent(s.st[2], s.ev[2 * c + 1], 0), drain);
+            HIP_TRY_ELSE(hipMemcpyAsync(out + lo * stride_ints, s.d_io[3] + lo * stride_ints, cnt * row_bytes,
+                                        hipMemcpyDeviceToHost, s.st[2]), drain);
         }
-#undef PIPE_TRY
         for (int k = 2; k >= 0; k--) HIP_TRY(hipStreamSynchronize(s.st[k]));
         return EOC_OK;
     }
@@ -335,7 +359,8 @@ int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *
     const size_t blk = hi - lo;
     if (!blk) return EOC_OK;
     HIP_TRY(hipSetDevice(s.device));
-    int rc = slot_grow(s, &s.d_wires, 1, &s.cap_wire_ints, n_wires * blk * stride_ints);
+    int32_t *d_wires;
+    int rc = Staging().take(d_wires, n_wires * blk * stride_ints).commit(s);
     if (rc) return rc;
     hipStream_t st = s.st[0];
     // Only the wires that matter cross PCIe: host -> device the wires some gate READS BEFORE any gate has written them
@@ -359,7 +384,7 @@ int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *
             }
             size_t e = w;
             while (e < n_wires && sel[e]) e++;
-            int32_t *dev = s.d_wires + w * blk * stride_ints;
+            int32_t *dev = d_wires + w * blk * stride_ints;
             int32_t *host = wires + (w * instances + lo) * stride_ints;
             if (to_device)
                 HIP_TRY(hipMemcpy2DAsync(dev, blk * stride_ints * 4, host, instances * stride_ints * 4, blk * stride_ints * 4,
@@ -372,7 +397,7 @@ int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *
         return EOC_OK;
     };
     rc = copy_runs(live_in, true);
-    if (rc == EOC_OK) rc = eoc_circuit_run_device(s.e, gates, n_gates, s.d_wires, n_wires, blk, st);
+    if (rc == EOC_OK) rc = eoc_circuit_run_device(s.e, gates, n_gates, d_wires, n_wires, blk, st);
     if (rc == EOC_OK) rc = copy_runs(written, false);
     return slot_finish(st, rc);
 }
@@ -386,10 +411,10 @@ int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in,
     if (!blk) return EOC_OK;
     HIP_TRY(hipSetDevice(s.device));
     const size_t n_out = n_luts * (size_t)std::max(1, n_tables);
-    const size_t tv_ints = n_luts * EOC_N, need = tv_ints + (1 + n_out) * blk * stride_ints;
-    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    const size_t tv_ints = n_luts * EOC_N;
+    int32_t *d_tv, *d_in, *d_out;
+    int rc = Staging().take(d_tv, tv_ints).take(d_in, blk * stride_ints).take(d_out, n_out * blk * stride_ints).commit(s);
     if (rc) return rc;
-    int32_t *d_tv = s.d_lut, *d_in = d_tv + tv_ints, *d_out = d_in + blk * stride_ints;
     hipStream_t st = s.st[0];
     const size_t row_bytes = stride_ints * 4;
     auto run = [&]() -> int {
@@ -414,10 +439,11 @@ int slot_lut2_block(Slot &s, int p, int n_tables, const int32_t *tv0, size_t n_f
     const size_t blk = hi - lo;
     if (!blk) return EOC_OK;
     HIP_TRY(hipSetDevice(s.device));
-    const size_t tv_ints = n_funcs * (size_t)(p / std::max(1, n_tables)) * EOC_N, need = tv_ints + (2 + n_funcs) * blk * stride_ints;
-    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    const size_t tv_ints = n_funcs * (size_t)(p / std::max(1, n_tables)) * EOC_N;
+    int32_t *d_tv, *d_x, *d_y, *d_out;
+    int rc = Staging().take(d_tv, tv_ints).take(d_x, blk * stride_ints)
+                 .take(d_y, blk * stride_ints).take(d_out, n_funcs * blk * stride_ints).commit(s);
     if (rc) return rc;
-    int32_t *d_tv = s.d_lut, *d_x = d_tv + tv_ints, *d_y = d_x + blk * stride_ints, *d_out = d_y + blk * stride_ints;
     hipStream_t st = s.st[0];
     const size_t row_bytes = stride_ints * 4;
     auto run = [&]() -> int {
@@ -441,10 +467,10 @@ int slot_int_block(Slot &s, const eoc_inode *nodes, size_t n_nodes, const int32_
     const size_t blk = hi - lo;
     if (!blk) return EOC_OK;
     HIP_TRY(hipSetDevice(s.device));
-    const size_t tv_ints = n_tv * EOC_N, need = tv_ints + n_wires * blk * stride_ints;
-    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    const size_t tv_ints = n_tv * EOC_N;
+    int32_t *d_tv, *d_wires;
+    int rc = Staging().take(d_tv, tv_ints).take(d_wires, n_wires * blk * stride_ints).commit(s);
     if (rc) return rc;
-    int32_t *d_tv = s.d_lut, *d_wires = d_tv + tv_ints;
     hipStream_t st = s.st[0];
     const size_t row_bytes = stride_ints * 4;
     auto run = [&]() -> int {
@@ -468,10 +494,10 @@ int slot_compact_block(Slot &s, const int32_t *lists, int32_t *out, size_t lo, s
     if (!blk) return EOC_OK;
     HIP_TRY(hipSetDevice(s.device));
     const size_t l0 = lo / EOC_N, l1 = (hi - 1) / EOC_N + 1;
-    const size_t list_ints = (l1 - l0) * 2 * EOC_N, need = list_ints + blk * stride_ints;
-    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    const size_t list_ints = (l1 - l0) * 2 * EOC_N;
+    int32_t *d_lists, *d_out;
+    int rc = Staging().take(d_lists, list_ints).take(d_out, blk * stride_ints).commit(s);
     if (rc) return rc;
-    int32_t *d_lists = s.d_lut, *d_out = d_lists + list_ints;
     hipStream_t st = s.st[0];
     auto run = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_lists, lists + l0 * 2 * EOC_N, list_ints * 4, hipMemcpyHostToDevice, st));
@@ -493,11 +519,11 @@ int slot_table_read_block(Slot &s, const int32_t *table, int log2_lists, int log
     HIP_TRY(hipSetDevice(s.device));
     const size_t depth = (size_t)log2_lists + 10 - log2_width, W = (size_t)1 << log2_width;
     const size_t tab_ints = ((size_t)2 * EOC_N) << log2_lists;
-    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth; // the converted form takes twice the ints
-    const size_t need = tab_ints + 3 * nsel * sel_ints + blk * W * stride_ints;
-    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth; // d_fft: the converted form takes twice the ints
+    int32_t *d_tab, *d_sel, *d_fft, *d_out;
+    int rc = Staging().take(d_tab, tab_ints).take(d_sel, nsel * sel_ints)
+                 .take(d_fft, 2 * nsel * sel_ints).take(d_out, blk * W * stride_ints).commit(s);
     if (rc) return rc;
-    int32_t *d_tab = s.d_lut, *d_sel = d_tab + tab_ints, *d_fft = d_sel + nsel * sel_ints, *d_out = d_fft + 2 * nsel * sel_ints;
     hipStream_t st = s.st[0];
     auto run = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_tab, table, tab_ints * 4, hipMemcpyHostToDevice, st));
@@ -525,11 +551,11 @@ int slot_table_update_block(Slot &s, int log2_lists, int log2_width, const int32
     HIP_TRY(hipSetDevice(s.device));
     const size_t depth = (size_t)log2_lists + 10 - log2_width, smp = (size_t)2 * EOC_N;
     const size_t tab_ints = smp << log2_lists;
-    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth; // the converted form takes twice the ints
-    const size_t need = tab_ints + 3 * nsel * sel_ints + blk * smp;
-    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, need);
+    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth; // d_fft: the converted form takes twice the ints
+    int32_t *d_tab, *d_sel, *d_fft, *d_vals;
+    int rc = Staging().take(d_tab, tab_ints).take(d_sel, nsel * sel_ints)
+                 .take(d_fft, 2 * nsel * sel_ints).take(d_vals, blk * smp).commit(s);
     if (rc) return rc;
-    int32_t *d_tab = s.d_lut, *d_sel = d_tab + tab_ints, *d_fft = d_sel + nsel * sel_ints, *d_vals = d_fft + 2 * nsel * sel_ints;
     hipStream_t st = s.st[0];
     auto run = [&]() -> int {
         HIP_TRY(hipMemsetAsync(d_tab, 0, tab_ints * 4, st));
@@ -555,9 +581,9 @@ int slot_pack_block(Slot &s, const int32_t *cts, size_t count, int32_t *lists, s
     HIP_TRY(hipSetDevice(s.device));
     const size_t s_lo = l_lo * EOC_N, blk = std::min(count, l_hi * EOC_N) - s_lo;
     const size_t in_ints = blk * stride_ints, out_ints = (l_hi - l_lo) * 2 * EOC_N;
-    int rc = slot_grow(s, &s.d_lut, 1, &s.cap_lut_ints, in_ints + out_ints);
+    int32_t *d_in, *d_out;
+    int rc = Staging().take(d_in, in_ints).take(d_out, out_ints).commit(s);
     if (rc) return rc;
-    int32_t *d_in = s.d_lut, *d_out = d_in + in_ints;
     hipStream_t st = s.st[0];
     auto run = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_in, cts + s_lo * stride_ints, in_ints * 4, hipMemcpyHostToDevice, st));
@@ -583,7 +609,6 @@ void destroy_slots_locked()
                 if (s.ev_as[r][k]) hipEventDestroy(s.ev_as[r][k]);
         }
         for (int k = 0; k < 4; k++) hipFree(s.d_io[k]);
-        hipFree(s.d_wires);
         hipFree(s.d_lut);
         for (int k = 0; k < 3; k++)
             if (s.st[k]) hipStreamDestroy(s.st[k]);
@@ -770,6 +795,19 @@ int drain_async_locked()
     }
     return rc;
 }
+// The entry of call `who` on the global context, under its G.mu lock: the engines are up (EOC_ERR_NO_DEVICE otherwise) and --
+// DRAINED, the last step in front of the call's work -- no asynchronous submission is pending (they share streams and the
+// engines' workspaces).  A call that checks arguments or returns early for an empty batch in between enters twice: up to
+// ENGINES first, up to DRAINED behind its checks.
+enum Entry { ENGINES, DRAINED };
+int enter_locked(const char *who, Entry upto = DRAINED)
+{
+    if (G.slots.empty()) {
+        eoc_set_error("%s: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback", who);
+        return EOC_ERR_NO_DEVICE;
+    }
+    return upto == DRAINED ? drain_async_locked() : EOC_OK;
+}
 
 int slot_async_reserve(Slot &s, size_t rows, size_t stride_ints)
 {
@@ -777,20 +815,7 @@ int slot_async_reserve(Slot &s, size_t rows, size_t stride_ints)
     for (int r = 0; r < 2; r++)
         for (int k = 0; k < 3; k++)
             if (!s.ev_as[r][k]) HIP_TRY(hipEventCreateWithFlags(&s.ev_as[r][k], hipEventDisableTiming));
-    if (rows <= s.cap_async) return EOC_OK;
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t cap = std::max<size_t>(rows, 1024);
-    for (int r = 0; r < 2; r++)
-        for (int k = 0; k < 4; k++) {
-            hipFree(s.d_as[r][k]);
-            s.d_as[r][k] = nullptr;
-        }
-    s.cap_async = 0;
-    for (int r = 0; r < 2; r++)
-        for (int k = 0; k < 4; k++) HIP_TRY(hipMalloc(&s.d_as[r][k], cap * stride_ints * 4));
-    s.cap_async = cap;
-    s.grows++;
-    return EOC_OK;
+    return slot_grow(s, &s.d_as[0][0], 8, &s.cap_async_ints, std::max<size_t>(rows, 1024) * stride_ints);
 }
 
 // queue one device's block of a submitted batch on buffer set r: operands by DMA on the H2D stream, kernels on the
@@ -802,30 +827,18 @@ int slot_async_block(Slot &s, int r, int op, const uint8_t *ops, const int32_t *
     if (rc) return rc;
     const int32_t *h[3] = {in0, in1, in2};
     const size_t bytes = count * stride_ints * 4;
-    auto fail = [&](int code) {
-        for (int k = 0; k < 3; k++) (void)hipStreamSynchronize(s.st[k]);
-        return code;
-    };
-#define AS_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t _e = (expr);                                                                              \
-        if (_e != hipSuccess) {                                                                              \
-            eoc_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);       \
-            return fail(EOC_ERR_HIP);                                                                        \
-        }                                                                                                    \
-    } while (0)
+    auto drain = [&](int code) { return drain_streams(s, code); };
     for (int k = 0; k < 3; k++)
-        if (h[k]) AS_TRY(hipMemcpyAsync(s.d_as[r][k], h[k], bytes, hipMemcpyHostToDevice, s.st[1]));
-    AS_TRY(hipEventRecord(s.ev_as[r][0], s.st[1]));
-    AS_TRY(hipStreamWaitEvent(s.st[0], s.ev_as[r][0], 0));
+        if (h[k]) HIP_TRY_ELSE(hipMemcpyAsync(s.d_as[r][k], h[k], bytes, hipMemcpyHostToDevice, s.st[1]), drain);
+    HIP_TRY_ELSE(hipEventRecord(s.ev_as[r][0], s.st[1]), drain);
+    HIP_TRY_ELSE(hipStreamWaitEvent(s.st[0], s.ev_as[r][0], 0), drain);
     rc = eoc_gate_batch_device(s.e, op, ops, h[0] ? s.d_as[r][0] : nullptr, h[1] ? s.d_as[r][1] : nullptr,
                                h[2] ? s.d_as[r][2] : nullptr, s.d_as[r][3], count, s.st[0]);
-    if (rc) return fail(rc);
-    AS_TRY(hipEventRecord(s.ev_as[r][1], s.st[0]));
-    AS_TRY(hipStreamWaitEvent(s.st[2], s.ev_as[r][1], 0));
-    AS_TRY(hipMemcpyAsync(out, s.d_as[r][3], bytes, hipMemcpyDeviceToHost, s.st[2]));
-    AS_TRY(hipEventRecord(s.ev_as[r][2], s.st[2]));
-#undef AS_TRY
+    if (rc) return drain(rc);
+    HIP_TRY_ELSE(hipEventRecord(s.ev_as[r][1], s.st[0]), drain);
+    HIP_TRY_ELSE(hipStreamWaitEvent(s.st[2], s.ev_as[r][1], 0), drain);
+    HIP_TRY_ELSE(hipMemcpyAsync(out, s.d_as[r][3], bytes, hipMemcpyDeviceToHost, s.st[2]), drain);
+    HIP_TRY_ELSE(hipEventRecord(s.ev_as[r][2], s.st[2]), drain);
     return EOC_OK;
 }
 
@@ -1176,20 +1189,14 @@ extern "C" int eoc_gate_batch(int op, const uint8_t *ops, const int32_t *in0, co
                               int32_t *out, size_t count)
 {
     std::lock_guard<std::mutex> g(G.mu); // calls on the global context are serialised, as in the reference (one global key)
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_gate_batch: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
+    if (int rc = enter_locked("eoc_gate_batch", ENGINES)) return rc;
     const bool const_only = !ops && (op == EOC_CONST0 || op == EOC_CONST1);
     if (!out || (!in0 && !const_only)) {
         eoc_set_error("eoc_gate_batch: null argument");
         return EOC_ERR_ARG;
     }
     if (!count) return EOC_OK;
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_gate_batch")) return rc;
     const size_t stride = (size_t)G.p.n + 1;
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
         return slot_gate_block(G.slots[i], op, ops ? ops + lo : nullptr, in0 ? in0 + lo * stride : nullptr,
@@ -1203,10 +1210,7 @@ static int lut_batch(const char *who, bool many, int p, int n_tables, const int3
                      size_t count)
 {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("%s: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback", who);
-        return EOC_ERR_NO_DEVICE;
-    }
+    if (int rc = enter_locked(who, ENGINES)) return rc;
     if (!tables || !in || !out || n_luts == 0) {
         eoc_set_error("%s: null argument or no table", who);
         return EOC_ERR_ARG;
@@ -1224,10 +1228,7 @@ static int lut_batch(const char *who, bool many, int p, int n_tables, const int3
         }
     }
     if (!count) return EOC_OK;
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked(who)) return rc;
     const size_t stride = (size_t)G.p.n + 1;
     const int32_t *tvp = tv.data();
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
@@ -1250,10 +1251,7 @@ int eoc_lut2_engines(int p, int n_tables, const int32_t *tables, size_t n_funcs,
                      size_t count)
 {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_lut2_batch: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
+    if (int rc = enter_locked("eoc_lut2_batch", ENGINES)) return rc;
     if (!tables || !x || !y || !out || n_funcs == 0) {
         eoc_set_error("eoc_lut2_batch: null argument or no function");
         return EOC_ERR_ARG;
@@ -1268,10 +1266,7 @@ int eoc_lut2_engines(int p, int n_tables, const int32_t *tables, size_t n_funcs,
             return EOC_ERR_ARG;
         }
     if (!count) return EOC_OK;
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_lut2_batch")) return rc;
     const size_t stride = (size_t)G.p.n + 1;
     const int32_t *tvp = tv.data();
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
@@ -1283,10 +1278,7 @@ extern "C" int eoc_int_circuit_run(const eoc_inode *nodes, size_t n_nodes, const
                                    const int32_t *table_T, size_t n_tv, int32_t *wires, size_t n_wires, size_t instances)
 try {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_int_circuit_run: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
+    if (int rc = enter_locked("eoc_int_circuit_run", ENGINES)) return rc;
     if (!wires || (!nodes && n_nodes) || (n_tv && (!tables || !table_p || !table_T))) {
         eoc_set_error("eoc_int_circuit_run: null argument");
         return EOC_ERR_ARG;
@@ -1314,10 +1306,7 @@ try {
             return EOC_ERR_ARG;
         }
     if (!n_nodes || !instances) return EOC_OK;
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_int_circuit_run")) return rc;
     const size_t stride = (size_t)G.p.n + 1;
     const int32_t *tvp = tv.data();
     return for_each_block(instances, [=](int i, size_t lo, size_t hi) {
@@ -1332,14 +1321,7 @@ try {
 int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out)
 {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_compact_expand: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_compact_expand")) return rc;
     const size_t stride = (size_t)G.p.n + 1;
     return for_each_block(count, [=](int i, size_t lo, size_t hi) {
         return slot_compact_block(G.slots[i], lists, out, lo, hi, stride);
@@ -1350,14 +1332,7 @@ int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out)
 int eoc_set_packing_key_engines(const void *blob, size_t len)
 {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_global_import_packing_key_blob: no GPU engine (eoc_gpu_init not called or failed)");
-        return EOC_ERR_NO_DEVICE;
-    }
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_global_import_packing_key_blob")) return rc;
     for (auto &s : G.slots) {
         int rc = eoc_engine_set_packing_key(s.e, blob, len);
         if (rc) return rc;
@@ -1369,17 +1344,11 @@ int eoc_set_packing_key_engines(const void *blob, size_t len)
 int eoc_pack_engines(const int32_t *cts, size_t count, int32_t *lists)
 {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_pack: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
+    if (int rc = enter_locked("eoc_pack", ENGINES)) return rc;
     if (!count) { // the engines still answer for a missing key
         return eoc_pack_device(G.slots[0].e, cts, 0, lists, nullptr);
     }
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_pack")) return rc;
     const size_t stride = (size_t)G.p.n + 1, n_lists = (count + EOC_N - 1) / EOC_N;
     return for_each_block(n_lists, [=](int i, size_t lo, size_t hi) {
         return slot_pack_block(G.slots[i], cts, count, lists, lo, hi, stride);
@@ -1391,14 +1360,7 @@ int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width,
                            int32_t *out)
 {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_table_read: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_table_read")) return rc;
     const size_t stride = (size_t)G.p.n + 1;
     return for_each_block(queries, [=](int i, size_t lo, size_t hi) {
         return slot_table_read_block(G.slots[i], table, log2_lists, log2_width, selectors, out, lo, hi, stride);
@@ -1410,14 +1372,7 @@ int eoc_table_update_engines(int32_t *table, int log2_lists, int log2_width, con
                              size_t queries)
 try {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_table_update: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_table_update")) return rc;
     const size_t tab_ints = ((size_t)2 * EOC_N) << log2_lists;
     std::vector<std::vector<int32_t>> deltas(G.slots.size());
     for (size_t i = 0; i < deltas.size(); i++) {
@@ -1441,16 +1396,10 @@ try {
 extern "C" int eoc_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires, size_t instances)
 {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_circuit_run: no GPU engine; there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
+    if (int rc = enter_locked("eoc_circuit_run", ENGINES)) return rc;
     if (!gates || !wires) return EOC_ERR_ARG;
     if (!n_gates || !instances) return EOC_OK;
-    {
-        int rc = drain_async_locked();
-        if (rc) return rc;
-    }
+    if (int rc = enter_locked("eoc_circuit_run")) return rc;
     const size_t stride = (size_t)G.p.n + 1;
     // a whole circuit instance stays on one device: no wire ever crosses GPUs
     return for_each_block(instances, [=](int i, size_t lo, size_t hi) {
@@ -1468,10 +1417,7 @@ extern "C" int eoc_gate_batch_submit(int op, const uint8_t *ops, const int32_t *
                                      int32_t *out, size_t count, uint64_t *ticket)
 {
     std::lock_guard<std::mutex> g(G.mu);
-    if (G.slots.empty()) {
-        eoc_set_error("eoc_gate_batch_submit: no GPU engine (eoc_gpu_init not called or failed); there is no CPU fallback");
-        return EOC_ERR_NO_DEVICE;
-    }
+    if (int rc = enter_locked("eoc_gate_batch_submit", ENGINES)) return rc;
     const bool const_only = !ops && (op == EOC_CONST0 || op == EOC_CONST1);
     if (!ticket || !out || (!in0 && !const_only)) {
         eoc_set_error("eoc_gate_batch_submit: null argument");
