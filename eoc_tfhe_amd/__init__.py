@@ -270,6 +270,11 @@ def lib():
         "eoc_table_update_device": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
         "eoc_engine_demux_launches": (u64, [vp]),
         "eoc_table_update": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, sz]),
+        # finite automata on encrypted bit strings
+        "eoc_automaton_step_device": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp]),
+        "eoc_automaton_run_device": (C.c_int, [vp, vp, sz, vp, vp, sz, vp, sz, C.c_int, vp, sz, vp]),
+        "eoc_engine_automaton_launches": (u64, [vp]),
+        "eoc_automaton_run": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, C.c_int, vp, sz]),
         # packing key switch: LWE samples -> compact lists
         "eoc_packing_key_blob_bytes": (sz, [PP]),
         "eoc_packing_key_export": (C.c_int, [vp, vp, sz]),
@@ -1038,6 +1043,31 @@ class Engine:
         _check(self.L.eoc_lut_enc_batch_device(self.h, d_lists, n_groups, 1 if per_row else 0, d_in, d_out, count, stream),
                "eoc_lut_enc_batch_device")
 
+    def automaton_step_device(self, trans, d_prev, prev_query_stride, d_sel_fft, sel_query_stride, d_next, queries, stream=None):
+        """One backward step of a public automaton for every state and query (eoc_automaton_step_device):
+        next[q] = A + C (x) (B - A), A = X^(-w0) prev[next0(q)], B = X^(-w1) prev[next1(q)].  trans: an Automaton or host
+        records [states][4] = (next0, w0, next1, w1); d_prev [states][2][N] per query, prev_query_stride TLWE samples between
+        the queries' vectors (0: one shared vector); the selector of query q lies sel_query_stride selectors behind query
+        q - 1's; d_next [queries][states][2][N].  Needs no key."""
+        t = _automaton_records(trans)
+        _check(self.L.eoc_automaton_step_device(self.h, t.ctypes.data, t.shape[0], d_prev, int(prev_query_stride), d_sel_fft,
+                                                int(sel_query_stride), d_next, queries, stream), "eoc_automaton_step_device")
+
+    def automaton_run_device(self, trans, d_final, d_sel_fft, steps, starts, log2_width, d_out, queries, stream=None):
+        """A public automaton over `queries` encrypted bit strings of `steps` bits (eoc_automaton_run_device):
+        d_final [states][2][N] (trivial_table or encrypted lists), d_sel_fft [queries][steps] converted selectors (bit 0 is
+        read first; None at steps = 0), starts: host state ids, d_out [queries][len(starts)][2^log2_width][n+1] ordinary
+        LWE samples.  No bootstrap: mean and variance of the error grow linearly in `steps` (noise.automaton_budget says how
+        far).  Only the key switch needs the cloud key."""
+        t = _automaton_records(trans)
+        st = np.ascontiguousarray(np.atleast_1d(starts), np.int32)
+        _check(self.L.eoc_automaton_run_device(self.h, t.ctypes.data, t.shape[0], d_final, d_sel_fft, int(steps), st.ctypes.data,
+                                               st.size, int(log2_width), d_out, queries, stream), "eoc_automaton_run_device")
+
+    def automaton_launches(self):
+        """k_automaton_step launches so far (eoc_engine_automaton_launches): `steps` per slice of a run's queries"""
+        return int(self.L.eoc_engine_automaton_launches(self.h))
+
     def tv_pack_device(self, p, d_vals, n_funcs, count, d_lists, stream=None):
         """LWE samples -> encrypted test polynomials (eoc_tv_pack_device): d_vals [n_funcs][p][count][n+1], d_lists
         [n_funcs][count][2][N]; list (f, s) holds values 0 .. p - 1 of row s by lut_test_polynomial's rule.  Needs the packing
@@ -1065,6 +1095,7 @@ class Engine:
                     ks_mfma_launches=int(self.L.eoc_engine_keyswitch_mfma_launches(self.h)),
                     cmux_launches=int(self.L.eoc_engine_cmux_launches(self.h)),
                     demux_launches=int(self.L.eoc_engine_demux_launches(self.h)),
+                    automaton_launches=int(self.L.eoc_engine_automaton_launches(self.h)),
                     pack_launches=int(self.L.eoc_engine_pack_launches(self.h)),
                     packed_samples=int(self.L.eoc_engine_packed_samples(self.h)))
 
@@ -1398,6 +1429,127 @@ def table_update(table, log2_lists, log2_width, selectors, values):
         sel_ptr = selectors.ctypes.data
     _check(lib().eoc_table_update(table.ctypes.data, d, lw, sel_ptr, values.ctypes.data, values.shape[0]), "eoc_table_update")
     return table
+
+
+def _automaton_records(trans):
+    """host records [states][4] int32 = (next0, w0, next1, w1) of an Automaton or of an array-like"""
+    t = np.ascontiguousarray(trans.trans if isinstance(trans, Automaton) else trans, np.int32)
+    if t.ndim != 2 or t.shape[1] != 4:
+        raise EocError(f"automaton: transitions must be [states][4] = (next0, w0, next1, w1), got {t.shape}")
+    return t
+
+
+class Automaton:
+    """A public deterministic (weighted) finite automaton over bits, in plain Python: state q goes to next0
+    with weight w0 under input bit 0 and to next1 with weight w1 under bit 1; weights live in [0, 2N) and add up modulo 2N
+    along a run.  `trans` [states][4] int32 = (next0, w0, next1, w1), `start` the start state, `accepting` the accepting
+    states of an acceptor (empty for a weighted automaton whose final vector is a table).  Bit 0 of an input is read first.
+    Evaluated on encrypted bits by Engine.automaton_run_device / automaton_run: no bootstrap, so the error's mean and
+    variance both grow linearly in the number of input bits (noise.automaton_budget)."""
+
+    def __init__(self, trans, start=0, accepting=()):
+        self.trans = np.ascontiguousarray(trans, np.int32).reshape(-1, 4)
+        self.start = int(start)
+        self.accepting = tuple(int(a) for a in accepting)
+        Q = self.states
+        t = self.trans
+        if not (1 <= Q <= 4096 and ((t[:, [0, 2]] >= 0) & (t[:, [0, 2]] < Q)).all() and ((t[:, [1, 3]] >= 0) & (t[:, [1, 3]] < 2 * N)).all()
+                and 0 <= self.start < Q and all(0 <= a < Q for a in self.accepting)):
+            raise EocError("Automaton: states in [1, 4096], successors and start inside the states, weights in [0, 2N)")
+
+    @property
+    def states(self):
+        return self.trans.shape[0]
+
+    def run_plain(self, bits, start=None):
+        """(end state, sum of the weights mod 2N) of the run over `bits`, bit 0 first"""
+        q, w = self.start if start is None else int(start), 0
+        for b in bits:
+            nxt, wt = self.trans[q, 2:] if int(b) else self.trans[q, :2]
+            q, w = int(nxt), (w + int(wt)) % (2 * N)
+        return q, w
+
+    def evaluate_plain(self, bits, final=None, start=None):
+        """what slot 0 of the encrypted run decodes to.  final None: 1 if the run ends in an accepting state, else 0.  final
+        given: a public table [states][<= N] of integers -- final[end state][sum of weights], negated past N (X^N = -1)."""
+        q, w = self.run_plain(bits, start)
+        if final is None:
+            return int(q in self.accepting)
+        v = int(np.asarray(final)[q][w % N])
+        return -v if w >= N else v
+
+    def final_bits(self):
+        """the acceptor's final vector in the clear: [states] of 0 / 1 (slot 0 of every state)"""
+        f = np.zeros(self.states, np.uint8)
+        f[list(self.accepting)] = 1
+        return f
+
+    @classmethod
+    def contains(cls, pattern_bits):
+        """accepts the strings that contain `pattern_bits` as a substring: the Knuth-Morris-Pratt automaton, len + 1 states,
+        the last one absorbing"""
+        pat = [int(b) & 1 for b in pattern_bits]
+        m = len(pat)
+        if m < 1:
+            raise EocError("Automaton.contains: empty pattern")
+        trans = np.zeros((m + 1, 4), np.int32)
+        for q in range(m):
+            for b in (0, 1):
+                s = pat[:q] + [b]
+                k = min(m, q + 1)
+                while k and s[len(s) - k:] != pat[:k]:
+                    k -= 1
+                trans[q, 2 * b] = k
+        trans[m, 0] = trans[m, 2] = m
+        return cls(trans, 0, (m,))
+
+    @classmethod
+    def divisible_by(cls, m):
+        """accepts the binary numbers divisible by m, MOST significant bit first: state = value so far mod m"""
+        m = int(m)
+        if m < 1:
+            raise EocError("Automaton.divisible_by: m >= 1")
+        trans = np.zeros((m, 4), np.int32)
+        for q in range(m):
+            trans[q, 0], trans[q, 2] = (2 * q) % m, (2 * q + 1) % m
+        return cls(trans, 0, (0,))
+
+    @classmethod
+    def popcount(cls):
+        """one state, weight 0 under bit 0 and 1 under bit 1: the run's weight is the number of set bits, and a final vector
+        holding a table f in its slots turns slot 0 into f(count) (evaluate_plain(bits, final=[f]))"""
+        return cls([[0, 0, 0, 1]], 0, ())
+
+
+def automaton_run(trans, final, selectors, starts, log2_width=0):
+    """eoc_automaton_run on the global context (a cloud key alone suffices): trans an Automaton or records [states][4], final
+    [states][2][N] TLWE samples (trivial_table or PublicKey.encrypt_*), selectors [queries][steps][2l][2][N] in torus form
+    (SecretKey.encrypt_selector_bits per query; bit 0 is read first), starts: state ids -> [queries][len(starts)]
+    [2^log2_width][n+1] LWE samples.  No bootstrap: the error's mean and variance grow linearly in the number of steps
+    (noise.automaton_budget)."""
+    t = _automaton_records(trans)
+    final = np.ascontiguousarray(final, np.int32)
+    lw = int(log2_width)
+    if final.ndim != 3 or final.shape != (t.shape[0], 2, N):
+        raise EocError(f"automaton_run: final must be [{t.shape[0]}][2][{N}], got {final.shape}")
+    if not 0 <= lw <= 10:
+        raise EocError(f"automaton_run: log2_width = {lw} outside [0, 10]")
+    selectors = np.ascontiguousarray(selectors, np.int32)
+    if selectors.ndim != 5 or selectors.shape[3:] != (2, N):
+        raise EocError(f"automaton_run: selectors must be [queries][steps][2l][2][{N}], got {selectors.shape}")
+    st = np.ascontiguousarray(np.atleast_1d(starts), np.int32)
+    queries, steps = selectors.shape[:2]
+    if lib().eoc_global_key_mode():
+        n = global_params().n
+    else:
+        e0 = lib().eoc_global_engine()
+        if not e0:
+            raise EocError("automaton_run: no key and no GPU engine on the global context")
+        n = lib().eoc_engine_params(e0).contents.n
+    out = np.empty((queries, st.size, 1 << lw, n + 1), np.int32)
+    _check(lib().eoc_automaton_run(t.ctypes.data, t.shape[0], final.ctypes.data, selectors.ctypes.data if steps else None, steps,
+                                   st.ctypes.data, st.size, lw, out.ctypes.data, queries), "eoc_automaton_run")
+    return out
 
 
 def pack(cts):

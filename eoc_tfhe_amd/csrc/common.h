@@ -32,6 +32,15 @@ int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width,
 // one zeroed delta table per engine, added into `table` on the host
 int eoc_table_update_engines(int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
                              size_t queries);
+// finite automata: the host-side validation every automaton call runs before anything touches a device
+// (engine.hip): trans [states][4] = {next0, w0, next1, w1}, starts [n_starts] (may be NULL with n_starts = 0).  EOC_ERR_ARG, with
+// the message under the caller's name `who`, for states outside [1, 4096], a successor outside [0, states), a weight outside
+// [0, 2N) or a start state outside [0, states)
+int eoc_automaton_check(const char *who, const int32_t *trans, size_t states, const int32_t *starts, size_t n_starts);
+// eoc_automaton_run's GPU half on the process-global engines (multi.hip): queries cut into eoc_shard_range blocks,
+// one per engine; every engine receives the final vector and converts its own selectors
+int eoc_automaton_run_engines(const int32_t *trans, size_t states, const int32_t *final_vec, const int32_t *selectors, size_t steps,
+                              const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t queries);
 // packing key switch: a whole EOCPKS1 blob with t = 4, basebit = 4 -> its parameters and the rows [n][4][2][N]
 // in torus form (a pointer into the blob); false for anything else (legacy.cpp)
 struct eoc_params;

@@ -111,6 +111,7 @@ struct eoc_engine {
     size_t table_ws_bytes = (size_t)256 << 20;
     uint64_t cmux_launches = 0; // k_cmux launches
     uint64_t demux_launches = 0; // k_demux launches
+    uint64_t automaton_launches = 0; // k_automaton_step launches
     // packing key switch: the packing key's image [n][4][2][512] complex scaled by 2^-9 (the engine's own),
     // the gathered mask columns [lists of a slice][n][N], and the byte budget that buffer is held to (lists are sliced to
     // fit; EOC_TFHE_PACK_WS_BYTES, diagnostics)
@@ -254,6 +255,7 @@ static int upload_tables(eoc_engine *e)
 }
 
 static void set_demux_attrs();
+static void set_automaton_attrs();
 extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **out)
 {
     if (!out || !valid_params(p)) {
@@ -316,6 +318,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
 #undef EOC_CMUX_ATTR
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
     set_demux_attrs(); // k_demux, k_cmux's LDS plan (defined behind every other kernel's first use: DESIGN.md 15)
+    set_automaton_attrs(); // k_automaton_step, the same plan, behind k_demux and the seeded kernels
     (void)hipGetLastError();
     *out = e;
     return EOC_OK;
@@ -2544,3 +2547,237 @@ extern "C" int eoc_dbg_chacha20_blocks_device(eoc_engine *e, const uint8_t key[3
     HIP_TRY(hipGetLastError());
     return EOC_OK;
 }
+
+// ---- finite automata on encrypted bit strings: leveled CMux steps -------------
+// The kernel of this section is a template first named here, behind every other kernel of the file (as k_demux was): the
+// earlier ones keep their text instruction for instruction.
+static const void *automaton_kernel(int l, int bg)
+{
+    const void *fn = nullptr;
+#define EOC_AUTO(L, B) EOC_IF_SHAPE(L, B, l, bg) fn = reinterpret_cast<const void *>(&k_automaton_step<L, B>);
+    EOC_PAIR_SHAPES(EOC_AUTO)
+#undef EOC_AUTO
+    return fn;
+}
+
+static void set_automaton_attrs()
+{
+#define EOC_AUTO_ATTR(L, B) (void)hipFuncSetAttribute(automaton_kernel(L, B), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
+    EOC_PAIR_SHAPES(EOC_AUTO_ATTR)
+#undef EOC_AUTO_ATTR
+}
+
+constexpr size_t kAutoMaxStates = 4096;
+
+// The public part of a call, checked on the host before anything touches a device: the kernel gathers through these records,
+// so it never sees an index that did not pass here.  trans [states][4] = {next0, w0, next1, w1}; starts may be NULL (a step).
+int eoc_automaton_check(const char *who, const int32_t *trans, size_t states, const int32_t *starts, size_t n_starts)
+{
+    if (!trans || states < 1 || states > kAutoMaxStates) {
+        eoc_set_error("%s: no transition table, or %zu states outside [1, %zu]", who, states, kAutoMaxStates);
+        return EOC_ERR_ARG;
+    }
+    for (size_t q = 0; q < states; q++) {
+        const int32_t *t = trans + 4 * q;
+        if (t[0] < 0 || (size_t)t[0] >= states || t[2] < 0 || (size_t)t[2] >= states || t[1] < 0 || t[1] >= 2 * kN || t[3] < 0 ||
+            t[3] >= 2 * kN) {
+            eoc_set_error("%s: state %zu has transitions (%d, %d) / (%d, %d): successors must lie in [0, %zu), weights in [0, %d)",
+                          who, q, t[0], t[1], t[2], t[3], states, 2 * kN);
+            return EOC_ERR_ARG;
+        }
+    }
+    for (size_t i = 0; i < n_starts; i++)
+        if (starts[i] < 0 || (size_t)starts[i] >= states) {
+            eoc_set_error("%s: start state %d (position %zu) outside [0, %zu)", who, starts[i], i, states);
+            return EOC_ERR_ARG;
+        }
+    return EOC_OK;
+}
+
+// transition records travel in the descriptor ring (same pinned copy, same wrap rules, the arena under capture)
+static size_t auto_trans_slots(size_t records) { return (records * sizeof(AutoTrans) + sizeof(GateDesc) - 1) / sizeof(GateDesc); }
+static int push_auto_trans(WS &W, const std::vector<AutoTrans> &recs, hipStream_t st, const AutoTrans **d_out)
+{
+    std::vector<GateDesc> slots(auto_trans_slots(recs.size()), GateDesc{});
+    memcpy(static_cast<void *>(slots.data()), recs.data(), recs.size() * sizeof(AutoTrans));
+    GateDesc *dd = nullptr;
+    int rc = push_descs(W, slots.data(), slots.size(), st, &dd);
+    *d_out = reinterpret_cast<const AutoTrans *>(dd);
+    return rc;
+}
+
+static int launch_automaton_step(eoc_engine *e, const AutoStepArgs &a, uint32_t ny, hipStream_t st)
+{
+    const void *fn = automaton_kernel(e->p.l, e->p.Bgbit);
+    if (!fn) {
+        eoc_set_error("k_automaton_step: no kernel for gadget length %d", e->p.l);
+        return EOC_ERR_STATE;
+    }
+    AutoStepArgs args = a;
+    args.Bgbit = e->p.Bgbit;
+    const d2 *tw = e->d_tw, *twist = e->d_twist;
+    void *kargs[] = {&args, &tw, &twist};
+    SpanGuard span(e, st, KIND_BLIND_ROTATE);
+    HIP_TRY(hipLaunchKernel(fn, dim3((a.nx + kCmuxItemsPerWG - 1) / kCmuxItemsPerWG, ny), dim3(128 * kCmuxItemsPerWG), kargs,
+                            kCmuxLds, st));
+    e->automaton_launches++;
+    return EOC_OK;
+}
+
+extern "C" int eoc_automaton_step_device(eoc_engine *e, const int32_t *trans, size_t states, const int32_t *d_prev,
+                                         size_t prev_query_stride, const void *d_sel_fft, size_t sel_query_stride, int32_t *d_next,
+                                         size_t queries, void *hip_stream)
+try {
+    // the public part first: a malformed automaton is refused whatever else is wrong, and before any device is touched
+    int rc = eoc_automaton_check("eoc_automaton_step_device", trans, states, nullptr, 0);
+    if (rc) return rc;
+    if (!e || !d_prev || !d_sel_fft || !d_next || (prev_query_stride && prev_query_stride < states)) {
+        eoc_set_error("eoc_automaton_step_device: null argument, or a query stride of %zu samples below the %zu states",
+                      prev_query_stride, states);
+        return EOC_ERR_ARG;
+    }
+    if (!queries) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    WS &Wk = e->ws;
+    if ((rc = ensure_ws(e, Wk, 0, auto_trans_slots(states), 0, st))) return rc;
+    std::vector<AutoTrans> recs(states);
+    memcpy(static_cast<void *>(recs.data()), trans, states * sizeof(AutoTrans));
+    const AutoTrans *d_tr = nullptr;
+    if ((rc = push_auto_trans(Wk, recs, st, &d_tr))) return rc;
+    const size_t sel = (size_t)e->kpl * 2 * kNH, smp = (size_t)2 * kN;
+    constexpr size_t kSlice = 32768; // queries per launch (grid y)
+    for (size_t q0 = 0; q0 < queries; q0 += kSlice) {
+        AutoStepArgs a{};
+        a.sel = static_cast<const d2 *>(d_sel_fft) + q0 * sel_query_stride * sel;
+        a.sel_y = sel_query_stride * sel;
+        a.trans = d_tr;
+        a.prev = d_prev + q0 * prev_query_stride * smp;
+        a.prev_y = prev_query_stride * smp;
+        a.next = d_next + q0 * states * smp;
+        a.next_y = states * smp;
+        a.nx = (uint32_t)states;
+        if ((rc = launch_automaton_step(e, a, (uint32_t)std::min(kSlice, queries - q0), st))) return rc;
+    }
+    ring_mark(Wk, st);
+    return EOC_OK;
+} catch (...) {
+    eoc_set_error("eoc_automaton_step_device: out of memory");
+    return EOC_ERR_ALLOC;
+}
+
+// V_steps = F, V_t = step under bit t of V_(t+1), t = steps - 1 .. 0, through the table read's two buffers; the LAST launch
+// (t = 0) runs over the start states alone -- its records are trans[starts[i]] -- and leaves [queries][n_starts] samples, which
+// k_tlwe_extract and the key switch take as a table read's.  steps = 0: nothing depends on a query; the start states' samples
+// of F are extracted and key-switched once and the block is copied to the other queries (doubling: log2(queries) copies).
+extern "C" int eoc_automaton_run_device(eoc_engine *e, const int32_t *trans, size_t states, const int32_t *d_final,
+                                        const void *d_sel_fft, size_t steps, const int32_t *starts, size_t n_starts, int log2_width,
+                                        int32_t *d_out, size_t queries, void *hip_stream)
+try {
+    // the public part first: a malformed automaton is refused whatever else is wrong, and before any device is touched
+    if (!starts || log2_width < 0 || log2_width > 10 || n_starts < 1 || n_starts > kAutoMaxStates) {
+        eoc_set_error("eoc_automaton_run_device: no start states, log2_width = %d outside [0, 10] or %zu start states outside "
+                      "[1, %zu]", log2_width, n_starts, kAutoMaxStates);
+        return EOC_ERR_ARG;
+    }
+    int rc = eoc_automaton_check("eoc_automaton_run_device", trans, states, starts, n_starts);
+    if (rc) return rc;
+    if (!e || !d_final || !d_out || (steps && !d_sel_fft)) {
+        eoc_set_error("eoc_automaton_run_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    const size_t W = (size_t)1 << log2_width, smp = (size_t)2 * kN, sel = (size_t)e->kpl * 2 * kNH;
+    const size_t vec = std::max(states, n_starts); // samples per query in either buffer
+    const size_t per_query = 2 * vec * smp * sizeof(int32_t);
+    if (steps && e->table_ws_bytes < per_query) {
+        eoc_set_error("eoc_automaton_run_device: one query over %zu states needs %zu bytes of workspace, the budget "
+                      "(EOC_TFHE_TABLE_WS_BYTES) is %zu", states, per_query, e->table_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    // queries per slice: grid y of the step and of the extraction, the byte budget, 2^20 extracted samples (the read's rule)
+    size_t qs = std::min({queries, (size_t)32768, (size_t)65535 / n_starts, std::max<size_t>(1, ((size_t)1 << 20) / (n_starts * W))});
+    if (steps) qs = std::min(qs, e->table_ws_bytes / per_query);
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->ksk) {
+        eoc_set_error("eoc_automaton_run_device: no key-switch key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    if (!queries) return EOC_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    WS &Wk = e->ws;
+    const size_t stride = (size_t)e->p.n + 1;
+    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    const unsigned ext_x = (unsigned)((W + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
+    if (!steps) {
+        const size_t cs = std::max<size_t>(1, ((size_t)1 << 20) / W); // start states per key switch
+        if ((rc = ensure_ws(e, Wk, std::min(cs, n_starts) * W, 0, 0, st))) return rc;
+        for (size_t i0 = 0; i0 < n_starts; i0 += cs) {
+            const size_t C = std::min(cs, n_starts - i0);
+            int32_t *o = d_out + i0 * W * stride;
+            {
+                SpanGuard span(e, st, KIND_PREPARE);
+                for (size_t i = 0; i < C; i++)
+                    hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, 1), dim3(256), 0, st, d_final + (size_t)starts[i0 + i] * smp,
+                                       (size_t)0, (uint32_t)W, Wk.d_ubar + i * W * kN, o + i * W * stride, e->p.n, prec_offset);
+                HIP_TRY(hipGetLastError());
+            }
+            const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
+            if ((rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(C * W), st, true, &gd))) return rc;
+            e->stats[2] += C * W;
+        }
+        const size_t block = n_starts * W * stride;
+        for (size_t have = 1; have < queries; have *= 2) {
+            const size_t cnt = std::min(have, queries - have);
+            HIP_TRY(hipMemcpyAsync(d_out + have * block, d_out, cnt * block * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        }
+        return EOC_OK;
+    }
+    rc = ensure_ws(e, Wk, qs * n_starts * W, auto_trans_slots(states + n_starts), 0, st);
+    for (int b = 0; b < 2 && !rc; b++)
+        rc = scratch_reserve(e, e->cmux[b], qs * vec * smp * sizeof(int32_t), b ? "automaton state vector 1" : "automaton state vector 0", st);
+    if (rc) return rc;
+    std::vector<AutoTrans> recs(states + n_starts);
+    memcpy(static_cast<void *>(recs.data()), trans, states * sizeof(AutoTrans));
+    for (size_t i = 0; i < n_starts; i++) recs[states + i] = recs[(size_t)starts[i]];
+    const AutoTrans *d_tr = nullptr;
+    if ((rc = push_auto_trans(Wk, recs, st, &d_tr))) return rc;
+    for (size_t q0 = 0; q0 < queries; q0 += qs) {
+        const size_t Q = std::min(qs, queries - q0);
+        const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * steps * sel;
+        const int32_t *cur = d_final; // the state vectors the next launch reads: cur_y ints between the queries' (0: shared)
+        size_t cur_y = 0;
+        for (size_t k = 0; k < steps; k++) {
+            const bool last = k + 1 == steps;
+            AutoStepArgs a{};
+            a.sel = selq + (steps - 1 - k) * sel;
+            a.sel_y = steps * sel;
+            a.trans = last ? d_tr + states : d_tr;
+            a.nx = (uint32_t)(last ? n_starts : states);
+            a.prev = cur;
+            a.prev_y = cur_y;
+            a.next = e->cmux[k & 1].i32();
+            a.next_y = (size_t)a.nx * smp;
+            if ((rc = launch_automaton_step(e, a, (uint32_t)Q, st))) return rc;
+            cur = a.next;
+            cur_y = a.next_y;
+        }
+        int32_t *o = d_out + q0 * n_starts * W * stride;
+        {
+            SpanGuard span(e, st, KIND_PREPARE);
+            hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, (unsigned)(Q * n_starts)), dim3(256), 0, st, cur, smp, (uint32_t)W,
+                               Wk.d_ubar, o, e->p.n, prec_offset);
+            HIP_TRY(hipGetLastError());
+        }
+        const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
+        if ((rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(Q * n_starts * W), st, true, &gd))) return rc;
+        e->stats[2] += Q * n_starts * W;
+    }
+    ring_mark(Wk, st);
+    return EOC_OK;
+} catch (...) {
+    eoc_set_error("eoc_automaton_run_device: out of memory");
+    return EOC_ERR_ALLOC;
+}
+extern "C" uint64_t eoc_engine_automaton_launches(eoc_engine *e) { return e ? e->automaton_launches : 0; }

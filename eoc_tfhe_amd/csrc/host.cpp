@@ -1541,6 +1541,27 @@ extern "C" int eoc_table_update(int32_t *table, int log2_lists, int log2_width, 
     }
     return eoc_table_update_engines(table, log2_lists, log2_width, selectors, values, queries);
 }
+// an automaton run on the global context's engines: the automaton is checked before a key or a device is
+// looked for; the engines come up behind the global key as for the read (a cloud key alone suffices)
+extern "C" int eoc_automaton_run(const int32_t *trans, size_t states, const int32_t *final_vec, const int32_t *selectors,
+                                 size_t steps, const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t queries)
+{
+    if (!final_vec || !out || !starts || (steps && !selectors) || log2_width < 0 || log2_width > 10 || n_starts < 1 ||
+        n_starts > 4096) {
+        eoc_set_error("eoc_automaton_run: null argument, log2_width = %d outside [0, 10] or %zu start states outside [1, 4096]",
+                      log2_width, n_starts);
+        return EOC_ERR_ARG;
+    }
+    if (int rc = eoc_automaton_check("eoc_automaton_run", trans, states, starts, n_starts)) return rc;
+    if (!queries) return EOC_OK;
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) {
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    }
+    return eoc_automaton_run_engines(trans, states, final_vec, selectors, steps, starts, n_starts, log2_width, out, queries);
+}
 extern "C" int eoc_global_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires,
                                       size_t instances)
 {

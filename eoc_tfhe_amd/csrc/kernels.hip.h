@@ -2169,4 +2169,108 @@ __global__ __launch_bounds__(256) void k_chacha20_blocks(SeedArgs A, uint64_t co
         o[k] = make_uint4(x[4 * k] + s[4 * k], x[4 * k + 1] + s[4 * k + 1], x[4 * k + 2] + s[4 * k + 2], x[4 * k + 3] + s[4 * k + 3]);
 }
 
+// =================================================================================================
+// Finite automata on encrypted bit strings: one backward step over all states.
+//   next[q] = A + C (x) (B - A),  A = X^(-w0(q)) prev[next0(q)],  B = X^(-w1(q)) prev[next1(q)]
+// prev, next: state vectors [states][2][N] of TLWE samples per query; C: the query's converted selector of this step's input
+// bit (one per query, shared by its states); the transition record {next0, w0, next1, w1} of state q is public, validated on
+// the host (next in [0, states), w in [0, 2N)) and read once per wave pair through a uniform address.  The external product
+// is k_cmux's -- the same text (ext_product_pair.inc) --, so a step equals the CMux of the two rotated successors bit for bit
+// by construction.  The mapping, the LDS plan and the dead pair's rule are k_cmux's; BOTH operands are gathered and rotated by
+// index arithmetic on their loads (coefficient j of X^(-w) P is P[(j + w) mod 2N], negated in the upper half of the period),
+// lane-contiguous up to the one wrap; A is not held across the product but reloaded at store time, as k_cmux reloads in0.
+// prev_y = 0 reads one shared vector for every query (the first step reads the final vector in place).  next may not
+// overlap prev: a state may be its own successor, so the driver alternates two buffers.
+// grid: x = ceil(nx / kCmuxItemsPerWG) states, y = queries.  Templates defined and first used behind every other kernel, as
+// k_demux: the earlier kernels keep their text.
+// =================================================================================================
+struct AutoTrans {
+    int32_t next0, w0, next1, w1; // successor and weight under bit 0 / bit 1
+};
+static_assert(sizeof(AutoTrans) == 16, "one 16-byte record per state");
+
+struct AutoStepArgs {
+    const d2 *sel;          // converted selectors, one per query
+    const AutoTrans *trans; // [nx] records, validated by the host
+    const int32_t *prev;    // [states][2][N] per query
+    int32_t *next;          // [nx][2][N] per query
+    size_t sel_y;           // strides per query, in d2 ...
+    size_t prev_y, next_y;  // ... and in int32 (prev_y = 0: one vector for all queries)
+    uint32_t nx;            // states along x
+    int Bgbit;
+};
+
+template <int L, int BGBIT = 0>
+__global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_automaton_step(AutoStepArgs A, const d2 *__restrict__ g_tw,
+                                                                              const d2 *__restrict__ g_twist)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    d2 *s_tw = reinterpret_cast<d2 *>(smem);
+    d2 *s_twist = s_tw + kTwEntries;
+    d2 *s_scr_all = s_twist + kNH;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = wv & 1;
+    d2 *scr = s_scr_all + wv * kScr;
+    d2 *scr_partner = s_scr_all + (wv ^ 1) * kScr;
+    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128 * kCmuxItemsPerWG);
+
+    const uint32_t x_raw = blockIdx.x * kCmuxItemsPerWG + (uint32_t)(wv >> 1);
+    const bool live = x_raw < A.nx;
+    const size_t ix = live ? x_raw : A.nx - 1, iy = blockIdx.y;
+    const AutoTrans tr = A.trans[ix]; // uniform: one record per wave pair
+    const int32_t *pv = A.prev + iy * A.prev_y + (size_t)h * kN;
+    const int32_t *pa = pv + (size_t)tr.next0 * (2 * kN);
+    const int32_t *pb = pv + (size_t)tr.next1 * (2 * kN);
+    const int w0 = tr.w0 & (2 * kN - 1), w1 = tr.w1 & (2 * kN - 1);
+    const d2 *sel = A.sel + iy * A.sel_y;
+
+    const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
+    uint32_t offset = 0;
+#pragma unroll
+    for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
+    const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
+
+    // offset + (X^(-w1) B_h - X^(-w0) A_h): coefficient lane + 64 r in dlo[r], lane + 64 r + 512 in dhi[r]
+    uint32_t dlo[8], dhi[8];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
+        const int ia = (j + w0) & (2 * kN - 1), ib = (j + w1) & (2 * kN - 1);
+        const uint32_t a = (uint32_t)pa[ia & (kN - 1)], b = (uint32_t)pb[ib & (kN - 1)];
+        const uint32_t v = offset + ((ib & kN) ? 0u - b : b) - ((ia & kN) ? 0u - a : a);
+        if (r < 8) dlo[r] = v;
+        else dhi[r - 8] = v;
+    }
+    __syncthreads(); // the tables
+
+    auto load_row = [&](int p, int c, d2 (&b)[8]) __attribute__((always_inline)) {
+        const d2 *row = sel + ((size_t)(h * L + (p - 1)) * 2 + c) * kNH + lane;
+#pragma unroll
+        for (int r = 0; r < 8; r++) b[r] = row[r * 64];
+    };
+    d2 S[8], ut[8];
+    {
+        const d2 (*const xp_t2)[4] = nullptr, (*const xp_t1)[4] = nullptr; // tables from LDS, as k_cmux
+#define EOC_XP_STAMP(k) do { } while (0)
+#include "ext_product_pair.inc"
+#undef EOC_XP_STAMP
+    }
+    if (!live) return;
+    int32_t *po = A.next + ix * (size_t)(2 * kN) + iy * A.next_y + (size_t)h * kN;
+    // the gather indices are formed again from a value the compiler cannot match with the load phase's: carried across the
+    // product, those sixteen registers are what spills <3,7>
+    int w0s = w0;
+    asm volatile("" : "+s"(w0s));
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int j = lane + 64 * r;
+        const d2 y = cmulc(S[r], ut[r]); // 1/512 is in the selector's image
+        const int i0 = (j + w0s) & (2 * kN - 1), i1 = (j + kNH + w0s) & (2 * kN - 1);
+        const uint32_t a0 = (uint32_t)pa[i0 & (kN - 1)], a1 = (uint32_t)pa[i1 & (kN - 1)];
+        po[j] = (int32_t)(((i0 & kN) ? 0u - a0 : a0) + wrap_trunc(y.x));
+        po[j + kNH] = (int32_t)(((i1 & kN) ? 0u - a1 : a1) + wrap_trunc(y.y));
+    }
+}
+
 } // namespace eoc

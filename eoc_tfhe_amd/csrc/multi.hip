@@ -540,6 +540,38 @@ int slot_table_read_block(Slot &s, const int32_t *table, int log2_lists, int log
     return slot_finish(st, run());
 }
 
+// one device's block [lo, hi) of the queries of an automaton run: the final vector and the block's selectors in
+// torus form in, converted on the device, out [queries][n_starts][W][stride] on the host
+int slot_automaton_block(Slot &s, const int32_t *trans, size_t states, const int32_t *final_vec, const int32_t *selectors,
+                         size_t steps, const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t lo, size_t hi,
+                         size_t stride_ints)
+{
+    const size_t blk = hi - lo;
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t fin_ints = states * 2 * EOC_N, out_ints = n_starts * ((size_t)1 << log2_width) * stride_ints;
+    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * steps; // d_fft: the converted form takes twice the ints
+    int32_t *d_fin, *d_sel, *d_fft, *d_out;
+    int rc = Staging().take(d_fin, fin_ints).take(d_sel, nsel * sel_ints)
+                 .take(d_fft, 2 * nsel * sel_ints).take(d_out, blk * out_ints).commit(s);
+    if (rc) return rc;
+    hipStream_t st = s.st[0];
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_fin, final_vec, fin_ints * 4, hipMemcpyHostToDevice, st));
+        if (nsel) {
+            HIP_TRY(hipMemcpyAsync(d_sel, selectors + lo * steps * sel_ints, nsel * sel_ints * 4, hipMemcpyHostToDevice, st));
+            int r = eoc_tgsw_to_fft_device(s.e, d_sel, nsel, d_fft, st);
+            if (r) return r;
+        }
+        int r = eoc_automaton_run_device(s.e, trans, states, d_fin, nsel ? d_fft : nullptr, steps, starts, n_starts, log2_width,
+                                         d_out, blk, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(out + lo * out_ints, d_out, blk * out_ints * 4, hipMemcpyDeviceToHost, st));
+        return EOC_OK;
+    };
+    return slot_finish(st, run());
+}
+
 // one device's block [lo, hi) of the queries of an encrypted-index table update: the block's selectors (torus
 // form, converted on the device) and values in; the block is accumulated into a zeroed table on the device, which comes back
 // as `delta` [2^d][2][N] for the host to add
@@ -1364,6 +1396,20 @@ int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width,
     const size_t stride = (size_t)G.p.n + 1;
     return for_each_block(queries, [=](int i, size_t lo, size_t hi) {
         return slot_table_read_block(G.slots[i], table, log2_lists, log2_width, selectors, out, lo, hi, stride);
+    });
+}
+
+// eoc_automaton_run's engine half (host.cpp has checked the pointers, holds the global key's lock and has brought the engines
+// up; the automaton itself is validated by every engine's call before it touches its device)
+int eoc_automaton_run_engines(const int32_t *trans, size_t states, const int32_t *final_vec, const int32_t *selectors, size_t steps,
+                              const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t queries)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (int rc = enter_locked("eoc_automaton_run")) return rc;
+    const size_t stride = (size_t)G.p.n + 1;
+    return for_each_block(queries, [=](int i, size_t lo, size_t hi) {
+        return slot_automaton_block(G.slots[i], trans, states, final_vec, selectors, steps, starts, n_starts, log2_width, out, lo,
+                                    hi, stride);
     });
 }
 

@@ -502,6 +502,53 @@ def table_update_budget(params, lwe_key, tlwe_key, p, log2_lists, log2_width, si
     return lo
 
 
+# ---- finite automata on encrypted bit strings: a chain of CMux steps ----------------------------------------------
+# A run is `steps` CMuxes in a row on the path the input selects, V_t[q] = A + C_t (x) (B - A) with A, B rotated successors and
+# no bootstrap in between: every step adds its own error to what it selects, so BOTH the variance and the mean of the output's
+# error grow linearly in the number of steps.  A rotation X^(-w) permutes the coefficients of an error polynomial and negates
+# those that wrap: variances are unchanged, and a mean polynomial keeps its entries' magnitudes at other slots.
+def automaton_var(params, tlwe_key, bits, final_var=0.0):
+    """variance (torus units) of every coefficient of the output of an automaton run (eoc_automaton_run_device) over the input
+    `bits`, before the key switch, around its mean: final_var (0 for a trivial final vector, compact_var for a public-key-
+    encrypted one) + the sum of cmux_var(bit) over the steps.  Linear in the number of steps, as the mean is
+    (automaton_mean_bound): nothing refreshes the sample between steps."""
+    return float(final_var) + float(sum(cmux_var(params, tlwe_key, int(b) & 1) for b in bits))
+
+
+def automaton_mean_bound(params, tlwe_key, steps):
+    """bound on |mean error| (torus units) of any slot of a run of `steps` steps, before the key switch: steps (q/2)(1 + |s'|).
+    One step whose bit is 1 leaves cmux_mean, a polynomial whose entries are at most (q/2)(1 + |s'|) in magnitude; the later
+    steps' rotations permute and negate its entries, so the per-step bound holds at whatever slot is read.  Linear in the
+    number of steps, as the variance is (automaton_var)."""
+    q = 2.0 ** (-int(params.l) * int(params.Bgbit))
+    hw = int(np.asarray(tlwe_key, np.int64).sum())
+    return int(steps) * (q / 2) * (1 + hw)
+
+
+def automaton_budget(params, lwe_key, tlwe_key, p, sigmas=6.0, final_var=0.0, ksk=None):
+    """how many steps (input bits) a run tolerates before its key-switched output no longer decodes with margin on the message
+    space p (p = 2: a boolean at +-1/8): the largest number of steps with
+        automaton_mean_bound(steps) + |ks_mean| + sigmas sqrt(automaton_var(all-ones, steps) + ks_var) <= 1 / (4p)
+    Mean and variance both grow linearly in the steps; on the default sets the mean term is the one that binds.  0 if not even
+    the key switch alone fits.  Computed from the model (`predict`, cmux_var); nothing fitted."""
+    pr = predict(params, lwe_key, tlwe_key, ksk)
+    v1 = cmux_var(params, tlwe_key, 1)
+    margin = 1.0 / (4 * int(p))
+
+    def fits(s):
+        return (automaton_mean_bound(params, tlwe_key, s) + abs(pr["ks_mean"])
+                + float(sigmas) * np.sqrt(float(final_var) + s * v1 + pr["ks_var"]) <= margin)
+    if not fits(0):
+        return 0
+    lo, hi = 0, 1
+    while fits(hi) and hi < 1 << 40:
+        lo, hi = hi, hi * 2
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+    return lo
+
+
 # ---- packing key switch: LWE samples into compact lists (DESIGN.md 13) ----------------------------------------------------------
 PACK_T, PACK_BASEBIT = 4, 4
 

@@ -740,6 +740,48 @@ int eoc_table_update(int32_t *table, int log2_lists, int log2_width, const int32
                      size_t queries);
 
 /* ------------------------------------------------------------------------------------------------
+ * finite automata on encrypted bit strings: a PUBLIC deterministic (weighted) automaton run over a string of
+ * TGSW-encrypted bits, one external product per state and input bit, no bootstrap.
+ *   automaton   `states` states, trans HOST [states][4] int32 = {next0, w0, next1, w1}: the successor and the weight under input
+ *               bit 0 / bit 1; successors in [0, states), weights in [0, 2N), states in [1, 4096].  starts HOST [n_starts] state
+ *               ids, n_starts in [1, 4096].  Both are validated on the host before anything touches a device (EOC_ERR_ARG) and
+ *               travel through the engine's descriptor ring: the calls stay asynchronous and can be captured.
+ *   query       `steps` converted selectors (eoc_tgsw_to_fft_device); selector t holds input bit t, bit 0 is read FIRST by the
+ *               automaton.  d_sel_fft is [queries][steps].
+ *   final       d_final [states][2][N] TLWE samples under s': trivial (eoc_table_trivial) or encrypted lists.  An acceptor puts
+ *               mu on slot 0 of the accepting states; a weighted automaton puts a public table in the slots.
+ *   rule        V_steps = final;  V_t[q] = A + C_t (x) (B - A),  A = X^(-w0(q)) V_(t+1)[next0(q)],  B = X^(-w1(q)) V_(t+1)[next1(q)],
+ *               t = steps - 1 .. 0; the result for start state s is V_0[s], whose slots 0 .. W-1 (W = 2^log2_width) are extracted
+ *               and key-switched as a table read's: d_out [queries][n_starts][W][n+1].  Slot 0 holds final[end state] at slot
+ *               (sum of the weights along the run), negacyclically.  steps = 0 extracts from d_final directly.
+ *   step        eoc_automaton_step_device: one step for every state and query, the building block (eoc_cmux_device's
+ *               counterpart): d_prev [states][2][N] per query, prev_query_stride TLWE samples between the queries' vectors (0:
+ *               one vector shared by all queries; otherwise >= states), selector of query q at q sel_query_stride selectors,
+ *               d_next [queries][states][2][N], which may not overlap d_prev.  Needs no key.
+ *   run         eoc_automaton_run_device: `steps` launches per slice of queries (the last over the start states alone), then
+ *               the extraction and the key switch (EOC_ERR_NO_KEY without a cloud key).  Workspace: two state vectors of
+ *               queries max(states, n_starts) TLWE samples in the table read's buffers, grown by eoc_engine_reserve's rule
+ *               (EOC_ERR_STATE under capture), held to the read's byte budget (EOC_TFHE_TABLE_WS_BYTES; a budget below one
+ *               query's need is EOC_ERR_ARG); a slice extracts at most 2^20 samples.  Stats: keyswitches += queries n_starts W;
+ *               eoc_engine_automaton_launches counts the k_automaton_step launches (steps per slice) and
+ *               eoc_engine_cmux_launches does not move; eoc_engine_kernel_times books them under the blind rotation.
+ *   noise       additive: noise.automaton_var / automaton_mean_bound / automaton_budget.
+ *   security    the selectors are the table read's (above); the automaton, the start states and the string length are public.
+ * EOC_ERR_ARG for a null pointer or a malformed automaton; queries 0 is a no-op. */
+int eoc_automaton_step_device(eoc_engine *e, const int32_t *trans, size_t states, const int32_t *d_prev, size_t prev_query_stride,
+                              const void *d_sel_fft, size_t sel_query_stride, int32_t *d_next, size_t queries, void *hip_stream);
+int eoc_automaton_run_device(eoc_engine *e, const int32_t *trans, size_t states, const int32_t *d_final, const void *d_sel_fft,
+                             size_t steps, const int32_t *starts, size_t n_starts, int log2_width, int32_t *d_out, size_t queries,
+                             void *hip_stream);
+uint64_t eoc_engine_automaton_launches(eoc_engine *e);
+/* the run on the global context (host buffers, synchronous): final_vec [states][2][N], selectors in TORUS form
+ * [queries][steps][2l][2][N] (NULL at steps = 0), out [queries][n_starts][W][n+1].  The automaton is validated before a key or a
+ * device is looked for.  Queries are cut into eoc_shard_range blocks, one per engine; every engine receives the final vector and
+ * converts its own selectors.  The cloud key alone suffices (key mode 2). */
+int eoc_automaton_run(const int32_t *trans, size_t states, const int32_t *final_vec, const int32_t *selectors, size_t steps,
+                      const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t queries);
+
+/* ------------------------------------------------------------------------------------------------
  * packing key switch: LWE samples under the LWE key s (gate or LUT outputs) -> compact TLWE lists under s',
  * the layout of eoc_pk_encrypt_*, eoc_table_trivial and the table of eoc_table_read_device.  1 024 results leave in 8 KiB
  * instead of 2 MB (Set A) / 2.5 MB (Set B), and a value the server computed can become a table.
