@@ -1360,6 +1360,42 @@ def int_circuit_run(nodes, tables, wires, instances=None):
     return wires
 
 
+def _global_n(who):
+    """n of the global context: from its key, else from its first GPU engine (a cloud key alone suffices)"""
+    if lib().eoc_global_key_mode():
+        return global_params().n
+    e0 = lib().eoc_global_engine()
+    if not e0:
+        raise EocError(f"{who}: no key and no GPU engine on the global context")
+    return lib().eoc_engine_params(e0).contents.n
+
+
+def _table_call_args(who, table, log2_lists, log2_width, selectors, values=None):
+    """The checks table_read and table_update share, under the caller's name `who`: table (an int32 array already)
+    [2^log2_lists][2][N], log2_width in [0, 10], selectors [queries][depth][2l][2][N] with depth = log2_lists + 10 - log2_width.
+    An update passes its `values`: they must be [queries][2][N], their count is the selectors', and depth 0 takes no
+    selectors.  Returns (log2_lists, log2_width, selectors or None, values) as ints and contiguous int32 arrays."""
+    d, lw = int(log2_lists), int(log2_width)
+    if table.ndim != 3 or table.shape[1:] != (2, N) or not 0 <= d <= 12 or table.shape[0] != 1 << d:
+        raise EocError(f"{who}: table must be [2^log2_lists][2][{N}] with log2_lists in [0, 12], got {table.shape}")
+    if not 0 <= lw <= 10:
+        raise EocError(f"{who}: log2_width = {lw} outside [0, 10]")
+    depth = d + 10 - lw
+    queries = "queries"
+    if values is not None:
+        values = np.ascontiguousarray(values, np.int32)
+        if values.ndim != 3 or values.shape[1:] != (2, N):
+            raise EocError(f"{who}: values must be [queries][2][{N}], got {values.shape}")
+        queries = values.shape[0]
+        if not depth:
+            return d, lw, None, values
+    selectors = np.ascontiguousarray(selectors, np.int32)
+    if (selectors.ndim != 5 or selectors.shape[1] != depth or selectors.shape[3:] != (2, N)
+            or (values is not None and selectors.shape[0] != queries)):
+        raise EocError(f"{who}: selectors must be [{queries}][{depth}][2l][2][{N}], got {selectors.shape}")
+    return d, lw, selectors, values
+
+
 def compact_expand(lists, count=None):
     """eoc_compact_expand on the global context (a cloud key alone suffices): lists [L][2][N] (PublicKey.encrypt_*) ->
     [count][n+1] LWE samples, count = L N unless given (the messages the lists were made for)"""
@@ -1369,12 +1405,7 @@ def compact_expand(lists, count=None):
     count = lists.shape[0] * N if count is None else int(count)
     if count > lists.shape[0] * N:
         raise EocError(f"compact_expand: {lists.shape[0]} lists hold at most {lists.shape[0] * N} samples, not {count}")
-    out = np.empty((count, global_params().n + 1), np.int32) if lib().eoc_global_key_mode() else None
-    if out is None:
-        e0 = lib().eoc_global_engine()
-        if not e0:
-            raise EocError("compact_expand: no key and no GPU engine on the global context")
-        out = np.empty((count, lib().eoc_engine_params(e0).contents.n + 1), np.int32)
+    out = np.empty((count, _global_n("compact_expand") + 1), np.int32)
     _check(lib().eoc_compact_expand(lists.ctypes.data, count, out.ctypes.data), "eoc_compact_expand")
     return out
 
@@ -1384,23 +1415,8 @@ def table_read(table, log2_lists, log2_width, selectors):
     PublicKey.encrypt_*), selectors [queries][10 - log2_width + log2_lists][2l][2][N] in torus form
     (SecretKey.encrypt_index per query) -> [queries][2^log2_width][n+1] LWE samples"""
     table = np.ascontiguousarray(table, np.int32)
-    d, lw = int(log2_lists), int(log2_width)
-    if table.ndim != 3 or table.shape[1:] != (2, N) or not 0 <= d <= 12 or table.shape[0] != 1 << d:
-        raise EocError(f"table_read: table must be [2^log2_lists][2][{N}] with log2_lists in [0, 12], got {table.shape}")
-    if not 0 <= lw <= 10:
-        raise EocError(f"table_read: log2_width = {lw} outside [0, 10]")
-    depth = d + 10 - lw
-    selectors = np.ascontiguousarray(selectors, np.int32)
-    if selectors.ndim != 5 or selectors.shape[1] != depth or selectors.shape[3:] != (2, N):
-        raise EocError(f"table_read: selectors must be [queries][{depth}][2l][2][{N}], got {selectors.shape}")
-    if lib().eoc_global_key_mode():
-        n = global_params().n
-    else:
-        e0 = lib().eoc_global_engine()
-        if not e0:
-            raise EocError("table_read: no key and no GPU engine on the global context")
-        n = lib().eoc_engine_params(e0).contents.n
-    out = np.empty((selectors.shape[0], 1 << lw, n + 1), np.int32)
+    d, lw, selectors, _ = _table_call_args("table_read", table, log2_lists, log2_width, selectors)
+    out = np.empty((selectors.shape[0], 1 << lw, _global_n("table_read") + 1), np.int32)
     _check(lib().eoc_table_read(table.ctypes.data, d, lw, selectors.ctypes.data, selectors.shape[0], out.ctypes.data),
            "eoc_table_read")
     return out
@@ -1412,21 +1428,8 @@ def table_update(table, log2_lists, log2_width, selectors, values):
     log2_lists = 0, log2_width = 10), values [queries][2][N] TLWE samples (pack of W samples, PublicKey.encrypt_*,
     trivial_table) with the entry in slots 0 .. W-1 and 0 elsewhere"""
     table = np.array(table, np.int32, order="C")                              # a copy: the C call updates in place
-    d, lw = int(log2_lists), int(log2_width)
-    if table.ndim != 3 or table.shape[1:] != (2, N) or not 0 <= d <= 12 or table.shape[0] != 1 << d:
-        raise EocError(f"table_update: table must be [2^log2_lists][2][{N}] with log2_lists in [0, 12], got {table.shape}")
-    if not 0 <= lw <= 10:
-        raise EocError(f"table_update: log2_width = {lw} outside [0, 10]")
-    depth = d + 10 - lw
-    values = np.ascontiguousarray(values, np.int32)
-    if values.ndim != 3 or values.shape[1:] != (2, N):
-        raise EocError(f"table_update: values must be [queries][2][{N}], got {values.shape}")
-    sel_ptr = None
-    if depth:
-        selectors = np.ascontiguousarray(selectors, np.int32)
-        if selectors.ndim != 5 or selectors.shape[:2] != (values.shape[0], depth) or selectors.shape[3:] != (2, N):
-            raise EocError(f"table_update: selectors must be [{values.shape[0]}][{depth}][2l][2][{N}], got {selectors.shape}")
-        sel_ptr = selectors.ctypes.data
+    d, lw, selectors, values = _table_call_args("table_update", table, log2_lists, log2_width, selectors, values)
+    sel_ptr = None if selectors is None else selectors.ctypes.data
     _check(lib().eoc_table_update(table.ctypes.data, d, lw, sel_ptr, values.ctypes.data, values.shape[0]), "eoc_table_update")
     return table
 
@@ -1539,14 +1542,7 @@ def automaton_run(trans, final, selectors, starts, log2_width=0):
         raise EocError(f"automaton_run: selectors must be [queries][steps][2l][2][{N}], got {selectors.shape}")
     st = np.ascontiguousarray(np.atleast_1d(starts), np.int32)
     queries, steps = selectors.shape[:2]
-    if lib().eoc_global_key_mode():
-        n = global_params().n
-    else:
-        e0 = lib().eoc_global_engine()
-        if not e0:
-            raise EocError("automaton_run: no key and no GPU engine on the global context")
-        n = lib().eoc_engine_params(e0).contents.n
-    out = np.empty((queries, st.size, 1 << lw, n + 1), np.int32)
+    out = np.empty((queries, st.size, 1 << lw, _global_n("automaton_run") + 1), np.int32)
     _check(lib().eoc_automaton_run(t.ctypes.data, t.shape[0], final.ctypes.data, selectors.ctypes.data if steps else None, steps,
                                    st.ctypes.data, st.size, lw, out.ctypes.data, queries), "eoc_automaton_run")
     return out

@@ -30,8 +30,8 @@ using namespace eoc;
     } while (0)
 
 // The six pair shapes (gadget length l, Bgbit; Bgbit 0 = any, read at run time): the two default sets, then every length.
-// Every ladder over k_blind_rotate* / k_br_enc / k_cmux / k_demux and both attribute blocks are generated from this list, in
-// this order (the device compiler emits the instances in the order they are named: DESIGN.md 15).
+// Every ladder over k_blind_rotate* / k_br_enc and the instance lists of the leveled families (LeveledFamily) are generated
+// from this list, in this order (the device compiler emits the instances in the order they are named: DESIGN.md 15).
 #define EOC_PAIR_SHAPES(X) X(2, 10) X(3, 7) X(1, 0) X(2, 0) X(3, 0) X(4, 0)
 // one rung: taken by the first shape of the list that fits gadget (l, bg), while `fn` is still unset
 #define EOC_IF_SHAPE(L, B, l, bg) if (!fn && (l) == L && (B == 0 || (bg) == B))
@@ -254,8 +254,21 @@ static int upload_tables(eoc_engine *e)
     return EOC_OK;
 }
 
-static void set_demux_attrs();
-static void set_automaton_attrs();
+// One family of leveled kernels (kernels.hip.h, leveled_pair.inc): a wave pair per item, k_cmux's grid, block and LDS plan,
+// args struct Args.  The three families go through one lookup, one attribute routine and one launcher (leveled_kernel,
+// set_leveled_attrs, launch_leveled).
+// WHERE a family is defined is part of the device code's text: a description is the first place that names its template's
+// instances, the device compiler emits templates in the order of their first use, and branch labels carry the function's
+// number.  kCmuxFamily stands right behind eoc_engine_create, where k_cmux was first named (behind k_keyswitch_waves, ahead
+// of the blind-rotation kernels); kDemuxFamily and kAutomatonFamily each open their section, behind every kernel that
+// existed when they were added, so the earlier kernels keep their text instruction for instruction.  A new family goes
+// behind the last one, with its section.
+template <class Args> struct LeveledFamily {
+    const char *name;               // the kernel's, for error messages
+    uint64_t eoc_engine::*launches; // the counter a launch bumps
+    const void *fn[6];              // the instances, in the order of EOC_PAIR_SHAPES
+};
+static void set_leveled_attrs(); // of all three families: defined behind the last one
 extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **out)
 {
     if (!out || !valid_params(p)) {
@@ -311,18 +324,17 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
     EOC_KS_ATTR(8, 8, 64);
 #undef EOC_KS_ATTR
     if (!e->ks_waves_ok) (void)hipGetLastError();
-    // so does k_cmux (tables + four transpose scratches); a device that refuses it cannot run the leveled calls
-#define EOC_CMUX_ATTR(LL, BB) \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cmux<LL, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
-    EOC_PAIR_SHAPES(EOC_CMUX_ATTR)
-#undef EOC_CMUX_ATTR
+    // so do the leveled kernels (tables + four transpose scratches); a device that refuses it cannot run the leveled calls
+    set_leveled_attrs();
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
-    set_demux_attrs(); // k_demux, k_cmux's LDS plan (defined behind every other kernel's first use: DESIGN.md 15)
-    set_automaton_attrs(); // k_automaton_step, the same plan, behind k_demux and the seeded kernels
     (void)hipGetLastError();
     *out = e;
     return EOC_OK;
 }
+// first named here: see LeveledFamily
+#define EOC_INSTANCE(L, B) reinterpret_cast<const void *>(&k_cmux<L, B>),
+static const LeveledFamily<CmuxArgs> kCmuxFamily = {"k_cmux", &eoc_engine::cmux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE)}};
+#undef EOC_INSTANCE
 
 static void free_ws(eoc_engine::Workspace &W)
 {
@@ -1562,25 +1574,33 @@ extern "C" int eoc_tgsw_to_fft_device(eoc_engine *e, const int32_t *d_tgsw, size
     return launch_fft_fwd(e, d_tgsw, static_cast<double *>(d_fft), count * e->kpl * 2, 0x1p-9, (hipStream_t)hip_stream);
 }
 
-static int launch_cmux(eoc_engine *e, const CmuxArgs &a, uint32_t ny, hipStream_t st)
+// the instance of a leveled family (LeveledFamily, above eoc_engine_create) for gadget (l, bg); nullptr: none
+static const void *leveled_kernel(const void *const (&instances)[6], int l, int bg)
 {
     const void *fn = nullptr;
-    const int l = e->p.l, bg = e->p.Bgbit;
-#define EOC_CMUX(L, B) EOC_IF_SHAPE(L, B, l, bg) fn = reinterpret_cast<const void *>(&k_cmux<L, B>);
-    EOC_PAIR_SHAPES(EOC_CMUX)
-#undef EOC_CMUX
+    int i = 0;
+#define EOC_LEVELED(L, B) EOC_IF_SHAPE(L, B, l, bg) fn = instances[i]; i++;
+    EOC_PAIR_SHAPES(EOC_LEVELED)
+#undef EOC_LEVELED
+    return fn;
+}
+// one launch of a family over nx x ny items: a.Bgbit is set here
+template <class Args>
+static int launch_leveled(eoc_engine *e, const LeveledFamily<Args> &family, const Args &a, uint32_t ny, hipStream_t st)
+{
+    const void *fn = leveled_kernel(family.fn, e->p.l, e->p.Bgbit);
     if (!fn) {
-        eoc_set_error("k_cmux: no kernel for gadget length %d", l);
+        eoc_set_error("%s: no kernel for gadget length %d", family.name, e->p.l);
         return EOC_ERR_STATE;
     }
-    CmuxArgs args = a;
-    args.Bgbit = bg;
+    Args args = a;
+    args.Bgbit = e->p.Bgbit;
     const d2 *tw = e->d_tw, *twist = e->d_twist;
     void *kargs[] = {&args, &tw, &twist};
     SpanGuard span(e, st, KIND_BLIND_ROTATE);
     HIP_TRY(hipLaunchKernel(fn, dim3((a.nx + kCmuxItemsPerWG - 1) / kCmuxItemsPerWG, ny), dim3(128 * kCmuxItemsPerWG), kargs,
                             kCmuxLds, st));
-    e->cmux_launches++;
+    (e->*family.launches)++;
     return EOC_OK;
 }
 
@@ -1606,7 +1626,7 @@ extern "C" int eoc_cmux_device(eoc_engine *e, const void *d_sel_fft, const int32
         a.in0_x = a.in1_x = a.out_x = smp;
         a.nx = (uint32_t)std::min(kSlice, count - i0);
         a.rot = 0;
-        int rc = launch_cmux(e, a, 1, (hipStream_t)hip_stream);
+        int rc = launch_leveled(e, kCmuxFamily, a, 1, (hipStream_t)hip_stream);
         if (rc) return rc;
     }
     return EOC_OK;
@@ -1671,11 +1691,39 @@ static int table_walk_rotations(eoc_engine *e, const TableWalk &tw, const d2 *se
         a.out = e->cmux[out_buf(tw, i)].i32();
         a.out_y = tw.smp;
         a.rot = sign > 0 ? (int)(tw.W << i) : 2 * kN - (int)(tw.W << i);
-        int rc = launch_cmux(e, a, (uint32_t)Q, st);
+        int rc = launch_leveled(e, kCmuxFamily, a, (uint32_t)Q, st);
         if (rc) return rc;
         *cur = a.out;
         *cur_y = a.out_y;
     }
+    return EOC_OK;
+}
+
+// The tail of a leveled read: slots w < W of ny TLWE samples become rows y W + w of the key-switch operand and of `o`
+// (k_tlwe_extract), and one key switch over the ny W rows leaves the LWE samples in `o`, p.n + 1 ints apart.
+// pick == NULL: sample y is samples + y * stride, one launch.  pick: sample y is samples + pick[y] * stride (public indices,
+// checked by the caller), one launch each.
+static int extract_and_keyswitch(eoc_engine *e, WS &Wk, const int32_t *samples, size_t stride, const int32_t *pick, size_t W,
+                                 size_t ny, int32_t *o, hipStream_t st)
+{
+    const size_t out_stride = (size_t)e->p.n + 1;
+    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    const unsigned ext_x = (unsigned)((W + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
+    {
+        SpanGuard span(e, st, KIND_PREPARE);
+        if (!pick)
+            hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, (unsigned)ny), dim3(256), 0, st, samples, stride, (uint32_t)W, Wk.d_ubar,
+                               o, e->p.n, prec_offset);
+        else
+            for (size_t i = 0; i < ny; i++)
+                hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, 1), dim3(256), 0, st, samples + (size_t)pick[i] * stride, (size_t)0,
+                                   (uint32_t)W, Wk.d_ubar + i * W * kN, o + i * W * out_stride, e->p.n, prec_offset);
+        HIP_TRY(hipGetLastError());
+    }
+    const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
+    int rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(ny * W), st, true, &gd);
+    if (rc) return rc;
+    e->stats[2] += ny * W;
     return EOC_OK;
 }
 
@@ -1700,8 +1748,6 @@ extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int 
     rc = ensure_ws(e, Wk, qs * W, 0, 0, st);
     if (!rc) rc = table_walk_reserve(e, tw, st);
     if (rc) return rc;
-    const size_t stride = (size_t)e->p.n + 1;
-    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
     for (size_t q0 = 0; q0 < queries; q0 += qs) {
         const size_t Q = std::min(qs, queries - q0);
         const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * depth * sel;
@@ -1722,24 +1768,15 @@ extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int 
             a.out_x = smp;
             a.out_y = (size_t)a.nx * smp;
             a.rot = 0;
-            if ((rc = launch_cmux(e, a, (uint32_t)Q, st))) return rc;
+            if ((rc = launch_leveled(e, kCmuxFamily, a, (uint32_t)Q, st))) return rc;
             cur = a.out;
             cur_y = a.out_y;
         }
         // rotations: X^(-W 2^i) under bit i brings slot W 2^i to slot 0; launch t = d + i of the query writes buffer t & 1
         rc = table_walk_rotations(e, tw, selq, -1, &cur, &cur_y, [](const TableWalk &w, int i) { return (w.d + i) & 1; }, Q, st);
         if (rc) return rc;
-        int32_t *o = d_out + q0 * W * stride;
-        {
-            SpanGuard span(e, st, KIND_PREPARE);
-            hipLaunchKernelGGL(k_tlwe_extract, dim3((unsigned)((W + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG), (unsigned)Q),
-                               dim3(256), 0, st, cur, cur_y, (uint32_t)W, Wk.d_ubar, o, e->p.n, prec_offset);
-            HIP_TRY(hipGetLastError());
-        }
-        const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
-        rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(Q * W), st, true, &gd);
+        rc = extract_and_keyswitch(e, Wk, cur, cur_y, nullptr, W, Q, d_out + q0 * W * ((size_t)e->p.n + 1), st);
         if (rc) return rc;
-        e->stats[2] += Q * W;
     }
     return EOC_OK;
 }
@@ -2189,41 +2226,10 @@ try {
 }
 
 // ---- encrypted-index table updates: the demultiplexer and table[idx] += v ----
-// The kernels of this section are templates first named here, behind every other kernel of the file: the device compiler
-// emits kernels in the order of their first use, so the earlier ones keep their text instruction for instruction.
-static const void *demux_kernel(int l, int bg)
-{
-    const void *fn = nullptr;
-#define EOC_DEMUX(L, B) EOC_IF_SHAPE(L, B, l, bg) fn = reinterpret_cast<const void *>(&k_demux<L, B>);
-    EOC_PAIR_SHAPES(EOC_DEMUX)
-#undef EOC_DEMUX
-    return fn;
-}
-
-static void set_demux_attrs()
-{
-#define EOC_DEMUX_ATTR(L, B) (void)hipFuncSetAttribute(demux_kernel(L, B), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
-    EOC_PAIR_SHAPES(EOC_DEMUX_ATTR)
-#undef EOC_DEMUX_ATTR
-}
-
-static int launch_demux(eoc_engine *e, const DemuxArgs &a, uint32_t ny, hipStream_t st)
-{
-    const void *fn = demux_kernel(e->p.l, e->p.Bgbit);
-    if (!fn) {
-        eoc_set_error("k_demux: no kernel for gadget length %d", e->p.l);
-        return EOC_ERR_STATE;
-    }
-    DemuxArgs args = a;
-    args.Bgbit = e->p.Bgbit;
-    const d2 *tw = e->d_tw, *twist = e->d_twist;
-    void *kargs[] = {&args, &tw, &twist};
-    SpanGuard span(e, st, KIND_BLIND_ROTATE);
-    HIP_TRY(hipLaunchKernel(fn, dim3((a.nx + kCmuxItemsPerWG - 1) / kCmuxItemsPerWG, ny), dim3(128 * kCmuxItemsPerWG), kargs,
-                            kCmuxLds, st));
-    e->demux_launches++;
-    return EOC_OK;
-}
+// The kernels of this section (k_demux, then k_sample_add) are templates first named here: see LeveledFamily.
+#define EOC_INSTANCE(L, B) reinterpret_cast<const void *>(&k_demux<L, B>),
+static const LeveledFamily<DemuxArgs> kDemuxFamily = {"k_demux", &eoc_engine::demux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE)}};
+#undef EOC_INSTANCE
 
 extern "C" int eoc_demux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in, int32_t *d_out0, int32_t *d_out1,
                                 size_t count, int accumulate, void *hip_stream)
@@ -2247,7 +2253,7 @@ extern "C" int eoc_demux_device(eoc_engine *e, const void *d_sel_fft, const int3
         a.in_x = a.out_x = smp;
         a.nx = (uint32_t)std::min(kSlice, count - i0);
         a.accumulate = accumulate != 0;
-        int rc = launch_demux(e, a, 1, (hipStream_t)hip_stream);
+        int rc = launch_leveled(e, kDemuxFamily, a, 1, (hipStream_t)hip_stream);
         if (rc) return rc;
     }
     return EOC_OK;
@@ -2308,7 +2314,7 @@ extern "C" int eoc_table_update_device(eoc_engine *e, int32_t *d_table, int log2
                 a.accumulate = 0;
             }
             a.out1 = a.out0 + smp;
-            if ((rc = launch_demux(e, a, (uint32_t)Q, st))) return rc;
+            if ((rc = launch_leveled(e, kDemuxFamily, a, (uint32_t)Q, st))) return rc;
             cur = a.out0;
             cur_y = a.out_y;
         }
@@ -2549,22 +2555,20 @@ extern "C" int eoc_dbg_chacha20_blocks_device(eoc_engine *e, const uint8_t key[3
 }
 
 // ---- finite automata on encrypted bit strings: leveled CMux steps -------------
-// The kernel of this section is a template first named here, behind every other kernel of the file (as k_demux was): the
-// earlier ones keep their text instruction for instruction.
-static const void *automaton_kernel(int l, int bg)
+// The kernel of this section is a template first named here, the last of the file: see LeveledFamily.
+#define EOC_INSTANCE(L, B) reinterpret_cast<const void *>(&k_automaton_step<L, B>),
+static const LeveledFamily<AutoStepArgs> kAutomatonFamily = {"k_automaton_step", &eoc_engine::automaton_launches,
+                                                             {EOC_PAIR_SHAPES(EOC_INSTANCE)}};
+#undef EOC_INSTANCE
+// the > 64 KiB dynamic-LDS attribute of every leveled instance (eoc_engine_create)
+static void set_leveled_attrs()
 {
-    const void *fn = nullptr;
-#define EOC_AUTO(L, B) EOC_IF_SHAPE(L, B, l, bg) fn = reinterpret_cast<const void *>(&k_automaton_step<L, B>);
-    EOC_PAIR_SHAPES(EOC_AUTO)
-#undef EOC_AUTO
-    return fn;
-}
-
-static void set_automaton_attrs()
-{
-#define EOC_AUTO_ATTR(L, B) (void)hipFuncSetAttribute(automaton_kernel(L, B), hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
-    EOC_PAIR_SHAPES(EOC_AUTO_ATTR)
-#undef EOC_AUTO_ATTR
+    auto set = [](const auto &family) {
+        for (const void *fn : family.fn) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
+    };
+    set(kCmuxFamily);
+    set(kDemuxFamily);
+    set(kAutomatonFamily);
 }
 
 constexpr size_t kAutoMaxStates = 4096;
@@ -2606,24 +2610,6 @@ static int push_auto_trans(WS &W, const std::vector<AutoTrans> &recs, hipStream_
     return rc;
 }
 
-static int launch_automaton_step(eoc_engine *e, const AutoStepArgs &a, uint32_t ny, hipStream_t st)
-{
-    const void *fn = automaton_kernel(e->p.l, e->p.Bgbit);
-    if (!fn) {
-        eoc_set_error("k_automaton_step: no kernel for gadget length %d", e->p.l);
-        return EOC_ERR_STATE;
-    }
-    AutoStepArgs args = a;
-    args.Bgbit = e->p.Bgbit;
-    const d2 *tw = e->d_tw, *twist = e->d_twist;
-    void *kargs[] = {&args, &tw, &twist};
-    SpanGuard span(e, st, KIND_BLIND_ROTATE);
-    HIP_TRY(hipLaunchKernel(fn, dim3((a.nx + kCmuxItemsPerWG - 1) / kCmuxItemsPerWG, ny), dim3(128 * kCmuxItemsPerWG), kargs,
-                            kCmuxLds, st));
-    e->automaton_launches++;
-    return EOC_OK;
-}
-
 extern "C" int eoc_automaton_step_device(eoc_engine *e, const int32_t *trans, size_t states, const int32_t *d_prev,
                                          size_t prev_query_stride, const void *d_sel_fft, size_t sel_query_stride, int32_t *d_next,
                                          size_t queries, void *hip_stream)
@@ -2658,7 +2644,7 @@ try {
         a.next = d_next + q0 * states * smp;
         a.next_y = states * smp;
         a.nx = (uint32_t)states;
-        if ((rc = launch_automaton_step(e, a, (uint32_t)std::min(kSlice, queries - q0), st))) return rc;
+        if ((rc = launch_leveled(e, kAutomatonFamily, a, (uint32_t)std::min(kSlice, queries - q0), st))) return rc;
     }
     ring_mark(Wk, st);
     return EOC_OK;
@@ -2708,24 +2694,12 @@ try {
     hipStream_t st = (hipStream_t)hip_stream;
     WS &Wk = e->ws;
     const size_t stride = (size_t)e->p.n + 1;
-    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
-    const unsigned ext_x = (unsigned)((W + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
     if (!steps) {
         const size_t cs = std::max<size_t>(1, ((size_t)1 << 20) / W); // start states per key switch
         if ((rc = ensure_ws(e, Wk, std::min(cs, n_starts) * W, 0, 0, st))) return rc;
         for (size_t i0 = 0; i0 < n_starts; i0 += cs) {
-            const size_t C = std::min(cs, n_starts - i0);
-            int32_t *o = d_out + i0 * W * stride;
-            {
-                SpanGuard span(e, st, KIND_PREPARE);
-                for (size_t i = 0; i < C; i++)
-                    hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, 1), dim3(256), 0, st, d_final + (size_t)starts[i0 + i] * smp,
-                                       (size_t)0, (uint32_t)W, Wk.d_ubar + i * W * kN, o + i * W * stride, e->p.n, prec_offset);
-                HIP_TRY(hipGetLastError());
-            }
-            const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
-            if ((rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(C * W), st, true, &gd))) return rc;
-            e->stats[2] += C * W;
+            rc = extract_and_keyswitch(e, Wk, d_final, smp, starts + i0, W, std::min(cs, n_starts - i0), d_out + i0 * W * stride, st);
+            if (rc) return rc;
         }
         const size_t block = n_starts * W * stride;
         for (size_t have = 1; have < queries; have *= 2) {
@@ -2759,20 +2733,11 @@ try {
             a.prev_y = cur_y;
             a.next = e->cmux[k & 1].i32();
             a.next_y = (size_t)a.nx * smp;
-            if ((rc = launch_automaton_step(e, a, (uint32_t)Q, st))) return rc;
+            if ((rc = launch_leveled(e, kAutomatonFamily, a, (uint32_t)Q, st))) return rc;
             cur = a.next;
             cur_y = a.next_y;
         }
-        int32_t *o = d_out + q0 * n_starts * W * stride;
-        {
-            SpanGuard span(e, st, KIND_PREPARE);
-            hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, (unsigned)(Q * n_starts)), dim3(256), 0, st, cur, smp, (uint32_t)W,
-                               Wk.d_ubar, o, e->p.n, prec_offset);
-            HIP_TRY(hipGetLastError());
-        }
-        const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
-        if ((rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(Q * n_starts * W), st, true, &gd))) return rc;
-        e->stats[2] += Q * n_starts * W;
+        if ((rc = extract_and_keyswitch(e, Wk, cur, smp, nullptr, W, Q * n_starts, d_out + q0 * n_starts * W * stride, st))) return rc;
     }
     ring_mark(Wk, st);
     return EOC_OK;

@@ -1,6 +1,6 @@
 // The external product of a WAVE PAIR, any gadget length: k_blind_rotate's step where the key rows are not streamed
-// (blind_rotate_pair.inc) and k_cmux include this one text, inside a scope of their own, so the two agree bit for bit by
-// construction.  A text and not a function: as a function template, force-inlined, it compiled every instance that uses it
+// (blind_rotate_pair.inc) and the leveled kernels' frame (leveled_pair.inc: k_cmux, k_demux, k_automaton_step) include this
+// one text, inside a scope of their own, so they agree bit for bit by construction.  A text and not a function: as a function template, force-inlined, it compiled every instance that uses it
 // to different code (kernels.hip.h, above k_blind_rotate).
 // Wave h holds the digit words of input polynomial h.  It runs the l forward transforms (two at a time, skewed on the one
 // scratch; an odd last one alone), multiplies the spectra, which stay in registers, by rows (h, p) for the OTHER output

@@ -909,6 +909,14 @@ constexpr int kBRLds = (kTwEntries + kNH + 2 * kScr) * 16 + kAbarLds; // 37 632 
 //   * the measured exceptions: the rotation block (16 ds_bpermute + the 32-way rot_digits switch) as a function renames
 //     registers in k_blind_rotate<2,10> and changes the length of twenty other instances, and the three-line sum of the
 //     gadget offset as a helper inverts the step loop's entry test (see Gadget).  Both stay in the kernels' text;
+//   * the leveled kernels' frame (k_cmux, k_demux, k_automaton_step: LDS carve, wave roles, the dead pair's rule, gadget,
+//     row loader, product) as a struct returned by a force-inlined function, the row loader a function template called from
+//     the lambda, tried on k_demux alone: the 125 other kernels identical, all six k_demux instances changed in 26 to 184
+//     lines (equal metadata, length within 3 instructions).  As included text (leveled_pair.inc) all eighteen are identical
+//     -- in the order the kernels had it: the same lines with the gadget's sum ahead of the kernel's operand pointers, so
+//     that two parts would do instead of three, changed all eighteen in 42 to 365 lines.  Of the small pieces, the row
+//     loader (load_selector_row) and the store phases' cmulc + wrap_trunc pair (leveled_words) change nothing as
+//     force-inlined functions; the negacyclic gather does (EOC_NEGACYCLIC, a macro);
 //   * the ORDER in which kernels are emitted is part of the assembly text (branch labels carry the function's number): plain
 //     kernels come first, in the order of their definitions, then the templates in the order of their first use in
 //     engine.hip.  A plain kernel added anywhere, or a template instance first used ahead of an existing one, renumbers the
@@ -1622,6 +1630,8 @@ __global__ __launch_bounds__(256) void k_compact_expand(const int32_t *__restric
 // the twiddle tables; the pairs of a workgroup meet at the two exchange barriers (a pair past the end of the grid computes
 // the last item again and stores nothing, so every barrier is reached by all waves).  Nothing here is loop-invariant, so
 // the tables are read from LDS in every pass, as the pair kernel's gadget-length-3 instance does.
+// This mapping, the LDS plan, the dead pair's rule and the product are the leveled frame, leveled_pair.inc: one text that
+// k_cmux, k_demux and k_automaton_step include around their operand pointers, their load phase and their store phase.
 // grid: x = ceil(nx / kCmuxItemsPerWG), y = ny; item (x, y) is addressed by strides in int32 (samples) / d2 (selectors).
 // =================================================================================================
 constexpr int kCmuxItemsPerWG = 2;
@@ -1638,69 +1648,57 @@ struct CmuxArgs {
     int Bgbit;
 };
 
+// The small pieces of the leveled kernels (their frame is leveled_pair.inc).
+// Rows (h, p) of the converted selector `sel` for output polynomial c: 16 bytes per lane, 1 KiB contiguous per wave and
+// instruction
+template <int L> __device__ __forceinline__ void load_selector_row(const d2 *sel, int h, int lane, int p, int c, d2 (&b)[8])
+{
+    const d2 *row = sel + ((size_t)(h * L + (p - 1)) * 2 + c) * kNH + lane;
+#pragma unroll
+    for (int r = 0; r < 8; r++) b[r] = row[r * 64];
+}
+// register r of the product, un-twisted and truncated: coefficients lane + 64 r (x) and lane + 64 r + 512 (y) of C (x) x
+__device__ __forceinline__ uint2 leveled_words(const d2 &s, const d2 &u)
+{
+    const d2 y = cmulc(s, u); // 1/512 is in the selector's image
+    return make_uint2(wrap_trunc(y.x), wrap_trunc(y.y));
+}
+// Position idx of the 2N-period of a polynomial of the ring X^N = -1, from v = its coefficient idx mod N: the upper half of
+// the period is negated.  A macro: as a force-inlined function, of (p, idx) or of (idx, v) alone, it leaves every k_cmux
+// byte-identical and changes every k_automaton_step in 45 to 680 lines (tools/isa_diff.py).
+#define EOC_NEGACYCLIC(idx, v) (((idx) & kN) ? 0u - (v) : (v))
+
 template <int L, int BGBIT = 0>
 __global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_cmux(CmuxArgs A, const d2 *__restrict__ g_tw,
                                                                     const d2 *__restrict__ g_twist)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    d2 *s_tw = reinterpret_cast<d2 *>(smem);
-    d2 *s_twist = s_tw + kTwEntries;
-    d2 *s_scr_all = s_twist + kNH;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = wv & 1;
-    d2 *scr = s_scr_all + wv * kScr;
-    d2 *scr_partner = s_scr_all + (wv ^ 1) * kScr;
-    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128 * kCmuxItemsPerWG);
-
-    const uint32_t x_raw = blockIdx.x * kCmuxItemsPerWG + (uint32_t)(wv >> 1);
-    const bool live = x_raw < A.nx;
-    const size_t ix = live ? x_raw : A.nx - 1, iy = blockIdx.y;
+#define EOC_LEVELED_PART 1
+#include "leveled_pair.inc"
     const int32_t *pa = A.in0 + ix * A.in0_x + iy * A.in0_y + (size_t)h * kN;
     const int32_t *pb = A.in1 + ix * A.in1_x + iy * A.in1_y + (size_t)h * kN;
     const d2 *sel = A.sel + ix * A.sel_x + iy * A.sel_y;
-
-    const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
-    uint32_t offset = 0;
-#pragma unroll
-    for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
-    const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
-
-    // offset + (X^rot B_h - A_h): coefficient lane + 64 r in dlo[r], lane + 64 r + 512 in dhi[r].  The rotation is index
-    // arithmetic on B's loads (X^N = -1: the upper half of the 2N-period is negated)
-    uint32_t dlo[8], dhi[8];
+#define EOC_LEVELED_PART 2
+#include "leveled_pair.inc"
+    // offset + (X^rot B_h - A_h).  The rotation is index arithmetic on B's loads (X^N = -1: the upper half of the 2N-period
+    // is negated)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
         const int idx = (j - A.rot) & (2 * kN - 1);
         const uint32_t b = (uint32_t)pb[idx & (kN - 1)];
-        const uint32_t v = offset + ((idx & kN) ? 0u - b : b) - (uint32_t)pa[j];
+        const uint32_t v = offset + EOC_NEGACYCLIC(idx, b) - (uint32_t)pa[j];
         if (r < 8) dlo[r] = v;
         else dhi[r - 8] = v;
     }
-    __syncthreads(); // the tables
-
-    // rows (h, p) of the selector for output polynomial c: 16 bytes per lane, 1 KiB contiguous per wave and instruction
-    auto load_row = [&](int p, int c, d2 (&b)[8]) __attribute__((always_inline)) {
-        const d2 *row = sel + ((size_t)(h * L + (p - 1)) * 2 + c) * kNH + lane;
-#pragma unroll
-        for (int r = 0; r < 8; r++) b[r] = row[r * 64];
-    };
-    d2 S[8], ut[8];
-    {
-        const d2 (*const xp_t2)[4] = nullptr, (*const xp_t1)[4] = nullptr; // nothing is loop-invariant here: tables from LDS
-#define EOC_XP_STAMP(k) do { } while (0)
-#include "ext_product_pair.inc"
-#undef EOC_XP_STAMP
-    }
-    if (!live) return;
+#define EOC_LEVELED_PART 3
+#include "leveled_pair.inc"
     int32_t *po = A.out + ix * A.out_x + iy * A.out_y + (size_t)h * kN;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const int j = lane + 64 * r;
-        const d2 y = cmulc(S[r], ut[r]); // 1/512 is in the selector's image
-        po[j] = (int32_t)((uint32_t)pa[j] + wrap_trunc(y.x));
-        po[j + kNH] = (int32_t)((uint32_t)pa[j + kNH] + wrap_trunc(y.y));
+        const uint2 e = leveled_words(S[r], ut[r]);
+        po[j] = (int32_t)((uint32_t)pa[j] + e.x);
+        po[j + kNH] = (int32_t)((uint32_t)pa[j + kNH] + e.y);
     }
 }
 
@@ -1897,15 +1895,16 @@ __global__ __launch_bounds__(256) void k_tvpack_cols(const int32_t *__restrict__
 //   E = C (x) x,  out1 = E,  out0 = x - E (word by word)
 // x: a TLWE sample [2][N]; C: a converted selector, as k_cmux's.  E is k_cmux's external product with in0 = 0, in1 = x,
 // rot = 0 before the add -- the same text (ext_product_pair.inc), so the two agree bit for bit by construction.  The mapping,
-// the LDS plan and the dead pair's rule are k_cmux's: wave h decomposes offset + x_h (no difference, no rotation), produces
-// E_h and writes polynomial h of BOTH children.  x is not held across the product: x - E is formed at store time from a
-// reload of x (8 KiB per item, L2-resident), which is what keeps the second output out of the register count.
+// the LDS plan and the dead pair's rule are the leveled frame (leveled_pair.inc, described above k_cmux): wave h decomposes
+// offset + x_h (no difference, no rotation), produces E_h and writes polynomial h of BOTH children.  x is not held across the
+// product: x - E is formed at store time from a reload of x (8 KiB per item, L2-resident), which is what keeps the second
+// output out of the register count.
 // accumulate = 0: plain stores (out0 / out1 may not overlap x).  accumulate = 1: vector integer atomicAdd into the
 // destination, lane-contiguous (256 bytes per wave and instruction) as k_pack_rows leaves its results: the last stage of an
 // update adds its leaves straight into the table, every word an integer sum, so colliding queries and any order of arrival
 // give the same words.
-// grid: x = ceil(nx / kCmuxItemsPerWG) parents, y = ny; item (x, y) by strides in int32 (samples) / d2 (selectors).  Templates
-// defined and first used behind every other kernel, as k_tvpack_cols: the earlier kernels keep their text.
+// grid: x = ceil(nx / kCmuxItemsPerWG) parents, y = ny; item (x, y) by strides in int32 (samples) / d2 (selectors).  Where
+// the templates are defined and first used is part of every later kernel's text: engine.hip, LeveledFamily.
 // =================================================================================================
 struct DemuxArgs {
     const d2 *sel;            // converted selectors
@@ -1922,74 +1921,41 @@ template <int L, int BGBIT = 0>
 __global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_demux(DemuxArgs A, const d2 *__restrict__ g_tw,
                                                                      const d2 *__restrict__ g_twist)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    d2 *s_tw = reinterpret_cast<d2 *>(smem);
-    d2 *s_twist = s_tw + kTwEntries;
-    d2 *s_scr_all = s_twist + kNH;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = wv & 1;
-    d2 *scr = s_scr_all + wv * kScr;
-    d2 *scr_partner = s_scr_all + (wv ^ 1) * kScr;
-    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128 * kCmuxItemsPerWG);
-
-    const uint32_t x_raw = blockIdx.x * kCmuxItemsPerWG + (uint32_t)(wv >> 1);
-    const bool live = x_raw < A.nx;
-    const size_t ix = live ? x_raw : A.nx - 1, iy = blockIdx.y;
+#define EOC_LEVELED_PART 1
+#include "leveled_pair.inc"
     const int32_t *px = A.in + ix * A.in_x + iy * A.in_y + (size_t)h * kN;
     const d2 *sel = A.sel + ix * A.sel_x + iy * A.sel_y;
-
-    const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
-    uint32_t offset = 0;
-#pragma unroll
-    for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
-    const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
-
-    // offset + x_h: coefficient lane + 64 r in dlo[r], lane + 64 r + 512 in dhi[r]
-    uint32_t dlo[8], dhi[8];
+#define EOC_LEVELED_PART 2
+#include "leveled_pair.inc"
+    // offset + x_h
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         dlo[r] = offset + (uint32_t)px[lane + 64 * r];
         dhi[r] = offset + (uint32_t)px[lane + 64 * r + kNH];
     }
-    __syncthreads(); // the tables
-
-    auto load_row = [&](int p, int c, d2 (&b)[8]) __attribute__((always_inline)) {
-        const d2 *row = sel + ((size_t)(h * L + (p - 1)) * 2 + c) * kNH + lane;
-#pragma unroll
-        for (int r = 0; r < 8; r++) b[r] = row[r * 64];
-    };
-    d2 S[8], ut[8];
-    {
-        const d2 (*const xp_t2)[4] = nullptr, (*const xp_t1)[4] = nullptr; // tables from LDS, as k_cmux
-#define EOC_XP_STAMP(k) do { } while (0)
-#include "ext_product_pair.inc"
-#undef EOC_XP_STAMP
-    }
-    if (!live) return;
+#define EOC_LEVELED_PART 3
+#include "leveled_pair.inc"
     const size_t oo = ix * A.out_x + iy * A.out_y + (size_t)h * kN;
     int32_t *p0 = A.out0 + oo, *p1 = A.out1 + oo;
     if (A.accumulate) {
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const int j = lane + 64 * r;
-            const d2 y = cmulc(S[r], ut[r]); // 1/512 is in the selector's image
-            const uint32_t e0 = wrap_trunc(y.x), e1 = wrap_trunc(y.y);
-            atomicAdd(p1 + j, (int)e0);
-            atomicAdd(p1 + j + kNH, (int)e1);
-            atomicAdd(p0 + j, (int)((uint32_t)px[j] - e0));
-            atomicAdd(p0 + j + kNH, (int)((uint32_t)px[j + kNH] - e1));
+            const uint2 e = leveled_words(S[r], ut[r]);
+            atomicAdd(p1 + j, (int)e.x);
+            atomicAdd(p1 + j + kNH, (int)e.y);
+            atomicAdd(p0 + j, (int)((uint32_t)px[j] - e.x));
+            atomicAdd(p0 + j + kNH, (int)((uint32_t)px[j + kNH] - e.y));
         }
     } else {
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const int j = lane + 64 * r;
-            const d2 y = cmulc(S[r], ut[r]);
-            const uint32_t e0 = wrap_trunc(y.x), e1 = wrap_trunc(y.y);
-            p1[j] = (int32_t)e0;
-            p1[j + kNH] = (int32_t)e1;
-            p0[j] = (int32_t)((uint32_t)px[j] - e0);
-            p0[j + kNH] = (int32_t)((uint32_t)px[j + kNH] - e1);
+            const uint2 e = leveled_words(S[r], ut[r]);
+            p1[j] = (int32_t)e.x;
+            p1[j + kNH] = (int32_t)e.y;
+            p0[j] = (int32_t)((uint32_t)px[j] - e.x);
+            p0[j + kNH] = (int32_t)((uint32_t)px[j + kNH] - e.y);
         }
     }
 }
@@ -2176,13 +2142,13 @@ __global__ __launch_bounds__(256) void k_chacha20_blocks(SeedArgs A, uint64_t co
 // bit (one per query, shared by its states); the transition record {next0, w0, next1, w1} of state q is public, validated on
 // the host (next in [0, states), w in [0, 2N)) and read once per wave pair through a uniform address.  The external product
 // is k_cmux's -- the same text (ext_product_pair.inc) --, so a step equals the CMux of the two rotated successors bit for bit
-// by construction.  The mapping, the LDS plan and the dead pair's rule are k_cmux's; BOTH operands are gathered and rotated by
-// index arithmetic on their loads (coefficient j of X^(-w) P is P[(j + w) mod 2N], negated in the upper half of the period),
-// lane-contiguous up to the one wrap; A is not held across the product but reloaded at store time, as k_cmux reloads in0.
+// by construction.  The mapping, the LDS plan and the dead pair's rule are the leveled frame (leveled_pair.inc, described
+// above k_cmux); BOTH operands are gathered and rotated by index arithmetic on their loads (coefficient j of X^(-w) P is
+// P[(j + w) mod 2N], negated in the upper half of the period), lane-contiguous up to the one wrap; A is not held across the
+// product but reloaded at store time, as k_cmux reloads in0.
 // prev_y = 0 reads one shared vector for every query (the first step reads the final vector in place).  next may not
 // overlap prev: a state may be its own successor, so the driver alternates two buffers.
-// grid: x = ceil(nx / kCmuxItemsPerWG) states, y = queries.  Templates defined and first used behind every other kernel, as
-// k_demux: the earlier kernels keep their text.
+// grid: x = ceil(nx / kCmuxItemsPerWG) states, y = queries.  Defined and first used behind k_demux (engine.hip, LeveledFamily).
 // =================================================================================================
 struct AutoTrans {
     int32_t next0, w0, next1, w1; // successor and weight under bit 0 / bit 1
@@ -2204,59 +2170,28 @@ template <int L, int BGBIT = 0>
 __global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_automaton_step(AutoStepArgs A, const d2 *__restrict__ g_tw,
                                                                               const d2 *__restrict__ g_twist)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    d2 *s_tw = reinterpret_cast<d2 *>(smem);
-    d2 *s_twist = s_tw + kTwEntries;
-    d2 *s_scr_all = s_twist + kNH;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = wv & 1;
-    d2 *scr = s_scr_all + wv * kScr;
-    d2 *scr_partner = s_scr_all + (wv ^ 1) * kScr;
-    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 128 * kCmuxItemsPerWG);
-
-    const uint32_t x_raw = blockIdx.x * kCmuxItemsPerWG + (uint32_t)(wv >> 1);
-    const bool live = x_raw < A.nx;
-    const size_t ix = live ? x_raw : A.nx - 1, iy = blockIdx.y;
+#define EOC_LEVELED_PART 1
+#include "leveled_pair.inc"
     const AutoTrans tr = A.trans[ix]; // uniform: one record per wave pair
     const int32_t *pv = A.prev + iy * A.prev_y + (size_t)h * kN;
     const int32_t *pa = pv + (size_t)tr.next0 * (2 * kN);
     const int32_t *pb = pv + (size_t)tr.next1 * (2 * kN);
     const int w0 = tr.w0 & (2 * kN - 1), w1 = tr.w1 & (2 * kN - 1);
     const d2 *sel = A.sel + iy * A.sel_y;
-
-    const int Bgbit = BGBIT > 0 ? BGBIT : A.Bgbit;
-    uint32_t offset = 0;
-#pragma unroll
-    for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
-    const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
-
-    // offset + (X^(-w1) B_h - X^(-w0) A_h): coefficient lane + 64 r in dlo[r], lane + 64 r + 512 in dhi[r]
-    uint32_t dlo[8], dhi[8];
+#define EOC_LEVELED_PART 2
+#include "leveled_pair.inc"
+    // offset + (X^(-w1) B_h - X^(-w0) A_h)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
         const int ia = (j + w0) & (2 * kN - 1), ib = (j + w1) & (2 * kN - 1);
         const uint32_t a = (uint32_t)pa[ia & (kN - 1)], b = (uint32_t)pb[ib & (kN - 1)];
-        const uint32_t v = offset + ((ib & kN) ? 0u - b : b) - ((ia & kN) ? 0u - a : a);
+        const uint32_t v = offset + EOC_NEGACYCLIC(ib, b) - EOC_NEGACYCLIC(ia, a);
         if (r < 8) dlo[r] = v;
         else dhi[r - 8] = v;
     }
-    __syncthreads(); // the tables
-
-    auto load_row = [&](int p, int c, d2 (&b)[8]) __attribute__((always_inline)) {
-        const d2 *row = sel + ((size_t)(h * L + (p - 1)) * 2 + c) * kNH + lane;
-#pragma unroll
-        for (int r = 0; r < 8; r++) b[r] = row[r * 64];
-    };
-    d2 S[8], ut[8];
-    {
-        const d2 (*const xp_t2)[4] = nullptr, (*const xp_t1)[4] = nullptr; // tables from LDS, as k_cmux
-#define EOC_XP_STAMP(k) do { } while (0)
-#include "ext_product_pair.inc"
-#undef EOC_XP_STAMP
-    }
-    if (!live) return;
+#define EOC_LEVELED_PART 3
+#include "leveled_pair.inc"
     int32_t *po = A.next + ix * (size_t)(2 * kN) + iy * A.next_y + (size_t)h * kN;
     // the gather indices are formed again from a value the compiler cannot match with the load phase's: carried across the
     // product, those sixteen registers are what spills <3,7>
@@ -2265,12 +2200,13 @@ __global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_automaton_step(Aut
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const int j = lane + 64 * r;
-        const d2 y = cmulc(S[r], ut[r]); // 1/512 is in the selector's image
+        const uint2 e = leveled_words(S[r], ut[r]);
         const int i0 = (j + w0s) & (2 * kN - 1), i1 = (j + kNH + w0s) & (2 * kN - 1);
         const uint32_t a0 = (uint32_t)pa[i0 & (kN - 1)], a1 = (uint32_t)pa[i1 & (kN - 1)];
-        po[j] = (int32_t)(((i0 & kN) ? 0u - a0 : a0) + wrap_trunc(y.x));
-        po[j + kNH] = (int32_t)(((i1 & kN) ? 0u - a1 : a1) + wrap_trunc(y.y));
+        po[j] = (int32_t)(EOC_NEGACYCLIC(i0, a0) + e.x);
+        po[j + kNH] = (int32_t)(EOC_NEGACYCLIC(i1, a1) + e.y);
     }
 }
+#undef EOC_NEGACYCLIC
 
 } // namespace eoc

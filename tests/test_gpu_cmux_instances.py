@@ -1,4 +1,4 @@
-"""Every k_cmux instance launch_cmux() (engine.hip) can dispatch, on the MI355X, with the edge inputs of
+"""Every k_cmux instance launch_leveled() (engine.hip) can dispatch, on the MI355X, with the edge inputs of
 tests/leveled_edge_inputs.py: one test id per instance, named after the kernel.  <2,0> and <3,0> run nowhere else.
 
 An instance runs on a real key at n = 16 (only the key switch behind a table read uses n) through the public calls:

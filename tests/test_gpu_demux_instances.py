@@ -1,4 +1,4 @@
-"""Every k_demux instance launch_demux() (engine.hip) can dispatch, on the MI355X, with the edge words of
+"""Every k_demux instance launch_leveled() (engine.hip) can dispatch, on the MI355X, with the edge words of
 tests/leveled_edge_inputs.py taken as x itself (the demultiplexer decomposes the sample, not a difference): one test id per
 instance, named after the kernel.
 
