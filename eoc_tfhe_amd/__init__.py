@@ -319,6 +319,15 @@ def lib():
         "eoc_dbg_chacha20_blocks_device": (C.c_int, [vp, vp, u64, u64, sz, vp, vp]),
         "eoc_seeded_expand": (C.c_int, [vp, u64, vp, sz, vp]),
         "eoc_global_import_seeded_cloud_key_blob": (C.c_int, [vp, sz]),
+        # inner products with public integer weights on compact lists
+        "eoc_weights_image_bytes": (sz, [sz, sz]),
+        "eoc_weights_to_device": (C.c_int, [vp, vp, sz, sz, vp, vp]),
+        "eoc_dot_device": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, vp, vp]),
+        "eoc_linear_device": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, vp, vp]),
+        "eoc_engine_dot_launches": (u64, [vp]),
+        "eoc_linear": (C.c_int, [vp, sz, sz, vp, sz, vp, vp]),
+        "eoc_pk_encrypt_torus": (C.c_int, [vp, sz, u64, u64, vp, sz, vp]),
+        "eoc_pk_encrypt_torus_keyed": (C.c_int, [vp, sz, vp, u64, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -743,6 +752,26 @@ class PublicKey:
         encrypt_bits"""
         return self._encrypt(values, p, enc_seed, first_list)
 
+    def encrypt_torus(self, msgs, enc_seed=None, first_list=0):
+        """arbitrary Torus32 messages (int32 per slot, e.g. x_k * Delta for Engine.linear_device) -> compact lists
+        (eoc_pk_encrypt_torus); the same streams, u, e1 and e2 as encrypt_bits, randomness as encrypt_bits"""
+        msgs = np.ascontiguousarray(np.asarray(msgs).ravel(), np.int32)
+        out = np.empty((self.list_count(msgs.size), 2, N), np.int32)
+        if enc_seed is not None:            # reproducible test mode: NOT secure (include/eoc_tfhe_gpu.h)
+            _check(self.L.eoc_pk_encrypt_torus(self.blob, len(self.blob), enc_seed, first_list, msgs.ctypes.data, msgs.size,
+                                               out.ctypes.data), "eoc_pk_encrypt_torus")
+            return out
+        if first_list:
+            raise EocError("first_list is a test-mode argument: secure encryption draws a fresh key per call")
+        key = np.frombuffer(os.urandom(32), np.uint8).copy()    # fresh per call, as _encrypt
+        try:
+            rc = self.L.eoc_pk_encrypt_torus_keyed(self.blob, len(self.blob), key.ctypes.data, 0, msgs.ctypes.data, msgs.size,
+                                                   out.ctypes.data)
+        finally:
+            key[:] = 0
+        _check(rc, "eoc_pk_encrypt_torus_keyed")
+        return out
+
 
 def trivial_table(messages):
     """Public data as a table for table_read (eoc_table_trivial): Torus32 messages -> trivial TLWE lists [L][2][N], c0 = 0,
@@ -1063,6 +1092,36 @@ class Engine:
         st = np.ascontiguousarray(np.atleast_1d(starts), np.int32)
         _check(self.L.eoc_automaton_run_device(self.h, t.ctypes.data, t.shape[0], d_final, d_sel_fft, int(steps), st.ctypes.data,
                                                st.size, int(log2_width), d_out, queries, stream), "eoc_automaton_run_device")
+
+    def weights_image_bytes(self, rows, cols):
+        """bytes of the device image of a rows x cols model (eoc_weights_image_bytes)"""
+        return int(self.L.eoc_weights_image_bytes(int(rows), int(cols)))
+
+    def weights_to_device(self, weights, d_image, stream=None):
+        """Public int8 weights [rows][cols], every value in [-127, 127] -> the device image at d_image
+        (eoc_weights_to_device; weights_image_bytes(rows, cols) bytes: the spectra [rows][L][512] complex, then the zero-padded
+        weights).  A model load: no key, synchronous.  Returns (rows, cols)."""
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.size == 0 or not np.issubdtype(w.dtype, np.integer) or np.abs(w.astype(np.int64)).max() > 127:
+            raise EocError(f"weights_to_device: weights must be a non-empty integer matrix [rows][cols] in [-127, 127], got "
+                           f"{w.dtype} {w.shape}")
+        w = np.ascontiguousarray(w, np.int8)
+        _check(self.L.eoc_weights_to_device(self.h, w.ctypes.data, w.shape[0], w.shape[1], d_image, stream), "eoc_weights_to_device")
+        return w.shape
+
+    def dot_device(self, d_image, rows, cols, d_lists, batch, d_bias, d_u, stream=None):
+        """Inner products with public weights (eoc_dot_device): d_lists [batch][ceil(cols / N)][2][N], d_bias
+        [rows] Torus32 or None, d_u [batch][rows][N+1]: LWE samples under s' (keyswitch_device's input).  No key needed."""
+        _check(self.L.eoc_dot_device(self.h, d_image, rows, cols, d_lists, batch, d_bias, d_u, stream), "eoc_dot_device")
+
+    def linear_device(self, d_image, rows, cols, d_lists, batch, d_bias, d_out, stream=None):
+        """dot_device followed by the key switch (eoc_linear_device): d_out [batch][rows][n+1], ordinary LWE samples of phase
+        bias[r] + sum_k w[r][k] phase(slot k of vector b).  Needs the cloud key."""
+        _check(self.L.eoc_linear_device(self.h, d_image, rows, cols, d_lists, batch, d_bias, d_out, stream), "eoc_linear_device")
+
+    def dot_launches(self):
+        """k_dot_mask launches so far (eoc_engine_dot_launches): one per slice of a call's input vectors"""
+        return int(self.L.eoc_engine_dot_launches(self.h))
 
     def automaton_launches(self):
         """k_automaton_step launches so far (eoc_engine_automaton_launches): `steps` per slice of a run's queries"""
@@ -1548,6 +1607,29 @@ def automaton_run(trans, final, selectors, starts, log2_width=0):
     return out
 
 
+def linear(weights, lists, bias=None):
+    """eoc_linear on the global context (a cloud key alone suffices): public int8 weights [rows][cols] in [-127, 127], lists
+    [batch][ceil(cols / N)][2][N] (PublicKey.encrypt_*, pack), bias [rows] Torus32 or None -> LWE samples [batch][rows][n+1]
+    of phase bias[r] + sum_k w[r][k] phase(slot k of vector b)"""
+    w = np.asarray(weights)
+    if w.ndim != 2 or w.size == 0 or not np.issubdtype(w.dtype, np.integer) or np.abs(w.astype(np.int64)).max() > 127:
+        raise EocError(f"linear: weights must be a non-empty integer matrix [rows][cols] in [-127, 127], got {w.dtype} {w.shape}")
+    w = np.ascontiguousarray(w, np.int8)
+    rows, cols = w.shape
+    L = -(-cols // N)
+    lists = np.ascontiguousarray(lists, np.int32)
+    if lists.ndim != 4 or lists.shape[1:] != (L, 2, N):
+        raise EocError(f"linear: lists must be [batch][{L}][2][{N}], got {lists.shape}")
+    if bias is not None:
+        bias = np.ascontiguousarray(bias, np.int32)
+        if bias.shape != (rows,):
+            raise EocError(f"linear: bias must be [{rows}], got {bias.shape}")
+    out = np.empty((lists.shape[0], rows, _global_n("linear") + 1), np.int32)
+    _check(lib().eoc_linear(w.ctypes.data, rows, cols, lists.ctypes.data, lists.shape[0],
+                            None if bias is None else bias.ctypes.data, out.ctypes.data), "eoc_linear")
+    return out
+
+
 def pack(cts):
     """eoc_pack on the global context (the packing key alone suffices: global_import_packing_key_blob): LWE samples
     [count][n+1] -> compact lists [ceil(count / N)][2][N], sample i in slot i mod N of list i / N"""
@@ -1967,3 +2049,5 @@ class Circuit:
 
 
 from .int_circuits import IntCircuit, bit_function2, radix_add, radix_less_than  # noqa: E402,F401
+from . import dinn  # noqa: E402,F401
+from .dinn import DenseLayer, Network  # noqa: E402,F401

@@ -51,6 +51,10 @@ bool eoc_seeded_cloud_key_blob_parts(const void *buf, size_t len, eoc_params *p,
                                      const int32_t **ksk_bodies);
 // eoc_pack's GPU half on the process-global engines (multi.hip): WHOLE lists cut into eoc_shard_range blocks, one per engine
 int eoc_pack_engines(const int32_t *cts, size_t count, int32_t *lists);
+// eoc_linear's GPU half on the process-global engines (multi.hip): WHOLE input vectors cut into eoc_shard_range
+// blocks, one per engine
+int eoc_linear_engines(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch, const int32_t *h_bias,
+                       int32_t *h_out);
 // the packing key on every process-global engine (multi.hip)
 int eoc_set_packing_key_engines(const void *blob, size_t len);
 // eoc_lut2_batch's GPU half on the process-global engines (multi.hip): rows cut into eoc_shard_range blocks, one

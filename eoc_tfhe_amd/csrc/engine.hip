@@ -124,6 +124,11 @@ struct eoc_engine {
     // seeded selectors: the expanded torus-form rows [rows][2][N] in front of the key-load transform
     Scratch seed_stage;
     uint64_t seed_launches = 0; // k_seed_masks launches
+    // inner products with public weights: the list spectra [vectors of a slice][L][2][512] complex, and the
+    // byte budget that buffer is held to (vectors are sliced to fit; EOC_TFHE_DOT_WS_BYTES, diagnostics)
+    Scratch dot_specs;
+    size_t dot_ws_bytes = (size_t)256 << 20;
+    uint64_t dot_launches = 0; // k_dot_mask launches
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
     struct Span { hipEvent_t a, b; int kind; };
@@ -269,6 +274,7 @@ template <class Args> struct LeveledFamily {
     const void *fn[6];              // the instances, in the order of EOC_PAIR_SHAPES
 };
 static void set_leveled_attrs(); // of all three families: defined behind the last one
+static void set_dot_attrs();     // of k_dot_mask: defined at the end of the file, where the kernel is first named
 extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **out)
 {
     if (!out || !valid_params(p)) {
@@ -311,6 +317,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
         if (const char *s = getenv("EOC_TFHE_INT_SLICE_ROWS")) e->int_slice_rows = atoi(s);
         if (const char *s = getenv("EOC_TFHE_TABLE_WS_BYTES")) e->table_ws_bytes = (size_t)strtoull(s, nullptr, 10);
         if (const char *s = getenv("EOC_TFHE_PACK_WS_BYTES")) e->pack_ws_bytes = (size_t)strtoull(s, nullptr, 10);
+        if (const char *s = getenv("EOC_TFHE_DOT_WS_BYTES")) e->dot_ws_bytes = (size_t)strtoull(s, nullptr, 10);
     }
     // the key-switch kernel uses > 64 KiB of dynamic LDS: raise the limit once, here, not on the launch path
     // (a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to k_keyswitch_generic: slow, exact)
@@ -327,6 +334,7 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
     // so do the leveled kernels (tables + four transpose scratches); a device that refuses it cannot run the leveled calls
     set_leveled_attrs();
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
+    set_dot_attrs();
     (void)hipGetLastError();
     *out = e;
     return EOC_OK;
@@ -366,7 +374,7 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
     }
     hipFree(e->d_ksl);
     hipFree(e->d_pks);
-    for (Scratch *s : {&e->cmux[0], &e->cmux[1], &e->pack_cols, &e->lut2, &e->seed_stage}) hipFree(s->p);
+    for (Scratch *s : {&e->cmux[0], &e->cmux[1], &e->pack_cols, &e->lut2, &e->seed_stage, &e->dot_specs}) hipFree(s->p);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -2746,3 +2754,185 @@ try {
     return EOC_ERR_ALLOC;
 }
 extern "C" uint64_t eoc_engine_automaton_launches(eoc_engine *e) { return e ? e->automaton_launches : 0; }
+
+// ---- inner products with public integer weights on compact lists -------------
+// The device image of a model: the weight spectra [rows][L][512] complex (k_fft_fwd_polys at scale 1 of the weight
+// polynomials V_{r,l}), then the weights themselves [rows][L N] int8, zero past `cols`: what the body's integer sum reads.
+constexpr size_t kDotMaxDim = (size_t)1 << 20; // rows and cols of a model: every grid and item count stays inside 32 bits
+static inline size_t dot_lists(size_t cols) { return (cols + kN - 1) / kN; }
+static inline bool dot_shape_ok(size_t rows, size_t cols) { return rows >= 1 && cols >= 1 && rows <= kDotMaxDim && cols <= kDotMaxDim; }
+extern "C" size_t eoc_weights_image_bytes(size_t rows, size_t cols)
+{
+    return dot_shape_ok(rows, cols) ? rows * dot_lists(cols) * (kNH * sizeof(d2) + kN) : 0;
+}
+
+// A model load: validated on the host, no key; the image is complete when the call returns (`hip_stream` is drained)
+extern "C" int eoc_weights_to_device(eoc_engine *e, const int8_t *h_w, size_t rows, size_t cols, void *d_image, void *hip_stream)
+try {
+    if (!e || !h_w || !d_image) {
+        eoc_set_error("eoc_weights_to_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!dot_shape_ok(rows, cols)) {
+        eoc_set_error("eoc_weights_to_device: rows = %zu, cols = %zu: both must lie in [1, 2^20]", rows, cols);
+        return EOC_ERR_ARG;
+    }
+    for (size_t k = 0; k < rows * cols; k++)
+        if (h_w[k] == -128) {
+            eoc_set_error("eoc_weights_to_device: weight (%zu, %zu) is -128; weights lie in [-127, 127]", k / cols, k % cols);
+            return EOC_ERR_ARG;
+        }
+    const size_t L = dot_lists(cols), npoly = rows * L;
+    std::vector<int32_t> V(npoly * kN, 0);
+    std::vector<int8_t> pad(npoly * kN, 0);
+    for (size_t r = 0; r < rows; r++)
+        for (size_t k = 0; k < cols; k++) {
+            const int32_t w = h_w[r * cols + k];
+            const size_t j = k % kN;
+            V[(r * L + k / kN) * kN + (j ? kN - j : 0)] = j ? -w : w;
+            pad[r * L * kN + k] = (int8_t)w;
+        }
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (stream_is_capturing(st)) {
+        eoc_set_error("eoc_weights_to_device: a model load allocates and synchronises; it cannot be captured");
+        return EOC_ERR_STATE;
+    }
+    DevTmp d_v;
+    HIP_TRY(d_v.alloc(V.size() * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(d_v.p, V.data(), V.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    int rc = launch_fft_fwd(e, d_v.i32(), static_cast<double *>(d_image), npoly, 1.0, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(static_cast<char *>(d_image) + npoly * kNH * sizeof(d2), pad.data(), pad.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st)); // the host vectors and the staging buffer end with this call
+    return EOC_OK;
+} catch (...) {
+    eoc_set_error("eoc_weights_to_device: out of memory");
+    return EOC_ERR_ALLOC;
+}
+
+// Both device calls: per slice of whole input vectors, k_fft_fwd_polys of the slice's lists into the workspace, k_dot_init
+// (the start of every mask row, the whole body), k_dot_mask (one wave per sample and chunk).  d_out = NULL: the samples under
+// s' go to d_u [batch][rows][N+1].  Otherwise the mask rows are the key switch's operand rows and the key switch follows
+// (init_done), as behind k_compact_expand.  All arguments travel as kernel arguments: no descriptor ring slot.
+static int dot_locked(eoc_engine *e, const char *who, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists,
+                      size_t batch, const int32_t *d_bias, int32_t *d_u, int32_t *d_out, hipStream_t st)
+{
+    const size_t L = dot_lists(cols), per_vec = L * 2 * kNH * sizeof(d2);
+    if (e->dot_ws_bytes < per_vec) {
+        eoc_set_error("%s: one input vector needs %zu bytes of workspace, the budget (EOC_TFHE_DOT_WS_BYTES) is %zu", who, per_vec,
+                      e->dot_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    WS &W = e->ws;
+    const size_t bs = std::min({batch, e->dot_ws_bytes / per_vec, std::max<size_t>(1, ((size_t)1 << 20) / rows)});
+    int rc = scratch_reserve(e, e->dot_specs, bs * per_vec, "list spectra", st);
+    if (!rc && d_out) rc = ensure_ws(e, W, bs * rows, 0, 0, st);
+    if (rc) return rc;
+    const d2 *wspec = static_cast<const d2 *>(d_image);
+    const int8_t *wts = reinterpret_cast<const int8_t *>(wspec + rows * L * kNH);
+    const d2 *lspec = static_cast<const d2 *>(e->dot_specs.p);
+    const uint32_t nchunks = (uint32_t)((L + kDotChunk - 1) / kDotChunk);
+    const size_t n = (size_t)e->p.n;
+    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    for (size_t b0 = 0; b0 < batch; b0 += bs) {
+        const size_t B = std::min(bs, batch - b0), S = B * rows;
+        const int32_t *lists = d_lists + b0 * L * 2 * kN;
+        uint32_t *mask = d_out ? W.d_ubar : reinterpret_cast<uint32_t *>(d_u + b0 * rows * (kN + 1));
+        const size_t mask_stride = d_out ? (size_t)kN : (size_t)kN + 1;
+        int32_t *body = d_out ? d_out + b0 * rows * (n + 1) : d_u + b0 * rows * (kN + 1);
+        {
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            rc = launch_fft_fwd(e, lists, static_cast<double *>(e->dot_specs.p), B * L * 2, 0x1p-9, st);
+            if (rc) return rc;
+        }
+        {
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            if (d_out)
+                hipLaunchKernelGGL(k_dot_init<true>, dim3((unsigned)S), dim3(256), 0, st, wts, lists, d_bias, (uint32_t)rows,
+                                   (uint32_t)L, mask, mask_stride, prec_offset, body, n + 1, (int)n, (int)n);
+            else
+                hipLaunchKernelGGL(k_dot_init<false>, dim3((unsigned)S), dim3(256), 0, st, wts, lists, d_bias, (uint32_t)rows,
+                                   (uint32_t)L, mask, mask_stride, 0u, body, (size_t)kN + 1, 0, kN);
+            HIP_TRY(hipGetLastError());
+        }
+        {
+            const uint32_t items = (uint32_t)(S * nchunks);
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            hipLaunchKernelGGL(k_dot_mask<kDotChunk>, dim3((items + kDotWavesPerWG - 1) / kDotWavesPerWG), dim3(64 * kDotWavesPerWG), kDotLds, st,
+                               wspec, lspec, mask, mask_stride, (uint32_t)rows, (uint32_t)L, nchunks, items, (const d2 *)e->d_tw,
+                               (const d2 *)e->d_twist);
+            HIP_TRY(hipGetLastError());
+            e->dot_launches++;
+        }
+        if (d_out) {
+            const GateDesc d{OP_RAW, 0, nullptr, nullptr, nullptr, body};
+            rc = launch_keyswitch(e, W, nullptr, 1, (uint32_t)S, st, true, &d);
+            if (rc) return rc;
+            e->stats[2] += S;
+        }
+    }
+    return EOC_OK;
+}
+
+static bool dot_ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+// argument checks shared by both device calls; out: the output buffer of out_stride words per sample
+static int dot_check(eoc_engine *e, const char *who, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists,
+                     size_t batch, const int32_t *d_bias, const int32_t *out, size_t out_stride)
+{
+    if (!e || !d_image || !d_lists || !out) {
+        eoc_set_error("%s: null argument", who);
+        return EOC_ERR_ARG;
+    }
+    if (!dot_shape_ok(rows, cols)) {
+        eoc_set_error("%s: rows = %zu, cols = %zu: both must lie in [1, 2^20]", who, rows, cols);
+        return EOC_ERR_ARG;
+    }
+    const size_t out_bytes = batch * rows * out_stride * 4;
+    if (dot_ranges_overlap(out, out_bytes, d_lists, batch * dot_lists(cols) * 2 * kN * 4) ||
+        dot_ranges_overlap(out, out_bytes, d_image, eoc_weights_image_bytes(rows, cols)) ||
+        dot_ranges_overlap(out, out_bytes, d_bias, rows * 4)) {
+        eoc_set_error("%s: the output must not overlap the lists, the weight image or the bias", who);
+        return EOC_ERR_ARG;
+    }
+    return EOC_OK;
+}
+
+extern "C" int eoc_dot_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists, size_t batch,
+                              const int32_t *d_bias, int32_t *d_u, void *hip_stream)
+{
+    if (e && batch * rows == 0) return EOC_OK;
+    if (int rc = dot_check(e, "eoc_dot_device", d_image, rows, cols, d_lists, batch, d_bias, d_u, (size_t)kN + 1)) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    return dot_locked(e, "eoc_dot_device", d_image, rows, cols, d_lists, batch, d_bias, d_u, nullptr, (hipStream_t)hip_stream);
+}
+
+extern "C" int eoc_linear_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists, size_t batch,
+                                 const int32_t *d_bias, int32_t *d_out, void *hip_stream)
+{
+    if (!e) {
+        eoc_set_error("eoc_linear_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->ksk) {
+        eoc_set_error("eoc_linear_device: no key-switch key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    if (batch * rows == 0) return EOC_OK;
+    if (int rc = dot_check(e, "eoc_linear_device", d_image, rows, cols, d_lists, batch, d_bias, d_out, (size_t)e->p.n + 1)) return rc;
+    return dot_locked(e, "eoc_linear_device", d_image, rows, cols, d_lists, batch, d_bias, nullptr, d_out, (hipStream_t)hip_stream);
+}
+extern "C" uint64_t eoc_engine_dot_launches(eoc_engine *e) { return e ? e->dot_launches : 0; }
+// tables + four transpose scratches, as k_pack_rows (eoc_engine_create)
+static void set_dot_attrs()
+{
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dot_mask<kDotChunk>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              kDotLds);
+}

@@ -948,14 +948,15 @@ void compact_encrypt(const eoc_params &p, const int32_t *A, const int32_t *B, co
     }
 }
 } // namespace eoc_host
-// ints = false: bits (+-2^29, eoc_encrypt_bits' encoding); true: eoc_encrypt_ints' encoding at p in {2, 4, 8}.  Everything is
-// checked before anything is written.
+// ints = false: bits (+-2^29, eoc_encrypt_bits' encoding); true: eoc_encrypt_ints' encoding at p in {2, 4, 8}; torus given:
+// the Torus32 messages themselves (values is not read).  Everything is checked before anything is written.
 static int pk_encrypt(const char *what, const void *pk, size_t pk_len, const uint8_t *enc_key, bool keyed, uint64_t enc_seed,
-                      uint64_t first_list, bool ints, int p, const uint8_t *values, size_t count, int32_t *lists)
+                      uint64_t first_list, bool ints, int p, const uint8_t *values, size_t count, int32_t *lists,
+                      const int32_t *torus = nullptr)
 {
     eoc_params prm;
     std::vector<int32_t> ab;
-    if (!pk || !values || !lists || (keyed && !enc_key)) {
+    if (!pk || (!values && !torus) || !lists || (keyed && !enc_key)) {
         eoc_set_error("%s: null argument", what);
         return EOC_ERR_ARG;
     }
@@ -973,11 +974,22 @@ static int pk_encrypt(const char *what, const void *pk, size_t pk_len, const uin
             return EOC_ERR_ARG;
         }
     if (!count) return EOC_OK;
-    std::vector<int32_t> msgs(count);
+    std::vector<int32_t> msgs(torus ? 0 : count);
     const int32_t one8 = eoc_modswitch_to_torus32(1, 8);
-    for (size_t i = 0; i < count; i++) msgs[i] = ints ? int_phase(values[i], p) : (values[i] ? one8 : -one8);
-    eoc_host::compact_encrypt(prm, ab.data(), ab.data() + EOC_N, enc_key, enc_seed, first_list, msgs.data(), count, lists);
+    for (size_t i = 0; i < msgs.size(); i++) msgs[i] = ints ? int_phase(values[i], p) : (values[i] ? one8 : -one8);
+    eoc_host::compact_encrypt(prm, ab.data(), ab.data() + EOC_N, enc_key, enc_seed, first_list, torus ? torus : msgs.data(), count,
+                              lists);
     return EOC_OK;
+}
+extern "C" int eoc_pk_encrypt_torus(const void *pk, size_t pk_len, uint64_t enc_seed, uint64_t first_list, const int32_t *msgs,
+                                    size_t count, int32_t *lists)
+{
+    return pk_encrypt("eoc_pk_encrypt_torus", pk, pk_len, nullptr, false, enc_seed, first_list, false, 0, nullptr, count, lists, msgs);
+}
+extern "C" int eoc_pk_encrypt_torus_keyed(const void *pk, size_t pk_len, const uint8_t enc_key[32], uint64_t first_list,
+                                          const int32_t *msgs, size_t count, int32_t *lists)
+{
+    return pk_encrypt("eoc_pk_encrypt_torus_keyed", pk, pk_len, enc_key, true, 0, first_list, false, 0, nullptr, count, lists, msgs);
 }
 extern "C" int eoc_pk_encrypt_bits(const void *pk, size_t pk_len, uint64_t enc_seed, uint64_t first_list, const uint8_t *bits,
                                    size_t count, int32_t *lists)
@@ -1380,6 +1392,23 @@ extern "C" int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *o
         if (rc) return rc;
     }
     return eoc_compact_expand_engines(lists, count, out);
+}
+// inner products with public weights on the global context's engines: WHOLE input vectors are cut over the
+// engines (brought up behind the global key on first use; a cloud key alone suffices)
+extern "C" int eoc_linear(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch, const int32_t *h_bias,
+                          int32_t *h_out)
+{
+    if (!h_w || !h_lists || !h_out) {
+        eoc_set_error("eoc_linear: null argument");
+        return EOC_ERR_ARG;
+    }
+    GlobalCtx &c = ctx();
+    std::lock_guard<std::mutex> g(c.mu);
+    if (c.params()) {
+        int rc = ensure_engine_locked();
+        if (rc) return rc;
+    }
+    return eoc_linear_engines(h_w, rows, cols, h_lists, batch, h_bias, h_out);
 }
 // seeded samples -> LWE samples on the global context's engines: samples are cut into eoc_shard_range blocks,
 // one per engine; every block's upload and kernel are queued before the first result is collected.  No key is used: the

@@ -2209,4 +2209,110 @@ __global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_automaton_step(Aut
 }
 #undef EOC_NEGACYCLIC
 
+// =================================================================================================
+// Inner products with public integer weights: output sample (b, r) is the LWE sample under s' with phase
+//   bias[r] + sum_k w[r][k] phase(slot k of vector b),
+// vector b = L compact lists [L][2][N], input k in slot k mod N of list k / N, w int8 in [-127, 127].  With the weight
+// polynomial V_{r,l}: V[0] = w[r][lN], V[N - k] = -w[r][lN + k], coefficient 0 of V C is sum_k w_k C[k], so the sample is
+// slot 0 of sum_l V_{r,l} (c0, c1)_{b,l}: mask a'_0 = P0[0], a'_i = -P0[N - i] with P0 = sum_l V_{r,l} c0_{b,l}, and body
+// b' = bias[r] + sum_k w[r][k] c1_b[k], an exact wrapping integer sum (no transform).
+// Format rule: the products of 8 consecutive lists (a chunk) are accumulated in the spectral domain, l ascending, the
+// weight spectrum (k_fft_fwd_polys at scale 1) in the digit's place and the list spectrum (k_fft_fwd_polys at scale 2^-9)
+// in the key row's; every chunk is inverse-transformed and converted once (|.| <= 8 * 1024 * 127 * 2^31 < 2^51:
+// wrap_trunc's contract holds unconditionally).  Chunks combine by integer addition, so their order -- and the atomics
+// below -- cannot change a bit.
+// =================================================================================================
+constexpr int kDotChunk = 8;      // lists per inverse transform (part of the format)
+constexpr int kDotWavesPerWG = 4;
+constexpr int kDotLds = (kTwEntries + kNH + kDotWavesPerWG * kScr) * 16; // 53 760 bytes: two workgroups per CU
+
+// Start of every output sample and the whole body: one workgroup per sample s = b rows + r of the slice.  The mask row
+// mask[s mask_stride + i], i < N, is filled with `fill` (0, or the key switch's 2^(31 - t basebit): k_dot_mask then adds
+// the mask words and the row is the key switch's operand, as k_compact_expand leaves it); body[s body_stride + m] = 0 for
+// m < nzero and body[s body_stride + body_at] = b'.  wts: the zero-padded weights [rows][L N] int8 behind the spectra of
+// the device image; lists: [batch][L][2][N].  grid: x = samples; block = 256.
+// Both kernels are templates (OPERAND: the key-switch form, whose body row is cleared in front of b'; CHUNK: the format's
+// chunk), defined and first used behind every other kernel: the device compiler emits kernels in that order, and the
+// earlier ones keep their label numbers (k_tvpack_cols).
+template <bool OPERAND>
+__global__ __launch_bounds__(256) void k_dot_init(const int8_t *__restrict__ wts, const int32_t *__restrict__ lists,
+                                                   const int32_t *__restrict__ bias, uint32_t rows, uint32_t L,
+                                                   uint32_t *__restrict__ mask, size_t mask_stride, uint32_t fill,
+                                                   int32_t *__restrict__ body, size_t body_stride, int nzero, int body_at)
+{
+    __shared__ uint32_t s_part[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t s = blockIdx.x, b = s / rows, r = s - b * rows;
+    const int8_t *w = wts + (size_t)r * L * kN;
+    const int32_t *c1 = lists + (size_t)b * L * 2 * kN + kN;
+    uint32_t acc = 0;
+    for (uint32_t l = 0; l < L; l++)
+        for (int j = tid; j < kN; j += 256)
+            acc += (uint32_t)(int32_t)w[(size_t)l * kN + j] * (uint32_t)c1[(size_t)l * 2 * kN + j];
+#pragma unroll
+    for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if (lane == 0) s_part[wv] = acc;
+    uint32_t *row = mask + (size_t)s * mask_stride;
+    for (int i = tid; i < kN; i += 256) row[i] = fill;
+    int32_t *o = body + (size_t)s * body_stride;
+    if constexpr (OPERAND) // the key switch's output row (0, ..., 0, b'); the sample form has its mask there
+        for (int m = tid; m < nzero; m += 256) o[m] = 0;
+    __syncthreads();
+    if (tid == 0) o[body_at] = (int32_t)((bias ? (uint32_t)bias[r] : 0u) + s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+}
+
+// One WAVE per (sample, chunk), as k_pack_rows: the one spectral accumulator stays in registers, nothing is exchanged
+// between waves, one barrier (the tables).  wspec [rows][L][512] complex, lspec [batch][L][2][512] complex (both
+// polynomials of every list are transformed by the one k_fft_fwd_polys launch; polynomial 0 is read), both 16 bytes per
+// lane, 1 KiB per wave and instruction.  The first list of a chunk starts the chain as a plain product (cmul0, as every
+// chain).  Coefficient j of the chunk's product goes to mask word (N - j) mod N, negated for j > 0: vector integer atomics,
+// lane-contiguous (descending).
+// grid: x = ceil(items / 4), items = samples x chunks; block = 256.
+template <int CHUNK>
+__global__ __launch_bounds__(64 * kDotWavesPerWG, 2) void k_dot_mask(const d2 *__restrict__ wspec, const d2 *__restrict__ lspec,
+                                                                     uint32_t *__restrict__ mask, size_t mask_stride,
+                                                                     uint32_t rows, uint32_t L, uint32_t nchunks,
+                                                                     uint32_t items, const d2 *__restrict__ g_tw,
+                                                                     const d2 *__restrict__ g_twist)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    d2 *s_tw = reinterpret_cast<d2 *>(smem);
+    d2 *s_twist = s_tw + kTwEntries;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    d2 *scr = s_twist + kNH + wv * kScr;
+    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 64 * kDotWavesPerWG);
+    __syncthreads(); // the tables; the only barrier
+    const uint32_t item = blockIdx.x * kDotWavesPerWG + (uint32_t)wv;
+    if (item >= items) return;
+    const uint32_t s = item / nchunks, chunk = item - s * nchunks;
+    const uint32_t b = s / rows, r = s - b * rows;
+    const uint32_t l_first = chunk * CHUNK, l_end = min(l_first + (uint32_t)CHUNK, L);
+
+    const d2 *pw = wspec + ((size_t)r * L + l_first) * kNH + lane;
+    const d2 *pc = lspec + ((size_t)b * L + l_first) * 2 * kNH + lane;
+    d2 S[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) S[q] = cmul0(pw[q * 64], pc[q * 64]);
+#pragma unroll 1
+    for (uint32_t l = l_first + 1; l < l_end; l++) {
+        pw += kNH;
+        pc += 2 * kNH;
+#pragma unroll
+        for (int q = 0; q < 8; q++) S[q] = cmac1(pw[q * 64], pc[q * 64], S[q]);
+    }
+
+    int *po = reinterpret_cast<int *>(mask + (size_t)s * mask_stride);
+    d2 ut[8];
+    fft_inv_wave(S, ut, s_tw, s_twist, scr, lane);
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const int j = lane + 64 * q;
+        const d2 y = cmulc(S[q], ut[q]); // 1/512 is in the list image
+        const uint32_t vx = wrap_trunc(y.x), vy = wrap_trunc(y.y);
+        atomicAdd(po + ((kN - j) & (kN - 1)), (int)(j ? 0u - vx : vx));
+        atomicAdd(po + (kNH - j), (int)(0u - vy));
+    }
+}
+
 } // namespace eoc

@@ -627,6 +627,34 @@ int slot_pack_block(Slot &s, const int32_t *cts, size_t count, int32_t *lists, s
     return slot_finish(st, run());
 }
 
+// one device's block of WHOLE input vectors [lo, hi) of an inner product with public weights: the weights
+// become the device image here (every engine builds its own), lists [batch][L][2][N] and bias [rows] (or NULL) in,
+// out [batch][rows][stride] on the host
+int slot_linear_block(Slot &s, const int8_t *h_w, size_t rows, size_t cols, const int32_t *lists, const int32_t *bias, int32_t *out,
+                      size_t lo, size_t hi, size_t stride_ints)
+{
+    const size_t blk = hi - lo;
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const size_t vec_ints = (cols + EOC_N - 1) / EOC_N * 2 * EOC_N, out_ints = rows * stride_ints;
+    int32_t *d_img, *d_lists, *d_bias, *d_out; // the image first: its spectra are read 16 bytes at a time
+    int rc = Staging().take(d_img, eoc_weights_image_bytes(rows, cols) / 4).take(d_lists, blk * vec_ints)
+                 .take(d_bias, rows).take(d_out, blk * out_ints).commit(s);
+    if (rc) return rc;
+    hipStream_t st = s.st[0];
+    auto run = [&]() -> int {
+        int r = eoc_weights_to_device(s.e, h_w, rows, cols, d_img, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(d_lists, lists + lo * vec_ints, blk * vec_ints * 4, hipMemcpyHostToDevice, st));
+        if (bias) HIP_TRY(hipMemcpyAsync(d_bias, bias, rows * 4, hipMemcpyHostToDevice, st));
+        r = eoc_linear_device(s.e, d_img, rows, cols, d_lists, blk, bias ? d_bias : nullptr, d_out, st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(out + lo * out_ints, d_out, blk * out_ints * 4, hipMemcpyDeviceToHost, st));
+        return EOC_OK;
+    };
+    return slot_finish(st, run());
+}
+
 void destroy_slots_locked()
 {
     for (auto &s : G.slots)
@@ -1384,6 +1412,25 @@ int eoc_pack_engines(const int32_t *cts, size_t count, int32_t *lists)
     const size_t stride = (size_t)G.p.n + 1, n_lists = (count + EOC_N - 1) / EOC_N;
     return for_each_block(n_lists, [=](int i, size_t lo, size_t hi) {
         return slot_pack_block(G.slots[i], cts, count, lists, lo, hi, stride);
+    });
+}
+
+// eoc_linear's engine half (host.cpp has checked the pointers, holds the global key's lock and has brought the engines up; the
+// model is validated by every engine's load before it touches its device): whole input vectors per engine
+int eoc_linear_engines(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch, const int32_t *h_bias,
+                       int32_t *h_out)
+{
+    std::lock_guard<std::mutex> g(G.mu);
+    if (int rc = enter_locked("eoc_linear", ENGINES)) return rc;
+    if (eoc_weights_image_bytes(rows, cols) == 0) {
+        eoc_set_error("eoc_linear: rows = %zu, cols = %zu: both must lie in [1, 2^20]", rows, cols);
+        return EOC_ERR_ARG;
+    }
+    if (!batch) return EOC_OK;
+    if (int rc = enter_locked("eoc_linear")) return rc;
+    const size_t stride = (size_t)G.p.n + 1;
+    return for_each_block(batch, [=](int i, size_t lo, size_t hi) {
+        return slot_linear_block(G.slots[i], h_w, rows, cols, h_lists, h_bias, h_out, lo, hi, stride);
     });
 }
 

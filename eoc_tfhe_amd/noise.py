@@ -638,3 +638,54 @@ def lut2_margin_sigma(p, n_tables, params, lwe_key, tlwe_key, x_var=None, y_var=
     vx = v_out if x_var is None else float(x_var)
     vy = v_out if y_var is None else float(y_var)
     return (lut_margin_sigma_var(p, max(int(n_tables), 1), vx, lwe_key), lut_margin_sigma_var(p, 1, vy, lwe_key))
+
+
+# ---- inner products with public integer weights on compact lists ---------------------------------------------
+def linear_var(params, w_row, slot_var):
+    """variance (torus units) of the phase of one output of eoc_dot_device around its mean: ||w||^2 slot_var for independent
+    slots of variance slot_var each -- for the slots of fresh lists, which share u and e1, the variance over lists AND rows of
+    independent zero-mean weights; one fixed row: linear_var_row (compact_var for fresh lists; a bootstrap output's total_var + pack_var behind
+    eoc_pack_device).  The operation itself adds nothing: the body is an exact integer sum and the mask differs from the
+    exact product by the conversion's few units of 2^-32 per chunk.  eoc_linear_device's key switch adds predict()['ks_var']
+    and ['ks_mean'] on top."""
+    w = np.asarray(w_row, np.float64).ravel()
+    return float((w * w).sum()) * float(slot_var)
+
+
+def linear_offset(params, pk_or_key, w_row, tlwe_key=None):
+    """mean error (torus units) of one output of eoc_dot_device on FRESH lists under one public key: every list's slots
+    carry compact_offset (a fresh binary u per list has mean 1/2, the key's e is the same for all of them), so the output
+    carries sum_k w_k compact_offset[k mod N] = (1/2) sum_l (V_l J e)[0] -- derived from the key, nothing fitted.
+    pk_or_key: a SecretKey (its own public key and TLWE key are used), or a PublicKey / EOCPK1 blob / (A, B) pair together
+    with tlwe_key."""
+    if tlwe_key is None:
+        tlwe_key, pk = pk_or_key.tlwe_key, pk_or_key.public_key_bytes()
+    else:
+        pk = pk_or_key
+    off = compact_offset(tlwe_key, pk)
+    w = np.asarray(w_row, np.float64).ravel()
+    return float((w * off[np.arange(w.size) % N]).sum())
+
+
+def linear_var_row(params, w_row, tlwe_key, pk):
+    """linear_var for ONE weight row on fresh lists under one key, exactly: the output's error is coefficient 0 of
+    V (u e + e2 - e1 s') summed over the lists, so its variance over the lists' randomness is
+      sum_l ||V_l e||^2 / 4 + ||w||^2 sigma^2 + sum_l ||V_l s'||^2 sigma^2.
+    linear_var(compact_var) is its mean over rows of independent zero-mean weights; over 200 random rows a single row is 0.66 - 2.10 of it
+    (standard deviation 0.29, either default set), because s' and a binary u have mean 1/2: V (1/2) J is the running sum of the weights, a
+    random walk whose energy does not average out inside one row.  Nothing is fitted."""
+    w = np.asarray(w_row, np.float64).ravel()
+    e = pk_noise(pk, tlwe_key)
+    s1 = np.asarray(tlwe_key, np.float64)
+    sig2 = _sig2(params)
+    out = float((w * w).sum()) * sig2
+    for l0 in range(0, w.size, N):
+        wl = np.zeros(N)
+        wl[:min(N, w.size - l0)] = w[l0:l0 + N]
+        V = np.concatenate(([wl[0]], -wl[:0:-1]))                      # V[0] = w[0], V[N - k] = -w[k]
+        for poly, scale in ((e, 0.25), (s1, sig2)):
+            full = np.convolve(V, poly)
+            r = full[:N].copy()
+            r[:N - 1] -= full[N:]
+            out += scale * float((r * r).sum())
+    return out

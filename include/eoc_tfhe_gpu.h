@@ -964,6 +964,60 @@ int eoc_dbg_chacha20_blocks_device(eoc_engine *e, const uint8_t key[32], uint64_
 int eoc_seeded_expand(const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies, size_t count, int32_t *out);
 int eoc_global_import_seeded_cloud_key_blob(const void *buf, size_t len);
 
+/* ---- inner products with public integer weights on compact lists --------------------------------------------
+ * A weighted sum of many encrypted values with PUBLIC weights, ready for one bootstrap: a dense layer of a discretised
+ * network, a linear classifier, a score.  With the inputs packed in lists, an output costs one spectral multiply-add per
+ * list, one inverse transform per 8 lists and ONE key switch -- not one key switch per input.
+ *   weights     w[rows][cols] int8, every value in [-127, 127] (-128: EOC_ERR_ARG); weights past `cols` are zero.
+ *               bias[rows] Torus32, optional.  rows, cols in [1, 2^20].
+ *   inputs      `batch` vectors of L = ceil(cols / N) lists each, [batch][L][2][N] int32, c0 first: input k of a vector in slot
+ *               k mod N of its list k / N (eoc_pk_encrypt_*, eoc_pack_device).
+ *   output      for every (vector b, row r) one LWE sample of dimension N under s', [N+1] -- what eoc_blind_rotate_device
+ *               emits and eoc_keyswitch_device takes -- of phase bias[r] + sum_k w[r][k] phase(slot k of vector b).
+ *   rule        wrapping 32-bit arithmetic.  Weight polynomial V of (r, l): V[0] = w[r][lN], V[N - k] = -w[r][lN + k];
+ *               coefficient 0 of V C is sum_k w_k C[k].  Body b' = bias[r] + sum_k w[r][k] c1_b[k], an exact integer sum.
+ *               Mask: P0 = sum_l V_{r,l} c0_{b,l}, a'_0 = P0[0], a'_i = -P0[N - i].  The products are negacyclic products in
+ *               the canonical transform: weight spectrum = the unscaled forward transform of V, list spectrum = the forward
+ *               transform at scale 2^-9 (eoc_tgsw_to_fft_device's image), accumulated list by list (ascending) in the chains'
+ *               nesting, the weight spectrum in the digit's place.  8 consecutive lists are a CHUNK: one inverse transform and
+ *               conversion per chunk (8 * 1024 * 127 * 2^31 < 2^51: the conversion's contract holds for every input); chunks
+ *               combine by integer addition.  The chunk is part of the format: eoc_dot_device equals the CPU reference
+ *               tests/c/dot_ref.c byte for byte, and the exact product up to the conversion's few units per chunk.
+ *   image       eoc_weights_to_device builds the model's device image once: the weight spectra [rows][L][512] complex f64
+ *               (sigma order, as every image), then the weights [rows][L N] int8, zero-padded; eoc_weights_image_bytes(rows,
+ *               cols) = rows L (8192 + 1024) bytes (0 for a shape that is refused).  A model load: checked on the host, no key,
+ *               allocates a staging buffer and drains `hip_stream` (EOC_ERR_STATE under capture).
+ *   noise       noise.linear_var = |w|^2 x the per-slot variance (the mean over rows of independent weights; one fixed row under
+ *               one key: noise.linear_var_row, exact); for fresh lists the fixed offset noise.linear_offset.
+ *   security    nothing new: the weights are public, the inputs are the lists of DESIGN.md 11 and every step is a public
+ *               linear map of them.
+ *   engine      eoc_dot_device needs NO key and writes d_u DEVICE [batch][rows][N+1]; eoc_linear_device is the same operation
+ *               followed by the key switch (EOC_ERR_NO_KEY without a cloud key), d_out DEVICE [batch][rows][n+1]: its mask
+ *               kernel writes the key switch's operand rows directly.  batch x rows = 0 is a no-op; EOC_ERR_ARG when the
+ *               output overlaps the lists, the image or the bias.  Workspace: the list spectra of a slice of whole vectors
+ *               (16 KiB per list; budget EOC_TFHE_DOT_WS_BYTES, default 256 MiB; slices of at most 2^20 samples), grown as
+ *               every workspace: EOC_ERR_STATE if it would grow under capture (run one call of the shape first;
+ *               eoc_engine_reserve(batch x rows, 0, 0) for eoc_linear_device).  Arguments travel as kernel arguments: no
+ *               descriptor ring slot.  eoc_engine_dot_launches counts one per slice; the key switches are counted in the
+ *               stats; eoc_engine_kernel_times books the new kernels under the key switch.
+ *   host        eoc_linear: host buffers on the global context (a cloud key alone suffices: key mode 2), synchronous; WHOLE
+ *               input vectors are cut into eoc_shard_range blocks, one per engine; every engine builds the image itself.
+ *   messages    eoc_pk_encrypt_torus(_keyed): lists of ARBITRARY Torus32 messages (int32 per slot), e.g. x_k Delta; the same
+ *               streams, u, e1 and e2 as eoc_pk_encrypt_bits -- the bits' lists are those of the messages +-2^29. */
+size_t eoc_weights_image_bytes(size_t rows, size_t cols);
+int eoc_weights_to_device(eoc_engine *e, const int8_t *h_w, size_t rows, size_t cols, void *d_image, void *hip_stream);
+int eoc_dot_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists, size_t batch,
+                   const int32_t *d_bias /* may be NULL */, int32_t *d_u, void *hip_stream);
+int eoc_linear_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists, size_t batch,
+                      const int32_t *d_bias /* may be NULL */, int32_t *d_out, void *hip_stream);
+uint64_t eoc_engine_dot_launches(eoc_engine *e);
+int eoc_linear(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch,
+               const int32_t *h_bias /* may be NULL */, int32_t *h_out);
+int eoc_pk_encrypt_torus(const void *pk, size_t pk_len, uint64_t enc_seed, uint64_t first_list, const int32_t *msgs,
+                         size_t count, int32_t *lists);
+int eoc_pk_encrypt_torus_keyed(const void *pk, size_t pk_len, const uint8_t enc_key[32], uint64_t first_list,
+                               const int32_t *msgs, size_t count, int32_t *lists);
+
 #ifdef __cplusplus
 }
 #endif
