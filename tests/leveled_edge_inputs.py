@@ -6,7 +6,9 @@ arbitrary samples; random words meet neither a rounding-cell end nor an all-end-
 conversion contract (|v| < 2^51, include/eoc_tfhe_gpu.h) needs a crafted key.  The rows made here do.
 
   cmux_differences(l, Bgbit)  named TLWE differences [k][2][N] uint32: zero, digits_min, digits_max, cells, deltas,
-                              alternating (the difference the alternating INPUTS of cmux_inputs have).
+                              alternating (the difference the alternating INPUTS of cmux_inputs have).  Also what
+                              k_demux decomposes as x itself (tests/test_gpu_demux_instances.py) and what the states of
+                              tests/automaton_edge_inputs.py put under k_automaton_step through its two rotations.
   cmux_inputs(l, Bgbit)       name -> (in0, in1) int32 [k][2][N] with in1 - in0 the named difference: in0 random full-range
                               words (so that the final + A wraps too), except `alternating`: INT32_MIN / INT32_MAX words in
                               opposite phase, where the subtraction itself wraps.

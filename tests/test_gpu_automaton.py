@@ -1,7 +1,8 @@
 """Finite automata on encrypted bit strings on the MI355X: k_automaton_step and the run driver against the
 composed reference (tests/automaton_oracle.py) word for word, the decrypted results against Automaton.evaluate_plain, a run
 captured into a hipGraph (the helpers of tests/capture_cases.py), and the calls next to it on the same engine left alone.
-Host side: tests/test_automaton_cpu.py."""
+Host side: tests/test_automaton_cpu.py.  Every k_automaton_step instance on edge differences, at every weight, with strides of its
+own and inside a run of one step: tests/test_gpu_automaton_instances.py."""
 import itertools
 
 import numpy as np
