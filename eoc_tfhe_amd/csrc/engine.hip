@@ -29,13 +29,7 @@ using namespace eoc;
         }                                                                                   \
     } while (0)
 
-// The six pair shapes (gadget length l, Bgbit; Bgbit 0 = any, read at run time): the two default sets, then every length.
-// Every ladder over k_blind_rotate* / k_br_enc and the instance lists of the leveled families (LeveledFamily) are generated
-// from this list, in this order (the device compiler emits the instances in the order they are named: DESIGN.md 15).
-#define EOC_PAIR_SHAPES(X) X(2, 10) X(3, 7) X(1, 0) X(2, 0) X(3, 0) X(4, 0)
-// one rung: taken by the first shape of the list that fits gadget (l, bg), while `fn` is still unset
-#define EOC_IF_SHAPE(L, B, l, bg) if (!fn && (l) == L && (B == 0 || (bg) == B))
-
+// ---- engine state, workspace and scratch ---------------------------------------------------
 // Grow-only device scratch, sized by a call's own arguments: grown by scratch_reserve alone, to exactly the bytes asked for
 struct Scratch {
     void *p = nullptr;
@@ -258,91 +252,6 @@ static int upload_tables(eoc_engine *e)
     HIP_TRY(hipDeviceSynchronize());
     return EOC_OK;
 }
-
-// One family of leveled kernels (kernels.hip.h, leveled_pair.inc): a wave pair per item, k_cmux's grid, block and LDS plan,
-// args struct Args.  The three families go through one lookup, one attribute routine and one launcher (leveled_kernel,
-// set_leveled_attrs, launch_leveled).
-// WHERE a family is defined is part of the device code's text: a description is the first place that names its template's
-// instances, the device compiler emits templates in the order of their first use, and branch labels carry the function's
-// number.  kCmuxFamily stands right behind eoc_engine_create, where k_cmux was first named (behind k_keyswitch_waves, ahead
-// of the blind-rotation kernels); kDemuxFamily and kAutomatonFamily each open their section, behind every kernel that
-// existed when they were added, so the earlier kernels keep their text instruction for instruction.  A new family goes
-// behind the last one, with its section.
-template <class Args> struct LeveledFamily {
-    const char *name;               // the kernel's, for error messages
-    uint64_t eoc_engine::*launches; // the counter a launch bumps
-    const void *fn[6];              // the instances, in the order of EOC_PAIR_SHAPES
-};
-static void set_leveled_attrs(); // of all three families: defined behind the last one
-static void set_dot_attrs();     // of k_dot_mask: defined at the end of the file, where the kernel is first named
-extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **out)
-{
-    if (!out || !valid_params(p)) {
-        eoc_set_error("eoc_engine_create: bad arguments (need 1 <= n <= 1023, 1 <= l <= 4, l * Bgbit <= 32, l * 2^Bgbit <= 8192 "
-                      "-- the FP64 external product is not exact beyond that --, ks_t * ks_basebit <= 31, ks_basebit <= 4)");
-        return EOC_ERR_ARG;
-    }
-    int cnt = eoc_device_count();
-    if (cnt <= 0 || device < 0 || device >= cnt) {
-        eoc_set_error("eoc_engine_create: no usable HIP device (count=%d, asked %d); the gate path has no CPU fallback",
-                      cnt, device);
-        return EOC_ERR_NO_DEVICE;
-    }
-    HIP_TRY(hipSetDevice(device));
-    eoc_engine *e = new (std::nothrow) eoc_engine();
-    if (!e) return EOC_ERR_ALLOC;
-    e->device = device;
-    e->p = *p;
-    e->kpl = 2 * p->l;
-    e->n1p = eoc_ksk_row_stride(p);
-    e->bara_stride = (p->n + 1 + 31) / 32 * 32; // rows 64 bytes apart: two jobs never share a (scalar) cache line
-    int rc = upload_tables(e);
-    if (rc) {
-        delete e;
-        return rc;
-    }
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) e->num_cus = cus;
-        if (const char *s = getenv("EOC_TFHE_PRIO_DUTY")) e->prio_duty_override = atoi(s);
-        if (const char *s = getenv("EOC_TFHE_PRIO_MULTI")) e->prio_multi = atoi(s);
-        if (const char *s = getenv("EOC_TFHE_BR_SLICE")) e->br_slice = atoi(s);
-        if (getenv("EOC_TFHE_NO_FOLD")) e->no_fold = true;
-        if (getenv("EOC_TFHE_NO_POOL")) e->no_pool = true;
-        if (const char *s = getenv("EOC_TFHE_SCALAR_ABAR")) e->scalar_abar = atoi(s) != 0;
-        if (const char *s = getenv("EOC_TFHE_BR_PARTS")) e->br_parts = atoi(s);
-        if (const char *s = getenv("EOC_TFHE_BR_WIDE")) e->br_wide = atoi(s);
-        if (const char *s = getenv("EOC_TFHE_KS_MFMA")) e->ks_mfma = atoi(s) != 0;
-        if (const char *s = getenv("EOC_TFHE_BR_TABLES_LDS")) e->br_tables_lds = atoi(s) != 0;
-        if (const char *s = getenv("EOC_TFHE_INT_SLICE_ROWS")) e->int_slice_rows = atoi(s);
-        if (const char *s = getenv("EOC_TFHE_TABLE_WS_BYTES")) e->table_ws_bytes = (size_t)strtoull(s, nullptr, 10);
-        if (const char *s = getenv("EOC_TFHE_PACK_WS_BYTES")) e->pack_ws_bytes = (size_t)strtoull(s, nullptr, 10);
-        if (const char *s = getenv("EOC_TFHE_DOT_WS_BYTES")) e->dot_ws_bytes = (size_t)strtoull(s, nullptr, 10);
-    }
-    // the key-switch kernel uses > 64 KiB of dynamic LDS: raise the limit once, here, not on the launch path
-    // (a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to k_keyswitch_generic: slow, exact)
-#define EOC_KS_ATTR(TT, NWV, IWV)                                                                              \
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_keyswitch_waves<TT, NWV, IWV>),                  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, KS3Cfg<TT, NWV, IWV>::LDS_BYTES) != hipSuccess) \
-        e->ks_waves_ok = false
-    EOC_KS_ATTR(8, 8, 16);
-    EOC_KS_ATTR(8, 8, 32);
-    EOC_KS_ATTR(8, 4, 64);
-    EOC_KS_ATTR(8, 8, 64);
-#undef EOC_KS_ATTR
-    if (!e->ks_waves_ok) (void)hipGetLastError();
-    // so do the leveled kernels (tables + four transpose scratches); a device that refuses it cannot run the leveled calls
-    set_leveled_attrs();
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
-    set_dot_attrs();
-    (void)hipGetLastError();
-    *out = e;
-    return EOC_OK;
-}
-// first named here: see LeveledFamily
-#define EOC_INSTANCE(L, B) reinterpret_cast<const void *>(&k_cmux<L, B>),
-static const LeveledFamily<CmuxArgs> kCmuxFamily = {"k_cmux", &eoc_engine::cmux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE)}};
-#undef EOC_INSTANCE
 
 static void free_ws(eoc_engine::Workspace &W)
 {
@@ -707,8 +616,13 @@ extern "C" int eoc_engine_cloud_key_device(eoc_engine *e, const void **d_bkfft, 
     return EOC_OK;
 }
 
-// ---- launch helpers -------------------------------------------------------------------------
-typedef eoc_engine::Workspace WS;
+// ---- kernel instances and attributes ---------------------------------------------------------
+// The six pair shapes (gadget length l, Bgbit; Bgbit 0 = any, read at run time): the two default sets, then every length.
+// The ladder over the blind-rotation pair kernels and the instance lists of the leveled families (LeveledFamily) are
+// generated from this list: X(L, B, A) per shape, A handed through to every rung.
+#define EOC_PAIR_SHAPES(X, A) X(2, 10, A) X(3, 7, A) X(1, 0, A) X(2, 0, A) X(3, 0, A) X(4, 0, A)
+// one rung: taken by the first shape of the list that fits gadget (l, bg), while `fn` is still unset
+#define EOC_IF_SHAPE(L, B, l, bg) if (!fn && (l) == L && (B == 0 || (bg) == B))
 
 // What one blind rotation runs over; launch_blind_rotate refuses the combinations that mean nothing.
 struct BRWork {
@@ -728,94 +642,16 @@ struct BRWork {
     uint32_t S = 0;
 };
 
-// THE PLAN: the launches a blind rotation of `njobs_total` jobs is cut into -- a pure function of these integers.
-// One launch holds at most `br_slice` jobs (default: what is resident at once, four workgroups per CU): a launch in
-// which every workgroup is resident from the start runs with the wave-priority alternation and finishes all its
-// workgroups within half a per cent of each other (3.0 ms per 1024 jobs), while a launch of several rounds settles at
-// a 10 % lower rate (the arbiter's age bias), so wide levels are cut into back-to-back single-round launches.
-// Two kernel shapes (kernels.hip.h).  The pair kernel (one ciphertext = one wave pair) fills the chip with 4 x CUs
-// ciphertexts; the wide kernel (one ciphertext = one wave, gadget length 2 only) with 8 x CUs, and saves the partial-chain
-// exchange and its barriers.  A level wider than the pair kernel's resident set runs as full wide launches plus a
-// remainder: on the pair kernel when it fits its resident set (a half-empty wide launch has one wave per SIMD and runs
-// at 0.7 of the pair kernel's rate), on the wide kernel otherwise (tools/wide_sweep.py; DESIGN.md 5.1).
-struct BRSeg { uint32_t off, njobs; bool wide; };
-struct BRPlan {
-    std::vector<BRSeg> segs;
-    int parts; // consecutive launches (step ranges) per segment
-};
-static BRPlan plan_blind_rotate(uint32_t njobs_total, int num_cus, int l, int kpl, int n, int br_slice, int br_parts, int br_wide)
-{
-    const uint32_t resident_pair = 4u * (uint32_t)num_cus, resident_wide = 8u * (uint32_t)num_cus;
-    const bool can_wide = l == 2 && br_wide != 0;
-    const bool force_wide = can_wide && br_wide > 0;
-    const int auto_parts = kpl * 2 * kNH * 16 > 80 * 1024 ? 2 : 1;
-    BRPlan plan;
-    plan.parts = std::max(1, std::min(br_parts > 0 ? br_parts : auto_parts, n));
-    plan.segs.reserve(njobs_total / resident_pair + 2);
-    auto even = [&](uint32_t off, uint32_t total, uint32_t slice, bool wide) { // even slices: 1536 jobs as 768 + 768
-        if (plan.parts > 1 && slice > 16u * (uint32_t)num_cus) slice = 16u * (uint32_t)num_cus; // acc_state capacity
-        const uint32_t nsl = (total + slice - 1) / slice;
-        slice = (total + nsl - 1) / nsl;
-        for (uint32_t o = 0; o < total; o += slice) plan.segs.push_back({off + o, std::min(slice, total - o), wide});
-    };
-    if (br_slice != 0) // diagnostics: fixed slice (> 0) or one launch (< 0), one kernel shape
-        even(0, njobs_total, br_slice > 0 ? (uint32_t)br_slice : njobs_total, force_wide);
-    else if (force_wide)
-        even(0, njobs_total, resident_wide, true);
-    else if (!can_wide || njobs_total <= resident_pair)
-        even(0, njobs_total, resident_pair, false);
-    else {
-        const uint32_t full = njobs_total / resident_wide * resident_wide, rem = njobs_total - full;
-        if (full) even(0, full, resident_wide, true);
-        if (rem) even(full, rem, rem <= resident_pair ? resident_pair : resident_wide, rem > resident_pair);
-    }
-    return plan;
-}
-
-// THE ARGUMENTS of one launch: part `part` of `parts` of segment `sg`
-static BRArgs blind_rotate_args(const eoc_engine *e, const WS &W, const BRWork &w, const BRSeg &sg, int part, int parts)
-{
-    BRArgs a{};
-    a.bkfft = e->bkfft;
-    a.bara = W.d_bara + (size_t)sg.off * e->bara_stride;
-    a.u = W.d_u + (size_t)sg.off * (kN + 1);
-    a.njobs = sg.njobs;
-    a.n = e->p.n;
-    a.Bgbit = e->p.Bgbit;
-    a.bara_stride = e->bara_stride;
-    a.mu = (int32_t)(1u << 29);
-    a.stamps = e->d_stamps;
-    a.ks_descs = w.fold != BRWork::NONE ? w.descs : nullptr;
-    a.prep = w.fold == BRWork::KS_AND_PREP; // KS alone: k_prepare wrote the rotation amounts (three-operand gates)
-    a.inline_desc = w.inline_desc != nullptr;
-    if (w.inline_desc) {
-        a.desc0 = *w.inline_desc;
-        a.ks_descs = reinterpret_cast<const GateDesc *>(W.d_descs); // non-null = fold; never dereferenced
-    }
-    a.ubar = W.d_ubar;
-    a.ks_S = w.fold != BRWork::NONE ? w.S : 1;
-    a.ks_prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
-    a.job0 = sg.off;
-    a.step_begin = (int)((long long)e->p.n * part / parts);
-    a.step_end = (int)((long long)e->p.n * (part + 1) / parts);
-    a.acc_state = W.d_acc_state;
-    // priority alternation pays only when every workgroup is resident from the start (four per CU)
-    const uint32_t resident = (sg.wide ? 8u : 4u) * (uint32_t)e->num_cus;
-    a.prio_duty = (e->prio_duty_override != INT32_MIN) ? e->prio_duty_override
-                  : (sg.njobs <= resident ? kPrioDuty : e->prio_multi);
-    return a;
-}
-
 // THE KERNEL: the instance for (shape, gadget, family, read-back form).  Exactly these are instantiated: six pair and two
 // wide shapes, each as gate / _tv / many-LUT / encrypted-seed kernel, each with the rotation amounts read back by vector
 // loads or (sabar, EOC_TFHE_SCALAR_ABAR=1) by scalar loads; and the two pair shapes of gadget length 2 a second time in
-// their earlier form (tables_lds, EOC_TFHE_BR_TABLES_LDS=1: kernels.hip.h, k_br_lds*), for the first three families only:
-// the encrypted-seed family has no earlier-form twin and runs its shipped form under that knob too.
+// their earlier form (tables_lds, EOC_TFHE_BR_TABLES_LDS=1: kernels.hip.h, k_br_lds*), for the first three families only.
 template <int L, int BGBIT> static const void *br_pair_kernel(BRWork::Seed seed, bool sabar)
 {
     switch (seed) {
     case BRWork::GATE: return sabar ? (const void *)&k_blind_rotate<L, BGBIT, true> : (const void *)&k_blind_rotate<L, BGBIT, false>;
     case BRWork::TV: return sabar ? (const void *)&k_blind_rotate_tv<L, BGBIT, true> : (const void *)&k_blind_rotate_tv<L, BGBIT, false>;
+    case BRWork::ENC: return sabar ? (const void *)&k_br_enc<L, BGBIT, true> : (const void *)&k_br_enc<L, BGBIT, false>;
     default: return sabar ? (const void *)&k_lut_many<L, BGBIT, true> : (const void *)&k_lut_many<L, BGBIT, false>;
     }
 }
@@ -832,120 +668,136 @@ template <int BGBIT> static const void *br_wide_kernel(BRWork::Seed seed, bool s
     switch (seed) {
     case BRWork::GATE: return sabar ? (const void *)&k_blind_rotate_wide<BGBIT, true> : (const void *)&k_blind_rotate_wide<BGBIT, false>;
     case BRWork::TV: return sabar ? (const void *)&k_blind_rotate_wide_tv<BGBIT, true> : (const void *)&k_blind_rotate_wide_tv<BGBIT, false>;
+    case BRWork::ENC: return sabar ? (const void *)&k_br_enc_wide<BGBIT, true> : (const void *)&k_br_enc_wide<BGBIT, false>;
     default: return sabar ? (const void *)&k_lut_many_wide<BGBIT, true> : (const void *)&k_lut_many_wide<BGBIT, false>;
     }
 }
-// the encrypted-seed family's instances (defined behind launch_lin: the device compiler emits kernels in the order of their
-// first use in this file, and the parent kernels keep their places, label numbers included, only if these come last)
-static const void *br_enc_kernel(bool wide, int l, int Bgbit, bool sabar);
 struct BRKernel { const void *fn; dim3 grid, block; unsigned lds; }; // fn == nullptr: no kernel for this gadget length
 static BRKernel blind_rotate_kernel(bool wide, int l, int Bgbit, bool sabar, bool tables_lds, BRWork::Seed seed, uint32_t njobs)
 {
-    if (seed == BRWork::ENC) {
-        const void *fn = br_enc_kernel(wide, l, Bgbit, sabar);
-        if (wide) return {fn, dim3((njobs + kBRWideJobsPerWG - 1) / kBRWideJobsPerWG), dim3(64 * kBRWideJobsPerWG), kBRWideLds};
-        return {fn, dim3(njobs), dim3(128), kBRLds};
-    }
     if (wide) {
         const void *fn = Bgbit == 10 ? br_wide_kernel<10>(seed, sabar) : br_wide_kernel<0>(seed, sabar); // 10: Set A
         return {fn, dim3((njobs + kBRWideJobsPerWG - 1) / kBRWideJobsPerWG), dim3(64 * kBRWideJobsPerWG), kBRWideLds};
     }
     const void *fn = nullptr;
-    if (l == 2 && tables_lds) fn = Bgbit == 10 ? br_pair_lds_kernel<2, 10>(seed, sabar) : br_pair_lds_kernel<2, 0>(seed, sabar);
-#define EOC_BR_PAIR(L, B) EOC_IF_SHAPE(L, B, l, Bgbit) fn = br_pair_kernel<L, B>(seed, sabar);
-    EOC_PAIR_SHAPES(EOC_BR_PAIR)
+    // the encrypted-seed family has no earlier-form twin: under EOC_TFHE_BR_TABLES_LDS=1 it keeps running its shipped form
+    if (l == 2 && tables_lds && seed != BRWork::ENC)
+        fn = Bgbit == 10 ? br_pair_lds_kernel<2, 10>(seed, sabar) : br_pair_lds_kernel<2, 0>(seed, sabar);
+#define EOC_BR_PAIR(L, B, FN) EOC_IF_SHAPE(L, B, l, Bgbit) fn = FN<L, B>(seed, sabar);
+    EOC_PAIR_SHAPES(EOC_BR_PAIR, br_pair_kernel)
 #undef EOC_BR_PAIR
     return {fn, dim3(njobs), dim3(128), kBRLds};
 }
 
-static int launch_blind_rotate(eoc_engine *e, WS &W, const BRWork &w, hipStream_t st)
+// One family of leveled kernels (kernels.hip.h, leveled_pair.inc): a wave pair per item, k_cmux's grid, block and LDS plan,
+// args struct Args.  The three families go through one lookup, one attribute routine and one launcher (leveled_kernel,
+// set_kernel_attrs, launch_leveled).
+template <class Args> struct LeveledFamily {
+    const char *name;               // the kernel's, for error messages
+    uint64_t eoc_engine::*launches; // the counter a launch bumps
+    const void *fn[6];              // the instances, in the order of EOC_PAIR_SHAPES
+};
+#define EOC_INSTANCE(L, B, KERNEL) reinterpret_cast<const void *>(&KERNEL<L, B>),
+static const LeveledFamily<CmuxArgs> kCmuxFamily = {"k_cmux", &eoc_engine::cmux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE, k_cmux)}};
+static const LeveledFamily<DemuxArgs> kDemuxFamily = {"k_demux", &eoc_engine::demux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE, k_demux)}};
+static const LeveledFamily<AutoStepArgs> kAutomatonFamily = {"k_automaton_step", &eoc_engine::automaton_launches,
+                                                             {EOC_PAIR_SHAPES(EOC_INSTANCE, k_automaton_step)}};
+#undef EOC_INSTANCE
+// the instance of a leveled family for gadget (l, bg); nullptr: none
+static const void *leveled_kernel(const void *const (&instances)[6], int l, int bg)
 {
-    const bool folds = w.fold != BRWork::NONE;
-    if ((w.seed != BRWork::GATE && !w.tv) || (w.seed == BRWork::MANY && (folds || w.n_tables == 0)) ||
-        (folds && !w.inline_desc && (!w.descs || !w.S)) || (w.inline_desc && (w.fold != BRWork::KS_AND_PREP || !w.S))) {
-        eoc_set_error("internal: blind rotation of family %d with fold %d: a table family needs its test polynomials, the "
-                      "many-LUT kernel has no fold, a fold needs descriptors and their row count", (int)w.seed, (int)w.fold);
-        return EOC_ERR_STATE;
+    const void *fn = nullptr;
+    int i = 0;
+#define EOC_LEVELED(L, B, TABLE) EOC_IF_SHAPE(L, B, l, bg) fn = TABLE[i]; i++;
+    EOC_PAIR_SHAPES(EOC_LEVELED, instances)
+#undef EOC_LEVELED
+    return fn;
+}
+
+// The wave shapes of the key switch at basebit 2, t 8 (both default sets): X(ncb, T, waves per workgroup, indices per wave),
+// keyed by ncb = n1p / 64, the blocks of 64 key columns: 4 (n <= 255), 8 (Set A), 12 (Set B), 16.  Waves per workgroup x
+// indices per wave are chosen so that 1024 gates give every SIMD its 3-4 waves: 4096 waves for n1p = 256 / 512 / 1024, 3072
+// (three 4-wave workgroups per CU) for n1p = 768.
+#define EOC_KS_SHAPES(X) X(4, 8, 8, 16) X(8, 8, 8, 32) X(12, 8, 4, 64) X(16, 8, 8, 64)
+
+// The dynamic-LDS limit of every kernel that asks for more than the default: raised once, at engine creation, not on the
+// launch path
+static void set_kernel_attrs(eoc_engine *e)
+{
+    // the key-switch waves use > 64 KiB: a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to
+    // k_keyswitch_generic: slow, exact
+#define EOC_KS_ATTR(NCB, TT, NWV, IWV)                                                                         \
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_keyswitch_waves<TT, NWV, IWV>),                  \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, KS3Cfg<TT, NWV, IWV>::LDS_BYTES) != hipSuccess) \
+        e->ks_waves_ok = false;
+    EOC_KS_SHAPES(EOC_KS_ATTR)
+#undef EOC_KS_ATTR
+    if (!e->ks_waves_ok) (void)hipGetLastError();
+    // the leveled kernels (tables + four transpose scratches); a device that refuses it cannot run the leveled calls
+    auto set = [](const auto &family) {
+        for (const void *fn : family.fn) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
+    };
+    set(kCmuxFamily);
+    set(kDemuxFamily);
+    set(kAutomatonFamily);
+    // k_pack_rows and k_dot_mask: tables + four transpose scratches as well
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dot_mask<kDotChunk>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              kDotLds);
+    (void)hipGetLastError();
+}
+
+extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **out)
+{
+    if (!out || !valid_params(p)) {
+        eoc_set_error("eoc_engine_create: bad arguments (need 1 <= n <= 1023, 1 <= l <= 4, l * Bgbit <= 32, l * 2^Bgbit <= 8192 "
+                      "-- the FP64 external product is not exact beyond that --, ks_t * ks_basebit <= 31, ks_basebit <= 4)");
+        return EOC_ERR_ARG;
     }
-    SpanGuard span(e, st, KIND_BLIND_ROTATE);
-    const BRPlan plan = plan_blind_rotate(w.njobs, e->num_cus, e->p.l, e->kpl, e->p.n, e->br_slice, e->br_parts, e->br_wide);
-    for (const BRSeg &sg : plan.segs) {
-        const BRKernel k = blind_rotate_kernel(sg.wide, e->p.l, e->p.Bgbit, e->scalar_abar, e->br_tables_lds, w.seed, sg.njobs);
-        if (!k.fn) return EOC_ERR_ARG;
-        for (int part = 0; part < plan.parts; part++) {
-            BRArgs a = blind_rotate_args(e, W, w, sg, part, plan.parts);
-            // the gate kernels take the first three arguments, the _tv and encrypted-seed kernels five, the many-LUT kernels
-            // all six
-            void *args[] = {&a, (void *)&e->d_tw, (void *)&e->d_twist, (void *)&w.tv, (void *)&w.tv_rows, (void *)&w.n_tables};
-            HIP_TRY(hipLaunchKernel(k.fn, k.grid, k.block, args, k.lds, st));
-            e->br_launches++;
-            e->br_wide_launches += sg.wide;
-        }
+    int cnt = eoc_device_count();
+    if (cnt <= 0 || device < 0 || device >= cnt) {
+        eoc_set_error("eoc_engine_create: no usable HIP device (count=%d, asked %d); the gate path has no CPU fallback",
+                      cnt, device);
+        return EOC_ERR_NO_DEVICE;
     }
+    HIP_TRY(hipSetDevice(device));
+    eoc_engine *e = new (std::nothrow) eoc_engine();
+    if (!e) return EOC_ERR_ALLOC;
+    e->device = device;
+    e->p = *p;
+    e->kpl = 2 * p->l;
+    e->n1p = eoc_ksk_row_stride(p);
+    e->bara_stride = (p->n + 1 + 31) / 32 * 32; // rows 64 bytes apart: two jobs never share a (scalar) cache line
+    int rc = upload_tables(e);
+    if (rc) {
+        delete e;
+        return rc;
+    }
+    {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) e->num_cus = cus;
+        if (const char *s = getenv("EOC_TFHE_PRIO_DUTY")) e->prio_duty_override = atoi(s);
+        if (const char *s = getenv("EOC_TFHE_PRIO_MULTI")) e->prio_multi = atoi(s);
+        if (const char *s = getenv("EOC_TFHE_BR_SLICE")) e->br_slice = atoi(s);
+        if (getenv("EOC_TFHE_NO_FOLD")) e->no_fold = true;
+        if (getenv("EOC_TFHE_NO_POOL")) e->no_pool = true;
+        if (const char *s = getenv("EOC_TFHE_SCALAR_ABAR")) e->scalar_abar = atoi(s) != 0;
+        if (const char *s = getenv("EOC_TFHE_BR_PARTS")) e->br_parts = atoi(s);
+        if (const char *s = getenv("EOC_TFHE_BR_WIDE")) e->br_wide = atoi(s);
+        if (const char *s = getenv("EOC_TFHE_KS_MFMA")) e->ks_mfma = atoi(s) != 0;
+        if (const char *s = getenv("EOC_TFHE_BR_TABLES_LDS")) e->br_tables_lds = atoi(s) != 0;
+        if (const char *s = getenv("EOC_TFHE_INT_SLICE_ROWS")) e->int_slice_rows = atoi(s);
+        if (const char *s = getenv("EOC_TFHE_TABLE_WS_BYTES")) e->table_ws_bytes = (size_t)strtoull(s, nullptr, 10);
+        if (const char *s = getenv("EOC_TFHE_PACK_WS_BYTES")) e->pack_ws_bytes = (size_t)strtoull(s, nullptr, 10);
+        if (const char *s = getenv("EOC_TFHE_DOT_WS_BYTES")) e->dot_ws_bytes = (size_t)strtoull(s, nullptr, 10);
+    }
+    set_kernel_attrs(e);
+    *out = e;
     return EOC_OK;
 }
 
-constexpr uint32_t kKsMfmaMinS = 1;
-static int launch_keyswitch(eoc_engine *e, WS &W, const GateDesc *d_descs, uint32_t ngates, uint32_t S, hipStream_t st,
-                            bool init_done, const GateDesc *inline_desc)
-{
-    KSArgs a;
-    a.inline_desc = inline_desc != nullptr;
-    if (inline_desc) a.desc0 = *inline_desc;
-    else a.desc0 = GateDesc{0, 0, nullptr, nullptr, nullptr, nullptr};
-    a.ksk = e->ksk;
-    a.u = W.d_u;
-    a.ubar = W.d_ubar;
-    a.n = e->p.n;
-    a.n1p = (int)e->n1p;
-    a.t = e->p.ks_t;
-    a.basebit = e->p.ks_basebit;
-    a.S = S;
-    a.mu = (int32_t)(1u << 29);
-    SpanGuard span(e, st, KIND_KEYSWITCH);
-    if (!init_done) { // levels with MUX (two extracted samples are summed) and the stand-alone key switch
-        hipLaunchKernelGGL(k_ks_init, dim3(S, ngates), dim3(256), 0, st, d_descs, a);
-        HIP_TRY(hipGetLastError());
-    }
-    const uint32_t ntiles = (S + KS_GT - 1) / KS_GT;
-    const int ncb = (int)(e->n1p / 64); // blocks of 64 key columns: 4 (n <= 255), 8 (Set A), 12 (Set B), 16
-    const int bb = e->p.ks_basebit, t = e->p.ks_t;
-#define EOC_KS_LAUNCH(TT, NWV, IWV)                                                                     \
-    do {                                                                                                  \
-        auto kfn = k_keyswitch_waves<TT, NWV, IWV>;                                                       \
-        constexpr int lds = KS3Cfg<TT, NWV, IWV>::LDS_BYTES;                                              \
-        constexpr int ns = KS3Cfg<TT, NWV, IWV>::NS;                                                      \
-        hipLaunchKernelGGL(kfn, dim3(ntiles * (unsigned)ncb * ns, ngates), dim3(64 * NWV), lds, st, d_descs, a); \
-    } while (0)
-    // basebit 2, t 8 (both default sets): waves per workgroup x indices per wave chosen so that 1024 gates give every SIMD
-    // its 3-4 waves: 4096 waves for n1p = 256 / 512 / 1024, 3072 (three 4-wave workgroups per CU) for n1p = 768
-    const bool fast = bb == 2 && t == 8 && e->ks_waves_ok;
-    // the matrix-core form from kKsMfmaMinS ciphertexts per gate group on (profiles/r08_ks_mfma_ab.txt: the sweep over S);
-    // EOC_TFHE_KS_MFMA = 0 | 1 forces either form.  The results are the same words either way.
-    const bool mfma = bb == 2 && t == 8 && e->ksl_ready && (e->ks_mfma == 1 || (e->ks_mfma < 0 && S >= kKsMfmaMinS));
-    if (mfma) {
-        ks_mfma_launch(ks_mfma_plan(S, (int)e->n1p), ngates, d_descs, a, e->d_ksl, st);
-        e->ks_mfma_launches++;
-    }
-    else if (fast && ncb == 4) EOC_KS_LAUNCH(8, 8, 16);
-    else if (fast && ncb == 8) EOC_KS_LAUNCH(8, 8, 32);
-    else if (fast && ncb == 12) EOC_KS_LAUNCH(8, 4, 64);
-    else if (fast && ncb == 16) EOC_KS_LAUNCH(8, 8, 64);
-    else // any other shape (no default set has one): the plain one-thread-per-word form
-        hipLaunchKernelGGL(k_keyswitch_generic, dim3(S, ngates), dim3(256), 0, st, d_descs, a);
-#undef EOC_KS_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return EOC_OK;
-}
-
-static inline bool op_const(int op) { return op == OP_CONST0 || op == OP_CONST1; }
-static inline bool op_free(int op) { return op == OP_NOT || op == OP_COPY || op_const(op); }
-static inline bool op_valid(int op) { return (op >= 0 && op <= OP_XOR3); }
-static inline bool op_lin3(int op) { return op == OP_MAJ || op == OP_XOR3; } // one bootstrap, three-operand linear stage
-static inline int op_inputs(int op) { return op_const(op) ? 0 : (op_free(op) ? 1 : (op == OP_MUX || op_lin3(op) ? 3 : 2)); }
-
-// kernels index gates with a grid dimension (y or z <= 65535): wider levels are cut into slices of this many gates
-constexpr size_t kMaxGatesPerLaunch = 32768;
+// ---- launch helpers -------------------------------------------------------------------------
+typedef eoc_engine::Workspace WS;
 
 // Descriptors of one launch group: written into the pinned host ring, copied to the same position of the device ring
 // ahead of the kernels.  The ring only wraps after a stream synchronisation, so a slot is never overwritten while a
@@ -1044,18 +896,173 @@ static void launch_lin(eoc_engine *e, WS &W, const LinDesc *dd, uint32_t cnt, ui
 #undef EOC_LIN_LAUNCH
 }
 
-// the shapes of blind_rotate_kernel() once more for the encrypted-seed family (no earlier-form twin)
-#define EOC_BR_ENC(KERNEL, ...) (sabar ? (const void *)&KERNEL<__VA_ARGS__, true> : (const void *)&KERNEL<__VA_ARGS__, false>)
-static const void *br_enc_kernel(bool wide, int l, int Bgbit, bool sabar)
+// THE PLAN: the launches a blind rotation of `njobs_total` jobs is cut into -- a pure function of these integers.
+// One launch holds at most `br_slice` jobs (default: what is resident at once, four workgroups per CU): a launch in
+// which every workgroup is resident from the start runs with the wave-priority alternation and finishes all its
+// workgroups within half a per cent of each other (3.0 ms per 1024 jobs), while a launch of several rounds settles at
+// a 10 % lower rate (the arbiter's age bias), so wide levels are cut into back-to-back single-round launches.
+// Two kernel shapes (kernels.hip.h).  The pair kernel (one ciphertext = one wave pair) fills the chip with 4 x CUs
+// ciphertexts; the wide kernel (one ciphertext = one wave, gadget length 2 only) with 8 x CUs, and saves the partial-chain
+// exchange and its barriers.  A level wider than the pair kernel's resident set runs as full wide launches plus a
+// remainder: on the pair kernel when it fits its resident set (a half-empty wide launch has one wave per SIMD and runs
+// at 0.7 of the pair kernel's rate), on the wide kernel otherwise (tools/wide_sweep.py; DESIGN.md 5.1).
+struct BRSeg { uint32_t off, njobs; bool wide; };
+struct BRPlan {
+    std::vector<BRSeg> segs;
+    int parts; // consecutive launches (step ranges) per segment
+};
+static BRPlan plan_blind_rotate(uint32_t njobs_total, int num_cus, int l, int kpl, int n, int br_slice, int br_parts, int br_wide)
 {
-    if (wide) return Bgbit == 10 ? EOC_BR_ENC(k_br_enc_wide, 10) : EOC_BR_ENC(k_br_enc_wide, 0);
-    const void *fn = nullptr;
-#define EOC_BR_ENC_PAIR(L, B) EOC_IF_SHAPE(L, B, l, Bgbit) fn = EOC_BR_ENC(k_br_enc, L, B);
-    EOC_PAIR_SHAPES(EOC_BR_ENC_PAIR)
-#undef EOC_BR_ENC_PAIR
-    return fn;
+    const uint32_t resident_pair = 4u * (uint32_t)num_cus, resident_wide = 8u * (uint32_t)num_cus;
+    const bool can_wide = l == 2 && br_wide != 0;
+    const bool force_wide = can_wide && br_wide > 0;
+    const int auto_parts = kpl * 2 * kNH * 16 > 80 * 1024 ? 2 : 1;
+    BRPlan plan;
+    plan.parts = std::max(1, std::min(br_parts > 0 ? br_parts : auto_parts, n));
+    plan.segs.reserve(njobs_total / resident_pair + 2);
+    auto even = [&](uint32_t off, uint32_t total, uint32_t slice, bool wide) { // even slices: 1536 jobs as 768 + 768
+        if (plan.parts > 1 && slice > 16u * (uint32_t)num_cus) slice = 16u * (uint32_t)num_cus; // acc_state capacity
+        const uint32_t nsl = (total + slice - 1) / slice;
+        slice = (total + nsl - 1) / nsl;
+        for (uint32_t o = 0; o < total; o += slice) plan.segs.push_back({off + o, std::min(slice, total - o), wide});
+    };
+    if (br_slice != 0) // diagnostics: fixed slice (> 0) or one launch (< 0), one kernel shape
+        even(0, njobs_total, br_slice > 0 ? (uint32_t)br_slice : njobs_total, force_wide);
+    else if (force_wide)
+        even(0, njobs_total, resident_wide, true);
+    else if (!can_wide || njobs_total <= resident_pair)
+        even(0, njobs_total, resident_pair, false);
+    else {
+        const uint32_t full = njobs_total / resident_wide * resident_wide, rem = njobs_total - full;
+        if (full) even(0, full, resident_wide, true);
+        if (rem) even(full, rem, rem <= resident_pair ? resident_pair : resident_wide, rem > resident_pair);
+    }
+    return plan;
 }
-#undef EOC_BR_ENC
+
+// THE ARGUMENTS of one launch: part `part` of `parts` of segment `sg`
+static BRArgs blind_rotate_args(const eoc_engine *e, const WS &W, const BRWork &w, const BRSeg &sg, int part, int parts)
+{
+    BRArgs a{};
+    a.bkfft = e->bkfft;
+    a.bara = W.d_bara + (size_t)sg.off * e->bara_stride;
+    a.u = W.d_u + (size_t)sg.off * (kN + 1);
+    a.njobs = sg.njobs;
+    a.n = e->p.n;
+    a.Bgbit = e->p.Bgbit;
+    a.bara_stride = e->bara_stride;
+    a.mu = (int32_t)(1u << 29);
+    a.stamps = e->d_stamps;
+    a.ks_descs = w.fold != BRWork::NONE ? w.descs : nullptr;
+    a.prep = w.fold == BRWork::KS_AND_PREP; // KS alone: k_prepare wrote the rotation amounts (three-operand gates)
+    a.inline_desc = w.inline_desc != nullptr;
+    if (w.inline_desc) {
+        a.desc0 = *w.inline_desc;
+        a.ks_descs = reinterpret_cast<const GateDesc *>(W.d_descs); // non-null = fold; never dereferenced
+    }
+    a.ubar = W.d_ubar;
+    a.ks_S = w.fold != BRWork::NONE ? w.S : 1;
+    a.ks_prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    a.job0 = sg.off;
+    a.step_begin = (int)((long long)e->p.n * part / parts);
+    a.step_end = (int)((long long)e->p.n * (part + 1) / parts);
+    a.acc_state = W.d_acc_state;
+    // priority alternation pays only when every workgroup is resident from the start (four per CU)
+    const uint32_t resident = (sg.wide ? 8u : 4u) * (uint32_t)e->num_cus;
+    a.prio_duty = (e->prio_duty_override != INT32_MIN) ? e->prio_duty_override
+                  : (sg.njobs <= resident ? kPrioDuty : e->prio_multi);
+    return a;
+}
+
+static int launch_blind_rotate(eoc_engine *e, WS &W, const BRWork &w, hipStream_t st)
+{
+    const bool folds = w.fold != BRWork::NONE;
+    if ((w.seed != BRWork::GATE && !w.tv) || (w.seed == BRWork::MANY && (folds || w.n_tables == 0)) ||
+        (folds && !w.inline_desc && (!w.descs || !w.S)) || (w.inline_desc && (w.fold != BRWork::KS_AND_PREP || !w.S))) {
+        eoc_set_error("internal: blind rotation of family %d with fold %d: a table family needs its test polynomials, the "
+                      "many-LUT kernel has no fold, a fold needs descriptors and their row count", (int)w.seed, (int)w.fold);
+        return EOC_ERR_STATE;
+    }
+    SpanGuard span(e, st, KIND_BLIND_ROTATE);
+    const BRPlan plan = plan_blind_rotate(w.njobs, e->num_cus, e->p.l, e->kpl, e->p.n, e->br_slice, e->br_parts, e->br_wide);
+    for (const BRSeg &sg : plan.segs) {
+        const BRKernel k = blind_rotate_kernel(sg.wide, e->p.l, e->p.Bgbit, e->scalar_abar, e->br_tables_lds, w.seed, sg.njobs);
+        if (!k.fn) return EOC_ERR_ARG;
+        for (int part = 0; part < plan.parts; part++) {
+            BRArgs a = blind_rotate_args(e, W, w, sg, part, plan.parts);
+            // the gate kernels take the first three arguments, the _tv and encrypted-seed kernels five, the many-LUT kernels
+            // all six
+            void *args[] = {&a, (void *)&e->d_tw, (void *)&e->d_twist, (void *)&w.tv, (void *)&w.tv_rows, (void *)&w.n_tables};
+            HIP_TRY(hipLaunchKernel(k.fn, k.grid, k.block, args, k.lds, st));
+            e->br_launches++;
+            e->br_wide_launches += sg.wide;
+        }
+    }
+    return EOC_OK;
+}
+
+constexpr uint32_t kKsMfmaMinS = 1;
+static int launch_keyswitch(eoc_engine *e, WS &W, const GateDesc *d_descs, uint32_t ngates, uint32_t S, hipStream_t st,
+                            bool init_done, const GateDesc *inline_desc)
+{
+    KSArgs a;
+    a.inline_desc = inline_desc != nullptr;
+    if (inline_desc) a.desc0 = *inline_desc;
+    else a.desc0 = GateDesc{0, 0, nullptr, nullptr, nullptr, nullptr};
+    a.ksk = e->ksk;
+    a.u = W.d_u;
+    a.ubar = W.d_ubar;
+    a.n = e->p.n;
+    a.n1p = (int)e->n1p;
+    a.t = e->p.ks_t;
+    a.basebit = e->p.ks_basebit;
+    a.S = S;
+    a.mu = (int32_t)(1u << 29);
+    SpanGuard span(e, st, KIND_KEYSWITCH);
+    if (!init_done) { // levels with MUX (two extracted samples are summed) and the stand-alone key switch
+        hipLaunchKernelGGL(k_ks_init, dim3(S, ngates), dim3(256), 0, st, d_descs, a);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint32_t ntiles = (S + KS_GT - 1) / KS_GT;
+    const int ncb = (int)(e->n1p / 64); // blocks of 64 key columns
+    const int bb = e->p.ks_basebit, t = e->p.ks_t;
+#define EOC_KS_LAUNCH(NCB, TT, NWV, IWV)                                                                  \
+    else if (fast && ncb == NCB) {                                                                        \
+        auto kfn = k_keyswitch_waves<TT, NWV, IWV>;                                                       \
+        constexpr int lds = KS3Cfg<TT, NWV, IWV>::LDS_BYTES;                                              \
+        constexpr int ns = KS3Cfg<TT, NWV, IWV>::NS;                                                      \
+        hipLaunchKernelGGL(kfn, dim3(ntiles * (unsigned)ncb * ns, ngates), dim3(64 * NWV), lds, st, d_descs, a); \
+    }
+    // basebit 2, t 8 (both default sets): the wave kernel of the engine's ncb (EOC_KS_SHAPES)
+    const bool fast = bb == 2 && t == 8 && e->ks_waves_ok;
+    // the matrix-core form from kKsMfmaMinS ciphertexts per gate group on (profiles/r08_ks_mfma_ab.txt: the sweep over S);
+    // EOC_TFHE_KS_MFMA = 0 | 1 forces either form.  The results are the same words either way.
+    const bool mfma = bb == 2 && t == 8 && e->ksl_ready && (e->ks_mfma == 1 || (e->ks_mfma < 0 && S >= kKsMfmaMinS));
+    if (mfma) {
+        ks_mfma_launch(ks_mfma_plan(S, (int)e->n1p), ngates, d_descs, a, e->d_ksl, st);
+        e->ks_mfma_launches++;
+    }
+    EOC_KS_SHAPES(EOC_KS_LAUNCH)
+    else // any other shape (no default set has one): the plain one-thread-per-word form
+        hipLaunchKernelGGL(k_keyswitch_generic, dim3(S, ngates), dim3(256), 0, st, d_descs, a);
+#undef EOC_KS_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return EOC_OK;
+}
+
+// k_pack_rows over the `L` lists whose columns a gather kernel has just laid out in pack_cols
+static int launch_pack_rows(eoc_engine *e, int32_t *lists, size_t L, hipStream_t st)
+{
+    const int n = e->p.n;
+    const uint32_t nchunks = (uint32_t)((n + kPackChunk - 1) / kPackChunk), items = (uint32_t)(L * nchunks);
+    SpanGuard span(e, st, KIND_KEYSWITCH);
+    hipLaunchKernelGGL(k_pack_rows, dim3((items + kPackWavesPerWG - 1) / kPackWavesPerWG), dim3(64 * kPackWavesPerWG), kPackLds, st,
+                       (const int32_t *)e->pack_cols.p, (const d2 *)e->d_pks, lists, n, nchunks, items, (const d2 *)e->d_tw,
+                       (const d2 *)e->d_twist);
+    HIP_TRY(hipGetLastError());
+    e->pack_launches++;
+    return EOC_OK;
+}
 
 // One bootstrap level: descriptors -> rotation amounts -> ONE blind rotation -> key switch(es) -> stats.  The callers say
 // what differs; ring_mark stays with them, once per call, behind everything the call pushed (free gates included).
@@ -1114,6 +1121,16 @@ static int run_bootstrap(eoc_engine *e, WS &W, const Level &lv, hipStream_t st)
     e->stats[1] += br.njobs;
     return EOC_OK;
 }
+
+// ---- gate batches ----------------------------------------------------------------------------
+static inline bool op_const(int op) { return op == OP_CONST0 || op == OP_CONST1; }
+static inline bool op_free(int op) { return op == OP_NOT || op == OP_COPY || op_const(op); }
+static inline bool op_valid(int op) { return (op >= 0 && op <= OP_XOR3); }
+static inline bool op_lin3(int op) { return op == OP_MAJ || op == OP_XOR3; } // one bootstrap, three-operand linear stage
+static inline int op_inputs(int op) { return op_const(op) ? 0 : (op_free(op) ? 1 : (op == OP_MUX || op_lin3(op) ? 3 : 2)); }
+
+// kernels index gates with a grid dimension (y or z <= 65535): wider levels are cut into slices of this many gates
+constexpr size_t kMaxGatesPerLaunch = 32768;
 
 // One "level": a set of gates that all run over the same S instances.  descs are host-side and
 // carry device pointers; free gates and bootstrapped gates are separated here.
@@ -1518,370 +1535,6 @@ extern "C" int eoc_keyswitch_device(eoc_engine *e, const int32_t *d_u, int32_t *
     return rc;
 }
 
-// ---- compact public-key lists (DESIGN.md 11) ------------------------------------------------
-// k_compact_expand writes the key switch's operand rows and the (0, ..., 0, b') output rows, then the key switch runs as it
-// does behind a folded blind rotation (init_done).  The descriptor travels as a kernel argument: no ring slot, nothing
-// copied, so a captured call needs only the workspace of one slice.  Slices of at most 2^20 samples.
-int eoc_compact_expand_device_from(eoc_engine *e, const int32_t *d_lists, size_t first_slot, size_t count, int32_t *d_out,
-                                   void *hip_stream)
-{
-    if (!e || !d_lists || !d_out) {
-        eoc_set_error("eoc_compact_expand_device: null argument");
-        return EOC_ERR_ARG;
-    }
-    if (!count) return EOC_OK;
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!e->ksk) {
-        eoc_set_error("eoc_compact_expand_device: no key-switch key loaded");
-        return EOC_ERR_NO_KEY;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    WS &W = e->ws;
-    constexpr size_t kSlice = (size_t)1 << 20;
-    int rc = ensure_ws(e, W, std::min(count, kSlice), 0, 0, st);
-    if (rc) return rc;
-    const size_t stride = (size_t)e->p.n + 1;
-    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
-    for (size_t r0 = 0; r0 < count; r0 += kSlice) {
-        const size_t S = std::min(kSlice, count - r0);
-        const uint64_t first = (uint64_t)(first_slot + r0);
-        const unsigned nwg = (unsigned)((first % kCompactSlotsPerWG + S + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
-        {
-            SpanGuard span(e, st, KIND_PREPARE);
-            hipLaunchKernelGGL(k_compact_expand, dim3(nwg), dim3(256), 0, st, d_lists, first, (uint32_t)S, W.d_ubar,
-                               d_out + r0 * stride, e->p.n, prec_offset);
-            HIP_TRY(hipGetLastError());
-        }
-        const GateDesc d{OP_RAW, 0, nullptr, nullptr, nullptr, d_out + r0 * stride};
-        rc = launch_keyswitch(e, W, nullptr, 1, (uint32_t)S, st, true, &d);
-        if (rc) return rc;
-        e->stats[2] += S;
-    }
-    return EOC_OK;
-}
-extern "C" int eoc_compact_expand_device(eoc_engine *e, const int32_t *d_lists, size_t count, int32_t *d_out, void *hip_stream)
-{
-    return eoc_compact_expand_device_from(e, d_lists, 0, count, d_out, hip_stream);
-}
-
-// ---- leveled operations: selectors, CMux, encrypted-index table reads (DESIGN.md 12) --------
-extern "C" size_t eoc_tgsw_fft_bytes(const eoc_params *p) { return p ? (size_t)2 * p->l * 2 * kNH * 16 : 0; }
-
-// torus-form selectors [count][2l][2][N] -> the layout the kernels multiply by, [count][2l][2][512] complex scaled by 2^-9:
-// the key-load transform (build_cloud_key_images), on the caller's stream.  No key is needed.
-extern "C" int eoc_tgsw_to_fft_device(eoc_engine *e, const int32_t *d_tgsw, size_t count, void *d_fft, void *hip_stream)
-{
-    if (!e || !d_tgsw || !d_fft) {
-        eoc_set_error("eoc_tgsw_to_fft_device: null argument");
-        return EOC_ERR_ARG;
-    }
-    if (!count) return EOC_OK;
-    std::lock_guard<std::mutex> g(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    return launch_fft_fwd(e, d_tgsw, static_cast<double *>(d_fft), count * e->kpl * 2, 0x1p-9, (hipStream_t)hip_stream);
-}
-
-// the instance of a leveled family (LeveledFamily, above eoc_engine_create) for gadget (l, bg); nullptr: none
-static const void *leveled_kernel(const void *const (&instances)[6], int l, int bg)
-{
-    const void *fn = nullptr;
-    int i = 0;
-#define EOC_LEVELED(L, B) EOC_IF_SHAPE(L, B, l, bg) fn = instances[i]; i++;
-    EOC_PAIR_SHAPES(EOC_LEVELED)
-#undef EOC_LEVELED
-    return fn;
-}
-// one launch of a family over nx x ny items: a.Bgbit is set here
-template <class Args>
-static int launch_leveled(eoc_engine *e, const LeveledFamily<Args> &family, const Args &a, uint32_t ny, hipStream_t st)
-{
-    const void *fn = leveled_kernel(family.fn, e->p.l, e->p.Bgbit);
-    if (!fn) {
-        eoc_set_error("%s: no kernel for gadget length %d", family.name, e->p.l);
-        return EOC_ERR_STATE;
-    }
-    Args args = a;
-    args.Bgbit = e->p.Bgbit;
-    const d2 *tw = e->d_tw, *twist = e->d_twist;
-    void *kargs[] = {&args, &tw, &twist};
-    SpanGuard span(e, st, KIND_BLIND_ROTATE);
-    HIP_TRY(hipLaunchKernel(fn, dim3((a.nx + kCmuxItemsPerWG - 1) / kCmuxItemsPerWG, ny), dim3(128 * kCmuxItemsPerWG), kargs,
-                            kCmuxLds, st));
-    (e->*family.launches)++;
-    return EOC_OK;
-}
-
-extern "C" int eoc_cmux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in0, const int32_t *d_in1, int32_t *d_out,
-                               size_t count, void *hip_stream)
-{
-    if (!e || !d_sel_fft || !d_in0 || !d_in1 || !d_out) {
-        eoc_set_error("eoc_cmux_device: null argument");
-        return EOC_ERR_ARG;
-    }
-    if (!count) return EOC_OK;
-    std::lock_guard<std::mutex> g(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t sel = (size_t)e->kpl * 2 * kNH, smp = (size_t)2 * kN;
-    constexpr size_t kSlice = (size_t)1 << 30; // items per launch (grid x)
-    for (size_t i0 = 0; i0 < count; i0 += kSlice) {
-        CmuxArgs a{};
-        a.sel = static_cast<const d2 *>(d_sel_fft) + i0 * sel;
-        a.in0 = d_in0 + i0 * smp;
-        a.in1 = d_in1 + i0 * smp;
-        a.out = d_out + i0 * smp;
-        a.sel_x = sel;
-        a.in0_x = a.in1_x = a.out_x = smp;
-        a.nx = (uint32_t)std::min(kSlice, count - i0);
-        a.rot = 0;
-        int rc = launch_leveled(e, kCmuxFamily, a, 1, (hipStream_t)hip_stream);
-        if (rc) return rc;
-    }
-    return EOC_OK;
-}
-
-// The walk over a table of 2^d lists of 2^(10 - r) slots that the encrypted-index read and update share: d tree stages and r
-// rotations per query, through two ping-pong buffers that hold 2^(d-1) and 2^(d-2) samples per query (the rotations one).
-// Queries are sliced so that both buffers together stay inside the byte budget (EOC_TFHE_TABLE_WS_BYTES) and a slice fits
-// grid y.
-struct TableWalk {
-    int d, r, depth;
-    size_t W, smp, sel; // slots per list; ints per TLWE sample and d2 per converted selector
-    size_t s0, s1;      // samples per query in buffer 0 and 1
-    size_t qs;          // queries per slice
-};
-// validation (messages under the caller's name `who`), the derived sizes, the budget check, queries per slice; ptrs_ok = the
-// caller's own pointers are there.  Reads nothing of the engine that changes after creation: called ahead of the lock.
-static int table_walk_plan(const eoc_engine *e, const char *who, bool ptrs_ok, int log2_lists, int log2_width, const void *d_sel_fft,
-                           size_t queries, TableWalk *tw)
-{
-    if (!e || !ptrs_ok || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10 ||
-        (!d_sel_fft && log2_lists + 10 - log2_width > 0)) {
-        eoc_set_error("%s: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]", who, log2_lists,
-                      log2_width);
-        return EOC_ERR_ARG;
-    }
-    const int d = log2_lists, r = 10 - log2_width;
-    *tw = TableWalk{d, r, d + r, (size_t)1 << log2_width, (size_t)2 * kN, (size_t)e->kpl * 2 * kNH,
-                    d >= 1 ? (size_t)1 << (d - 1) : 1, d >= 2 ? (size_t)1 << (d - 2) : 1, 0};
-    const size_t per_query = (tw->s0 + tw->s1) * tw->smp * sizeof(int32_t);
-    if (tw->depth > 0 && e->table_ws_bytes < per_query) {
-        eoc_set_error("%s: one query at log2_lists = %d needs %zu bytes of workspace, the budget (EOC_TFHE_TABLE_WS_BYTES) is %zu",
-                      who, d, per_query, e->table_ws_bytes);
-        return EOC_ERR_ARG;
-    }
-    tw->qs = std::min<size_t>(queries, 32768); // grid y
-    if (tw->depth > 0) tw->qs = std::min(tw->qs, e->table_ws_bytes / per_query);
-    return EOC_OK;
-}
-// the two buffers of a slice, by the scratch rule
-static int table_walk_reserve(eoc_engine *e, const TableWalk &tw, hipStream_t st)
-{
-    if (tw.depth == 0) return EOC_OK;
-    const size_t per_sample = tw.qs * tw.smp * sizeof(int32_t);
-    int rc = scratch_reserve(e, e->cmux[0], tw.s0 * per_sample, "table workspace (buffer 0)", st);
-    if (!rc) rc = scratch_reserve(e, e->cmux[1], tw.s1 * per_sample, "table workspace (buffer 1)", st);
-    return rc;
-}
-// The r rotations of a slice of Q queries: the CMux under selector bit i picks its input or the input times X^(sign W 2^i).
-// Rotation 0 reads *cur, *cur_y ints between the queries' samples (0: one shared sample); rotation i leaves one sample per
-// query in buffer out_buf(tw, i); *cur and *cur_y follow the last output.
-static int table_walk_rotations(eoc_engine *e, const TableWalk &tw, const d2 *selq, int sign, const int32_t **cur, size_t *cur_y,
-                                int (*out_buf)(const TableWalk &, int), size_t Q, hipStream_t st)
-{
-    for (int i = 0; i < tw.r; i++) {
-        CmuxArgs a{};
-        a.nx = 1;
-        a.sel = selq + (size_t)i * tw.sel;
-        a.sel_y = (size_t)tw.depth * tw.sel;
-        a.in0 = a.in1 = *cur;
-        a.in0_y = a.in1_y = *cur_y;
-        a.out = e->cmux[out_buf(tw, i)].i32();
-        a.out_y = tw.smp;
-        a.rot = sign > 0 ? (int)(tw.W << i) : 2 * kN - (int)(tw.W << i);
-        int rc = launch_leveled(e, kCmuxFamily, a, (uint32_t)Q, st);
-        if (rc) return rc;
-        *cur = a.out;
-        *cur_y = a.out_y;
-    }
-    return EOC_OK;
-}
-
-// The tail of a leveled read: slots w < W of ny TLWE samples become rows y W + w of the key-switch operand and of `o`
-// (k_tlwe_extract), and one key switch over the ny W rows leaves the LWE samples in `o`, p.n + 1 ints apart.
-// pick == NULL: sample y is samples + y * stride, one launch.  pick: sample y is samples + pick[y] * stride (public indices,
-// checked by the caller), one launch each.
-static int extract_and_keyswitch(eoc_engine *e, WS &Wk, const int32_t *samples, size_t stride, const int32_t *pick, size_t W,
-                                 size_t ny, int32_t *o, hipStream_t st)
-{
-    const size_t out_stride = (size_t)e->p.n + 1;
-    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
-    const unsigned ext_x = (unsigned)((W + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
-    {
-        SpanGuard span(e, st, KIND_PREPARE);
-        if (!pick)
-            hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, (unsigned)ny), dim3(256), 0, st, samples, stride, (uint32_t)W, Wk.d_ubar,
-                               o, e->p.n, prec_offset);
-        else
-            for (size_t i = 0; i < ny; i++)
-                hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, 1), dim3(256), 0, st, samples + (size_t)pick[i] * stride, (size_t)0,
-                                   (uint32_t)W, Wk.d_ubar + i * W * kN, o + i * W * out_stride, e->p.n, prec_offset);
-        HIP_TRY(hipGetLastError());
-    }
-    const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
-    int rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(ny * W), st, true, &gd);
-    if (rc) return rc;
-    e->stats[2] += ny * W;
-    return EOC_OK;
-}
-
-extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
-                                     size_t queries, int32_t *d_out, void *hip_stream)
-{
-    TableWalk tw;
-    int rc = table_walk_plan(e, "eoc_table_read_device", d_table && d_out, log2_lists, log2_width, d_sel_fft, queries, &tw);
-    if (rc) return rc;
-    tw.qs = std::min(tw.qs, std::max<size_t>(1, ((size_t)1 << 20) / tw.W)); // 2^20 extracted samples a slice (lut_levels' rule)
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!e->ksk) {
-        eoc_set_error("eoc_table_read_device: no key-switch key loaded");
-        return EOC_ERR_NO_KEY;
-    }
-    if (!queries) return EOC_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    WS &Wk = e->ws;
-    const int d = tw.d, r = tw.r, depth = tw.depth;
-    const size_t W = tw.W, smp = tw.smp, sel = tw.sel, qs = tw.qs;
-    rc = ensure_ws(e, Wk, qs * W, 0, 0, st);
-    if (!rc) rc = table_walk_reserve(e, tw, st);
-    if (rc) return rc;
-    for (size_t q0 = 0; q0 < queries; q0 += qs) {
-        const size_t Q = std::min(qs, queries - q0);
-        const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * depth * sel;
-        const int32_t *cur = d_table; // the TLWE samples the next launch reads: [Q][cur_y / smp] (cur_y = 0: shared)
-        size_t cur_y = 0;
-        int t = 0;
-        for (int v = 0; v < d; v++, t++) { // tree: nodes (2j, 2j + 1) -> j with bit r + v
-            CmuxArgs a{};
-            a.nx = (uint32_t)1 << (d - 1 - v);
-            a.sel = selq + (size_t)(r + v) * sel;
-            a.sel_x = 0;
-            a.sel_y = (size_t)depth * sel;
-            a.in0 = cur;
-            a.in1 = cur + smp;
-            a.in0_x = a.in1_x = 2 * smp;
-            a.in0_y = a.in1_y = cur_y;
-            a.out = e->cmux[t & 1].i32();
-            a.out_x = smp;
-            a.out_y = (size_t)a.nx * smp;
-            a.rot = 0;
-            if ((rc = launch_leveled(e, kCmuxFamily, a, (uint32_t)Q, st))) return rc;
-            cur = a.out;
-            cur_y = a.out_y;
-        }
-        // rotations: X^(-W 2^i) under bit i brings slot W 2^i to slot 0; launch t = d + i of the query writes buffer t & 1
-        rc = table_walk_rotations(e, tw, selq, -1, &cur, &cur_y, [](const TableWalk &w, int i) { return (w.d + i) & 1; }, Q, st);
-        if (rc) return rc;
-        rc = extract_and_keyswitch(e, Wk, cur, cur_y, nullptr, W, Q, d_out + q0 * W * ((size_t)e->p.n + 1), st);
-        if (rc) return rc;
-    }
-    return EOC_OK;
-}
-
-// ---- packing key switch: LWE samples -> compact TLWE lists (DESIGN.md 13) -------------------
-static_assert(kPackT == EOC_PACK_T && kPackBasebit == EOC_PACK_BASEBIT, "the kernels' decomposition is the format's");
-extern "C" int eoc_engine_set_packing_key(eoc_engine *e, const void *blob, size_t len)
-{
-    eoc_params bp;
-    const int32_t *rows = nullptr;
-    if (!e || !eoc_packing_key_blob_rows(blob, len, &bp, &rows)) {
-        eoc_set_error("eoc_engine_set_packing_key: null argument or not a whole EOCPKS1 blob (t = %d, basebit = %d)", kPackT,
-                      kPackBasebit);
-        return EOC_ERR_ARG;
-    }
-    const eoc_params &p = e->p;
-    if (bp.n != p.n || bp.l != p.l || bp.Bgbit != p.Bgbit || bp.ks_t != p.ks_t || bp.ks_basebit != p.ks_basebit ||
-        bp.ks_stdev != p.ks_stdev || bp.bk_stdev != p.bk_stdev) {
-        eoc_set_error("eoc_engine_set_packing_key: the blob's parameters (n = %d, l = %d) are not the engine's (n = %d, l = %d)",
-                      bp.n, bp.l, p.n, p.l);
-        return EOC_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> g(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t npoly = (size_t)p.n * kPackT * 2;
-    HIP_TRY(hipDeviceSynchronize()); // nothing in flight may still read the image that is about to be replaced
-    hipFree(e->d_pks);
-    e->d_pks = nullptr;
-    DevTmp d_rows, d_img;
-    HIP_TRY(d_rows.alloc(npoly * kN * sizeof(int32_t)));
-    HIP_TRY(d_img.alloc(npoly * kNH * sizeof(d2)));
-    HIP_TRY(hipMemcpy(d_rows.p, rows, npoly * kN * sizeof(int32_t), hipMemcpyHostToDevice));
-    // the key-load transform (build_cloud_key_images, eoc_tgsw_to_fft_device); NULL stream, drained inside
-    int rc = key_image(e, d_rows.i32(), d_img.p, npoly);
-    if (rc) return rc;
-    e->d_pks = static_cast<d2 *>(d_img.release());
-    return EOC_OK;
-}
-
-// k_pack_rows over the `L` lists whose columns a gather kernel has just laid out in pack_cols
-static int launch_pack_rows(eoc_engine *e, int32_t *lists, size_t L, hipStream_t st)
-{
-    const int n = e->p.n;
-    const uint32_t nchunks = (uint32_t)((n + kPackChunk - 1) / kPackChunk), items = (uint32_t)(L * nchunks);
-    SpanGuard span(e, st, KIND_KEYSWITCH);
-    hipLaunchKernelGGL(k_pack_rows, dim3((items + kPackWavesPerWG - 1) / kPackWavesPerWG), dim3(64 * kPackWavesPerWG), kPackLds, st,
-                       (const int32_t *)e->pack_cols.p, (const d2 *)e->d_pks, lists, n, nchunks, items, (const d2 *)e->d_tw,
-                       (const d2 *)e->d_twist);
-    HIP_TRY(hipGetLastError());
-    e->pack_launches++;
-    return EOC_OK;
-}
-
-// k_pack_gather lays the mask columns out as polynomials and starts every list as (0, B); k_pack_rows subtracts the chunks.
-// All arguments travel as kernel arguments: no descriptor ring slot.  Lists are sliced by the byte budget of the columns.
-extern "C" int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count, int32_t *d_lists, void *hip_stream)
-{
-    if (!e || !d_in || !d_lists) {
-        eoc_set_error("eoc_pack_device: null argument");
-        return EOC_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!e->d_pks) {
-        eoc_set_error("eoc_pack_device: no packing key loaded (eoc_engine_set_packing_key)");
-        return EOC_ERR_NO_KEY;
-    }
-    if (!count) return EOC_OK;
-    const size_t n = (size_t)e->p.n, per_list = n * kN * sizeof(int32_t), n_lists = (count + kN - 1) / kN;
-    if (e->pack_ws_bytes < per_list) {
-        eoc_set_error("eoc_pack_device: one list needs %zu bytes of workspace, the budget (EOC_TFHE_PACK_WS_BYTES) is %zu",
-                      per_list, e->pack_ws_bytes);
-        return EOC_ERR_ARG;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    const size_t ls = std::min({n_lists, e->pack_ws_bytes / per_list, (size_t)65535}); // grid z
-    int rc = scratch_reserve(e, e->pack_cols, ls * per_list, "packing columns", st);
-    if (rc) return rc;
-    for (size_t l0 = 0; l0 < n_lists; l0 += ls) {
-        const size_t L = std::min(ls, n_lists - l0), cnt = std::min(count - l0 * kN, L * kN);
-        const int32_t *in = d_in + l0 * kN * (n + 1);
-        int32_t *lists = d_lists + l0 * 2 * kN;
-        {
-            SpanGuard span(e, st, KIND_KEYSWITCH);
-            hipLaunchKernelGGL(k_pack_gather, dim3(kN / kPackTile, (unsigned)((n + 1 + kPackTile - 1) / kPackTile), (unsigned)L),
-                               dim3(256), 0, st, in, cnt, (int)n, e->pack_cols.i32(), lists);
-            HIP_TRY(hipGetLastError());
-        }
-        rc = launch_pack_rows(e, lists, L, st);
-        if (rc) return rc;
-    }
-    e->packed_samples += count;
-    return EOC_OK;
-}
-extern "C" uint64_t eoc_engine_pack_launches(eoc_engine *e) { return e ? e->pack_launches : 0; }
-extern "C" uint64_t eoc_engine_packed_samples(eoc_engine *e) { return e ? e->packed_samples : 0; }
-
 // ---- programmable bootstrapping ----------------------------------------
 // Table lookups, n_tables = 0: one level of n_luts x rows jobs, [table][row]: one OP_RAW descriptor per table (all read the
 // same input rows, job_base = table x rows, out = the table's output block) serves k_prepare, the blind rotation and the key
@@ -2233,177 +1886,52 @@ try {
     return EOC_ERR_ALLOC;
 }
 
-// ---- encrypted-index table updates: the demultiplexer and table[idx] += v (DESIGN.md 15) ----
-// The kernels of this section (k_demux, then k_sample_add) are templates first named here: see LeveledFamily.
-#define EOC_INSTANCE(L, B) reinterpret_cast<const void *>(&k_demux<L, B>),
-static const LeveledFamily<DemuxArgs> kDemuxFamily = {"k_demux", &eoc_engine::demux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE)}};
-#undef EOC_INSTANCE
-
-extern "C" int eoc_demux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in, int32_t *d_out0, int32_t *d_out1,
-                                size_t count, int accumulate, void *hip_stream)
+// ---- compact public-key lists (DESIGN.md 11) ------------------------------------------------
+// k_compact_expand writes the key switch's operand rows and the (0, ..., 0, b') output rows, then the key switch runs as it
+// does behind a folded blind rotation (init_done).  The descriptor travels as a kernel argument: no ring slot, nothing
+// copied, so a captured call needs only the workspace of one slice.  Slices of at most 2^20 samples.
+int eoc_compact_expand_device_from(eoc_engine *e, const int32_t *d_lists, size_t first_slot, size_t count, int32_t *d_out,
+                                   void *hip_stream)
 {
-    if (!e || !d_sel_fft || !d_in || !d_out0 || !d_out1) {
-        eoc_set_error("eoc_demux_device: null argument");
+    if (!e || !d_lists || !d_out) {
+        eoc_set_error("eoc_compact_expand_device: null argument");
         return EOC_ERR_ARG;
     }
     if (!count) return EOC_OK;
     std::lock_guard<std::mutex> g(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t sel = (size_t)e->kpl * 2 * kNH, smp = (size_t)2 * kN;
-    constexpr size_t kSlice = (size_t)1 << 30; // items per launch (grid x)
-    for (size_t i0 = 0; i0 < count; i0 += kSlice) {
-        DemuxArgs a{};
-        a.sel = static_cast<const d2 *>(d_sel_fft) + i0 * sel;
-        a.in = d_in + i0 * smp;
-        a.out0 = d_out0 + i0 * smp;
-        a.out1 = d_out1 + i0 * smp;
-        a.sel_x = sel;
-        a.in_x = a.out_x = smp;
-        a.nx = (uint32_t)std::min(kSlice, count - i0);
-        a.accumulate = accumulate != 0;
-        int rc = launch_leveled(e, kDemuxFamily, a, 1, (hipStream_t)hip_stream);
-        if (rc) return rc;
+    if (!e->ksk) {
+        eoc_set_error("eoc_compact_expand_device: no key-switch key loaded");
+        return EOC_ERR_NO_KEY;
     }
-    return EOC_OK;
-}
-
-extern "C" int eoc_table_update_device(eoc_engine *e, int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
-                                       const int32_t *d_vals, size_t queries, void *hip_stream)
-{
-    // the read's walk and its two buffers: the storing stages leave 2^(d-1) and 2^(d-2) samples per query, the rotations one
-    TableWalk tw;
-    int rc = table_walk_plan(e, "eoc_table_update_device", d_table && d_vals, log2_lists, log2_width, d_sel_fft, queries, &tw);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!queries) return EOC_OK;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if ((rc = table_walk_reserve(e, tw, st))) return rc;
-    const int d = tw.d, r = tw.r, depth = tw.depth;
-    const size_t smp = tw.smp, sel = tw.sel, qs = tw.qs;
-    for (size_t q0 = 0; q0 < queries; q0 += qs) {
-        const size_t Q = std::min(qs, queries - q0);
-        const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * depth * sel;
-        const int32_t *cur = d_vals + q0 * smp; // one sample per query until the tree starts
-        size_t cur_y = smp;
-        // rotations: X^(W 2^i) under bit i carries the value to slot W (idx mod 2^r).  Rotation i leaves its result in
-        // buffer (d - 1 + r - 1 - i) & 1, so the last one ends where the first storing stage does not write
-        rc = table_walk_rotations(e, tw, selq, +1, &cur, &cur_y, [](const TableWalk &w, int i) { return (w.d + w.r - i) & 1; }, Q,
-                                  st);
-        if (rc) return rc;
-        if (d == 0) { // one list: the rotated value is the leaf
-            const bool vec = (((uintptr_t)cur | (uintptr_t)d_table) & 15) == 0;
-            SpanGuard span(e, st, KIND_BLIND_ROTATE);
-            if (vec) hipLaunchKernelGGL(k_sample_add<4>, dim3(2 * kN / (256 * 4), (unsigned)Q), dim3(256), 0, st, cur, d_table);
-            else hipLaunchKernelGGL(k_sample_add<1>, dim3(2 * kN / 256, (unsigned)Q), dim3(256), 0, st, cur, d_table);
+    WS &W = e->ws;
+    constexpr size_t kSlice = (size_t)1 << 20;
+    int rc = ensure_ws(e, W, std::min(count, kSlice), 0, 0, st);
+    if (rc) return rc;
+    const size_t stride = (size_t)e->p.n + 1;
+    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    for (size_t r0 = 0; r0 < count; r0 += kSlice) {
+        const size_t S = std::min(kSlice, count - r0);
+        const uint64_t first = (uint64_t)(first_slot + r0);
+        const unsigned nwg = (unsigned)((first % kCompactSlotsPerWG + S + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
+        {
+            SpanGuard span(e, st, KIND_PREPARE);
+            hipLaunchKernelGGL(k_compact_expand, dim3(nwg), dim3(256), 0, st, d_lists, first, (uint32_t)S, W.d_ubar,
+                               d_out + r0 * stride, e->p.n, prec_offset);
             HIP_TRY(hipGetLastError());
-            continue;
         }
-        // tree: stage t under bit r + (d - 1 - t), parent j of 2^t -> children 2j (x - E) and 2j + 1 (E).  Stage t < d - 1
-        // stores [Q][2^(t+1)] samples into buffer (d - 2 - t) & 1 (the larger buffer takes the last storing stage); stage
-        // d - 1 accumulates its 2^d leaves into the table
-        for (int t = 0; t < d; t++) {
-            DemuxArgs a{};
-            a.nx = (uint32_t)1 << t;
-            a.sel = selq + (size_t)(r + d - 1 - t) * sel;
-            a.sel_x = 0;
-            a.sel_y = (size_t)depth * sel;
-            a.in = cur;
-            a.in_x = smp;
-            a.in_y = cur_y;
-            a.out_x = 2 * smp;
-            if (t == d - 1) {
-                a.out0 = d_table;
-                a.out_y = 0;
-                a.accumulate = 1;
-            } else {
-                a.out0 = e->cmux[(d - 2 - t) & 1].i32();
-                a.out_y = (size_t)2 * a.nx * smp;
-                a.accumulate = 0;
-            }
-            a.out1 = a.out0 + smp;
-            if ((rc = launch_leveled(e, kDemuxFamily, a, (uint32_t)Q, st))) return rc;
-            cur = a.out0;
-            cur_y = a.out_y;
-        }
+        const GateDesc d{OP_RAW, 0, nullptr, nullptr, nullptr, d_out + r0 * stride};
+        rc = launch_keyswitch(e, W, nullptr, 1, (uint32_t)S, st, true, &d);
+        if (rc) return rc;
+        e->stats[2] += S;
     }
     return EOC_OK;
 }
-extern "C" uint64_t eoc_engine_demux_launches(eoc_engine *e) { return e ? e->demux_launches : 0; }
-
-extern "C" int eoc_engine_set_profiling(eoc_engine *e, int on)
+extern "C" int eoc_compact_expand_device(eoc_engine *e, const int32_t *d_lists, size_t count, int32_t *d_out, void *hip_stream)
 {
-    if (!e) return EOC_ERR_ARG;
-    std::lock_guard<std::mutex> g(e->mu);
-    e->profiling = on != 0;
-    return EOC_OK;
+    return eoc_compact_expand_device_from(e, d_lists, 0, count, d_out, hip_stream);
 }
-
-// drains the recorded event pairs (synchronises the device) and returns accumulated times
-extern "C" int eoc_engine_kernel_times(eoc_engine *e, double ms[3], uint64_t launches[3], int reset)
-{
-    if (!e || !ms || !launches) return EOC_ERR_ARG;
-    std::lock_guard<std::mutex> g(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    for (auto &sp : e->spans) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) {
-            e->kernel_ms[sp.kind] += t;
-            e->kernel_launches[sp.kind] += 1;
-        }
-        hipEventDestroy(sp.a);
-        hipEventDestroy(sp.b);
-    }
-    e->spans.clear();
-    for (int i = 0; i < 3; i++) {
-        ms[i] = e->kernel_ms[i];
-        launches[i] = e->kernel_launches[i];
-        if (reset) {
-            e->kernel_ms[i] = 0;
-            e->kernel_launches[i] = 0;
-        }
-    }
-    return EOC_OK;
-}
-
-#ifdef EOC_STAMPS
-// diagnostic build only: allocate / read back the in-kernel stamp buffer ([waves][16] cycle sums)
-extern "C" int eoc_dbg_stamps(eoc_engine *e, size_t waves, unsigned long long *host_out)
-{
-    if (!e) return EOC_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    if (!host_out) {
-        hipFree(e->d_stamps);
-        HIP_TRY(hipMalloc(&e->d_stamps, waves * 16 * 8));
-        HIP_TRY(hipMemset(e->d_stamps, 0, waves * 16 * 8));
-        return EOC_OK;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(host_out, e->d_stamps, waves * 16 * 8, hipMemcpyDeviceToHost));
-    return EOC_OK;
-}
-#endif
-
-extern "C" int eoc_engine_stats(eoc_engine *e, uint64_t out[3])
-{
-    if (!e || !out) return EOC_ERR_ARG;
-    for (int i = 0; i < 3; i++) out[i] = e->stats[i];
-    return EOC_OK;
-}
-extern "C" uint64_t eoc_engine_workspace_grows(eoc_engine *e) { return e ? e->ws_grows : 0; }
-extern "C" uint64_t eoc_engine_blind_rotate_launches(eoc_engine *e) { return e ? e->br_launches : 0; }
-extern "C" uint64_t eoc_engine_blind_rotate_wide_launches(eoc_engine *e) { return e ? e->br_wide_launches : 0; }
-extern "C" uint64_t eoc_engine_keyswitch_mfma_launches(eoc_engine *e) { return e ? e->ks_mfma_launches : 0; }
-extern "C" uint64_t eoc_engine_cmux_launches(eoc_engine *e) { return e ? e->cmux_launches : 0; }
-extern "C" size_t eoc_engine_resident_jobs(eoc_engine *e)
-{
-    if (!e) return 0;
-    const bool wide = e->p.l == 2 && e->br_wide != 0;
-    return (size_t)(wide ? 8 : 4) * (size_t)e->num_cus;
-}
-extern "C" int eoc_engine_device(eoc_engine *e) { return e ? e->device : -1; }
-extern "C" const eoc_params *eoc_engine_params(eoc_engine *e) { return e ? &e->p : nullptr; }
 
 // ---- seeded ciphertexts, selectors and cloud key: masks expanded on the device ----------
 enum { TAG_SEED_LWE = 10, TAG_SEED_BK = 11, TAG_SEED_KSK = 12, TAG_SEED_TGSW = 13 }; // host.cpp, Stream::Tag
@@ -2540,7 +2068,6 @@ extern "C" int eoc_engine_load_seeded_cloud_key(eoc_engine *e, const void *blob,
     e->ksk = e->d_ksk;
     return install_ks_limbs(e);
 }
-extern "C" uint64_t eoc_engine_seed_launches(eoc_engine *e) { return e ? e->seed_launches : 0; }
 
 // the kernels' block function, all 16 words of n_blocks blocks ChaCha20(key, counter + i, nonce): known-answer tests
 extern "C" int eoc_dbg_chacha20_blocks_device(eoc_engine *e, const uint8_t key[32], uint64_t counter, uint64_t nonce,
@@ -2562,23 +2089,313 @@ extern "C" int eoc_dbg_chacha20_blocks_device(eoc_engine *e, const uint8_t key[3
     return EOC_OK;
 }
 
-// ---- finite automata on encrypted bit strings: leveled CMux steps (DESIGN.md 17) -------------
-// The kernel of this section is a template first named here, the last of the file: see LeveledFamily.
-#define EOC_INSTANCE(L, B) reinterpret_cast<const void *>(&k_automaton_step<L, B>),
-static const LeveledFamily<AutoStepArgs> kAutomatonFamily = {"k_automaton_step", &eoc_engine::automaton_launches,
-                                                             {EOC_PAIR_SHAPES(EOC_INSTANCE)}};
-#undef EOC_INSTANCE
-// the > 64 KiB dynamic-LDS attribute of every leveled instance (eoc_engine_create)
-static void set_leveled_attrs()
+// ---- leveled operations: selectors, CMux, encrypted-index table reads (DESIGN.md 12) --------
+extern "C" size_t eoc_tgsw_fft_bytes(const eoc_params *p) { return p ? (size_t)2 * p->l * 2 * kNH * 16 : 0; }
+
+// torus-form selectors [count][2l][2][N] -> the layout the kernels multiply by, [count][2l][2][512] complex scaled by 2^-9:
+// the key-load transform (build_cloud_key_images), on the caller's stream.  No key is needed.
+extern "C" int eoc_tgsw_to_fft_device(eoc_engine *e, const int32_t *d_tgsw, size_t count, void *d_fft, void *hip_stream)
 {
-    auto set = [](const auto &family) {
-        for (const void *fn : family.fn) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kCmuxLds);
-    };
-    set(kCmuxFamily);
-    set(kDemuxFamily);
-    set(kAutomatonFamily);
+    if (!e || !d_tgsw || !d_fft) {
+        eoc_set_error("eoc_tgsw_to_fft_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    return launch_fft_fwd(e, d_tgsw, static_cast<double *>(d_fft), count * e->kpl * 2, 0x1p-9, (hipStream_t)hip_stream);
 }
 
+// one launch of a family over nx x ny items: a.Bgbit is set here
+template <class Args>
+static int launch_leveled(eoc_engine *e, const LeveledFamily<Args> &family, const Args &a, uint32_t ny, hipStream_t st)
+{
+    const void *fn = leveled_kernel(family.fn, e->p.l, e->p.Bgbit);
+    if (!fn) {
+        eoc_set_error("%s: no kernel for gadget length %d", family.name, e->p.l);
+        return EOC_ERR_STATE;
+    }
+    Args args = a;
+    args.Bgbit = e->p.Bgbit;
+    const d2 *tw = e->d_tw, *twist = e->d_twist;
+    void *kargs[] = {&args, &tw, &twist};
+    SpanGuard span(e, st, KIND_BLIND_ROTATE);
+    HIP_TRY(hipLaunchKernel(fn, dim3((a.nx + kCmuxItemsPerWG - 1) / kCmuxItemsPerWG, ny), dim3(128 * kCmuxItemsPerWG), kargs,
+                            kCmuxLds, st));
+    (e->*family.launches)++;
+    return EOC_OK;
+}
+
+extern "C" int eoc_cmux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in0, const int32_t *d_in1, int32_t *d_out,
+                               size_t count, void *hip_stream)
+{
+    if (!e || !d_sel_fft || !d_in0 || !d_in1 || !d_out) {
+        eoc_set_error("eoc_cmux_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t sel = (size_t)e->kpl * 2 * kNH, smp = (size_t)2 * kN;
+    constexpr size_t kSlice = (size_t)1 << 30; // items per launch (grid x)
+    for (size_t i0 = 0; i0 < count; i0 += kSlice) {
+        CmuxArgs a{};
+        a.sel = static_cast<const d2 *>(d_sel_fft) + i0 * sel;
+        a.in0 = d_in0 + i0 * smp;
+        a.in1 = d_in1 + i0 * smp;
+        a.out = d_out + i0 * smp;
+        a.sel_x = sel;
+        a.in0_x = a.in1_x = a.out_x = smp;
+        a.nx = (uint32_t)std::min(kSlice, count - i0);
+        a.rot = 0;
+        int rc = launch_leveled(e, kCmuxFamily, a, 1, (hipStream_t)hip_stream);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+// The walk over a table of 2^d lists of 2^(10 - r) slots that the encrypted-index read and update share: d tree stages and r
+// rotations per query, through two ping-pong buffers that hold 2^(d-1) and 2^(d-2) samples per query (the rotations one).
+// Queries are sliced so that both buffers together stay inside the byte budget (EOC_TFHE_TABLE_WS_BYTES) and a slice fits
+// grid y.
+struct TableWalk {
+    int d, r, depth;
+    size_t W, smp, sel; // slots per list; ints per TLWE sample and d2 per converted selector
+    size_t s0, s1;      // samples per query in buffer 0 and 1
+    size_t qs;          // queries per slice
+};
+// validation (messages under the caller's name `who`), the derived sizes, the budget check, queries per slice; ptrs_ok = the
+// caller's own pointers are there.  Reads nothing of the engine that changes after creation: called ahead of the lock.
+static int table_walk_plan(const eoc_engine *e, const char *who, bool ptrs_ok, int log2_lists, int log2_width, const void *d_sel_fft,
+                           size_t queries, TableWalk *tw)
+{
+    if (!e || !ptrs_ok || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10 ||
+        (!d_sel_fft && log2_lists + 10 - log2_width > 0)) {
+        eoc_set_error("%s: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]", who, log2_lists,
+                      log2_width);
+        return EOC_ERR_ARG;
+    }
+    const int d = log2_lists, r = 10 - log2_width;
+    *tw = TableWalk{d, r, d + r, (size_t)1 << log2_width, (size_t)2 * kN, (size_t)e->kpl * 2 * kNH,
+                    d >= 1 ? (size_t)1 << (d - 1) : 1, d >= 2 ? (size_t)1 << (d - 2) : 1, 0};
+    const size_t per_query = (tw->s0 + tw->s1) * tw->smp * sizeof(int32_t);
+    if (tw->depth > 0 && e->table_ws_bytes < per_query) {
+        eoc_set_error("%s: one query at log2_lists = %d needs %zu bytes of workspace, the budget (EOC_TFHE_TABLE_WS_BYTES) is %zu",
+                      who, d, per_query, e->table_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    tw->qs = std::min<size_t>(queries, 32768); // grid y
+    if (tw->depth > 0) tw->qs = std::min(tw->qs, e->table_ws_bytes / per_query);
+    return EOC_OK;
+}
+// the two buffers of a slice, by the scratch rule
+static int table_walk_reserve(eoc_engine *e, const TableWalk &tw, hipStream_t st)
+{
+    if (tw.depth == 0) return EOC_OK;
+    const size_t per_sample = tw.qs * tw.smp * sizeof(int32_t);
+    int rc = scratch_reserve(e, e->cmux[0], tw.s0 * per_sample, "table workspace (buffer 0)", st);
+    if (!rc) rc = scratch_reserve(e, e->cmux[1], tw.s1 * per_sample, "table workspace (buffer 1)", st);
+    return rc;
+}
+// The r rotations of a slice of Q queries: the CMux under selector bit i picks its input or the input times X^(sign W 2^i).
+// Rotation 0 reads *cur, *cur_y ints between the queries' samples (0: one shared sample); rotation i leaves one sample per
+// query in buffer out_buf(tw, i); *cur and *cur_y follow the last output.
+static int table_walk_rotations(eoc_engine *e, const TableWalk &tw, const d2 *selq, int sign, const int32_t **cur, size_t *cur_y,
+                                int (*out_buf)(const TableWalk &, int), size_t Q, hipStream_t st)
+{
+    for (int i = 0; i < tw.r; i++) {
+        CmuxArgs a{};
+        a.nx = 1;
+        a.sel = selq + (size_t)i * tw.sel;
+        a.sel_y = (size_t)tw.depth * tw.sel;
+        a.in0 = a.in1 = *cur;
+        a.in0_y = a.in1_y = *cur_y;
+        a.out = e->cmux[out_buf(tw, i)].i32();
+        a.out_y = tw.smp;
+        a.rot = sign > 0 ? (int)(tw.W << i) : 2 * kN - (int)(tw.W << i);
+        int rc = launch_leveled(e, kCmuxFamily, a, (uint32_t)Q, st);
+        if (rc) return rc;
+        *cur = a.out;
+        *cur_y = a.out_y;
+    }
+    return EOC_OK;
+}
+
+// The tail of a leveled read: slots w < W of ny TLWE samples become rows y W + w of the key-switch operand and of `o`
+// (k_tlwe_extract), and one key switch over the ny W rows leaves the LWE samples in `o`, p.n + 1 ints apart.
+// pick == NULL: sample y is samples + y * stride, one launch.  pick: sample y is samples + pick[y] * stride (public indices,
+// checked by the caller), one launch each.
+static int extract_and_keyswitch(eoc_engine *e, WS &Wk, const int32_t *samples, size_t stride, const int32_t *pick, size_t W,
+                                 size_t ny, int32_t *o, hipStream_t st)
+{
+    const size_t out_stride = (size_t)e->p.n + 1;
+    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    const unsigned ext_x = (unsigned)((W + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
+    {
+        SpanGuard span(e, st, KIND_PREPARE);
+        if (!pick)
+            hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, (unsigned)ny), dim3(256), 0, st, samples, stride, (uint32_t)W, Wk.d_ubar,
+                               o, e->p.n, prec_offset);
+        else
+            for (size_t i = 0; i < ny; i++)
+                hipLaunchKernelGGL(k_tlwe_extract, dim3(ext_x, 1), dim3(256), 0, st, samples + (size_t)pick[i] * stride, (size_t)0,
+                                   (uint32_t)W, Wk.d_ubar + i * W * kN, o + i * W * out_stride, e->p.n, prec_offset);
+        HIP_TRY(hipGetLastError());
+    }
+    const GateDesc gd{OP_RAW, 0, nullptr, nullptr, nullptr, o};
+    int rc = launch_keyswitch(e, Wk, nullptr, 1, (uint32_t)(ny * W), st, true, &gd);
+    if (rc) return rc;
+    e->stats[2] += ny * W;
+    return EOC_OK;
+}
+
+extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
+                                     size_t queries, int32_t *d_out, void *hip_stream)
+{
+    TableWalk tw;
+    int rc = table_walk_plan(e, "eoc_table_read_device", d_table && d_out, log2_lists, log2_width, d_sel_fft, queries, &tw);
+    if (rc) return rc;
+    tw.qs = std::min(tw.qs, std::max<size_t>(1, ((size_t)1 << 20) / tw.W)); // 2^20 extracted samples a slice (lut_levels' rule)
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->ksk) {
+        eoc_set_error("eoc_table_read_device: no key-switch key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    if (!queries) return EOC_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    WS &Wk = e->ws;
+    const int d = tw.d, r = tw.r, depth = tw.depth;
+    const size_t W = tw.W, smp = tw.smp, sel = tw.sel, qs = tw.qs;
+    rc = ensure_ws(e, Wk, qs * W, 0, 0, st);
+    if (!rc) rc = table_walk_reserve(e, tw, st);
+    if (rc) return rc;
+    for (size_t q0 = 0; q0 < queries; q0 += qs) {
+        const size_t Q = std::min(qs, queries - q0);
+        const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * depth * sel;
+        const int32_t *cur = d_table; // the TLWE samples the next launch reads: [Q][cur_y / smp] (cur_y = 0: shared)
+        size_t cur_y = 0;
+        int t = 0;
+        for (int v = 0; v < d; v++, t++) { // tree: nodes (2j, 2j + 1) -> j with bit r + v
+            CmuxArgs a{};
+            a.nx = (uint32_t)1 << (d - 1 - v);
+            a.sel = selq + (size_t)(r + v) * sel;
+            a.sel_x = 0;
+            a.sel_y = (size_t)depth * sel;
+            a.in0 = cur;
+            a.in1 = cur + smp;
+            a.in0_x = a.in1_x = 2 * smp;
+            a.in0_y = a.in1_y = cur_y;
+            a.out = e->cmux[t & 1].i32();
+            a.out_x = smp;
+            a.out_y = (size_t)a.nx * smp;
+            a.rot = 0;
+            if ((rc = launch_leveled(e, kCmuxFamily, a, (uint32_t)Q, st))) return rc;
+            cur = a.out;
+            cur_y = a.out_y;
+        }
+        // rotations: X^(-W 2^i) under bit i brings slot W 2^i to slot 0; launch t = d + i of the query writes buffer t & 1
+        rc = table_walk_rotations(e, tw, selq, -1, &cur, &cur_y, [](const TableWalk &w, int i) { return (w.d + i) & 1; }, Q, st);
+        if (rc) return rc;
+        rc = extract_and_keyswitch(e, Wk, cur, cur_y, nullptr, W, Q, d_out + q0 * W * ((size_t)e->p.n + 1), st);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+// ---- encrypted-index table updates: the demultiplexer and table[idx] += v (DESIGN.md 15) ----
+extern "C" int eoc_demux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in, int32_t *d_out0, int32_t *d_out1,
+                                size_t count, int accumulate, void *hip_stream)
+{
+    if (!e || !d_sel_fft || !d_in || !d_out0 || !d_out1) {
+        eoc_set_error("eoc_demux_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t sel = (size_t)e->kpl * 2 * kNH, smp = (size_t)2 * kN;
+    constexpr size_t kSlice = (size_t)1 << 30; // items per launch (grid x)
+    for (size_t i0 = 0; i0 < count; i0 += kSlice) {
+        DemuxArgs a{};
+        a.sel = static_cast<const d2 *>(d_sel_fft) + i0 * sel;
+        a.in = d_in + i0 * smp;
+        a.out0 = d_out0 + i0 * smp;
+        a.out1 = d_out1 + i0 * smp;
+        a.sel_x = sel;
+        a.in_x = a.out_x = smp;
+        a.nx = (uint32_t)std::min(kSlice, count - i0);
+        a.accumulate = accumulate != 0;
+        int rc = launch_leveled(e, kDemuxFamily, a, 1, (hipStream_t)hip_stream);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+extern "C" int eoc_table_update_device(eoc_engine *e, int32_t *d_table, int log2_lists, int log2_width, const void *d_sel_fft,
+                                       const int32_t *d_vals, size_t queries, void *hip_stream)
+{
+    // the read's walk and its two buffers: the storing stages leave 2^(d-1) and 2^(d-2) samples per query, the rotations one
+    TableWalk tw;
+    int rc = table_walk_plan(e, "eoc_table_update_device", d_table && d_vals, log2_lists, log2_width, d_sel_fft, queries, &tw);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!queries) return EOC_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if ((rc = table_walk_reserve(e, tw, st))) return rc;
+    const int d = tw.d, r = tw.r, depth = tw.depth;
+    const size_t smp = tw.smp, sel = tw.sel, qs = tw.qs;
+    for (size_t q0 = 0; q0 < queries; q0 += qs) {
+        const size_t Q = std::min(qs, queries - q0);
+        const d2 *selq = static_cast<const d2 *>(d_sel_fft) + q0 * depth * sel;
+        const int32_t *cur = d_vals + q0 * smp; // one sample per query until the tree starts
+        size_t cur_y = smp;
+        // rotations: X^(W 2^i) under bit i carries the value to slot W (idx mod 2^r).  Rotation i leaves its result in
+        // buffer (d - 1 + r - 1 - i) & 1, so the last one ends where the first storing stage does not write
+        rc = table_walk_rotations(e, tw, selq, +1, &cur, &cur_y, [](const TableWalk &w, int i) { return (w.d + w.r - i) & 1; }, Q,
+                                  st);
+        if (rc) return rc;
+        if (d == 0) { // one list: the rotated value is the leaf
+            const bool vec = (((uintptr_t)cur | (uintptr_t)d_table) & 15) == 0;
+            SpanGuard span(e, st, KIND_BLIND_ROTATE);
+            if (vec) hipLaunchKernelGGL(k_sample_add<4>, dim3(2 * kN / (256 * 4), (unsigned)Q), dim3(256), 0, st, cur, d_table);
+            else hipLaunchKernelGGL(k_sample_add<1>, dim3(2 * kN / 256, (unsigned)Q), dim3(256), 0, st, cur, d_table);
+            HIP_TRY(hipGetLastError());
+            continue;
+        }
+        // tree: stage t under bit r + (d - 1 - t), parent j of 2^t -> children 2j (x - E) and 2j + 1 (E).  Stage t < d - 1
+        // stores [Q][2^(t+1)] samples into buffer (d - 2 - t) & 1 (the larger buffer takes the last storing stage); stage
+        // d - 1 accumulates its 2^d leaves into the table
+        for (int t = 0; t < d; t++) {
+            DemuxArgs a{};
+            a.nx = (uint32_t)1 << t;
+            a.sel = selq + (size_t)(r + d - 1 - t) * sel;
+            a.sel_x = 0;
+            a.sel_y = (size_t)depth * sel;
+            a.in = cur;
+            a.in_x = smp;
+            a.in_y = cur_y;
+            a.out_x = 2 * smp;
+            if (t == d - 1) {
+                a.out0 = d_table;
+                a.out_y = 0;
+                a.accumulate = 1;
+            } else {
+                a.out0 = e->cmux[(d - 2 - t) & 1].i32();
+                a.out_y = (size_t)2 * a.nx * smp;
+                a.accumulate = 0;
+            }
+            a.out1 = a.out0 + smp;
+            if ((rc = launch_leveled(e, kDemuxFamily, a, (uint32_t)Q, st))) return rc;
+            cur = a.out0;
+            cur_y = a.out_y;
+        }
+    }
+    return EOC_OK;
+}
+
+// ---- finite automata on encrypted bit strings: leveled CMux steps (DESIGN.md 17) -------------
 constexpr size_t kAutoMaxStates = 4096;
 
 // The public part of a call, checked on the host before anything touches a device: the kernel gathers through these records,
@@ -2753,7 +2570,83 @@ try {
     eoc_set_error("eoc_automaton_run_device: out of memory");
     return EOC_ERR_ALLOC;
 }
-extern "C" uint64_t eoc_engine_automaton_launches(eoc_engine *e) { return e ? e->automaton_launches : 0; }
+
+// ---- packing key switch: LWE samples -> compact TLWE lists (DESIGN.md 13) -------------------
+static_assert(kPackT == EOC_PACK_T && kPackBasebit == EOC_PACK_BASEBIT, "the kernels' decomposition is the format's");
+extern "C" int eoc_engine_set_packing_key(eoc_engine *e, const void *blob, size_t len)
+{
+    eoc_params bp;
+    const int32_t *rows = nullptr;
+    if (!e || !eoc_packing_key_blob_rows(blob, len, &bp, &rows)) {
+        eoc_set_error("eoc_engine_set_packing_key: null argument or not a whole EOCPKS1 blob (t = %d, basebit = %d)", kPackT,
+                      kPackBasebit);
+        return EOC_ERR_ARG;
+    }
+    const eoc_params &p = e->p;
+    if (bp.n != p.n || bp.l != p.l || bp.Bgbit != p.Bgbit || bp.ks_t != p.ks_t || bp.ks_basebit != p.ks_basebit ||
+        bp.ks_stdev != p.ks_stdev || bp.bk_stdev != p.bk_stdev) {
+        eoc_set_error("eoc_engine_set_packing_key: the blob's parameters (n = %d, l = %d) are not the engine's (n = %d, l = %d)",
+                      bp.n, bp.l, p.n, p.l);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t npoly = (size_t)p.n * kPackT * 2;
+    HIP_TRY(hipDeviceSynchronize()); // nothing in flight may still read the image that is about to be replaced
+    hipFree(e->d_pks);
+    e->d_pks = nullptr;
+    DevTmp d_rows, d_img;
+    HIP_TRY(d_rows.alloc(npoly * kN * sizeof(int32_t)));
+    HIP_TRY(d_img.alloc(npoly * kNH * sizeof(d2)));
+    HIP_TRY(hipMemcpy(d_rows.p, rows, npoly * kN * sizeof(int32_t), hipMemcpyHostToDevice));
+    // the key-load transform (build_cloud_key_images, eoc_tgsw_to_fft_device); NULL stream, drained inside
+    int rc = key_image(e, d_rows.i32(), d_img.p, npoly);
+    if (rc) return rc;
+    e->d_pks = static_cast<d2 *>(d_img.release());
+    return EOC_OK;
+}
+
+// k_pack_gather lays the mask columns out as polynomials and starts every list as (0, B); k_pack_rows subtracts the chunks.
+// All arguments travel as kernel arguments: no descriptor ring slot.  Lists are sliced by the byte budget of the columns.
+extern "C" int eoc_pack_device(eoc_engine *e, const int32_t *d_in, size_t count, int32_t *d_lists, void *hip_stream)
+{
+    if (!e || !d_in || !d_lists) {
+        eoc_set_error("eoc_pack_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->d_pks) {
+        eoc_set_error("eoc_pack_device: no packing key loaded (eoc_engine_set_packing_key)");
+        return EOC_ERR_NO_KEY;
+    }
+    if (!count) return EOC_OK;
+    const size_t n = (size_t)e->p.n, per_list = n * kN * sizeof(int32_t), n_lists = (count + kN - 1) / kN;
+    if (e->pack_ws_bytes < per_list) {
+        eoc_set_error("eoc_pack_device: one list needs %zu bytes of workspace, the budget (EOC_TFHE_PACK_WS_BYTES) is %zu",
+                      per_list, e->pack_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t ls = std::min({n_lists, e->pack_ws_bytes / per_list, (size_t)65535}); // grid z
+    int rc = scratch_reserve(e, e->pack_cols, ls * per_list, "packing columns", st);
+    if (rc) return rc;
+    for (size_t l0 = 0; l0 < n_lists; l0 += ls) {
+        const size_t L = std::min(ls, n_lists - l0), cnt = std::min(count - l0 * kN, L * kN);
+        const int32_t *in = d_in + l0 * kN * (n + 1);
+        int32_t *lists = d_lists + l0 * 2 * kN;
+        {
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            hipLaunchKernelGGL(k_pack_gather, dim3(kN / kPackTile, (unsigned)((n + 1 + kPackTile - 1) / kPackTile), (unsigned)L),
+                               dim3(256), 0, st, in, cnt, (int)n, e->pack_cols.i32(), lists);
+            HIP_TRY(hipGetLastError());
+        }
+        rc = launch_pack_rows(e, lists, L, st);
+        if (rc) return rc;
+    }
+    e->packed_samples += count;
+    return EOC_OK;
+}
 
 // ---- inner products with public integer weights on compact lists -------------
 // The device image of a model: the weight spectra [rows][L][512] complex (k_fft_fwd_polys at scale 1 of the weight
@@ -2929,10 +2822,84 @@ extern "C" int eoc_linear_device(eoc_engine *e, const void *d_image, size_t rows
     if (int rc = dot_check(e, "eoc_linear_device", d_image, rows, cols, d_lists, batch, d_bias, d_out, (size_t)e->p.n + 1)) return rc;
     return dot_locked(e, "eoc_linear_device", d_image, rows, cols, d_lists, batch, d_bias, nullptr, d_out, (hipStream_t)hip_stream);
 }
-extern "C" uint64_t eoc_engine_dot_launches(eoc_engine *e) { return e ? e->dot_launches : 0; }
-// tables + four transpose scratches, as k_pack_rows (eoc_engine_create)
-static void set_dot_attrs()
+
+// ---- introspection: profiling, statistics, counters ------------------------------------------
+extern "C" int eoc_engine_set_profiling(eoc_engine *e, int on)
 {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dot_mask<kDotChunk>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kDotLds);
+    if (!e) return EOC_ERR_ARG;
+    std::lock_guard<std::mutex> g(e->mu);
+    e->profiling = on != 0;
+    return EOC_OK;
 }
+
+// drains the recorded event pairs (synchronises the device) and returns accumulated times
+extern "C" int eoc_engine_kernel_times(eoc_engine *e, double ms[3], uint64_t launches[3], int reset)
+{
+    if (!e || !ms || !launches) return EOC_ERR_ARG;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    for (auto &sp : e->spans) {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) {
+            e->kernel_ms[sp.kind] += t;
+            e->kernel_launches[sp.kind] += 1;
+        }
+        hipEventDestroy(sp.a);
+        hipEventDestroy(sp.b);
+    }
+    e->spans.clear();
+    for (int i = 0; i < 3; i++) {
+        ms[i] = e->kernel_ms[i];
+        launches[i] = e->kernel_launches[i];
+        if (reset) {
+            e->kernel_ms[i] = 0;
+            e->kernel_launches[i] = 0;
+        }
+    }
+    return EOC_OK;
+}
+
+#ifdef EOC_STAMPS
+// diagnostic build only: allocate / read back the in-kernel stamp buffer ([waves][16] cycle sums)
+extern "C" int eoc_dbg_stamps(eoc_engine *e, size_t waves, unsigned long long *host_out)
+{
+    if (!e) return EOC_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    if (!host_out) {
+        hipFree(e->d_stamps);
+        HIP_TRY(hipMalloc(&e->d_stamps, waves * 16 * 8));
+        HIP_TRY(hipMemset(e->d_stamps, 0, waves * 16 * 8));
+        return EOC_OK;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(host_out, e->d_stamps, waves * 16 * 8, hipMemcpyDeviceToHost));
+    return EOC_OK;
+}
+#endif
+
+extern "C" int eoc_engine_stats(eoc_engine *e, uint64_t out[3])
+{
+    if (!e || !out) return EOC_ERR_ARG;
+    for (int i = 0; i < 3; i++) out[i] = e->stats[i];
+    return EOC_OK;
+}
+extern "C" uint64_t eoc_engine_workspace_grows(eoc_engine *e) { return e ? e->ws_grows : 0; }
+extern "C" uint64_t eoc_engine_blind_rotate_launches(eoc_engine *e) { return e ? e->br_launches : 0; }
+extern "C" uint64_t eoc_engine_blind_rotate_wide_launches(eoc_engine *e) { return e ? e->br_wide_launches : 0; }
+extern "C" uint64_t eoc_engine_keyswitch_mfma_launches(eoc_engine *e) { return e ? e->ks_mfma_launches : 0; }
+extern "C" uint64_t eoc_engine_cmux_launches(eoc_engine *e) { return e ? e->cmux_launches : 0; }
+extern "C" uint64_t eoc_engine_demux_launches(eoc_engine *e) { return e ? e->demux_launches : 0; }
+extern "C" uint64_t eoc_engine_automaton_launches(eoc_engine *e) { return e ? e->automaton_launches : 0; }
+extern "C" uint64_t eoc_engine_pack_launches(eoc_engine *e) { return e ? e->pack_launches : 0; }
+extern "C" uint64_t eoc_engine_packed_samples(eoc_engine *e) { return e ? e->packed_samples : 0; }
+extern "C" uint64_t eoc_engine_seed_launches(eoc_engine *e) { return e ? e->seed_launches : 0; }
+extern "C" uint64_t eoc_engine_dot_launches(eoc_engine *e) { return e ? e->dot_launches : 0; }
+extern "C" size_t eoc_engine_resident_jobs(eoc_engine *e)
+{
+    if (!e) return 0;
+    const bool wide = e->p.l == 2 && e->br_wide != 0;
+    return (size_t)(wide ? 8 : 4) * (size_t)e->num_cus;
+}
+extern "C" int eoc_engine_device(eoc_engine *e) { return e ? e->device : -1; }
+extern "C" const eoc_params *eoc_engine_params(eoc_engine *e) { return e ? &e->p : nullptr; }

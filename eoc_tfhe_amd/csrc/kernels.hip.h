@@ -917,11 +917,8 @@ constexpr int kBRLds = (kTwEntries + kNH + 2 * kScr) * 16 + kAbarLds; // 37 632 
 //     that two parts would do instead of three, changed all eighteen in 42 to 365 lines.  Of the small pieces, the row
 //     loader (load_selector_row) and the store phases' cmulc + wrap_trunc pair (leveled_words) change nothing as
 //     force-inlined functions; the negacyclic gather does (EOC_NEGACYCLIC, a macro);
-//   * the ORDER in which kernels are emitted is part of the assembly text (branch labels carry the function's number): plain
-//     kernels come first, in the order of their definitions, then the templates in the order of their first use in
-//     engine.hip.  A plain kernel added anywhere, or a template instance first used ahead of an existing one, renumbers the
-//     labels of everything behind it (same instructions, different text for tools/isa_diff.py): new kernels are templates
-//     whose first use lies behind every earlier one (k_br_enc*: engine.hip's br_enc_kernel; k_tvpack_cols: tv_pack_locked).
+//   * kernels are compared modulo the function's number in the code object (tools/isa_diff.py drops it from the block
+//     labels): a new kernel may be plain and may stand where it belongs, here and in engine.hip.
 // The body's constant TV selects the accumulator: false = the gate test vector (mu, ..., mu),
 // true = a test polynomial per job.  The gate kernel's name, template arguments and argument list are what
 // tests/test_isa_guard.py and the profiles look up and what the shipped code was measured as: they do not change.
@@ -1864,8 +1861,7 @@ __global__ __launch_bounds__(64 * kPackWavesPerWG, 2) void k_pack_rows(const int
 // coefficients reads ONE sample: a wave loads 64 mask words (256 contiguous bytes) and stores, per key index, 64 copies of
 // one of them (256 contiguous bytes): no transpose, no LDS.  grid: x = N / 64 coefficient tiles, y = ceil((n + 1) / 64)
 // column tiles, z = lists of the slice (list = f rows + s - list0); block = 256 (wave w: columns w, w + 4, ...).  A template
-// over the message space p (defined and first used behind every other kernel: the device compiler emits kernels in that
-// order, and the earlier ones keep their label numbers).
+// over the message space p.
 template <int p>
 __global__ __launch_bounds__(256) void k_tvpack_cols(const int32_t *__restrict__ in, uint32_t rows, uint32_t list0, int n,
                                                      int32_t *__restrict__ cols, int32_t *__restrict__ lists)
@@ -1903,8 +1899,7 @@ __global__ __launch_bounds__(256) void k_tvpack_cols(const int32_t *__restrict__
 // destination, lane-contiguous (256 bytes per wave and instruction) as k_pack_rows leaves its results: the last stage of an
 // update adds its leaves straight into the table, every word an integer sum, so colliding queries and any order of arrival
 // give the same words.
-// grid: x = ceil(nx / kCmuxItemsPerWG) parents, y = ny; item (x, y) by strides in int32 (samples) / d2 (selectors).  Where
-// the templates are defined and first used is part of every later kernel's text: engine.hip, LeveledFamily.
+// grid: x = ceil(nx / kCmuxItemsPerWG) parents, y = ny; item (x, y) by strides in int32 (samples) / d2 (selectors).
 // =================================================================================================
 struct DemuxArgs {
     const d2 *sel;            // converted selectors
@@ -2116,8 +2111,6 @@ __global__ __launch_bounds__(256) void k_seed_masks(SeedArgs A)
 }
 
 // block i of [n_blocks][16] = ChaCha20(key, counter + i, nonce): the block function above, all 16 words (known-answer tests).
-// A template, as k_seed_masks, so that the code object lists both behind every earlier kernel (labels of the earlier
-// kernels keep their numbers: tools/isa_diff.py compares them as text).
 template <int WORDS>
 __global__ __launch_bounds__(256) void k_chacha20_blocks(SeedArgs A, uint64_t counter, uint64_t nonce, uint32_t *__restrict__ out)
 {
@@ -2148,7 +2141,7 @@ __global__ __launch_bounds__(256) void k_chacha20_blocks(SeedArgs A, uint64_t co
 // product but reloaded at store time, as k_cmux reloads in0.
 // prev_y = 0 reads one shared vector for every query (the first step reads the final vector in place).  next may not
 // overlap prev: a state may be its own successor, so the driver alternates two buffers.
-// grid: x = ceil(nx / kCmuxItemsPerWG) states, y = queries.  Defined and first used behind k_demux (engine.hip, LeveledFamily).
+// grid: x = ceil(nx / kCmuxItemsPerWG) states, y = queries.
 // =================================================================================================
 struct AutoTrans {
     int32_t next0, w0, next1, w1; // successor and weight under bit 0 / bit 1
@@ -2232,8 +2225,7 @@ constexpr int kDotLds = (kTwEntries + kNH + kDotWavesPerWG * kScr) * 16; // 53 7
 // m < nzero and body[s body_stride + body_at] = b'.  wts: the zero-padded weights [rows][L N] int8 behind the spectra of
 // the device image; lists: [batch][L][2][N].  grid: x = samples; block = 256.
 // Both kernels are templates (OPERAND: the key-switch form, whose body row is cleared in front of b'; CHUNK: the format's
-// chunk), defined and first used behind every other kernel: the device compiler emits kernels in that order, and the
-// earlier ones keep their label numbers (k_tvpack_cols).
+// chunk).
 template <bool OPERAND>
 __global__ __launch_bounds__(256) void k_dot_init(const int8_t *__restrict__ wts, const int32_t *__restrict__ lists,
                                                    const int32_t *__restrict__ bias, uint32_t rows, uint32_t L,

@@ -45,12 +45,17 @@ def kernel_meta(text):
     return meta
 
 
+# a branch target: .LBB<function's number in the code object>_<block index>
+_BLOCK_LABEL = re.compile(r"(?<![\w.$])\.LBB\d+_(\d+)\b")
+
+
 def kernel_bodies(text):
     """mangled kernel name -> its instructions, stripped, from the kernel's label to its .Lfunc_end: the whole function,
     not only what precedes the first s_endpgm (the blind-rotation kernels leave early once).  Comments, directives and
-    labels are dropped."""
+    labels are dropped.  Branch targets lose the function's number and keep the block index (.LBB17_4 -> .LBB_4): the
+    number says where in the code object the kernel was emitted, not what it does.  Nothing else is touched."""
     bodies = {}
     for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, flags=re.M | re.S):
         lines = (ln.strip() for ln in m.group(2).splitlines())
-        bodies[m.group(1)] = [ln for ln in lines if ln and not ln.startswith((";", "."))]
+        bodies[m.group(1)] = [_BLOCK_LABEL.sub(r".LBB_\1", ln) for ln in lines if ln and not ln.startswith((";", "."))]
     return bodies

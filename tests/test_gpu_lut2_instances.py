@@ -10,7 +10,10 @@ The seed lists have BOTH polynomials non-zero: pairs of br_edge_inputs.extreme_p
 with one list per group (per_row = 0) and with one list per job (per_row = 1: job (g, s) uses list (g + s) mod G of the same
 lists, so the per-group reference serves both).  The conversion contract (include/eoc_tfhe_gpu.h): every (l, Bgbit) here but
 Set A's (2, 10) keeps any input below 2^51; the oracle's recorded maximum is asserted below 2^51 for every reference
-(test_gpu_br_instances.reference), Set A's shape included."""
+(test_gpu_br_instances.reference), Set A's shape included.
+
+The family has no earlier-form twin: the two gadget-length-2 pair shapes run once more with EOC_TFHE_BR_TABLES_LDS=1, where
+blind_rotate_kernel() must still pick k_br_enc."""
 import numpy as np
 import pytest
 
@@ -68,6 +71,20 @@ def run_enc(eng, lists, n_groups, per_row, rows):
 
 @pytest.mark.parametrize("shape,readback", INSTANCES, ids=[kernel_name(*i) for i in INSTANCES])
 def test_instance_bit_exact_on_edge_inputs(eoc, monkeypatch, shape, readback):
+    check_instance(eoc, monkeypatch, shape, readback)
+
+
+LDS_SHAPES = [s for s in SHAPES if s.startswith("lds")]
+
+
+@pytest.mark.parametrize("shape", LDS_SHAPES, ids=[f"k_br_enc<{SHAPES[s][0]},vabar>+tables_lds" for s in LDS_SHAPES])
+def test_family_runs_its_shipped_form_under_the_earlier_form_knob(eoc, monkeypatch, shape):
+    """EOC_TFHE_BR_TABLES_LDS=1 sends the other three families of gadget length 2 to their k_br_lds* twins; this family has
+    none, and blind_rotate_kernel() keeps it on k_br_enc: the same inputs, the same reference, the same words"""
+    check_instance(eoc, monkeypatch, shape, "vabar")
+
+
+def check_instance(eoc, monkeypatch, shape, readback):
     _, (l, Bgbit), env = SHAPES[shape]
     wide = shape.startswith("wide")
     for n in (1, 2):

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Did the kernels change?  Compares two assembly files of engine.hip (hipcc -S with the flags of tests/isa_lib.py, one
-from the parent commit and one from the working tree) kernel by kernel, as text.
+from the parent commit and one from the working tree) kernel by kernel: the instructions as text, modulo the function's
+number in the code object (branch targets keep their block index and lose that number: isa_lib.kernel_bodies), and the
+metadata (registers, spills, scratch, LDS) as they are.  Where a kernel stands in the code object is therefore no
+difference; one line says whether the kernels both sides have are emitted in the same order (information only).
 
     python tools/isa_diff.py parent.s new.s --must-match k_blind_rotateILi2ELi10E --must-match k_keyswitch
 
@@ -49,6 +52,12 @@ def main():
         print(f"DIFFERENT{' (must match)' if must else ''}  {name}: {len(a)} -> {len(b)} instructions, "
               f"{changed_lines(a, b)} changed lines")
         print(f"    old {ma}\n    new {mb}")
+    order = [[k for k in b if k in bodies[0] and k in bodies[1]] for b in bodies]
+    moved = next((i for i, (a, b) in enumerate(zip(*order)) if a != b), None)
+    if moved is None:
+        print(f"order: the {len(order[0])} common kernels are emitted in the same order")
+    else:
+        print(f"order: changed, first at index {moved} of {len(order[0])} common kernels: {order[0][moved]} -> {order[1][moved]}")
     print(f"summary: {same} identical, {different} different, {meta_changed} with changed metadata, "
           f"{failed} must-match failures")
     return 1 if failed else 0
