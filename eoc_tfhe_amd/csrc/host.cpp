@@ -1147,6 +1147,12 @@ int ensure_engine_locked()
     c.engine_ready = true;
     return EOC_OK;
 }
+EngineGuard::EngineGuard() : lock(ctx().mu), keyed(ctx().params() != nullptr), rc(keyed ? ensure_engine_locked() : EOC_OK) {}
+int no_public_key()
+{
+    fprintf(stderr, "Public key not initialized. Generate the public key first.\n");
+    return EOC_ERR_NO_KEY;
+}
 void drop_keys_locked()
 {
     GlobalCtx &c = ctx();
@@ -1162,6 +1168,17 @@ void drop_keys_locked()
 } // namespace eoc_host
 
 using namespace eoc_host;
+
+// the global secret key (caller holds ctx().mu), or NULL behind the reference's message (eoc-tfhe-run.cpp:277-278, 421-424):
+// the caller then answers NULL / -1 / EOC_ERR_NO_KEY
+static eoc_secret_key *global_secret_key()
+{
+    if (!ctx().sk) fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
+    return ctx().sk;
+}
+// the eoc_global_* calls that evaluate (caller holds ctx().mu): they need the PUBLIC (cloud) key only -- the message and
+// EOC_ERR_NO_KEY without one --, and the engines behind it, created and loaded on first use; no CPU fallback
+static int global_engines_locked() { return ctx().params() ? ensure_engine_locked() : no_public_key(); }
 
 extern "C" const char *generateGateKey(int minimum_lambda, uint64_t seed)
 {
@@ -1206,10 +1223,7 @@ extern "C" const char *encryptBit(int bit, const char *)
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.sk) { // eoc-tfhe-run.cpp:277-278
-        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
-        return nullptr;
-    }
+    if (!global_secret_key()) return nullptr;
     std::vector<int32_t> ct(c.sk->p.n + 1);
     uint8_t b = bit ? 1 : 0;
     if (c.enc_secure) eoc_encrypt_bits_keyed(c.sk, c.enc_key, c.enc_counter++, &b, 1, ct.data());
@@ -1223,7 +1237,7 @@ extern "C" const char *constantBit(int bit)
     std::lock_guard<std::mutex> g(c.mu);
     const eoc_params *p = c.params();
     if (!p) { // the sample length comes from the key's parameter set (a cloud key is enough: nothing secret is involved)
-        fprintf(stderr, "Public key not initialized. Generate the public key first.\n");
+        no_public_key();
         return nullptr;
     }
     std::vector<int32_t> ct(p->n + 1, 0); // lweNoiselessTrivial(+-1/8)
@@ -1235,10 +1249,7 @@ extern "C" int decryptBit(const char *b64ct, const char *)
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.sk) { // eoc-tfhe-run.cpp:421-424
-        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
-        return -1;
-    }
+    if (!global_secret_key()) return -1;
     std::vector<int32_t> ct;
     if (!b64_to_sample(b64ct, c.sk->p.n, ct, nullptr)) {
         fprintf(stderr, "decryptBit: malformed ciphertext\n");
@@ -1251,11 +1262,9 @@ static const char *gate_strings(int op, const char *c1, const char *c2, const ch
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.params()) { // eoc-tfhe-run.cpp:465-468: the gates need the PUBLIC (cloud) key only, as addCiphertexts does
-        fprintf(stderr, "Public key not initialized. Generate the public key first.\n");
-        return nullptr;
-    }
-    if (ensure_engine_locked()) return nullptr; // no GPU: no gates (message already on stderr)
+    // eoc-tfhe-run.cpp:465-468: the gates need the PUBLIC (cloud) key only, as addCiphertexts does; no GPU: no gates (message
+    // already on stderr)
+    if (global_engines_locked()) return nullptr;
     const int n = c.params()->n;
     std::vector<int32_t> a, b, cc, out(n + 1);
     if (!b64_to_sample(c1, n, a, nullptr) || (op != EOC_NOT && !b64_to_sample(c2, n, b, nullptr)) ||
@@ -1294,10 +1303,7 @@ extern "C" int eoc_global_encrypt_bits(const uint8_t *bits, size_t count, int32_
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.sk) {
-        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
+    if (!global_secret_key()) return EOC_ERR_NO_KEY;
     int rc = c.enc_secure ? eoc_encrypt_bits_keyed(c.sk, c.enc_key, c.enc_counter, bits, count, cts)
                           : eoc_encrypt_bits(c.sk, c.enc_seed, c.enc_counter, bits, count, cts);
     c.enc_counter += count;
@@ -1307,10 +1313,7 @@ extern "C" int eoc_global_tgsw_encrypt_bits(const uint8_t *bits, size_t count, i
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.sk) {
-        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
+    if (!global_secret_key()) return EOC_ERR_NO_KEY;
     int rc = c.enc_secure ? eoc_tgsw_encrypt_bits_keyed(c.sk, c.enc_key, c.enc_counter, bits, count, out)
                           : eoc_tgsw_encrypt_bits(c.sk, c.enc_seed, c.enc_counter, bits, count, out);
     if (rc == EOC_OK) c.enc_counter += count;
@@ -1320,20 +1323,14 @@ extern "C" int eoc_global_decrypt_bits(const int32_t *cts, size_t count, uint8_t
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.sk) {
-        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
+    if (!global_secret_key()) return EOC_ERR_NO_KEY;
     return eoc_decrypt_bits(c.sk, cts, count, bits);
 }
 extern "C" int eoc_global_encrypt_ints(int p, const uint8_t *values, size_t count, int32_t *cts)
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.sk) {
-        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
+    if (!global_secret_key()) return EOC_ERR_NO_KEY;
     int rc = encrypt_ints(c.sk, c.enc_secure ? c.enc_key : nullptr, c.enc_seed, c.enc_counter, p, values, count, cts);
     if (rc == EOC_OK) c.enc_counter += count;
     return rc;
@@ -1342,10 +1339,7 @@ extern "C" int eoc_global_decrypt_ints(int p, const int32_t *cts, size_t count, 
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.sk) {
-        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
+    if (!global_secret_key()) return EOC_ERR_NO_KEY;
     return eoc_decrypt_ints(c.sk, p, cts, count, values);
 }
 // batch of gates on the global key's engine (created and loaded on first use); no CPU fallback
@@ -1354,12 +1348,7 @@ extern "C" int eoc_global_gate_batch(int op, const uint8_t *ops, const int32_t *
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.params()) {
-        fprintf(stderr, "Public key not initialized. Generate the public key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
-    int rc = ensure_engine_locked();
-    if (rc) return rc;
+    if (int rc = global_engines_locked()) return rc;
     return eoc_gate_batch(op, ops, in0, in1, in2, out, count);
 }
 // the asynchronous form on the global key's engine (buffers from eoc_host_alloc; eoc_gate_batch_wait completes it)
@@ -1368,107 +1357,15 @@ extern "C" int eoc_global_gate_batch_submit(int op, const uint8_t *ops, const in
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.params()) {
-        fprintf(stderr, "Public key not initialized. Generate the public key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
-    int rc = ensure_engine_locked();
-    if (rc) return rc;
+    if (int rc = global_engines_locked()) return rc;
     return eoc_gate_batch_submit(op, ops, in0, in1, in2, out, count, ticket);
-}
-// compact lists -> LWE samples on the global context's engines (brought up behind the global key on first use; a cloud key
-// alone suffices)
-extern "C" int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *out)
-{
-    if (!lists || !out) {
-        eoc_set_error("eoc_compact_expand: null argument");
-        return EOC_ERR_ARG;
-    }
-    if (!count) return EOC_OK;
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) {
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    }
-    return eoc_compact_expand_engines(lists, count, out);
-}
-// inner products with public weights on the global context's engines: WHOLE input vectors are cut over the
-// engines (brought up behind the global key on first use; a cloud key alone suffices)
-extern "C" int eoc_linear(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch, const int32_t *h_bias,
-                          int32_t *h_out)
-{
-    if (!h_w || !h_lists || !h_out) {
-        eoc_set_error("eoc_linear: null argument");
-        return EOC_ERR_ARG;
-    }
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) {
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    }
-    return eoc_linear_engines(h_w, rows, cols, h_lists, batch, h_bias, h_out);
-}
-// seeded samples -> LWE samples on the global context's engines: samples are cut into eoc_shard_range blocks,
-// one per engine; every block's upload and kernel are queued before the first result is collected.  No key is used: the
-// engines come up behind the global key when there is one, engines of eoc_gpu_init serve without
-extern "C" int eoc_seeded_expand(const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies, size_t count, int32_t *out)
-{
-    if (!seed || !bodies || !out) {
-        eoc_set_error("eoc_seeded_expand: null argument");
-        return EOC_ERR_ARG;
-    }
-    if (!count) return EOC_OK;
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) {
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    }
-    const int world = eoc_gpu_engine_count();
-    if (world <= 0) {
-        eoc_set_error("eoc_seeded_expand: no engine (install a key or call eoc_gpu_init first)");
-        return EOC_ERR_STATE;
-    }
-    struct Block {
-        eoc_engine *e = nullptr;
-        void *d_bodies = nullptr, *d_out = nullptr;
-        size_t lo = 0, hi = 0;
-    };
-    std::vector<Block> blocks(world);
-    int rc = EOC_OK;
-    for (int r = 0; r < world && !rc; r++) {
-        Block &b = blocks[r];
-        eoc_shard_range(count, r, world, &b.lo, &b.hi);
-        if (b.lo == b.hi) continue;
-        b.e = eoc_global_engine_at(r);
-        const size_t S = b.hi - b.lo, st = size_t(eoc_engine_params(b.e)->n) + 1;
-        rc = eoc_device_alloc(b.e, S * 4, &b.d_bodies);
-        if (!rc) rc = eoc_device_alloc(b.e, S * st * 4, &b.d_out);
-        if (!rc) rc = eoc_host_to_device(b.e, b.d_bodies, bodies + b.lo, S * 4);
-        if (!rc) rc = eoc_seeded_expand_device(b.e, seed, first_idx + b.lo, static_cast<const int32_t *>(b.d_bodies), S,
-                                               static_cast<int32_t *>(b.d_out), nullptr);
-    }
-    for (Block &b : blocks) {
-        if (!b.e) continue;
-        const size_t st = size_t(eoc_engine_params(b.e)->n) + 1;
-        if (!rc) rc = eoc_device_to_host(b.e, out + b.lo * st, b.d_out, (b.hi - b.lo) * st * 4); // behind the NULL-stream kernel
-        else eoc_engine_synchronize(b.e);
-        if (b.d_bodies) eoc_device_free(b.e, b.d_bodies);
-        if (b.d_out) eoc_device_free(b.e, b.d_out);
-    }
-    return rc;
 }
 // ---- packing key switch on the global context ----
 static int global_list_call(const int32_t *lists, size_t count, void *out, int p, int what)
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.sk) {
-        fprintf(stderr, "Secret key not initialized. Generate the secret key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
+    if (!global_secret_key()) return EOC_ERR_NO_KEY;
     if (what == 0) return eoc_list_phases(c.sk, lists, count, static_cast<int32_t *>(out));
     if (what == 1) return eoc_decrypt_list_bits(c.sk, lists, count, static_cast<uint8_t *>(out));
     return eoc_decrypt_list_ints(c.sk, p, lists, count, static_cast<uint8_t *>(out));
@@ -1485,123 +1382,12 @@ extern "C" int eoc_global_decrypt_list_ints(int p, const int32_t *lists, size_t 
 {
     return global_list_call(lists, count, values, p, 2);
 }
-// the packing key of the global context's engines: works behind a cloud key alone (key mode 2); the blob's parameters must be
-// the context's
-extern "C" int eoc_global_import_packing_key_blob(const void *buf, size_t len)
-{
-    eoc_params bp;
-    if (eoc_packing_key_blob_params(buf, len, &bp) != EOC_OK) return EOC_ERR_ARG;
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) { // the engines come up behind the global key on first use; engines of eoc_gpu_init serve without one
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    } else if (eoc_gpu_engine_count() == 0) {
-        fprintf(stderr, "Public key not initialized. Generate the public key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
-    return eoc_set_packing_key_engines(buf, len);
-}
-// LWE samples -> compact lists on the global context's engines: WHOLE lists are cut over the engines
-extern "C" int eoc_pack(const int32_t *cts, size_t count, int32_t *lists)
-{
-    if (!cts || !lists) {
-        eoc_set_error("eoc_pack: null argument");
-        return EOC_ERR_ARG;
-    }
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) {
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    }
-    return eoc_pack_engines(cts, count, lists);
-}
-// two-input lookups on the global context's engines (brought up behind the global key on first use; a cloud key and an
-// imported packing key suffice: key mode 2)
-extern "C" int eoc_lut2_batch(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y,
-                              int32_t *out, size_t count)
-{
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) {
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    }
-    return eoc_lut2_engines(p, n_tables, tables, n_funcs, x, y, out, count);
-}
-// an encrypted-index table read on the global context's engines (brought up behind the global key on first use; a cloud key
-// alone suffices)
-extern "C" int eoc_table_read(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries,
-                              int32_t *out)
-{
-    const bool depth0 = log2_lists == 0 && log2_width == 10;
-    if (!table || !out || (!selectors && !depth0) || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10) {
-        eoc_set_error("eoc_table_read: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]",
-                      log2_lists, log2_width);
-        return EOC_ERR_ARG;
-    }
-    if (!queries) return EOC_OK;
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) {
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    }
-    return eoc_table_read_engines(table, log2_lists, log2_width, selectors, queries, out);
-}
-// an encrypted-index table update on the global context's engines: no key is used, the engines come up behind
-// the global key as for the read
-extern "C" int eoc_table_update(int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
-                                size_t queries)
-{
-    const bool depth0 = log2_lists == 0 && log2_width == 10;
-    if (!table || !values || (!selectors && !depth0) || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10) {
-        eoc_set_error("eoc_table_update: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]",
-                      log2_lists, log2_width);
-        return EOC_ERR_ARG;
-    }
-    if (!queries) return EOC_OK;
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) {
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    }
-    return eoc_table_update_engines(table, log2_lists, log2_width, selectors, values, queries);
-}
-// an automaton run on the global context's engines: the automaton is checked before a key or a device is
-// looked for; the engines come up behind the global key as for the read (a cloud key alone suffices)
-extern "C" int eoc_automaton_run(const int32_t *trans, size_t states, const int32_t *final_vec, const int32_t *selectors,
-                                 size_t steps, const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t queries)
-{
-    if (!final_vec || !out || !starts || (steps && !selectors) || log2_width < 0 || log2_width > 10 || n_starts < 1 ||
-        n_starts > 4096) {
-        eoc_set_error("eoc_automaton_run: null argument, log2_width = %d outside [0, 10] or %zu start states outside [1, 4096]",
-                      log2_width, n_starts);
-        return EOC_ERR_ARG;
-    }
-    if (int rc = eoc_automaton_check("eoc_automaton_run", trans, states, starts, n_starts)) return rc;
-    if (!queries) return EOC_OK;
-    GlobalCtx &c = ctx();
-    std::lock_guard<std::mutex> g(c.mu);
-    if (c.params()) {
-        int rc = ensure_engine_locked();
-        if (rc) return rc;
-    }
-    return eoc_automaton_run_engines(trans, states, final_vec, selectors, steps, starts, n_starts, log2_width, out, queries);
-}
 extern "C" int eoc_global_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires,
                                       size_t instances)
 {
     GlobalCtx &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    if (!c.params()) {
-        fprintf(stderr, "Public key not initialized. Generate the public key first.\n");
-        return EOC_ERR_NO_KEY;
-    }
-    int rc = ensure_engine_locked();
-    if (rc) return rc;
+    if (int rc = global_engines_locked()) return rc;
     return eoc_circuit_run(gates, n_gates, wires, n_wires, instances);
 }
 

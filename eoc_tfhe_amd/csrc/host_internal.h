@@ -61,6 +61,16 @@ void lwe_encrypt_secure(const eoc_secret_key *sk, const uint8_t enc_key[32], uin
 bool arm_secure_encryption_locked();
 void wipe_secret_key(eoc_secret_key *sk); // explicit_bzero over the master key and the key bits
 int ensure_engine_locked(); // caller holds ctx().mu
+// The global key's side of a host-buffer call on the global engines (multi.hip), held from behind the call's first checks to
+// its return: ctx().mu locked and, when the context has a key (`keyed`), the engines brought up behind it -- rc is
+// ensure_engine_locked()'s answer; EOC_OK without a key, where engines of eoc_gpu_init serve
+struct EngineGuard {
+    std::unique_lock<std::mutex> lock;
+    bool keyed;
+    int rc;
+    EngineGuard();
+};
+int no_public_key(); // "Public key not initialized. ..." on stderr (eoc-tfhe-run.cpp:465-468); returns EOC_ERR_NO_KEY
 // compact public-key encryption: the public key (A, B) of a secret key [N] each, and lists [ceil(count / N)][2][N]
 // of msgs[count] under it (enc_key != NULL: ChaCha20 streams under it, else the seeded test streams of enc_seed)
 void make_public_key(const eoc_secret_key *sk, int32_t *A, int32_t *B);

@@ -12,7 +12,7 @@
 // Caller buffers from eoc_host_alloc (pinned, device-mapped) are read in place by the linear-stage kernel and receive
 // the result by one asynchronous copy; pageable caller buffers go through the runtime's staged copies.
 #include "common.h"
-#include "../../include/eoc_tfhe_gpu.h"
+#include "host_internal.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: the library is dlopen'ed when a broadcast is wanted
@@ -352,54 +352,93 @@ int slot_gate_block(Slot &s, int op, const uint8_t *ops, const int32_t *in0, con
     return EOC_OK;
 }
 
+// ---- the frame of the one-stream block functions ------------------------------------------------------
+// Every host-buffer call but the gate batch runs a block like this: nothing for an empty block; the device selected; the
+// staging buffer carved (Staging::commit); body(st) on the slot's kernel stream -- copies in, ONE device call, copies out, all
+// asynchronous --; slot_finish.  A block function states its sizes, its take(...) chain and that body, nothing else.  (The
+// sizes of an empty block are computed and dropped: no size formula reads memory.)
+template <class Body> int slot_block(Slot &s, size_t blk, Staging pieces, Body body)
+{
+    if (!blk) return EOC_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    if (int rc = pieces.commit(s)) return rc;
+    return slot_finish(s.st[0], body(s.st[0]));
+}
+// a body's copies, asynchronous on its stream (an empty piece has no copy): `ints` contiguous words ...
+int copy_in(int32_t *d, const int32_t *h, size_t ints, hipStream_t st)
+{
+    if (ints) HIP_TRY(hipMemcpyAsync(d, h, ints * 4, hipMemcpyHostToDevice, st));
+    return EOC_OK;
+}
+int copy_out(int32_t *h, const int32_t *d, size_t ints, hipStream_t st)
+{
+    if (ints) HIP_TRY(hipMemcpyAsync(h, d, ints * 4, hipMemcpyDeviceToHost, st));
+    return EOC_OK;
+}
+// ... and `rows` rows of `row_ints` words, dense on the device and `h_pitch` words apart on the host: rows [lo, hi) of every
+// plane of a host array [rows][count][stride] are h + lo stride, h_pitch = count stride, row_ints = (hi - lo) stride
+int copy_in_2d(int32_t *d, const int32_t *h, size_t h_pitch, size_t row_ints, size_t rows, hipStream_t st)
+{
+    if (rows && row_ints) HIP_TRY(hipMemcpy2DAsync(d, row_ints * 4, h, h_pitch * 4, row_ints * 4, rows, hipMemcpyHostToDevice, st));
+    return EOC_OK;
+}
+int copy_out_2d(int32_t *h, size_t h_pitch, const int32_t *d, size_t row_ints, size_t rows, hipStream_t st)
+{
+    if (rows && row_ints) HIP_TRY(hipMemcpy2DAsync(h, h_pitch * 4, d, row_ints * 4, row_ints * 4, rows, hipMemcpyDeviceToHost, st));
+    return EOC_OK;
+}
+// the selectors of a leveled call's block: `nsel` of them in torus form up into d_sel and converted into d_fft (the converted
+// form takes twice the ints); *conv = d_fft, NULL when the walk has no selector (depth 0, no step)
+int upload_and_convert_selectors(Slot &s, const int32_t *h_sel, size_t nsel, int32_t *d_sel, int32_t *d_fft, const int32_t **conv,
+                                 hipStream_t st)
+{
+    *conv = nsel ? d_fft : nullptr;
+    if (!nsel) return EOC_OK;
+    int rc = copy_in(d_sel, h_sel, nsel * eoc_tgsw_len(&G.p), st);
+    return rc ? rc : eoc_tgsw_to_fft_device(s.e, d_sel, nsel, d_fft, st);
+}
+
 // one device's block of circuit instances [lo, hi) of a host wire array [n_wires][instances][stride]
 int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *wires, size_t n_wires, size_t instances,
                        size_t lo, size_t hi, size_t stride_ints)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
+    const size_t blk = hi - lo, row = blk * stride_ints;
     int32_t *d_wires;
-    int rc = Staging().take(d_wires, n_wires * blk * stride_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    // Only the wires that matter cross PCIe: host -> device the wires some gate READS BEFORE any gate has written them
-    // (the circuit's inputs), device -> host the wires some gate WRITES; a wire nobody touches keeps the caller's bytes
-    // and a wire that is overwritten before it is read is never sent (an 8-bit adder moves 16 of its 57 wires in and
-    // 41 out).  Gates are evaluated in netlist order semantics (eoc_circuit_run_device levelises on hazards), so the
-    // scan below is in that order.  Consecutive wires travel as one strided copy: row w of the device array holds
-    // instances [lo, hi) of wire w.
-    std::vector<uint8_t> live_in(n_wires, 0), written(n_wires, 0);
-    for (size_t k = 0; k < n_gates; k++) {
-        const int32_t ins[3] = {gates[k].in0, gates[k].in1, gates[k].in2};
-        for (int a = 0; a < 3; a++)
-            if (ins[a] >= 0 && (size_t)ins[a] < n_wires && !written[ins[a]]) live_in[ins[a]] = 1;
-        if (gates[k].out >= 0 && (size_t)gates[k].out < n_wires) written[gates[k].out] = 1;
-    }
-    auto copy_runs = [&](const std::vector<uint8_t> &sel, bool to_device) -> int {
-        for (size_t w = 0; w < n_wires;) {
-            if (!sel[w]) {
-                w++;
-                continue;
-            }
-            size_t e = w;
-            while (e < n_wires && sel[e]) e++;
-            int32_t *dev = d_wires + w * blk * stride_ints;
-            int32_t *host = wires + (w * instances + lo) * stride_ints;
-            if (to_device)
-                HIP_TRY(hipMemcpy2DAsync(dev, blk * stride_ints * 4, host, instances * stride_ints * 4, blk * stride_ints * 4,
-                                         e - w, hipMemcpyHostToDevice, st));
-            else
-                HIP_TRY(hipMemcpy2DAsync(host, instances * stride_ints * 4, dev, blk * stride_ints * 4, blk * stride_ints * 4,
-                                         e - w, hipMemcpyDeviceToHost, st));
-            w = e;
+    return slot_block(s, blk, Staging().take(d_wires, n_wires * row), [&](hipStream_t st) {
+        // Only the wires that matter cross PCIe: host -> device the wires some gate READS BEFORE any gate has written them
+        // (the circuit's inputs), device -> host the wires some gate WRITES; a wire nobody touches keeps the caller's bytes
+        // and a wire that is overwritten before it is read is never sent (an 8-bit adder moves 16 of its 57 wires in and
+        // 41 out).  Gates are evaluated in netlist order semantics (eoc_circuit_run_device levelises on hazards), so the
+        // scan below is in that order.  Consecutive wires travel as one strided copy: row w of the device array holds
+        // instances [lo, hi) of wire w.
+        std::vector<uint8_t> live_in(n_wires, 0), written(n_wires, 0);
+        for (size_t k = 0; k < n_gates; k++) {
+            const int32_t ins[3] = {gates[k].in0, gates[k].in1, gates[k].in2};
+            for (int a = 0; a < 3; a++)
+                if (ins[a] >= 0 && (size_t)ins[a] < n_wires && !written[ins[a]]) live_in[ins[a]] = 1;
+            if (gates[k].out >= 0 && (size_t)gates[k].out < n_wires) written[gates[k].out] = 1;
         }
-        return EOC_OK;
-    };
-    rc = copy_runs(live_in, true);
-    if (rc == EOC_OK) rc = eoc_circuit_run_device(s.e, gates, n_gates, d_wires, n_wires, blk, st);
-    if (rc == EOC_OK) rc = copy_runs(written, false);
-    return slot_finish(st, rc);
+        auto copy_runs = [&](const std::vector<uint8_t> &sel, bool to_device) -> int {
+            int rc = EOC_OK;
+            for (size_t w = 0; w < n_wires && !rc;) {
+                if (!sel[w]) {
+                    w++;
+                    continue;
+                }
+                size_t e = w;
+                while (e < n_wires && sel[e]) e++;
+                int32_t *dev = d_wires + w * row, *host = wires + (w * instances + lo) * stride_ints;
+                rc = to_device ? copy_in_2d(dev, host, instances * stride_ints, row, e - w, st)
+                               : copy_out_2d(host, instances * stride_ints, dev, row, e - w, st);
+                w = e;
+            }
+            return rc;
+        };
+        int rc = copy_runs(live_in, true);
+        if (!rc) rc = eoc_circuit_run_device(s.e, gates, n_gates, d_wires, n_wires, blk, st);
+        if (!rc) rc = copy_runs(written, false);
+        return rc;
+    });
 }
 
 // one device's block [lo, hi) of a table-lookup batch: in [count][stride], out [n_luts][count][stride] on the host; n_tables
@@ -407,28 +446,18 @@ int slot_circuit_block(Slot &s, const eoc_gate *gates, size_t n_gates, int32_t *
 int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in, int32_t *out, size_t count, size_t lo,
                    size_t hi, size_t stride_ints, int n_tables)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
-    const size_t n_out = n_luts * (size_t)std::max(1, n_tables);
-    const size_t tv_ints = n_luts * EOC_N;
+    const size_t blk = hi - lo, row = blk * stride_ints;
+    const size_t n_out = n_luts * (size_t)std::max(1, n_tables), tv_ints = n_luts * EOC_N;
     int32_t *d_tv, *d_in, *d_out;
-    int rc = Staging().take(d_tv, tv_ints).take(d_in, blk * stride_ints).take(d_out, n_out * blk * stride_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    const size_t row_bytes = stride_ints * 4;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d_tv, tv, tv_ints * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_in, in + lo * stride_ints, blk * row_bytes, hipMemcpyHostToDevice, st));
-        int r = n_tables ? eoc_lut_many_batch_device(s.e, n_tables, d_tv, n_luts, d_in, d_out, blk, st)
-                         : eoc_lut_batch_device(s.e, d_tv, n_luts, d_in, d_out, blk, st);
-        if (r) return r;
+    return slot_block(s, blk, Staging().take(d_tv, tv_ints).take(d_in, row).take(d_out, n_out * row), [&](hipStream_t st) {
+        int rc = copy_in(d_tv, tv, tv_ints, st);
+        if (!rc) rc = copy_in(d_in, in + lo * stride_ints, row, st);
+        if (!rc) rc = n_tables ? eoc_lut_many_batch_device(s.e, n_tables, d_tv, n_luts, d_in, d_out, blk, st)
+                               : eoc_lut_batch_device(s.e, d_tv, n_luts, d_in, d_out, blk, st);
         // table t's block lands at rows [t count + lo, t count + hi) of the caller's array
-        HIP_TRY(hipMemcpy2DAsync(out + lo * stride_ints, count * row_bytes, d_out, blk * row_bytes, blk * row_bytes, n_out,
-                                 hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+        if (!rc) rc = copy_out_2d(out + lo * stride_ints, count * stride_ints, d_out, row, n_out, st);
+        return rc;
+    });
 }
 
 // one device's block [lo, hi) of a two-input lookup batch: tv0 [n_funcs][p / T][N], x, y [count][stride] on the
@@ -436,27 +465,18 @@ int slot_lut_block(Slot &s, const int32_t *tv, size_t n_luts, const int32_t *in,
 int slot_lut2_block(Slot &s, int p, int n_tables, const int32_t *tv0, size_t n_funcs, const int32_t *x, const int32_t *y,
                     int32_t *out, size_t count, size_t lo, size_t hi, size_t stride_ints)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
+    const size_t blk = hi - lo, row = blk * stride_ints;
     const size_t tv_ints = n_funcs * (size_t)(p / std::max(1, n_tables)) * EOC_N;
     int32_t *d_tv, *d_x, *d_y, *d_out;
-    int rc = Staging().take(d_tv, tv_ints).take(d_x, blk * stride_ints)
-                 .take(d_y, blk * stride_ints).take(d_out, n_funcs * blk * stride_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    const size_t row_bytes = stride_ints * 4;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d_tv, tv0, tv_ints * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_x, x + lo * stride_ints, blk * row_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_y, y + lo * stride_ints, blk * row_bytes, hipMemcpyHostToDevice, st));
-        int r = eoc_lut2_batch_device(s.e, p, n_tables, d_tv, n_funcs, d_x, d_y, d_out, blk, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpy2DAsync(out + lo * stride_ints, count * row_bytes, d_out, blk * row_bytes, blk * row_bytes, n_funcs,
-                                 hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+    return slot_block(s, blk, Staging().take(d_tv, tv_ints).take(d_x, row).take(d_y, row).take(d_out, n_funcs * row),
+                      [&](hipStream_t st) {
+        int rc = copy_in(d_tv, tv0, tv_ints, st);
+        if (!rc) rc = copy_in(d_x, x + lo * stride_ints, row, st);
+        if (!rc) rc = copy_in(d_y, y + lo * stride_ints, row, st);
+        if (!rc) rc = eoc_lut2_batch_device(s.e, p, n_tables, d_tv, n_funcs, d_x, d_y, d_out, blk, st);
+        if (!rc) rc = copy_out_2d(out + lo * stride_ints, count * stride_ints, d_out, row, n_funcs, st);
+        return rc;
+    });
 }
 
 // one device's block [lo, hi) of an integer circuit's instances: wires [n_wires][instances][stride] on the host, every wire's
@@ -464,49 +484,45 @@ int slot_lut2_block(Slot &s, int p, int n_tables, const int32_t *tv0, size_t n_f
 int slot_int_block(Slot &s, const eoc_inode *nodes, size_t n_nodes, const int32_t *tv, size_t n_tv, int32_t *wires,
                    size_t n_wires, size_t instances, size_t lo, size_t hi, size_t stride_ints)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
-    const size_t tv_ints = n_tv * EOC_N;
-    int32_t *d_tv, *d_wires;
-    int rc = Staging().take(d_tv, tv_ints).take(d_wires, n_wires * blk * stride_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    const size_t row_bytes = stride_ints * 4;
-    auto run = [&]() -> int {
-        if (tv_ints) HIP_TRY(hipMemcpyAsync(d_tv, tv, tv_ints * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpy2DAsync(d_wires, blk * row_bytes, wires + lo * stride_ints, instances * row_bytes, blk * row_bytes,
-                                 n_wires, hipMemcpyHostToDevice, st));
-        int r = eoc_int_circuit_run_device(s.e, nodes, n_nodes, tv_ints ? d_tv : nullptr, n_tv, d_wires, n_wires, blk, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpy2DAsync(wires + lo * stride_ints, instances * row_bytes, d_wires, blk * row_bytes, blk * row_bytes,
-                                 n_wires, hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+    const size_t blk = hi - lo, row = blk * stride_ints, tv_ints = n_tv * EOC_N;
+    int32_t *d_tv, *d_wires, *h_blk = wires + lo * stride_ints;
+    return slot_block(s, blk, Staging().take(d_tv, tv_ints).take(d_wires, n_wires * row), [&](hipStream_t st) {
+        int rc = copy_in(d_tv, tv, tv_ints, st);
+        if (!rc) rc = copy_in_2d(d_wires, h_blk, instances * stride_ints, row, n_wires, st);
+        if (!rc) rc = eoc_int_circuit_run_device(s.e, nodes, n_nodes, tv_ints ? d_tv : nullptr, n_tv, d_wires, n_wires, blk, st);
+        if (!rc) rc = copy_out_2d(h_blk, instances * stride_ints, d_wires, row, n_wires, st);
+        return rc;
+    });
 }
 
 // one device's block [lo, hi) of a compact-list expansion: lists [ceil(count / N)][2][N], out [count][stride] on the host.
 // Only the lists the block touches cross PCIe; the block's first sample sits at slot lo mod N of the first of them.
 int slot_compact_block(Slot &s, const int32_t *lists, int32_t *out, size_t lo, size_t hi, size_t stride_ints)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
-    const size_t l0 = lo / EOC_N, l1 = (hi - 1) / EOC_N + 1;
+    const size_t blk = hi - lo, l0 = lo / EOC_N, l1 = (hi - 1) / EOC_N + 1;
     const size_t list_ints = (l1 - l0) * 2 * EOC_N;
     int32_t *d_lists, *d_out;
-    int rc = Staging().take(d_lists, list_ints).take(d_out, blk * stride_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d_lists, lists + l0 * 2 * EOC_N, list_ints * 4, hipMemcpyHostToDevice, st));
-        int r = eoc_compact_expand_device_from(s.e, d_lists, lo - l0 * EOC_N, blk, d_out, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(out + lo * stride_ints, d_out, blk * stride_ints * 4, hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+    return slot_block(s, blk, Staging().take(d_lists, list_ints).take(d_out, blk * stride_ints), [&](hipStream_t st) {
+        int rc = copy_in(d_lists, lists + l0 * 2 * EOC_N, list_ints, st);
+        if (!rc) rc = eoc_compact_expand_device_from(s.e, d_lists, lo - l0 * EOC_N, blk, d_out, st);
+        if (!rc) rc = copy_out(out + lo * stride_ints, d_out, blk * stride_ints, st);
+        return rc;
+    });
+}
+
+// one device's block [lo, hi) of a seeded expansion: bodies [count] on the host, sample lo has the mask stream
+// first_idx + lo, out [count][stride]
+int slot_seeded_block(Slot &s, const uint8_t *seed, uint64_t first_idx, const int32_t *bodies, int32_t *out, size_t lo, size_t hi,
+                      size_t stride_ints)
+{
+    const size_t blk = hi - lo;
+    int32_t *d_bodies, *d_out;
+    return slot_block(s, blk, Staging().take(d_bodies, blk).take(d_out, blk * stride_ints), [&](hipStream_t st) {
+        int rc = copy_in(d_bodies, bodies + lo, blk, st);
+        if (!rc) rc = eoc_seeded_expand_device(s.e, seed, first_idx + lo, d_bodies, blk, d_out, st);
+        if (!rc) rc = copy_out(out + lo * stride_ints, d_out, blk * stride_ints, st);
+        return rc;
+    });
 }
 
 // one device's block [lo, hi) of the queries of an encrypted-index table read: the whole table and the block's
@@ -514,30 +530,18 @@ int slot_compact_block(Slot &s, const int32_t *lists, int32_t *out, size_t lo, s
 int slot_table_read_block(Slot &s, const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors,
                           int32_t *out, size_t lo, size_t hi, size_t stride_ints)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
-    const size_t depth = (size_t)log2_lists + 10 - log2_width, W = (size_t)1 << log2_width;
-    const size_t tab_ints = ((size_t)2 * EOC_N) << log2_lists;
-    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth; // d_fft: the converted form takes twice the ints
+    const size_t blk = hi - lo, depth = (size_t)log2_lists + 10 - log2_width, out_ints = stride_ints << log2_width;
+    const size_t tab_ints = ((size_t)2 * EOC_N) << log2_lists, sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth;
     int32_t *d_tab, *d_sel, *d_fft, *d_out;
-    int rc = Staging().take(d_tab, tab_ints).take(d_sel, nsel * sel_ints)
-                 .take(d_fft, 2 * nsel * sel_ints).take(d_out, blk * W * stride_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d_tab, table, tab_ints * 4, hipMemcpyHostToDevice, st));
-        if (nsel) {
-            HIP_TRY(hipMemcpyAsync(d_sel, selectors + lo * depth * sel_ints, nsel * sel_ints * 4, hipMemcpyHostToDevice, st));
-            int r = eoc_tgsw_to_fft_device(s.e, d_sel, nsel, d_fft, st);
-            if (r) return r;
-        }
-        int r = eoc_table_read_device(s.e, d_tab, log2_lists, log2_width, d_fft, blk, d_out, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(out + lo * W * stride_ints, d_out, blk * W * stride_ints * 4, hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+    return slot_block(s, blk, Staging().take(d_tab, tab_ints).take(d_sel, nsel * sel_ints).take(d_fft, 2 * nsel * sel_ints)
+                                  .take(d_out, blk * out_ints), [&](hipStream_t st) {
+        const int32_t *conv;
+        int rc = copy_in(d_tab, table, tab_ints, st);
+        if (!rc) rc = upload_and_convert_selectors(s, selectors + lo * depth * sel_ints, nsel, d_sel, d_fft, &conv, st);
+        if (!rc) rc = eoc_table_read_device(s.e, d_tab, log2_lists, log2_width, conv, blk, d_out, st);
+        if (!rc) rc = copy_out(out + lo * out_ints, d_out, blk * out_ints, st);
+        return rc;
+    });
 }
 
 // one device's block [lo, hi) of the queries of an automaton run: the final vector and the block's selectors in
@@ -546,30 +550,18 @@ int slot_automaton_block(Slot &s, const int32_t *trans, size_t states, const int
                          size_t steps, const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t lo, size_t hi,
                          size_t stride_ints)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
-    const size_t fin_ints = states * 2 * EOC_N, out_ints = n_starts * ((size_t)1 << log2_width) * stride_ints;
-    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * steps; // d_fft: the converted form takes twice the ints
+    const size_t blk = hi - lo, fin_ints = states * 2 * EOC_N, out_ints = n_starts * (stride_ints << log2_width);
+    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * steps;
     int32_t *d_fin, *d_sel, *d_fft, *d_out;
-    int rc = Staging().take(d_fin, fin_ints).take(d_sel, nsel * sel_ints)
-                 .take(d_fft, 2 * nsel * sel_ints).take(d_out, blk * out_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d_fin, final_vec, fin_ints * 4, hipMemcpyHostToDevice, st));
-        if (nsel) {
-            HIP_TRY(hipMemcpyAsync(d_sel, selectors + lo * steps * sel_ints, nsel * sel_ints * 4, hipMemcpyHostToDevice, st));
-            int r = eoc_tgsw_to_fft_device(s.e, d_sel, nsel, d_fft, st);
-            if (r) return r;
-        }
-        int r = eoc_automaton_run_device(s.e, trans, states, d_fin, nsel ? d_fft : nullptr, steps, starts, n_starts, log2_width,
-                                         d_out, blk, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(out + lo * out_ints, d_out, blk * out_ints * 4, hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+    return slot_block(s, blk, Staging().take(d_fin, fin_ints).take(d_sel, nsel * sel_ints).take(d_fft, 2 * nsel * sel_ints)
+                                  .take(d_out, blk * out_ints), [&](hipStream_t st) {
+        const int32_t *conv;
+        int rc = copy_in(d_fin, final_vec, fin_ints, st);
+        if (!rc) rc = upload_and_convert_selectors(s, selectors + lo * steps * sel_ints, nsel, d_sel, d_fft, &conv, st);
+        if (!rc) rc = eoc_automaton_run_device(s.e, trans, states, d_fin, conv, steps, starts, n_starts, log2_width, d_out, blk, st);
+        if (!rc) rc = copy_out(out + lo * out_ints, d_out, blk * out_ints, st);
+        return rc;
+    });
 }
 
 // one device's block [lo, hi) of the queries of an encrypted-index table update: the block's selectors (torus
@@ -578,53 +570,34 @@ int slot_automaton_block(Slot &s, const int32_t *trans, size_t states, const int
 int slot_table_update_block(Slot &s, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
                             int32_t *delta, size_t lo, size_t hi)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
-    const size_t depth = (size_t)log2_lists + 10 - log2_width, smp = (size_t)2 * EOC_N;
-    const size_t tab_ints = smp << log2_lists;
-    const size_t sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth; // d_fft: the converted form takes twice the ints
+    const size_t blk = hi - lo, depth = (size_t)log2_lists + 10 - log2_width, smp = (size_t)2 * EOC_N;
+    const size_t tab_ints = smp << log2_lists, sel_ints = eoc_tgsw_len(&G.p), nsel = blk * depth;
     int32_t *d_tab, *d_sel, *d_fft, *d_vals;
-    int rc = Staging().take(d_tab, tab_ints).take(d_sel, nsel * sel_ints)
-                 .take(d_fft, 2 * nsel * sel_ints).take(d_vals, blk * smp).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    auto run = [&]() -> int {
+    return slot_block(s, blk, Staging().take(d_tab, tab_ints).take(d_sel, nsel * sel_ints).take(d_fft, 2 * nsel * sel_ints)
+                                  .take(d_vals, blk * smp), [&](hipStream_t st) -> int {
+        const int32_t *conv;
         HIP_TRY(hipMemsetAsync(d_tab, 0, tab_ints * 4, st));
-        HIP_TRY(hipMemcpyAsync(d_vals, values + lo * smp, blk * smp * 4, hipMemcpyHostToDevice, st));
-        if (nsel) {
-            HIP_TRY(hipMemcpyAsync(d_sel, selectors + lo * depth * sel_ints, nsel * sel_ints * 4, hipMemcpyHostToDevice, st));
-            int r = eoc_tgsw_to_fft_device(s.e, d_sel, nsel, d_fft, st);
-            if (r) return r;
-        }
-        int r = eoc_table_update_device(s.e, d_tab, log2_lists, log2_width, nsel ? d_fft : nullptr, d_vals, blk, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(delta, d_tab, tab_ints * 4, hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+        int rc = copy_in(d_vals, values + lo * smp, blk * smp, st);
+        if (!rc) rc = upload_and_convert_selectors(s, selectors + lo * depth * sel_ints, nsel, d_sel, d_fft, &conv, st);
+        if (!rc) rc = eoc_table_update_device(s.e, d_tab, log2_lists, log2_width, conv, d_vals, blk, st);
+        if (!rc) rc = copy_out(delta, d_tab, tab_ints, st);
+        return rc;
+    });
 }
 
 // one device's block of WHOLE lists [l_lo, l_hi) of a packing key switch: cts [count][stride] on the host,
 // lists [ceil(count / N)][2][N] out
 int slot_pack_block(Slot &s, const int32_t *cts, size_t count, int32_t *lists, size_t l_lo, size_t l_hi, size_t stride_ints)
 {
-    if (l_hi == l_lo) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
     const size_t s_lo = l_lo * EOC_N, blk = std::min(count, l_hi * EOC_N) - s_lo;
     const size_t in_ints = blk * stride_ints, out_ints = (l_hi - l_lo) * 2 * EOC_N;
     int32_t *d_in, *d_out;
-    int rc = Staging().take(d_in, in_ints).take(d_out, out_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d_in, cts + s_lo * stride_ints, in_ints * 4, hipMemcpyHostToDevice, st));
-        int r = eoc_pack_device(s.e, d_in, blk, d_out, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(lists + l_lo * 2 * EOC_N, d_out, out_ints * 4, hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+    return slot_block(s, l_hi - l_lo, Staging().take(d_in, in_ints).take(d_out, out_ints), [&](hipStream_t st) {
+        int rc = copy_in(d_in, cts + s_lo * stride_ints, in_ints, st);
+        if (!rc) rc = eoc_pack_device(s.e, d_in, blk, d_out, st);
+        if (!rc) rc = copy_out(lists + l_lo * 2 * EOC_N, d_out, out_ints, st);
+        return rc;
+    });
 }
 
 // one device's block of WHOLE input vectors [lo, hi) of an inner product with public weights: the weights
@@ -633,26 +606,17 @@ int slot_pack_block(Slot &s, const int32_t *cts, size_t count, int32_t *lists, s
 int slot_linear_block(Slot &s, const int8_t *h_w, size_t rows, size_t cols, const int32_t *lists, const int32_t *bias, int32_t *out,
                       size_t lo, size_t hi, size_t stride_ints)
 {
-    const size_t blk = hi - lo;
-    if (!blk) return EOC_OK;
-    HIP_TRY(hipSetDevice(s.device));
-    const size_t vec_ints = (cols + EOC_N - 1) / EOC_N * 2 * EOC_N, out_ints = rows * stride_ints;
+    const size_t blk = hi - lo, vec_ints = (cols + EOC_N - 1) / EOC_N * 2 * EOC_N, out_ints = rows * stride_ints;
     int32_t *d_img, *d_lists, *d_bias, *d_out; // the image first: its spectra are read 16 bytes at a time
-    int rc = Staging().take(d_img, eoc_weights_image_bytes(rows, cols) / 4).take(d_lists, blk * vec_ints)
-                 .take(d_bias, rows).take(d_out, blk * out_ints).commit(s);
-    if (rc) return rc;
-    hipStream_t st = s.st[0];
-    auto run = [&]() -> int {
-        int r = eoc_weights_to_device(s.e, h_w, rows, cols, d_img, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(d_lists, lists + lo * vec_ints, blk * vec_ints * 4, hipMemcpyHostToDevice, st));
-        if (bias) HIP_TRY(hipMemcpyAsync(d_bias, bias, rows * 4, hipMemcpyHostToDevice, st));
-        r = eoc_linear_device(s.e, d_img, rows, cols, d_lists, blk, bias ? d_bias : nullptr, d_out, st);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(out + lo * out_ints, d_out, blk * out_ints * 4, hipMemcpyDeviceToHost, st));
-        return EOC_OK;
-    };
-    return slot_finish(st, run());
+    return slot_block(s, blk, Staging().take(d_img, eoc_weights_image_bytes(rows, cols) / 4).take(d_lists, blk * vec_ints)
+                                  .take(d_bias, rows).take(d_out, blk * out_ints), [&](hipStream_t st) {
+        int rc = eoc_weights_to_device(s.e, h_w, rows, cols, d_img, st);
+        if (!rc) rc = copy_in(d_lists, lists + lo * vec_ints, blk * vec_ints, st);
+        if (!rc && bias) rc = copy_in(d_bias, bias, rows, st);
+        if (!rc) rc = eoc_linear_device(s.e, d_img, rows, cols, d_lists, blk, bias ? d_bias : nullptr, d_out, st);
+        if (!rc) rc = copy_out(out + lo * out_ints, d_out, blk * out_ints, st);
+        return rc;
+    });
 }
 
 void destroy_slots_locked()
@@ -868,6 +832,23 @@ int enter_locked(const char *who, Entry upto = DRAINED)
     }
     return upto == DRAINED ? drain_async_locked() : EOC_OK;
 }
+// The tail of every entry, under G.mu: enter_locked(who), then fn(slot, lo, hi, stride) for the slot's block [lo, hi) of the
+// call's `total` units (rows, instances, queries, lists, vectors), over the slots as for_each_block runs them
+template <class F> int run_blocks_locked(const char *who, size_t total, F fn)
+{
+    if (int rc = enter_locked(who)) return rc;
+    const size_t stride = (size_t)G.p.n + 1;
+    return for_each_block(total, [=](int i, size_t lo, size_t hi) { return fn(G.slots[i], lo, hi, stride); });
+}
+// The locks of an entry that raises the engines, from where it takes them to its return: the global key's first (host.cpp;
+// key.rc is what bringing the engines up behind the key answered, EOC_OK without a key), then G.mu -- the one order there is:
+// ensure_engine_locked, eoc_global_gate_batch and eoc_global_circuit_run call in here with the key's lock held, which is why
+// the entries they reach (eoc_gate_batch, eoc_lut_batch / _many_, eoc_int_circuit_run, eoc_circuit_run) take G.mu alone
+struct KeyedCall {
+    eoc_host::EngineGuard key;
+    std::lock_guard<std::mutex> g;
+    KeyedCall() : g(G.mu) {}
+};
 
 int slot_async_reserve(Slot &s, size_t rows, size_t stride_ints)
 {
@@ -1256,10 +1237,8 @@ extern "C" int eoc_gate_batch(int op, const uint8_t *ops, const int32_t *in0, co
         return EOC_ERR_ARG;
     }
     if (!count) return EOC_OK;
-    if (int rc = enter_locked("eoc_gate_batch")) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
-    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
-        return slot_gate_block(G.slots[i], op, ops ? ops + lo : nullptr, in0 ? in0 + lo * stride : nullptr,
+    return run_blocks_locked("eoc_gate_batch", count, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_gate_block(s, op, ops ? ops + lo : nullptr, in0 ? in0 + lo * stride : nullptr,
                                in1 ? in1 + lo * stride : nullptr, in2 ? in2 + lo * stride : nullptr, out + lo * stride,
                                hi - lo, stride);
     });
@@ -1288,11 +1267,9 @@ static int lut_batch(const char *who, bool many, int p, int n_tables, const int3
         }
     }
     if (!count) return EOC_OK;
-    if (int rc = enter_locked(who)) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
     const int32_t *tvp = tv.data();
-    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
-        return slot_lut_block(G.slots[i], tvp, n_luts, in, out, count, lo, hi, stride, n_tables);
+    return run_blocks_locked(who, count, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_lut_block(s, tvp, n_luts, in, out, count, lo, hi, stride, n_tables);
     });
 }
 extern "C" int eoc_lut_batch(int p, const int32_t *tables, size_t n_luts, const int32_t *in, int32_t *out, size_t count)
@@ -1305,12 +1282,13 @@ extern "C" int eoc_lut_many_batch(int p, int n_tables, const int32_t *tables, si
     return lut_batch("eoc_lut_many_batch", true, p, n_tables, tables, n_luts, in, out, count);
 }
 
-// eoc_lut2_batch's engine half (host.cpp holds the global key's lock and has brought the engines up): tables
-// [n_funcs][p][p]; the level-1 polynomials are built on the host
-int eoc_lut2_engines(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y, int32_t *out,
-                     size_t count)
+// two-input lookups (a cloud key and an imported packing key suffice: key mode 2): tables [n_funcs][p][p]; the
+// level-1 polynomials are built on the host
+extern "C" int eoc_lut2_batch(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y,
+                              int32_t *out, size_t count)
 {
-    std::lock_guard<std::mutex> g(G.mu);
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
     if (int rc = enter_locked("eoc_lut2_batch", ENGINES)) return rc;
     if (!tables || !x || !y || !out || n_funcs == 0) {
         eoc_set_error("eoc_lut2_batch: null argument or no function");
@@ -1326,11 +1304,9 @@ int eoc_lut2_engines(int p, int n_tables, const int32_t *tables, size_t n_funcs,
             return EOC_ERR_ARG;
         }
     if (!count) return EOC_OK;
-    if (int rc = enter_locked("eoc_lut2_batch")) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
     const int32_t *tvp = tv.data();
-    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
-        return slot_lut2_block(G.slots[i], p, n_tables, tvp, n_funcs, x, y, out, count, lo, hi, stride);
+    return run_blocks_locked("eoc_lut2_batch", count, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_lut2_block(s, p, n_tables, tvp, n_funcs, x, y, out, count, lo, hi, stride);
     });
 }
 
@@ -1366,106 +1342,160 @@ try {
             return EOC_ERR_ARG;
         }
     if (!n_nodes || !instances) return EOC_OK;
-    if (int rc = enter_locked("eoc_int_circuit_run")) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
     const int32_t *tvp = tv.data();
-    return for_each_block(instances, [=](int i, size_t lo, size_t hi) {
-        return slot_int_block(G.slots[i], nodes, n_nodes, tvp, n_tv, wires, n_wires, instances, lo, hi, stride);
+    return run_blocks_locked("eoc_int_circuit_run", instances, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_int_block(s, nodes, n_nodes, tvp, n_tv, wires, n_wires, instances, lo, hi, stride);
     });
 } catch (...) {
     eoc_set_error("eoc_int_circuit_run: out of memory");
     return EOC_ERR_ALLOC;
 }
 
-// eoc_compact_expand's engine half (host.cpp holds the global key's lock and has brought the engines up)
-int eoc_compact_expand_engines(const int32_t *lists, size_t count, int32_t *out)
+// compact lists -> LWE samples (a cloud key alone suffices): samples cut over the engines
+extern "C" int eoc_compact_expand(const int32_t *lists, size_t count, int32_t *out)
 {
-    std::lock_guard<std::mutex> g(G.mu);
-    if (int rc = enter_locked("eoc_compact_expand")) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
-    return for_each_block(count, [=](int i, size_t lo, size_t hi) {
-        return slot_compact_block(G.slots[i], lists, out, lo, hi, stride);
+    if (!lists || !out) {
+        eoc_set_error("eoc_compact_expand: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
+    return run_blocks_locked("eoc_compact_expand", count, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_compact_block(s, lists, out, lo, hi, stride);
     });
 }
 
-// eoc_global_import_packing_key_blob's engine half: every engine parses, converts and keeps its own image
-int eoc_set_packing_key_engines(const void *blob, size_t len)
+// seeded samples -> LWE samples: samples cut over the engines.  No key is used: the engines come up behind the
+// global key when there is one, engines of eoc_gpu_init serve without
+extern "C" int eoc_seeded_expand(const uint8_t seed[32], uint64_t first_idx, const int32_t *bodies, size_t count, int32_t *out)
 {
-    std::lock_guard<std::mutex> g(G.mu);
+    if (!seed || !bodies || !out) {
+        eoc_set_error("eoc_seeded_expand: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
+    if (G.slots.empty()) {
+        eoc_set_error("eoc_seeded_expand: no engine (install a key or call eoc_gpu_init first)");
+        return EOC_ERR_STATE;
+    }
+    return run_blocks_locked("eoc_seeded_expand", count, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_seeded_block(s, seed, first_idx, bodies, out, lo, hi, stride);
+    });
+}
+
+// the packing key of the global context's engines: works behind a cloud key alone (key mode 2), and on engines
+// of eoc_gpu_init without any key; the blob's parameters must be the context's.  Every engine parses, converts and keeps its
+// own image
+extern "C" int eoc_global_import_packing_key_blob(const void *buf, size_t len)
+{
+    eoc_params bp;
+    if (eoc_packing_key_blob_params(buf, len, &bp) != EOC_OK) return EOC_ERR_ARG;
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
+    if (!call.key.keyed && G.slots.empty()) return eoc_host::no_public_key();
     if (int rc = enter_locked("eoc_global_import_packing_key_blob")) return rc;
     for (auto &s : G.slots) {
-        int rc = eoc_engine_set_packing_key(s.e, blob, len);
+        int rc = eoc_engine_set_packing_key(s.e, buf, len);
         if (rc) return rc;
     }
     return EOC_OK;
 }
 
-// eoc_pack's engine half (host.cpp holds the global key's lock and has brought the engines up): whole lists per engine
-int eoc_pack_engines(const int32_t *cts, size_t count, int32_t *lists)
+// LWE samples -> compact lists: WHOLE lists are cut over the engines
+extern "C" int eoc_pack(const int32_t *cts, size_t count, int32_t *lists)
 {
-    std::lock_guard<std::mutex> g(G.mu);
+    if (!cts || !lists) {
+        eoc_set_error("eoc_pack: null argument");
+        return EOC_ERR_ARG;
+    }
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
     if (int rc = enter_locked("eoc_pack", ENGINES)) return rc;
     if (!count) { // the engines still answer for a missing key
         return eoc_pack_device(G.slots[0].e, cts, 0, lists, nullptr);
     }
-    if (int rc = enter_locked("eoc_pack")) return rc;
-    const size_t stride = (size_t)G.p.n + 1, n_lists = (count + EOC_N - 1) / EOC_N;
-    return for_each_block(n_lists, [=](int i, size_t lo, size_t hi) {
-        return slot_pack_block(G.slots[i], cts, count, lists, lo, hi, stride);
+    return run_blocks_locked("eoc_pack", (count + EOC_N - 1) / EOC_N, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_pack_block(s, cts, count, lists, lo, hi, stride);
     });
 }
 
-// eoc_linear's engine half (host.cpp has checked the pointers, holds the global key's lock and has brought the engines up; the
-// model is validated by every engine's load before it touches its device): whole input vectors per engine
-int eoc_linear_engines(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch, const int32_t *h_bias,
-                       int32_t *h_out)
+// inner products with public weights (a cloud key alone suffices): WHOLE input vectors are cut over the engines;
+// the model is validated by every engine's load before it touches its device
+extern "C" int eoc_linear(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch, const int32_t *h_bias,
+                          int32_t *h_out)
 {
-    std::lock_guard<std::mutex> g(G.mu);
+    if (!h_w || !h_lists || !h_out) {
+        eoc_set_error("eoc_linear: null argument");
+        return EOC_ERR_ARG;
+    }
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
     if (int rc = enter_locked("eoc_linear", ENGINES)) return rc;
     if (eoc_weights_image_bytes(rows, cols) == 0) {
         eoc_set_error("eoc_linear: rows = %zu, cols = %zu: both must lie in [1, 2^20]", rows, cols);
         return EOC_ERR_ARG;
     }
     if (!batch) return EOC_OK;
-    if (int rc = enter_locked("eoc_linear")) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
-    return for_each_block(batch, [=](int i, size_t lo, size_t hi) {
-        return slot_linear_block(G.slots[i], h_w, rows, cols, h_lists, h_bias, h_out, lo, hi, stride);
+    return run_blocks_locked("eoc_linear", batch, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_linear_block(s, h_w, rows, cols, h_lists, h_bias, h_out, lo, hi, stride);
     });
 }
 
-// eoc_table_read's engine half (host.cpp has checked the arguments, holds the global key's lock and has brought the engines up)
-int eoc_table_read_engines(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries,
-                           int32_t *out)
+// an encrypted-index table read (a cloud key alone suffices): queries cut over the engines
+extern "C" int eoc_table_read(const int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, size_t queries,
+                              int32_t *out)
 {
-    std::lock_guard<std::mutex> g(G.mu);
-    if (int rc = enter_locked("eoc_table_read")) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
-    return for_each_block(queries, [=](int i, size_t lo, size_t hi) {
-        return slot_table_read_block(G.slots[i], table, log2_lists, log2_width, selectors, out, lo, hi, stride);
+    const bool depth0 = log2_lists == 0 && log2_width == 10;
+    if (!table || !out || (!selectors && !depth0) || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10) {
+        eoc_set_error("eoc_table_read: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]",
+                      log2_lists, log2_width);
+        return EOC_ERR_ARG;
+    }
+    if (!queries) return EOC_OK;
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
+    return run_blocks_locked("eoc_table_read", queries, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_table_read_block(s, table, log2_lists, log2_width, selectors, out, lo, hi, stride);
     });
 }
 
-// eoc_automaton_run's engine half (host.cpp has checked the pointers, holds the global key's lock and has brought the engines
-// up; the automaton itself is validated by every engine's call before it touches its device)
-int eoc_automaton_run_engines(const int32_t *trans, size_t states, const int32_t *final_vec, const int32_t *selectors, size_t steps,
-                              const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t queries)
+// an automaton run (a cloud key alone suffices): the automaton is checked before a key or a device is looked
+// for (and again by every engine's call before it touches its device); queries cut over the engines
+extern "C" int eoc_automaton_run(const int32_t *trans, size_t states, const int32_t *final_vec, const int32_t *selectors,
+                                 size_t steps, const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t queries)
 {
-    std::lock_guard<std::mutex> g(G.mu);
-    if (int rc = enter_locked("eoc_automaton_run")) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
-    return for_each_block(queries, [=](int i, size_t lo, size_t hi) {
-        return slot_automaton_block(G.slots[i], trans, states, final_vec, selectors, steps, starts, n_starts, log2_width, out, lo,
-                                    hi, stride);
+    if (!final_vec || !out || !starts || (steps && !selectors) || log2_width < 0 || log2_width > 10 || n_starts < 1 ||
+        n_starts > 4096) {
+        eoc_set_error("eoc_automaton_run: null argument, log2_width = %d outside [0, 10] or %zu start states outside [1, 4096]",
+                      log2_width, n_starts);
+        return EOC_ERR_ARG;
+    }
+    if (int rc = eoc_automaton_check("eoc_automaton_run", trans, states, starts, n_starts)) return rc;
+    if (!queries) return EOC_OK;
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
+    return run_blocks_locked("eoc_automaton_run", queries, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_automaton_block(s, trans, states, final_vec, selectors, steps, starts, n_starts, log2_width, out, lo, hi, stride);
     });
 }
 
-// eoc_table_update's engine half (host.cpp has checked the arguments, holds the global key's lock and has brought the engines up)
-int eoc_table_update_engines(int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
-                             size_t queries)
+// an encrypted-index table update: no key is used, the engines come up behind the global key as for the read.
+// Queries cut over the engines, one zeroed delta table per engine with a block, added into `table` here
+extern "C" int eoc_table_update(int32_t *table, int log2_lists, int log2_width, const int32_t *selectors, const int32_t *values,
+                                size_t queries)
 try {
-    std::lock_guard<std::mutex> g(G.mu);
-    if (int rc = enter_locked("eoc_table_update")) return rc;
+    const bool depth0 = log2_lists == 0 && log2_width == 10;
+    if (!table || !values || (!selectors && !depth0) || log2_lists < 0 || log2_lists > 12 || log2_width < 0 || log2_width > 10) {
+        eoc_set_error("eoc_table_update: null argument, log2_lists = %d outside [0, 12] or log2_width = %d outside [0, 10]",
+                      log2_lists, log2_width);
+        return EOC_ERR_ARG;
+    }
+    if (!queries) return EOC_OK;
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
     const size_t tab_ints = ((size_t)2 * EOC_N) << log2_lists;
     std::vector<std::vector<int32_t>> deltas(G.slots.size());
     for (size_t i = 0; i < deltas.size(); i++) {
@@ -1474,8 +1504,8 @@ try {
         if (hi > lo) deltas[i].assign(tab_ints, 0);
     }
     std::vector<int32_t> *dp = deltas.data();
-    int rc = for_each_block(queries, [=](int i, size_t lo, size_t hi) {
-        return slot_table_update_block(G.slots[i], log2_lists, log2_width, selectors, values, dp[i].data(), lo, hi);
+    int rc = run_blocks_locked("eoc_table_update", queries, [=](Slot &s, size_t lo, size_t hi, size_t) {
+        return slot_table_update_block(s, log2_lists, log2_width, selectors, values, dp[&s - G.slots.data()].data(), lo, hi);
     });
     if (rc) return rc; // the caller's table is untouched
     for (const auto &dl : deltas)
@@ -1492,11 +1522,9 @@ extern "C" int eoc_circuit_run(const eoc_gate *gates, size_t n_gates, int32_t *w
     if (int rc = enter_locked("eoc_circuit_run", ENGINES)) return rc;
     if (!gates || !wires) return EOC_ERR_ARG;
     if (!n_gates || !instances) return EOC_OK;
-    if (int rc = enter_locked("eoc_circuit_run")) return rc;
-    const size_t stride = (size_t)G.p.n + 1;
     // a whole circuit instance stays on one device: no wire ever crosses GPUs
-    return for_each_block(instances, [=](int i, size_t lo, size_t hi) {
-        return slot_circuit_block(G.slots[i], gates, n_gates, wires, n_wires, instances, lo, hi, stride);
+    return run_blocks_locked("eoc_circuit_run", instances, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_circuit_block(s, gates, n_gates, wires, n_wires, instances, lo, hi, stride);
     });
 }
 

@@ -557,3 +557,212 @@ def test_key_of_another_shape_is_refused_by_the_engines(eoc):
         assert "global engine was initialised for" in str(ei.value)
         eoc.Tfhe.resetGateKey()
     eoc.gpu_shutdown()
+
+
+# ---- every host-buffer entry on ragged blocks of three engines ------------------------------------------------------------
+# The one-stream block functions share one frame (multi.hip): every entry runs it here with blocks of unequal size
+# (7 units: 3 + 2 + 2) and with an empty block (2 units: engine 2 has none).  eoc_gate_batch has both in
+# test_gate_batch_three_engines_ragged, eoc_circuit_run the 3 + 2 + 2 in test_circuit_run_instances_stay_on_one_engine.  The
+# reference of each case is its feature file's own: the oracle where that is quick at n = 40, else the feature file's device
+# call on ONE engine with the same keys (which that file compares with the oracle).
+RAGGED = (2, 7)
+N = 1024
+
+
+def one_engine(eoc, p, sk, packing=False):
+    eng = eoc.Engine(p)
+    eng.load_cloud_key(sk)
+    if packing:
+        blob = sk.packing_key_bytes()
+        eng.load_packing_key(blob)
+        eoc.global_import_packing_key_blob(blob)
+    return eng
+
+
+def blocks_of(eoc, name):
+    return [e[name] for e in eoc.stats_multi()["engines"]]
+
+
+@pytest.mark.parametrize("total", RAGGED)
+def test_seeded_expand_three_engines_ragged(eoc, ctx3, total):
+    p, sk, orc = ctx3
+    seed = bytes(range(7, 39))
+    bodies = np.random.default_rng(total).integers(-2**31, 2**31, total).astype(np.int32)
+    L = eoc.lib()
+    before = [L.eoc_engine_seed_launches(L.eoc_global_engine_at(i)) for i in range(3)]
+    got = eoc.seeded_expand(seed, bodies, 2**32 - 3)
+    per = [L.eoc_engine_seed_launches(L.eoc_global_engine_at(i)) - before[i] for i in range(3)]
+    assert np.array_equal(got, eoc.seeded_expand_host(p, seed, bodies, 2**32 - 3))
+    assert per == ([1, 1, 0] if total == 2 else [1, 1, 1])
+
+
+def test_seeded_expand_behind_a_pending_submission(eoc, ctx3):
+    """eoc_gate_batch_submit of 8 NAND gates, eoc_seeded_expand of 5 bodies with no wait in between, then the wait: the gates
+    equal the oracle's words and the expansion the host twin's.  Both orders gave right results before the expansion drained
+    pending submissions as every synchronous call does (it ran on the NULL stream beside them), so this case pins the new
+    ordering -- the expansion returns with the submission complete -- and is no regression catch."""
+    p, sk, orc = ctx3
+    rng = np.random.default_rng(21)
+    pin = [eoc.PinnedArray((8, p.n + 1)) for _ in range(3)]
+    pin[0].array[:] = sk.encrypt_bits(rng.integers(0, 2, 8).astype(np.uint8), 31, 0)
+    pin[1].array[:] = sk.encrypt_bits(rng.integers(0, 2, 8).astype(np.uint8), 32, 0)
+    pin[2].array[:] = 0
+    want = orc.gate_batch(ol.OPS["NAND"], pin[0].array.copy(), pin[1].array.copy())
+    seed = bytes(range(32))
+    bodies = rng.integers(-2**31, 2**31, 5).astype(np.int32)
+    ticket = eoc.gate_batch_submit(eoc.OPS["NAND"], pin[0].array, pin[1].array, out=pin[2].array)
+    got = eoc.seeded_expand(seed, bodies, 11)
+    drained = pin[2].array.copy()                # the expansion has drained the submission: the results are here already
+    eoc.gate_batch_wait(ticket)
+    assert np.array_equal(got, eoc.seeded_expand_host(p, seed, bodies, 11))
+    assert np.array_equal(drained, want) and np.array_equal(pin[2].array, want)
+    for a in pin:
+        a.free()
+
+
+@pytest.mark.parametrize("total", RAGGED)
+def test_lookups_three_engines_ragged(eoc, ctx3, total):
+    """eoc_lut_batch and eoc_lut_many_batch: rows cut 3 + 2 + 2 and 1 + 1 + 0, every table's block at its place in the output"""
+    import lut_many_oracle as lmo
+    import lut_oracle as lo
+    import test_gpu_lut as tl
+    import test_gpu_lut_many as tm
+    p, sk, orc = ctx3
+    cts = sk.encrypt_ints((np.arange(total) % 4).astype(np.uint8), 4, 8301)
+    _, tabs = tl.tables_for(4)
+    L = eoc.lib()
+    before = [L.eoc_worker_wakeups(i) for i in (1, 2)]
+    got = eoc.lut_batch(4, tabs, cts)
+    assert [L.eoc_worker_wakeups(i) - b for i, b in zip((1, 2), before)] == [1, 0 if total == 2 else 1]
+    assert np.array_equal(got, lo.lut_batch(orc, [eoc.lut_test_polynomial(4, t) for t in tabs], cts))
+    _, tabs = tm.tables_for(2, 4, 2)
+    got = eoc.lut_many_batch(4, tabs, cts)
+    assert got.shape == (2, 2, total, p.n + 1)
+    assert np.array_equal(got, lmo.lut_many_batch(orc, tm.packed(eoc, 4, tabs), cts, 2))
+
+
+@pytest.mark.parametrize("total", RAGGED)
+def test_lut2_three_engines_ragged(eoc, ctx3, total):
+    import lut2_oracle as l2
+    import test_gpu_lut2 as t2
+    p, sk, orc = ctx3
+    eng = one_engine(eoc, p, sk, packing=True)
+    xv, yv = np.arange(total, dtype=np.uint8) % 2, (np.arange(total, dtype=np.uint8) // 2) % 2
+    x, y = sk.encrypt_ints(xv, 2, 1402), sk.encrypt_ints(yv, 2, 2402)
+    tabs = np.stack([l2.lut2_tables(f, 2) for f in l2.functions(2)])
+    tv0 = np.stack([eoc.lut2_test_polynomials(2, t, 2) for t in tabs])
+    got = eoc.lut2_batch(2, tabs, x, y, n_tables=2)
+    assert np.array_equal(got, t2.lut2_device(eng, 2, 2, tv0, x, y))
+    eng.close()
+
+
+@pytest.mark.parametrize("total", RAGGED)
+def test_int_circuit_three_engines_ragged(eoc, ctx3, total):
+    """a two-node netlist (a lookup, then a lookup of a weighted sum of its output and the input) over 7 and 2 instances"""
+    import test_gpu_int_circuit as ti
+    p, sk, orc = ctx3
+    eng = one_engine(eoc, p, sk)
+    c = eoc.IntCircuit()
+    x = c.input(4, fresh=True)
+    n1 = c.lut([x], lambda m: (3 * m + 1) % 4, 4, 4)
+    c.lut([(2, n1), (1, x)], lambda m: (m + 2) % 4, 4, 4, allow_padding=True)
+    wires = np.zeros((c.n_wires, total, p.n + 1), np.int32)
+    wires[x] = sk.encrypt_ints((np.arange(total) % 4).astype(np.uint8), 4, 9101)
+    assert np.array_equal(eoc.int_circuit_run(c.nodes(), c.tables(), wires), ti.run_device(eoc, eng, c, wires))
+    eng.close()
+
+
+def test_circuit_run_with_an_empty_block(eoc, ctx3):
+    """two instances on three engines: engine 2 has no block; the 3 + 2 + 2 cut is test_circuit_run_instances_stay_on_one_engine"""
+    p, sk, orc = ctx3
+    gates = [eoc.Gate(eoc.OPS["NAND"], 0, 1, -1, 2), eoc.Gate(eoc.OPS["XOR"], 2, 0, -1, 3)]
+    wires = np.zeros((4, 2, p.n + 1), np.int32)
+    wires[0], wires[1] = sk.encrypt_bits(np.array([0, 1], np.uint8), 41, 0), sk.encrypt_bits(np.array([1, 1], np.uint8), 42, 0)
+    ref = wires.copy()
+    ref[2] = orc.gate_batch(ol.OPS["NAND"], ref[0], ref[1])
+    ref[3] = orc.gate_batch(ol.OPS["XOR"], ref[2], ref[0])
+    before = blocks_of(eoc, "bootstraps")
+    eoc.circuit_run(gates, wires, 2)
+    assert [a - b for a, b in zip(blocks_of(eoc, "bootstraps"), before)] == [2, 2, 0]
+    assert np.array_equal(wires, ref)
+
+
+def test_compact_expand_and_pack_three_engines_ragged(eoc, ctx3):
+    """2 N + 5 samples: the expansion cuts by sample (685 + 684 + 684: blocks start inside a list), the packing key switch by
+    WHOLE lists (one each, the last with five samples)"""
+    import test_gpu_compact as tc
+    import test_gpu_pack as tp
+    p, sk, orc = ctx3
+    eng = one_engine(eoc, p, sk, packing=True)
+    count = 2 * N + 5
+    bits = np.random.default_rng(80).integers(0, 2, count).astype(np.uint8)
+    lists = eoc.PublicKey(sk.public_key_bytes()).encrypt_bits(bits, enc_seed=800)
+    before = blocks_of(eoc, "keyswitches")
+    got = eoc.compact_expand(lists, count)
+    assert [a - b for a, b in zip(blocks_of(eoc, "keyswitches"), before)] == [685, 684, 684]
+    assert np.array_equal(got, tc.expand_device(eng, lists, count, p.n))
+    assert np.array_equal(sk.decrypt_bits(got), bits)
+    L = eoc.lib()
+    cts = sk.encrypt_bits(bits, 501)
+    packed = eoc.pack(cts)
+    assert [int(L.eoc_engine_packed_samples(L.eoc_global_engine_at(i))) for i in range(3)] == [N, N, 5]
+    assert np.array_equal(packed, tp.pack_device(eng, cts))
+    eng.close()
+
+
+@pytest.mark.parametrize("total", RAGGED)
+def test_table_read_and_update_three_engines_ragged(eoc, ctx3, total):
+    """log2_lists = 2, log2_width = 9 (three selectors a query): queries cut 3 + 2 + 2 and 1 + 1 + 0; the update adds one delta
+    table per engine that has a block"""
+    import test_gpu_cmux as tx
+    import test_gpu_table_update as tu
+    p, sk, orc = ctx3
+    eng = one_engine(eoc, p, sk)
+    d, lw, depth = 2, 9, 3
+    rng = np.random.default_rng(1200 + total)
+    table = eoc.PublicKey(sk.public_key_bytes()).encrypt_ints(rng.integers(0, 4, 4 * N).astype(np.uint8), 4, enc_seed=1210)
+    sel = tx.index_selectors(sk, [(5 * k + 7) % 8 for k in range(total)], depth, enc_seed=1220)
+    before = blocks_of(eoc, "keyswitches")
+    got = eoc.table_read(table, d, lw, sel)
+    per = [a - b for a, b in zip(blocks_of(eoc, "keyswitches"), before)]
+    assert per == [512 * b for b in ((1, 1, 0) if total == 2 else (3, 2, 2))]
+    assert np.array_equal(got, tx.read_device(eng, table, d, lw, sel, p.n))
+    values = rng.integers(-2**31, 2**31, (total, 2, N)).astype(np.int32)
+    assert np.array_equal(eoc.table_update(table, d, lw, sel, values), tu.update_device(eng, table, d, lw, sel, values))
+    eng.close()
+
+
+@pytest.mark.parametrize("total", RAGGED)
+def test_automaton_run_three_engines_ragged(eoc, ctx3, total):
+    """divisible_by(3) over two steps: queries cut 3 + 2 + 2 and 1 + 1 + 0"""
+    import test_gpu_automaton as ta
+    import test_gpu_cmux as tx
+    from test_automaton_cpu import acceptor_final
+    p, sk, orc = ctx3
+    eng = one_engine(eoc, p, sk)
+    aut, steps = eoc.Automaton.divisible_by(3), 2
+    final = acceptor_final(eoc, aut)
+    bits = [[(q >> t) & 1 for t in range(steps)] for q in range(total)]
+    sel = sk.encrypt_selector_bits(np.ravel(bits), enc_seed=1902)
+    ref, _ = ta.run_device(eng, aut, final, tx.convert(eng, sel), steps, [aut.start], 0, total, p.n)
+    got = eoc.automaton_run(aut, final, sel.reshape(total, steps, 2 * p.l, 2, N), [aut.start], 0)
+    assert np.array_equal(got, ref)
+    assert sk.decrypt_ints(got.reshape(-1, p.n + 1), 2).tolist() == [aut.evaluate_plain(b) for b in bits]
+    eng.close()
+
+
+@pytest.mark.parametrize("total", RAGGED)
+def test_linear_three_engines_ragged(eoc, ctx3, total):
+    """3 x 5 weights with a bias: WHOLE input vectors cut 3 + 2 + 2 and 1 + 1 + 0"""
+    import test_gpu_dot as td
+    p, sk, orc = ctx3
+    eng = one_engine(eoc, p, sk)
+    rng = np.random.default_rng(1600 + total)
+    w, lists = td.rand_weights(rng, 3, 5), td.rand_lists(rng, total, 5)
+    bias = rng.integers(-2**31, 2**31, 3).astype(np.int32)
+    before = blocks_of(eoc, "keyswitches")
+    got = eoc.linear(w, lists, bias)
+    per = [a - b for a, b in zip(blocks_of(eoc, "keyswitches"), before)]
+    assert per == [3 * b for b in ((1, 1, 0) if total == 2 else (3, 2, 2))]
+    assert np.array_equal(got, td.run(eng, w, lists, bias, linear=True))
+    eng.close()

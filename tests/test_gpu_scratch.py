@@ -124,8 +124,9 @@ def test_scratch_rule_refuses_capture_then_grows_once(eoc, call):
 
 
 def test_circuit_and_table_lookup_share_the_staging_buffer(eoc):
-    """one engine on the global context: the 8-bit adder over 4 instances, one table over 4 rows, the adder again -- every
-    word as the oracle's; a second round of the three calls grows no host-path buffer"""
+    """one engine on the global context: the 8-bit adder over 4 instances, one table over 4 rows, the adder again, five seeded
+    samples expanded -- every word as the oracle's (as the host twin's); a second round of the four calls grows no host-path
+    buffer"""
     from eoc_tfhe_amd import circuits
     p = eoc.default_params(0)
     p.n = 40                                                            # short LWE dimension: fast oracle
@@ -147,12 +148,15 @@ def test_circuit_and_table_lookup_share_the_staging_buffer(eoc):
     cts = sk.encrypt_ints(vals, 4, 8401)
     tab = lo.int_table(lambda m: (3 * m + 1) % 4, 4, 4)
     want_lut = lo.lut_batch(orc, eoc.lut_test_polynomial(4, tab), cts)
+    seed = bytes(range(32))
+    bodies = rng.integers(-2**31, 2**31, 5).astype(np.int32)
+    want_seeded = eoc.seeded_expand_host(p, seed, bodies, 3)
     eoc.gpu_shutdown()
     eoc.gpu_init(p, devices=[0])
     try:
         eoc.upload_cloud_key(sk)
 
-        def round_of_three():
+        def round_of_four():
             for step in range(3):
                 if step == 1:
                     assert np.array_equal(eoc.lut_batch(4, [tab], cts), want_lut)
@@ -160,11 +164,12 @@ def test_circuit_and_table_lookup_share_the_staging_buffer(eoc):
                 wires = wires0.copy()
                 eoc.circuit_run(gates, wires, S)
                 assert np.array_equal(wires, ref), step
+            assert np.array_equal(eoc.seeded_expand(seed, bodies, 3), want_seeded)
             return eoc.stats_multi()["host_buffer_grows"]
 
-        grows = round_of_three()
+        grows = round_of_four()
         assert grows >= 1
-        assert round_of_three() == grows
+        assert round_of_four() == grows
         tot = sum(sk.decrypt_bits(ref[sw[0] + i]).astype(np.int64) << i for i in range(9))
         assert np.array_equal(tot, A + B)
     finally:

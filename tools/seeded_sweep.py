@@ -7,6 +7,9 @@ two alternated rounds, of
            bodies_h2d), with the kernel's own time from the engine's events (eoc_engine_kernel_times, booked under prepare);
   h2d      a pinned-memory H2D copy of the same [count][n + 1] samples: the only way to put unseeded samples on the device.
 The expansion is checked once per point against the host twin on 64 samples spread over the batch.
+Global context, Set A, the same COUNTS on one engine and on three engines of device 0 (GLOBAL_DEVICES): eoc_seeded_expand on
+pageable host buffers, the whole synchronous call (bodies up, expansion, samples down), REPS calls, two rounds; the result is
+checked once per point against the host twin on the same 64 samples.
 Key install, PSETS (0, 1): eoc_engine_load_seeded_cloud_key (EOCCKS1 blob) alternated with eoc_engine_load_cloud_key (the
 torus-form arrays of the same key material, host-expanded), KEY_REPS calls each; both are synchronous."""
 import json
@@ -23,6 +26,7 @@ COUNTS = [int(x) for x in os.environ.get("COUNTS", "1024,16384,262144").split(",
 PSETS = [int(x) for x in os.environ.get("PSETS", "0,1").split(",")]
 REPS = int(os.environ.get("REPS", "10"))
 KEY_REPS = int(os.environ.get("KEY_REPS", "3"))
+GLOBAL_DEVICES = [[0], [0, 0, 0]]
 SEED = bytes(range(32))
 
 
@@ -68,6 +72,33 @@ def input_point(eoc, torch, eng, p, count):
                 expansion_equals_host=bool(ok))
 
 
+def global_point(eoc, p, count, devices):
+    rng = np.random.default_rng(count)
+    bodies = rng.integers(-2**31, 2**31, count).astype(np.int32)
+    seed = np.frombuffer(SEED, np.uint8)
+    out = np.zeros((count, p.n + 1), np.int32)
+    call = lambda: eoc.lib().eoc_seeded_expand(seed.ctypes.data, 0, bodies.ctypes.data, count, out.ctypes.data)
+    eoc.gpu_shutdown()
+    eoc.gpu_init(p, devices=devices)
+    try:
+        assert call() == 0, eoc.lib().eoc_last_error()
+        idx = np.unique(np.r_[0, count - 1, rng.integers(0, count, 62)])
+        ok = all(np.array_equal(out[i], eoc.seeded_expand_host(p, SEED, bodies[i:i + 1], int(i))[0]) for i in idx)
+        grows = eoc.stats_multi()["host_buffer_grows"]
+        ms = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            for _ in range(REPS):
+                call()
+            ms.append((time.perf_counter() - t0) / REPS * 1e3)
+        grows = eoc.stats_multi()["host_buffer_grows"] - grows
+        return dict(samples=count, engines=len(devices), global_expand_host_ms=sum(ms) / 2, rounds_ms=ms,
+                    us_per_sample=sum(ms) / 2 * 1e3 / count, host_buffer_grows_in_timed_calls=grows,
+                    expansion_equals_host=bool(ok))
+    finally:
+        eoc.gpu_shutdown()
+
+
 def key_point(eoc, torch, pset):
     p = eoc.default_params(pset)
     sk = eoc.SecretKey(p, 1, with_cloud_key=False)
@@ -97,6 +128,10 @@ def main():
         lines.append(json.dumps(dict(pset=0, **input_point(eoc, torch, eng, p, count))))
         print(lines[-1], flush=True)
     eng.close()
+    for devices in GLOBAL_DEVICES:
+        for count in COUNTS:
+            lines.append(json.dumps(dict(pset=0, **global_point(eoc, p, count, devices))))
+            print(lines[-1], flush=True)
     for pset in PSETS:
         lines.append(json.dumps(key_point(eoc, torch, pset)))
         print(lines[-1], flush=True)
