@@ -328,6 +328,13 @@ def lib():
         "eoc_linear": (C.c_int, [vp, sz, sz, vp, sz, vp, vp]),
         "eoc_pk_encrypt_torus": (C.c_int, [vp, sz, u64, u64, vp, sz, vp]),
         "eoc_pk_encrypt_torus_keyed": (C.c_int, [vp, sz, vp, u64, vp, sz, vp]),
+        # convolutions with public int8 kernels on compact lists
+        "eoc_conv_slots_to_device": (C.c_int, [vp, vp, sz, sz, vp, vp]),
+        "eoc_conv_device": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, vp, vp]),
+        "eoc_conv_linear_device": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]),
+        "eoc_conv_extract_device": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, vp]),
+        "eoc_engine_conv_launches": (u64, [vp]),
+        "eoc_conv_linear": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1123,6 +1130,42 @@ class Engine:
         """k_dot_mask launches so far (eoc_engine_dot_launches): one per slice of a call's input vectors"""
         return int(self.L.eoc_engine_dot_launches(self.h))
 
+    def conv_slots_to_device(self, slots, lists_per_vec, d_slots, stream=None):
+        """A public slot table [n_slots] (entry s: slot s mod N of list s / N of a vector's lists_per_vec lists; any order,
+        repeats allowed) -> the device table at d_slots, n_slots uint32 (eoc_conv_slots_to_device).  Every entry is checked
+        here, once, on the host; the run calls take the device table as it is.  Synchronous.  Returns n_slots."""
+        t = np.asarray(slots)
+        if t.ndim != 1 or t.size == 0 or not np.issubdtype(t.dtype, np.integer) or t.min() < 0 or t.max() >= 2**32:
+            raise EocError(f"conv_slots_to_device: slots must be a non-empty vector of slot numbers, got {t.dtype} {t.shape}")
+        t = np.ascontiguousarray(t, np.uint32)
+        _check(self.L.eoc_conv_slots_to_device(self.h, t.ctypes.data, t.size, int(lists_per_vec), d_slots, stream),
+               "eoc_conv_slots_to_device")
+        return t.size
+
+    def conv_device(self, d_image, rows, cols, d_lists, batch, d_bias, d_out_lists, stream=None):
+        """Convolutions with public int8 kernels (eoc_conv_device): the image of weights_to_device, rows = output
+        channels, list l of d_lists [batch][ceil(cols / N)][2][N] = input channel l, w[r][l N + k] = tap k of filter (r, l);
+        d_out_lists [batch][rows][2][N]: slot t of list (b, r) has phase bias[r] + sum_l sum_k w[r][l N + k] x_l[t + k]
+        (negacyclic: terms past slot N - 1 enter negated).  No key needed; the output is compact lists."""
+        _check(self.L.eoc_conv_device(self.h, d_image, rows, cols, d_lists, batch, d_bias, d_out_lists, stream), "eoc_conv_device")
+
+    def conv_linear_device(self, d_image, rows, cols, d_lists, batch, d_bias, d_slots, n_slots, d_out, stream=None):
+        """conv_device into a scratch buffer, then the samples of the slot table (conv_slots_to_device with lists_per_vec =
+        rows) extracted and key-switched (eoc_conv_linear_device): d_out [batch][n_slots][n+1], ordinary LWE samples.  Needs
+        the cloud key."""
+        _check(self.L.eoc_conv_linear_device(self.h, d_image, rows, cols, d_lists, batch, d_bias, d_slots, n_slots, d_out, stream),
+               "eoc_conv_linear_device")
+
+    def conv_extract_device(self, d_lists, lists_per_vec, batch, d_slots, n_slots, d_out, stream=None):
+        """the extraction and the key switch of conv_linear_device alone (eoc_conv_extract_device): d_lists
+        [batch][lists_per_vec][2][N] -> d_out [batch][n_slots][n+1].  Needs the cloud key."""
+        _check(self.L.eoc_conv_extract_device(self.h, d_lists, lists_per_vec, batch, d_slots, n_slots, d_out, stream),
+               "eoc_conv_extract_device")
+
+    def conv_launches(self):
+        """k_conv_lists launches so far (eoc_engine_conv_launches): one per slice of a call's input vectors"""
+        return int(self.L.eoc_engine_conv_launches(self.h))
+
     def automaton_launches(self):
         """k_automaton_step launches so far (eoc_engine_automaton_launches): `steps` per slice of a run's queries"""
         return int(self.L.eoc_engine_automaton_launches(self.h))
@@ -1627,6 +1670,34 @@ def linear(weights, lists, bias=None):
     out = np.empty((lists.shape[0], rows, _global_n("linear") + 1), np.int32)
     _check(lib().eoc_linear(w.ctypes.data, rows, cols, lists.ctypes.data, lists.shape[0],
                             None if bias is None else bias.ctypes.data, out.ctypes.data), "eoc_linear")
+    return out
+
+
+def conv_linear(weights, lists, slots, bias=None):
+    """eoc_conv_linear on the global context (a cloud key alone suffices): public int8 kernels [rows][cols] in [-127, 127]
+    (rows = output channels, w[r][l N + k] = tap k of filter (r, l)), lists [batch][ceil(cols / N)][2][N] (list l = input
+    channel l), slots [n_slots] (entry s: slot s mod N of output channel s / N), bias [rows] Torus32 or None -> LWE samples
+    [batch][n_slots][n+1] of phase bias[r] + sum_l sum_k w[r][l N + k] x_l[t + k]"""
+    w = np.asarray(weights)
+    if w.ndim != 2 or w.size == 0 or not np.issubdtype(w.dtype, np.integer) or np.abs(w.astype(np.int64)).max() > 127:
+        raise EocError(f"conv_linear: weights must be a non-empty integer matrix [rows][cols] in [-127, 127], got {w.dtype} {w.shape}")
+    w = np.ascontiguousarray(w, np.int8)
+    rows, cols = w.shape
+    L = -(-cols // N)
+    lists = np.ascontiguousarray(lists, np.int32)
+    if lists.ndim != 4 or lists.shape[1:] != (L, 2, N):
+        raise EocError(f"conv_linear: lists must be [batch][{L}][2][{N}], got {lists.shape}")
+    t = np.asarray(slots)
+    if t.ndim != 1 or (t.size and (not np.issubdtype(t.dtype, np.integer) or t.min() < 0 or t.max() >= rows * N)):
+        raise EocError(f"conv_linear: slots must be a vector of slot numbers in [0, {rows * N}), got {t.dtype} {t.shape}")
+    t = np.ascontiguousarray(t, np.uint32)
+    if bias is not None:
+        bias = np.ascontiguousarray(bias, np.int32)
+        if bias.shape != (rows,):
+            raise EocError(f"conv_linear: bias must be [{rows}], got {bias.shape}")
+    out = np.empty((lists.shape[0], t.size, _global_n("conv_linear") + 1), np.int32)
+    _check(lib().eoc_conv_linear(w.ctypes.data, rows, cols, lists.ctypes.data, lists.shape[0],
+                                 None if bias is None else bias.ctypes.data, t.ctypes.data, t.size, out.ctypes.data), "eoc_conv_linear")
     return out
 
 

@@ -123,6 +123,10 @@ struct eoc_engine {
     Scratch dot_specs;
     size_t dot_ws_bytes = (size_t)256 << 20;
     uint64_t dot_launches = 0; // k_dot_mask launches
+    // convolutions with public kernels: the output lists [vectors of a slice][rows][2][N] of
+    // eoc_conv_linear_device, between k_conv_lists and k_conv_extract; held to EOC_TFHE_DOT_WS_BYTES together with the spectra
+    Scratch conv_lists;
+    uint64_t conv_launches = 0; // k_conv_lists launches
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
     struct Span { hipEvent_t a, b; int kind; };
@@ -283,7 +287,7 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
     }
     hipFree(e->d_ksl);
     hipFree(e->d_pks);
-    for (Scratch *s : {&e->cmux[0], &e->cmux[1], &e->pack_cols, &e->lut2, &e->seed_stage, &e->dot_specs}) hipFree(s->p);
+    for (Scratch *s : {&e->cmux[0], &e->cmux[1], &e->pack_cols, &e->lut2, &e->seed_stage, &e->dot_specs, &e->conv_lists}) hipFree(s->p);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -722,6 +726,7 @@ static const void *leveled_kernel(const void *const (&instances)[6], int l, int 
 
 // The dynamic-LDS limit of every kernel that asks for more than the default: raised once, at engine creation, not on the
 // launch path
+static void set_conv_attrs(); // the convolution kernels are first named at the end of this file
 static void set_kernel_attrs(eoc_engine *e)
 {
     // the key-switch waves use > 64 KiB: a device that refuses it -- 64 KiB of LDS per workgroup -- sends every shape to
@@ -744,6 +749,7 @@ static void set_kernel_attrs(eoc_engine *e)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dot_mask<kDotChunk>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               kDotLds);
+    set_conv_attrs();
     (void)hipGetLastError();
 }
 
@@ -2775,9 +2781,9 @@ static bool dot_ranges_overlap(const void *a, size_t a_bytes, const void *b, siz
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
-// argument checks shared by both device calls; out: the output buffer of out_stride words per sample
-static int dot_check(eoc_engine *e, const char *who, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists,
-                     size_t batch, const int32_t *d_bias, const int32_t *out, size_t out_stride)
+// argument checks shared by the device calls of this section and the next; out: the output buffer of out_bytes bytes
+static int dot_check_bytes(eoc_engine *e, const char *who, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists,
+                           size_t batch, const int32_t *d_bias, const int32_t *out, size_t out_bytes)
 {
     if (!e || !d_image || !d_lists || !out) {
         eoc_set_error("%s: null argument", who);
@@ -2787,7 +2793,6 @@ static int dot_check(eoc_engine *e, const char *who, const void *d_image, size_t
         eoc_set_error("%s: rows = %zu, cols = %zu: both must lie in [1, 2^20]", who, rows, cols);
         return EOC_ERR_ARG;
     }
-    const size_t out_bytes = batch * rows * out_stride * 4;
     if (dot_ranges_overlap(out, out_bytes, d_lists, batch * dot_lists(cols) * 2 * kN * 4) ||
         dot_ranges_overlap(out, out_bytes, d_image, eoc_weights_image_bytes(rows, cols)) ||
         dot_ranges_overlap(out, out_bytes, d_bias, rows * 4)) {
@@ -2795,6 +2800,12 @@ static int dot_check(eoc_engine *e, const char *who, const void *d_image, size_t
         return EOC_ERR_ARG;
     }
     return EOC_OK;
+}
+// ... of out_stride words per sample (vector, row)
+static int dot_check(eoc_engine *e, const char *who, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists,
+                     size_t batch, const int32_t *d_bias, const int32_t *out, size_t out_stride)
+{
+    return dot_check_bytes(e, who, d_image, rows, cols, d_lists, batch, d_bias, out, batch * rows * out_stride * 4);
 }
 
 extern "C" int eoc_dot_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists, size_t batch,
@@ -2821,6 +2832,214 @@ extern "C" int eoc_linear_device(eoc_engine *e, const void *d_image, size_t rows
     if (batch * rows == 0) return EOC_OK;
     if (int rc = dot_check(e, "eoc_linear_device", d_image, rows, cols, d_lists, batch, d_bias, d_out, (size_t)e->p.n + 1)) return rc;
     return dot_locked(e, "eoc_linear_device", d_image, rows, cols, d_lists, batch, d_bias, nullptr, d_out, (hipStream_t)hip_stream);
+}
+
+// ---- convolutions with public int8 kernels on compact lists ------------------
+// The model, its image and the lists are the inner product's; the output keeps the whole product.  k_conv_lists and its
+// helpers are templates first named here, behind every other kernel of this file.
+constexpr size_t kConvMaxSlots = (size_t)1 << 20; // entries of a slot table: one vector's samples fit one key-switch slice
+constexpr size_t kConvMaxVecs = 65535;            // vectors of a slice: k_conv_extract's grid y
+
+static void set_conv_attrs()
+{
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_lists<kDotChunk, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kDotLds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_lists<kDotChunk, false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kDotLds);
+}
+
+// A slot table load, as a model load: validated once on the host (every entry below lists_per_vec N), no key, the table
+// is on the device when the call returns (`hip_stream` is drained); the run calls then take the device table as it is
+extern "C" int eoc_conv_slots_to_device(eoc_engine *e, const uint32_t *h_slots, size_t n_slots, size_t lists_per_vec,
+                                        uint32_t *d_slots, void *hip_stream)
+{
+    if (!e || !h_slots || !d_slots) {
+        eoc_set_error("eoc_conv_slots_to_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (n_slots < 1 || n_slots > kConvMaxSlots || lists_per_vec < 1 || lists_per_vec > kDotMaxDim) {
+        eoc_set_error("eoc_conv_slots_to_device: n_slots = %zu, lists_per_vec = %zu: both must lie in [1, 2^20]", n_slots, lists_per_vec);
+        return EOC_ERR_ARG;
+    }
+    for (size_t k = 0; k < n_slots; k++)
+        if (h_slots[k] >= lists_per_vec * kN) {
+            eoc_set_error("eoc_conv_slots_to_device: slot %zu is %u; a vector of %zu lists has slots [0, %zu)", k, h_slots[k],
+                          lists_per_vec, lists_per_vec * kN);
+            return EOC_ERR_ARG;
+        }
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (stream_is_capturing(st)) {
+        eoc_set_error("eoc_conv_slots_to_device: a table load synchronises; it cannot be captured");
+        return EOC_ERR_STATE;
+    }
+    HIP_TRY(hipMemcpyAsync(d_slots, h_slots, n_slots * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st)); // the host table ends with this call
+    return EOC_OK;
+}
+
+// The output lists of S = vectors x rows (vector, row) pairs of a slice whose list spectra stand in e->dot_specs: one chunk
+// per output -> the storing instance alone; otherwise k_conv_init, then the adding instance
+static int launch_conv_lists(eoc_engine *e, const void *d_image, size_t rows, size_t L, size_t S, const int32_t *d_bias,
+                             int32_t *d_lists_out, hipStream_t st)
+{
+    const d2 *wspec = static_cast<const d2 *>(d_image);
+    const d2 *lspec = static_cast<const d2 *>(e->dot_specs.p);
+    const uint32_t nchunks = (uint32_t)((L + kDotChunk - 1) / kDotChunk);
+    const uint32_t items = (uint32_t)(S * nchunks * 2);
+    const dim3 grid((items + kDotWavesPerWG - 1) / kDotWavesPerWG), block(64 * kDotWavesPerWG);
+    if (nchunks > 1) {
+        SpanGuard span(e, st, KIND_KEYSWITCH);
+        hipLaunchKernelGGL(k_conv_init<256>, dim3((unsigned)S), dim3(256), 0, st, d_bias, (uint32_t)rows, d_lists_out);
+        HIP_TRY(hipGetLastError());
+    }
+    SpanGuard span(e, st, KIND_KEYSWITCH);
+    if (nchunks == 1)
+        hipLaunchKernelGGL((k_conv_lists<kDotChunk, true>), grid, block, kDotLds, st, wspec, lspec, d_bias, d_lists_out,
+                           (uint32_t)rows, (uint32_t)L, nchunks, items, (const d2 *)e->d_tw, (const d2 *)e->d_twist);
+    else
+        hipLaunchKernelGGL((k_conv_lists<kDotChunk, false>), grid, block, kDotLds, st, wspec, lspec, d_bias, d_lists_out,
+                           (uint32_t)rows, (uint32_t)L, nchunks, items, (const d2 *)e->d_tw, (const d2 *)e->d_twist);
+    HIP_TRY(hipGetLastError());
+    e->conv_launches++;
+    return EOC_OK;
+}
+
+// B vectors of lists_per_vec lists each -> the samples (b, s) of the slot table, key-switched into d_out [B][n_slots][n+1]:
+// k_conv_extract writes the operand rows and the output rows, the key switch runs as behind k_compact_expand (init_done)
+static int launch_conv_extract(eoc_engine *e, const int32_t *d_lists, size_t lists_per_vec, size_t B, const uint32_t *d_slots,
+                               size_t n_slots, int32_t *d_out, hipStream_t st)
+{
+    WS &W = e->ws;
+    const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
+    {
+        SpanGuard span(e, st, KIND_KEYSWITCH);
+        hipLaunchKernelGGL(k_conv_extract<kCompactSlotsPerWG>,
+                           dim3((unsigned)((n_slots + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG), (unsigned)B), dim3(256), 0, st,
+                           d_lists, (uint32_t)lists_per_vec, d_slots, (uint32_t)n_slots, W.d_ubar, d_out, e->p.n, prec_offset);
+        HIP_TRY(hipGetLastError());
+    }
+    const GateDesc d{OP_RAW, 0, nullptr, nullptr, nullptr, d_out};
+    int rc = launch_keyswitch(e, W, nullptr, 1, (uint32_t)(B * n_slots), st, true, &d);
+    if (rc) return rc;
+    e->stats[2] += B * n_slots;
+    return EOC_OK;
+}
+
+// Both convolution calls: per slice of whole input vectors, k_fft_fwd_polys of the slice's lists into the workspace (both
+// polynomials are read), then the output lists -- the caller's (d_slots = NULL), or the scratch lists the slot table's
+// samples are extracted from and key-switched into d_out.  The budget EOC_TFHE_DOT_WS_BYTES holds the spectra and the scratch
+// lists of a slice together.  All arguments travel as kernel arguments: no descriptor ring slot.
+static int conv_locked(eoc_engine *e, const char *who, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists,
+                       size_t batch, const int32_t *d_bias, int32_t *d_out_lists, const uint32_t *d_slots, size_t n_slots,
+                       int32_t *d_out, hipStream_t st)
+{
+    const size_t L = dot_lists(cols), spec_vec = L * 2 * kNH * sizeof(d2), lists_vec = rows * 2 * kN * sizeof(int32_t);
+    const size_t per_vec = spec_vec + (d_slots ? lists_vec : 0);
+    if (e->dot_ws_bytes < per_vec) {
+        eoc_set_error("%s: one input vector needs %zu bytes of workspace, the budget (EOC_TFHE_DOT_WS_BYTES) is %zu", who, per_vec,
+                      e->dot_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    size_t bs = std::min({batch, e->dot_ws_bytes / per_vec, std::max<size_t>(1, ((size_t)1 << 20) / rows), kConvMaxVecs});
+    if (d_slots) bs = std::min(bs, std::max<size_t>(1, ((size_t)1 << 20) / n_slots));
+    int rc = scratch_reserve(e, e->dot_specs, bs * spec_vec, "list spectra", st);
+    if (!rc && d_slots) rc = scratch_reserve(e, e->conv_lists, bs * lists_vec, "convolution lists", st);
+    if (!rc && d_slots) rc = ensure_ws(e, e->ws, bs * n_slots, 0, 0, st);
+    if (rc) return rc;
+    for (size_t b0 = 0; b0 < batch; b0 += bs) {
+        const size_t B = std::min(bs, batch - b0);
+        {
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            rc = launch_fft_fwd(e, d_lists + b0 * L * 2 * kN, static_cast<double *>(e->dot_specs.p), B * L * 2, 0x1p-9, st);
+            if (rc) return rc;
+        }
+        int32_t *lists_out = d_slots ? e->conv_lists.i32() : d_out_lists + b0 * rows * 2 * kN;
+        rc = launch_conv_lists(e, d_image, rows, L, B * rows, d_bias, lists_out, st);
+        if (!rc && d_slots) rc = launch_conv_extract(e, lists_out, rows, B, d_slots, n_slots, d_out + b0 * n_slots * ((size_t)e->p.n + 1), st);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+extern "C" int eoc_conv_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists, size_t batch,
+                               const int32_t *d_bias, int32_t *d_out_lists, void *hip_stream)
+{
+    if (e && batch * rows == 0) return EOC_OK;
+    if (int rc = dot_check(e, "eoc_conv_device", d_image, rows, cols, d_lists, batch, d_bias, d_out_lists, (size_t)2 * kN)) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    return conv_locked(e, "eoc_conv_device", d_image, rows, cols, d_lists, batch, d_bias, d_out_lists, nullptr, 0, nullptr,
+                       (hipStream_t)hip_stream);
+}
+
+// the slot table of a call that extracts: entries in [1, 2^20], not under the output
+static int conv_slots_check(const char *who, const uint32_t *d_slots, size_t n_slots, const int32_t *d_out, size_t out_bytes)
+{
+    if (!d_slots || n_slots > kConvMaxSlots) {
+        eoc_set_error("%s: no slot table, or n_slots = %zu above 2^20", who, n_slots);
+        return EOC_ERR_ARG;
+    }
+    if (dot_ranges_overlap(d_out, out_bytes, d_slots, n_slots * sizeof(uint32_t))) {
+        eoc_set_error("%s: the output must not overlap the slot table", who);
+        return EOC_ERR_ARG;
+    }
+    return EOC_OK;
+}
+
+extern "C" int eoc_conv_linear_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists,
+                                      size_t batch, const int32_t *d_bias, const uint32_t *d_slots, size_t n_slots, int32_t *d_out,
+                                      void *hip_stream)
+{
+    if (!e) {
+        eoc_set_error("eoc_conv_linear_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->ksk) {
+        eoc_set_error("eoc_conv_linear_device: no key-switch key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    if (batch * n_slots == 0) return EOC_OK;
+    const size_t out_bytes = batch * n_slots * ((size_t)e->p.n + 1) * 4;
+    if (int rc = dot_check_bytes(e, "eoc_conv_linear_device", d_image, rows, cols, d_lists, batch, d_bias, d_out, out_bytes)) return rc;
+    if (int rc = conv_slots_check("eoc_conv_linear_device", d_slots, n_slots, d_out, out_bytes)) return rc;
+    return conv_locked(e, "eoc_conv_linear_device", d_image, rows, cols, d_lists, batch, d_bias, nullptr, d_slots, n_slots, d_out,
+                       (hipStream_t)hip_stream);
+}
+
+extern "C" int eoc_conv_extract_device(eoc_engine *e, const int32_t *d_lists, size_t lists_per_vec, size_t batch,
+                                       const uint32_t *d_slots, size_t n_slots, int32_t *d_out, void *hip_stream)
+{
+    if (!e) {
+        eoc_set_error("eoc_conv_extract_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->ksk) {
+        eoc_set_error("eoc_conv_extract_device: no key-switch key loaded");
+        return EOC_ERR_NO_KEY;
+    }
+    if (batch * n_slots == 0) return EOC_OK;
+    if (!d_lists || !d_out || lists_per_vec < 1 || lists_per_vec > kDotMaxDim) {
+        eoc_set_error("eoc_conv_extract_device: null argument, or lists_per_vec = %zu outside [1, 2^20]", lists_per_vec);
+        return EOC_ERR_ARG;
+    }
+    const size_t stride = (size_t)e->p.n + 1, out_bytes = batch * n_slots * stride * 4;
+    if (int rc = conv_slots_check("eoc_conv_extract_device", d_slots, n_slots, d_out, out_bytes)) return rc;
+    if (dot_ranges_overlap(d_out, out_bytes, d_lists, batch * lists_per_vec * 2 * kN * 4)) {
+        eoc_set_error("eoc_conv_extract_device: the output must not overlap the lists");
+        return EOC_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t bs = std::min({batch, std::max<size_t>(1, ((size_t)1 << 20) / n_slots), kConvMaxVecs});
+    int rc = ensure_ws(e, e->ws, bs * n_slots, 0, 0, st);
+    for (size_t b0 = 0; !rc && b0 < batch; b0 += bs)
+        rc = launch_conv_extract(e, d_lists + b0 * lists_per_vec * 2 * kN, lists_per_vec, std::min(bs, batch - b0), d_slots, n_slots,
+                                 d_out + b0 * n_slots * stride, st);
+    return rc;
 }
 
 // ---- introspection: profiling, statistics, counters ------------------------------------------
@@ -2895,6 +3114,7 @@ extern "C" uint64_t eoc_engine_pack_launches(eoc_engine *e) { return e ? e->pack
 extern "C" uint64_t eoc_engine_packed_samples(eoc_engine *e) { return e ? e->packed_samples : 0; }
 extern "C" uint64_t eoc_engine_seed_launches(eoc_engine *e) { return e ? e->seed_launches : 0; }
 extern "C" uint64_t eoc_engine_dot_launches(eoc_engine *e) { return e ? e->dot_launches : 0; }
+extern "C" uint64_t eoc_engine_conv_launches(eoc_engine *e) { return e ? e->conv_launches : 0; }
 extern "C" size_t eoc_engine_resident_jobs(eoc_engine *e)
 {
     if (!e) return 0;

@@ -2307,4 +2307,135 @@ __global__ __launch_bounds__(64 * kDotWavesPerWG, 2) void k_dot_mask(const d2 *_
     }
 }
 
+// =================================================================================================
+// Convolutions with public int8 kernels: the WHOLE product the inner product takes one slot of.  Same
+// weights, same image, same lists, same format rule; output (vector b, row r) is the TLWE list
+//   ( sum_l V_{r,l} c0_{b,l} ,  bias[r] + sum_l V_{r,l} c1_{b,l} )                                        [2][N] int32
+// whose slot t has phase bias[r] + sum_l sum_k w[r][lN + k] x_l[t + k], terms with t + k >= N entering negated (the
+// negacyclic wrap): a cross-correlation of input channel l (list l) with filter (r, l).  Both polynomials go through the
+// chunks of the inner product (8 lists, l ascending, cmul0 / cmac1, one inverse transform and one wrap_trunc per chunk
+// and polynomial; chunks combine by wrapping integer addition; the bias is added to every word of c1).  c0 is the
+// inner product's P0: word j here is mask word (N - j) mod N there, negated for j > 0, bit for bit.
+// All three kernels are templates (CHUNK: the format's chunk; SINGLE: one chunk per output; THREADS, G: the block and the
+// table entries per workgroup).
+// =================================================================================================
+
+// Start of every output list when several chunks add into it: c0 = 0, c1 = bias[r] in every word.  One workgroup per
+// list s = b rows + r of the slice, lane-contiguous words.  grid: x = lists; block = THREADS.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_conv_init(const int32_t *__restrict__ bias, uint32_t rows, int32_t *__restrict__ out)
+{
+    const uint32_t s = blockIdx.x, r = s % rows;
+    const uint32_t bv = bias ? (uint32_t)bias[r] : 0u;
+    int32_t *o = out + (size_t)s * (2 * kN);
+    for (int i = threadIdx.x; i < kN; i += THREADS) {
+        o[i] = 0;
+        o[kN + i] = (int32_t)bv;
+    }
+}
+
+// One WAVE per (output list, chunk, polynomial): k_dot_mask's frame (4 waves per workgroup, kDotLds, one barrier, one
+// spectral accumulator in registers, the shared device functions only).  The polynomial is the fastest-varying part of the
+// item index: the two waves that read the same weight rows sit in one workgroup.  wspec [rows][L][512] complex, lspec
+// [batch][L][2][512] complex -- both polynomials of the one k_fft_fwd_polys launch are read.  Coefficient j of the chunk's
+// product goes to word j of its polynomial.  SINGLE (nchunks == 1): plain vector stores with the bias folded in, no init
+// launch, no atomics; otherwise vector integer atomics on the lists k_conv_init started.
+// grid: x = ceil(items / 4), items = lists x chunks x 2; block = 256.
+template <int CHUNK, bool SINGLE>
+__global__ __launch_bounds__(64 * kDotWavesPerWG, 2) void k_conv_lists(const d2 *__restrict__ wspec, const d2 *__restrict__ lspec,
+                                                                       const int32_t *__restrict__ bias, int32_t *__restrict__ out,
+                                                                       uint32_t rows, uint32_t L, uint32_t nchunks, uint32_t items,
+                                                                       const d2 *__restrict__ g_tw, const d2 *__restrict__ g_twist)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    d2 *s_tw = reinterpret_cast<d2 *>(smem);
+    d2 *s_twist = s_tw + kTwEntries;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    d2 *scr = s_twist + kNH + wv * kScr;
+    load_tables(s_tw, s_twist, g_tw, g_twist, tid, 64 * kDotWavesPerWG);
+    __syncthreads(); // the tables; the only barrier
+    const uint32_t item = blockIdx.x * kDotWavesPerWG + (uint32_t)wv;
+    if (item >= items) return;
+    const uint32_t poly = item & 1u, sc = item >> 1;
+    const uint32_t s = SINGLE ? sc : sc / nchunks, chunk = SINGLE ? 0u : sc - s * nchunks;
+    const uint32_t b = s / rows, r = s - b * rows;
+    const uint32_t l_first = chunk * CHUNK, l_end = min(l_first + (uint32_t)CHUNK, L);
+
+    const d2 *pw = wspec + ((size_t)r * L + l_first) * kNH + lane;
+    const d2 *pc = lspec + (((size_t)b * L + l_first) * 2 + poly) * kNH + lane;
+    d2 S[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) S[q] = cmul0(pw[q * 64], pc[q * 64]);
+#pragma unroll 1
+    for (uint32_t l = l_first + 1; l < l_end; l++) {
+        pw += kNH;
+        pc += 2 * kNH;
+#pragma unroll
+        for (int q = 0; q < 8; q++) S[q] = cmac1(pw[q * 64], pc[q * 64], S[q]);
+    }
+
+    int *po = out + ((size_t)s * 2 + poly) * kN;
+    uint32_t bv = 0u;
+    if constexpr (SINGLE) bv = (poly && bias) ? (uint32_t)bias[r] : 0u;
+    d2 ut[8];
+    fft_inv_wave(S, ut, s_tw, s_twist, scr, lane);
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const int j = lane + 64 * q;
+        const d2 y = cmulc(S[q], ut[q]); // 1/512 is in the list image
+        const uint32_t vx = wrap_trunc(y.x), vy = wrap_trunc(y.y);
+        if constexpr (SINGLE) {
+            po[j] = (int)(vx + bv);
+            po[j + kNH] = (int)(vy + bv);
+        } else {
+            atomicAdd(po + j, (int)vx);
+            atomicAdd(po + j + kNH, (int)vy);
+        }
+    }
+}
+
+// k_compact_expand with a public slot table: sample (b, s), s < n_slots, is slot slots[s] mod N of list slots[s] / N of
+// vector b's `lists_per_vec` lists, and becomes key-switch operand row b n_slots + s (ubar: a'_i + 2^(31 - t basebit)) and
+// output row b n_slots + s (0, ..., 0, b').  The table is validated when it is loaded (eoc_conv_slots_to_device); a list
+// index past the vector is held to its last list all the same, so no table can make the kernel read outside the vector.
+// Slots may be unordered and may repeat.  A workgroup serves G consecutive table entries of one vector and stages c0 of
+// the list at hand in LDS, again whenever the list changes (the table is uniform over the workgroup, so every thread
+// reaches the same barriers); the same lane-contiguous loads and stores as k_compact_expand.
+// grid: x = ceil(n_slots / G), y = vectors of the slice; block = 256.
+template <int G>
+__global__ __launch_bounds__(256) void k_conv_extract(const int32_t *__restrict__ lists, uint32_t lists_per_vec,
+                                                      const uint32_t *__restrict__ slots, uint32_t n_slots,
+                                                      uint32_t *__restrict__ ubar, int32_t *__restrict__ out, int n,
+                                                      uint32_t prec_offset)
+{
+    __shared__ int32_t s_c0[kN];
+    const int32_t *vec = lists + (size_t)blockIdx.y * lists_per_vec * (2 * kN);
+    uint32_t staged = 0xFFFFFFFFu;
+    const int32_t *list = vec;
+    for (int q = 0; q < G; q++) {
+        const uint32_t t = blockIdx.x * G + q;
+        if (t >= n_slots) break;
+        const uint32_t slot = slots[t];
+        const uint32_t li = min(slot / (uint32_t)kN, lists_per_vec - 1u);
+        const int j = (int)(slot % (uint32_t)kN);
+        if (li != staged) {
+            __syncthreads(); // every row of the list staged before is written
+            list = vec + (size_t)li * (2 * kN);
+            for (int k = threadIdx.x; k < kN; k += 256) s_c0[k] = list[k];
+            __syncthreads();
+            staged = li;
+        }
+        const size_t s = (size_t)blockIdx.y * n_slots + t;
+        uint32_t *row = ubar + s * kN;
+        for (int i = threadIdx.x; i < kN; i += 256) {
+            const uint32_t v = (uint32_t)s_c0[(j - i) & (kN - 1)];
+            row[i] = (i <= j ? v : 0u - v) + prec_offset;
+        }
+        int32_t *o = out + s * (n + 1);
+        for (int m = threadIdx.x; m < n; m += 256) o[m] = 0;
+        if (threadIdx.x == 0) o[n] = list[kN + j];
+    }
+}
+
 } // namespace eoc

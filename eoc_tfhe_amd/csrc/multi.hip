@@ -206,7 +206,7 @@ int slot_grow(Slot &s, int32_t **bufs, int nbuf, size_t *cap, size_t need)
 // The staging buffer's pieces, sized and carved by ONE statement each: take(p, ints) in buffer order, then commit() grows
 // s.d_lut to the sum and sets every p.  No second formula exists that could disagree with the carving.
 struct Staging {
-    enum { kMaxPieces = 4 };
+    enum { kMaxPieces = 5 };
     int32_t **piece[kMaxPieces];
     size_t off[kMaxPieces], ints = 0;
     int n = 0;
@@ -614,6 +614,27 @@ int slot_linear_block(Slot &s, const int8_t *h_w, size_t rows, size_t cols, cons
         if (!rc) rc = copy_in(d_lists, lists + lo * vec_ints, blk * vec_ints, st);
         if (!rc && bias) rc = copy_in(d_bias, bias, rows, st);
         if (!rc) rc = eoc_linear_device(s.e, d_img, rows, cols, d_lists, blk, bias ? d_bias : nullptr, d_out, st);
+        if (!rc) rc = copy_out(out + lo * out_ints, d_out, blk * out_ints, st);
+        return rc;
+    });
+}
+
+// one device's block of WHOLE input vectors [lo, hi) of a convolution with public kernels: image and slot table
+// are loaded here (every engine its own; both loads validate), lists [batch][L][2][N], bias [rows] (or NULL) and slots
+// [n_slots] in, out [batch][n_slots][stride] on the host
+int slot_conv_block(Slot &s, const int8_t *h_w, size_t rows, size_t cols, const int32_t *lists, const int32_t *bias,
+                    const uint32_t *slots, size_t n_slots, int32_t *out, size_t lo, size_t hi, size_t stride_ints)
+{
+    const size_t blk = hi - lo, vec_ints = (cols + EOC_N - 1) / EOC_N * 2 * EOC_N, out_ints = n_slots * stride_ints;
+    int32_t *d_img, *d_lists, *d_bias, *d_slots, *d_out; // the image first: its spectra are read 16 bytes at a time
+    return slot_block(s, blk, Staging().take(d_img, eoc_weights_image_bytes(rows, cols) / 4).take(d_lists, blk * vec_ints)
+                                  .take(d_bias, rows).take(d_slots, n_slots).take(d_out, blk * out_ints), [&](hipStream_t st) {
+        uint32_t *d_tab = reinterpret_cast<uint32_t *>(d_slots);
+        int rc = eoc_weights_to_device(s.e, h_w, rows, cols, d_img, st);
+        if (!rc) rc = eoc_conv_slots_to_device(s.e, slots, n_slots, rows, d_tab, st);
+        if (!rc) rc = copy_in(d_lists, lists + lo * vec_ints, blk * vec_ints, st);
+        if (!rc && bias) rc = copy_in(d_bias, bias, rows, st);
+        if (!rc) rc = eoc_conv_linear_device(s.e, d_img, rows, cols, d_lists, blk, bias ? d_bias : nullptr, d_tab, n_slots, d_out, st);
         if (!rc) rc = copy_out(out + lo * out_ints, d_out, blk * out_ints, st);
         return rc;
     });
@@ -1441,6 +1462,29 @@ extern "C" int eoc_linear(const int8_t *h_w, size_t rows, size_t cols, const int
     if (!batch) return EOC_OK;
     return run_blocks_locked("eoc_linear", batch, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
         return slot_linear_block(s, h_w, rows, cols, h_lists, h_bias, h_out, lo, hi, stride);
+    });
+}
+
+// convolutions with public kernels (a cloud key alone suffices): WHOLE input vectors are cut over the engines;
+// the model and the slot table are validated by every engine's loads before it touches its device
+extern "C" int eoc_conv_linear(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch, const int32_t *h_bias,
+                               const uint32_t *h_slots, size_t n_slots, int32_t *h_out)
+{
+    if (!h_w || !h_lists || !h_slots || !h_out) {
+        eoc_set_error("eoc_conv_linear: null argument");
+        return EOC_ERR_ARG;
+    }
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
+    if (int rc = enter_locked("eoc_conv_linear", ENGINES)) return rc;
+    if (eoc_weights_image_bytes(rows, cols) == 0 || n_slots > ((size_t)1 << 20)) {
+        eoc_set_error("eoc_conv_linear: rows = %zu, cols = %zu, n_slots = %zu: rows and cols must lie in [1, 2^20], n_slots in [0, 2^20]",
+                      rows, cols, n_slots);
+        return EOC_ERR_ARG;
+    }
+    if (!batch || !n_slots) return EOC_OK;
+    return run_blocks_locked("eoc_conv_linear", batch, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_conv_block(s, h_w, rows, cols, h_lists, h_bias, h_slots, n_slots, h_out, lo, hi, stride);
     });
 }
 

@@ -689,3 +689,18 @@ def linear_var_row(params, w_row, tlwe_key, pk):
             r[:N - 1] -= full[N:]
             out += scale * float((r * r).sum())
     return out
+
+
+# ---- convolutions with public int8 kernels on compact lists ------------------------------------------------------
+def conv_row(w_row, t):
+    """the effective inner-product row of slot t of one output channel of eoc_conv_device: slot t has phase
+    bias + sum_l sum_k w[l N + k] x_l[t + k] with the negacyclic wrap, i.e. the inner product of the inputs with
+      w_eff[l N + m] = w[l N + m - t] (m >= t),  -w[l N + m - t + N] (m < t),
+    per list (w_row is padded with zeros to whole lists).  linear_var, linear_var_row and linear_offset of this row price the
+    slot -- the weight polynomial of w_eff is X^t V up to the sign of the wrap, nothing is fitted.  float64 [L N]."""
+    t = int(t)
+    if not 0 <= t < N:
+        raise ValueError(f"conv_row: slot {t} outside [0, {N})")
+    w = np.asarray(w_row, np.float64).ravel()
+    w = np.concatenate((w, np.zeros(-w.size % N))).reshape(-1, N)
+    return (np.concatenate((-w[:, N - t:], w[:, :N - t]), axis=1) if t else w).reshape(-1)

@@ -1018,6 +1018,59 @@ int eoc_pk_encrypt_torus(const void *pk, size_t pk_len, uint64_t enc_seed, uint6
 int eoc_pk_encrypt_torus_keyed(const void *pk, size_t pk_len, const uint8_t enc_key[32], uint64_t first_list,
                                const int32_t *msgs, size_t count, int32_t *lists);
 
+/* ---- convolutions with public int8 kernels on compact lists ---------------------------------------------------
+ * The inner product above keeps ONE coefficient of the product of a list with the weight polynomial; all N coefficients are
+ * the N shifts of a filter over the list.  These calls keep them: a convolution layer of a discretised network, a FIR filter,
+ * a sliding-window score.  Weights, image (eoc_weights_to_device, unchanged), lists and format rule are the inner product's.
+ *   layout      rows = output channels; list l of a vector = input channel l (L = ceil(cols / N) channels); w[r][lN + k] = tap k
+ *               of filter (r, l).  An image is stored row-major in one list per channel (height x width <= N): tap (i, j) of a
+ *               2-D filter is tap i width + j.
+ *   output      for every (vector b, row r) the whole TLWE list [2][N] int32, c0 first:
+ *                   out[b][r] = ( sum_l V_{r,l} c0_{b,l} ,  bias[r] + sum_l V_{r,l} c1_{b,l} )
+ *               slot t has phase bias[r] + sum_l sum_k w[r][lN + k] x_l[t + k]: a cross-correlation (the "conv" of machine
+ *               learning).  Terms with t + k >= N enter as -w x_l[t + k - N]: the negacyclic wrap is part of the rule; a caller
+ *               that wants a linear convolution of `len` inputs with K taps reads slots t <= len - K only.
+ *   rule        both polynomials through the inner product's chunks: 8 lists, l ascending, weight spectrum in the digit's place,
+ *               list spectrum (scale 2^-9) in the key row's, one inverse transform and one conversion per chunk and polynomial
+ *               (8 * 1024 * 127 * 2^31 < 2^51 for both), chunks combine by wrapping integer addition, the bias is added to every
+ *               word of c1.  Word j of out[b][r].c0 is mask word (N - j) mod N of eoc_dot_device's sample (b, r), negated for
+ *               j > 0, bit for bit.  eoc_conv_device equals the CPU reference tests/c/conv_ref.c byte for byte, and the exact
+ *               product up to the conversion's few units per chunk.
+ *   slots       a slot table names the samples a caller wants: entry s is slot slots[s] mod N of list slots[s] / N of a vector's
+ *               `rows` output lists, any order, repeats allowed, n_slots in [1, 2^20].  The run calls take the table as a DEVICE
+ *               pointer and do not read it on the host.  eoc_conv_slots_to_device loads it, as eoc_weights_to_device loads a
+ *               model: every entry is checked on the host against lists_per_vec x N (EOC_ERR_ARG), the copy drains `hip_stream`,
+ *               EOC_ERR_STATE under capture.  A table that did not come through it is not checked by the run calls; the kernel
+ *               holds a list index past the vector to its last list, so no table makes it read outside the vector.
+ *   noise       slot t is the inner product with the row noise.conv_row(w_row, t): noise.linear_var, linear_var_row and
+ *               linear_offset price it, nothing fitted.
+ *   engine      eoc_conv_device needs NO key and returns compact lists: 8 KiB per 1 024 results.  eoc_conv_linear_device is the
+ *               same operation into a scratch buffer, then the table's samples extracted and key-switched: d_out DEVICE
+ *               [batch][n_slots][n+1] (EOC_ERR_NO_KEY without a cloud key).  eoc_conv_extract_device is the extraction and the
+ *               key switch alone, on `lists_per_vec` lists per vector the caller holds.  batch x rows = 0 (batch x n_slots = 0) is
+ *               a no-op; EOC_ERR_ARG for a null pointer, a shape outside [1, 2^20], an output that overlaps an input.
+ *               Workspace: the list spectra (16 KiB per list) and, for eoc_conv_linear_device, the output lists (8 KiB per row)
+ *               of a slice of whole vectors, together inside EOC_TFHE_DOT_WS_BYTES (default 256 MiB; slices of at most 2^20
+ *               samples and 65 535 vectors); grown as every workspace: EOC_ERR_STATE if one would grow under capture (run one
+ *               call of the shape first).  Arguments travel as kernel arguments: no descriptor ring slot; every run call can be
+ *               captured.  eoc_engine_conv_launches counts one per slice; the key switches are counted in the stats;
+ *               eoc_engine_kernel_times books the new kernels under the key switch.
+ *   host        eoc_conv_linear: host buffers (the slot table too) on the global context (a cloud key alone suffices),
+ *               synchronous; WHOLE input vectors are cut into eoc_shard_range blocks, one per engine; every engine builds the
+ *               image and loads the table itself. */
+int eoc_conv_slots_to_device(eoc_engine *e, const uint32_t *h_slots, size_t n_slots, size_t lists_per_vec, uint32_t *d_slots,
+                             void *hip_stream);
+int eoc_conv_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists, size_t batch,
+                    const int32_t *d_bias /* may be NULL */, int32_t *d_out_lists /* [batch][rows][2][N] */, void *hip_stream);
+int eoc_conv_linear_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_lists, size_t batch,
+                           const int32_t *d_bias /* may be NULL */, const uint32_t *d_slots, size_t n_slots,
+                           int32_t *d_out /* [batch][n_slots][n+1] */, void *hip_stream);
+int eoc_conv_extract_device(eoc_engine *e, const int32_t *d_lists, size_t lists_per_vec, size_t batch, const uint32_t *d_slots,
+                            size_t n_slots, int32_t *d_out /* [batch][n_slots][n+1] */, void *hip_stream);
+uint64_t eoc_engine_conv_launches(eoc_engine *e);
+int eoc_conv_linear(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_lists, size_t batch,
+                    const int32_t *h_bias /* may be NULL */, const uint32_t *h_slots, size_t n_slots, int32_t *h_out);
+
 #ifdef __cplusplus
 }
 #endif
