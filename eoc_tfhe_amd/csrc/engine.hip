@@ -90,6 +90,7 @@ struct eoc_engine {
     int br_parts = 0;                       // consecutive launches per blind rotation (EOC_TFHE_BR_PARTS); 0 = by key-row size
     int br_wide = -1;                       // one-wave-per-ciphertext kernel: -1 = by launch width, 0 = never, 1 = whenever l = 2 (EOC_TFHE_BR_WIDE)
     int int_slice_rows = 0;                 // EOC_TFHE_INT_SLICE_ROWS: at most this many rows per slice of an integer circuit (diagnostics; 0 = the 2^20-sample rule alone)
+    size_t slice_samples = (size_t)1 << 20; // the sample rule: extracted samples (blind-rotation jobs) per slice of any call; EOC_TFHE_SLICE_SAMPLES lowers it (diagnostics: values outside [1, 2^20] are ignored)
     int bara_stride = 0;
     bool ks_waves_ok = true;                // the > 64 KiB dynamic-LDS attribute of k_keyswitch_waves was granted
     bool br_tables_lds = false;             // EOC_TFHE_BR_TABLES_LDS: gadget length 2 on the pair kernels' earlier form (tables read from LDS in the step loop)
@@ -793,6 +794,10 @@ extern "C" int eoc_engine_create(int device, const eoc_params *p, eoc_engine **o
         if (const char *s = getenv("EOC_TFHE_KS_MFMA")) e->ks_mfma = atoi(s) != 0;
         if (const char *s = getenv("EOC_TFHE_BR_TABLES_LDS")) e->br_tables_lds = atoi(s) != 0;
         if (const char *s = getenv("EOC_TFHE_INT_SLICE_ROWS")) e->int_slice_rows = atoi(s);
+        if (const char *s = getenv("EOC_TFHE_SLICE_SAMPLES")) {
+            const unsigned long long v = strtoull(s, nullptr, 10);
+            if (v >= 1 && v <= e->slice_samples) e->slice_samples = (size_t)v; // never above the shipped 2^20
+        }
         if (const char *s = getenv("EOC_TFHE_TABLE_WS_BYTES")) e->table_ws_bytes = (size_t)strtoull(s, nullptr, 10);
         if (const char *s = getenv("EOC_TFHE_PACK_WS_BYTES")) e->pack_ws_bytes = (size_t)strtoull(s, nullptr, 10);
         if (const char *s = getenv("EOC_TFHE_DOT_WS_BYTES")) e->dot_ws_bytes = (size_t)strtoull(s, nullptr, 10);
@@ -1141,9 +1146,10 @@ constexpr size_t kMaxGatesPerLaunch = 32768;
 // One "level": a set of gates that all run over the same S instances.  descs are host-side and
 // carry device pointers; free gates and bootstrapped gates are separated here.
 static int run_level(eoc_engine *e, WS &W, std::vector<GateDesc> &boot, std::vector<GateDesc> &freeg, size_t S,
-                     hipStream_t st)
+                     hipStream_t st, size_t job_cap = SIZE_MAX)
 {
     const int n = e->p.n;
+    job_cap = std::min(job_cap, W.ws_jobs); // jobs per slice: the caller's cap (a circuit's sample rule) inside the workspace
     for (size_t g0 = 0; g0 < freeg.size(); g0 += kMaxGatesPerLaunch) {
         const size_t cnt = std::min(kMaxGatesPerLaunch, freeg.size() - g0);
         GateDesc *dd = nullptr;
@@ -1162,7 +1168,7 @@ static int run_level(eoc_engine *e, WS &W, std::vector<GateDesc> &boot, std::vec
         size_t g1 = g0;
         while (g1 < boot.size() && g1 - g0 < kMaxGatesPerLaunch) {
             const uint32_t w = (uint32_t)S * (boot[g1].op == OP_MUX ? 2u : 1u);
-            if (g1 > g0 && (size_t)jobs + w > W.ws_jobs) break;
+            if (g1 > g0 && (size_t)jobs + w > job_cap) break;
             boot[g1].job_base = jobs;
             jobs += w;
             any_mux |= boot[g1].op == OP_MUX;
@@ -1482,11 +1488,11 @@ extern "C" int eoc_circuit_run_device(eoc_engine *e, const eoc_gate *gates, size
     }
     // a level wider than the job cap is evaluated in slices (run_level), so the workspace is bounded: 2^20 blind
     // rotations in flight need 9.6 GB of extracted samples and rotation amounts; wider levels gain nothing
-    const size_t job_cap = std::max<size_t>(max_gate_jobs, (size_t)1 << 20);
+    const size_t job_cap = std::max<size_t>(max_gate_jobs, e->slice_samples);
     int rc = ensure_ws(e, W, std::min(max_jobs, job_cap), n_gates + 64, 0, st);
     if (rc) return rc;
     for (int lv = 1; lv <= nlev; lv++) {
-        rc = run_level(e, W, boot[lv], freeg[lv], instances, st);
+        rc = run_level(e, W, boot[lv], freeg[lv], instances, st, job_cap);
         if (rc) return rc;
     }
     return EOC_OK;
@@ -1564,7 +1570,7 @@ static int lut_levels_locked(eoc_engine *e, const char *who, int n_tables, int e
     WS &W = e->ws;
     const bool many = n_tables > 0;
     const size_t stride = (size_t)e->p.n + 1, slots = n_luts * (many ? (size_t)n_tables : 1);
-    const size_t rows = std::min(count, std::max<size_t>(1, ((size_t)1 << 20) / slots));
+    const size_t rows = std::min(count, std::max<size_t>(1, e->slice_samples / slots));
     const size_t G = (enc == 2 && rows < count) ? 1 : n_luts; // tables per level
     std::vector<GateDesc> descs(many ? n_luts + slots : G);
     int rc = ensure_ws(e, W, slots * rows, descs.size(), 0, st);
@@ -1718,7 +1724,7 @@ extern "C" int eoc_lut2_batch_device(eoc_engine *e, int p, int n_tables, const i
     // rule) and at most kLut2WsBytes of both
     constexpr size_t kLut2WsBytes = (size_t)256 << 20;
     const size_t row_vals = n_funcs * (size_t)p * stride * sizeof(int32_t), row_lists = n_funcs * 2 * kN * sizeof(int32_t);
-    const size_t rows = std::min({count, std::max<size_t>(1, ((size_t)1 << 20) / (n_funcs * (size_t)p)),
+    const size_t rows = std::min({count, std::max<size_t>(1, e->slice_samples / (n_funcs * (size_t)p)),
                                   std::max<size_t>(1, kLut2WsBytes / (row_vals + row_lists))});
     // one buffer: the lists [n_funcs][rows][2][N] of a slice, then its level-1 outputs [n_funcs][p][rows][n+1]
     int rc = scratch_reserve(e, e->lut2, rows * (row_vals + row_lists), "two-input lookup workspace", st);
@@ -1798,7 +1804,7 @@ try {
             max_slots = std::max(max_slots, std::min(G.nodes.size() << theta, kMaxGatesPerLaunch));
         }
     // rows per slice: a group holds at most 2^20 extracted samples (the rule of lut_levels)
-    size_t rows = std::min(instances, std::max<size_t>(1, ((size_t)1 << 20) / std::max<size_t>(1, max_slots)));
+    size_t rows = std::min(instances, std::max<size_t>(1, e->slice_samples / std::max<size_t>(1, max_slots)));
     if (e->int_slice_rows > 0) rows = std::min(rows, (size_t)e->int_slice_rows);
     const size_t idx_slots = (tv_idx.size() * 4 + sizeof(GateDesc) - 1) / sizeof(GateDesc);
     const size_t stage_rows = (tv_idx.size() * (size_t)kN + 4 * stride - 1) / (4 * stride);
@@ -1912,13 +1918,13 @@ int eoc_compact_expand_device_from(eoc_engine *e, const int32_t *d_lists, size_t
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
     WS &W = e->ws;
-    constexpr size_t kSlice = (size_t)1 << 20;
-    int rc = ensure_ws(e, W, std::min(count, kSlice), 0, 0, st);
+    const size_t slice = e->slice_samples;
+    int rc = ensure_ws(e, W, std::min(count, slice), 0, 0, st);
     if (rc) return rc;
     const size_t stride = (size_t)e->p.n + 1;
     const uint32_t prec_offset = 1u << (32 - (1 + e->p.ks_basebit * e->p.ks_t));
-    for (size_t r0 = 0; r0 < count; r0 += kSlice) {
-        const size_t S = std::min(kSlice, count - r0);
+    for (size_t r0 = 0; r0 < count; r0 += slice) {
+        const size_t S = std::min(slice, count - r0);
         const uint64_t first = (uint64_t)(first_slot + r0);
         const unsigned nwg = (unsigned)((first % kCompactSlotsPerWG + S + kCompactSlotsPerWG - 1) / kCompactSlotsPerWG);
         {
@@ -2261,7 +2267,7 @@ extern "C" int eoc_table_read_device(eoc_engine *e, const int32_t *d_table, int 
     TableWalk tw;
     int rc = table_walk_plan(e, "eoc_table_read_device", d_table && d_out, log2_lists, log2_width, d_sel_fft, queries, &tw);
     if (rc) return rc;
-    tw.qs = std::min(tw.qs, std::max<size_t>(1, ((size_t)1 << 20) / tw.W)); // 2^20 extracted samples a slice (lut_levels' rule)
+    tw.qs = std::min(tw.qs, std::max<size_t>(1, e->slice_samples / tw.W)); // 2^20 extracted samples a slice (lut_levels' rule)
     std::lock_guard<std::mutex> g(e->mu);
     if (!e->ksk) {
         eoc_set_error("eoc_table_read_device: no key-switch key loaded");
@@ -2513,7 +2519,7 @@ try {
         return EOC_ERR_ARG;
     }
     // queries per slice: grid y of the step and of the extraction, the byte budget, 2^20 extracted samples (the read's rule)
-    size_t qs = std::min({queries, (size_t)32768, (size_t)65535 / n_starts, std::max<size_t>(1, ((size_t)1 << 20) / (n_starts * W))});
+    size_t qs = std::min({queries, (size_t)32768, (size_t)65535 / n_starts, std::max<size_t>(1, e->slice_samples / (n_starts * W))});
     if (steps) qs = std::min(qs, e->table_ws_bytes / per_query);
     std::lock_guard<std::mutex> g(e->mu);
     if (!e->ksk) {
@@ -2526,7 +2532,7 @@ try {
     WS &Wk = e->ws;
     const size_t stride = (size_t)e->p.n + 1;
     if (!steps) {
-        const size_t cs = std::max<size_t>(1, ((size_t)1 << 20) / W); // start states per key switch
+        const size_t cs = std::max<size_t>(1, e->slice_samples / W); // start states per key switch
         if ((rc = ensure_ws(e, Wk, std::min(cs, n_starts) * W, 0, 0, st))) return rc;
         for (size_t i0 = 0; i0 < n_starts; i0 += cs) {
             rc = extract_and_keyswitch(e, Wk, d_final, smp, starts + i0, W, std::min(cs, n_starts - i0), d_out + i0 * W * stride, st);
@@ -2726,7 +2732,7 @@ static int dot_locked(eoc_engine *e, const char *who, const void *d_image, size_
     }
     HIP_TRY(hipSetDevice(e->device));
     WS &W = e->ws;
-    const size_t bs = std::min({batch, e->dot_ws_bytes / per_vec, std::max<size_t>(1, ((size_t)1 << 20) / rows)});
+    const size_t bs = std::min({batch, e->dot_ws_bytes / per_vec, std::max<size_t>(1, e->slice_samples / rows)});
     int rc = scratch_reserve(e, e->dot_specs, bs * per_vec, "list spectra", st);
     if (!rc && d_out) rc = ensure_ws(e, W, bs * rows, 0, 0, st);
     if (rc) return rc;
@@ -2943,8 +2949,8 @@ static int conv_locked(eoc_engine *e, const char *who, const void *d_image, size
         return EOC_ERR_ARG;
     }
     HIP_TRY(hipSetDevice(e->device));
-    size_t bs = std::min({batch, e->dot_ws_bytes / per_vec, std::max<size_t>(1, ((size_t)1 << 20) / rows), kConvMaxVecs});
-    if (d_slots) bs = std::min(bs, std::max<size_t>(1, ((size_t)1 << 20) / n_slots));
+    size_t bs = std::min({batch, e->dot_ws_bytes / per_vec, std::max<size_t>(1, e->slice_samples / rows), kConvMaxVecs});
+    if (d_slots) bs = std::min(bs, std::max<size_t>(1, e->slice_samples / n_slots));
     int rc = scratch_reserve(e, e->dot_specs, bs * spec_vec, "list spectra", st);
     if (!rc && d_slots) rc = scratch_reserve(e, e->conv_lists, bs * lists_vec, "convolution lists", st);
     if (!rc && d_slots) rc = ensure_ws(e, e->ws, bs * n_slots, 0, 0, st);
@@ -3034,7 +3040,7 @@ extern "C" int eoc_conv_extract_device(eoc_engine *e, const int32_t *d_lists, si
     }
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    const size_t bs = std::min({batch, std::max<size_t>(1, ((size_t)1 << 20) / n_slots), kConvMaxVecs});
+    const size_t bs = std::min({batch, std::max<size_t>(1, e->slice_samples / n_slots), kConvMaxVecs});
     int rc = ensure_ws(e, e->ws, bs * n_slots, 0, 0, st);
     for (size_t b0 = 0; !rc && b0 < batch; b0 += bs)
         rc = launch_conv_extract(e, d_lists + b0 * lists_per_vec * 2 * kN, lists_per_vec, std::min(bs, batch - b0), d_slots, n_slots,

@@ -165,6 +165,16 @@ int32_t eoc_modswitch_from_torus32(int32_t phase, int32_t Msize);
 typedef struct eoc_engine eoc_engine;
 
 int eoc_device_count(void);
+/* Environment read here, once per engine (INTEGRATION.md section 6 lists every knob; none changes a result).  The slicing ones:
+ *   EOC_TFHE_SLICE_SAMPLES = k   the sample rule: at most k extracted samples (blind-rotation jobs) per slice of any device call
+ *                                -- table lookups, two-input lookups, a circuit level's job cap, integer circuits, compact
+ *                                expansion, table reads, automaton runs, inner products and convolutions.  Default and upper
+ *                                limit 2^20 (9.6 GB of workspace); a value outside [1, 2^20] is ignored, so the shipped slices
+ *                                cannot be widened.  Diagnostics: tests/test_gpu_slice_seams.py runs every call's second slice
+ *                                with it.  The grid limits (32 768 gates, nodes or queries, 65 535 vectors or lists per launch)
+ *                                are constants.
+ *   EOC_TFHE_INT_SLICE_ROWS, EOC_TFHE_TABLE_WS_BYTES, EOC_TFHE_PACK_WS_BYTES, EOC_TFHE_DOT_WS_BYTES: rows and bytes per slice of
+ *                                one family each, described at their calls below. */
 int eoc_engine_create(int device, const eoc_params *p, eoc_engine **out);
 void eoc_engine_destroy(eoc_engine *e);
 const char *eoc_last_error(void);

@@ -30,7 +30,7 @@ SEED = bytes(range(7, 39))
 # every knob eoc_engine_create reads: none of them may leak from one case's engine into another's
 KNOBS = ("EOC_TFHE_PRIO_DUTY", "EOC_TFHE_PRIO_MULTI", "EOC_TFHE_BR_SLICE", "EOC_TFHE_NO_FOLD", "EOC_TFHE_NO_POOL",
          "EOC_TFHE_SCALAR_ABAR", "EOC_TFHE_BR_PARTS", "EOC_TFHE_BR_WIDE", "EOC_TFHE_KS_MFMA", "EOC_TFHE_BR_TABLES_LDS",
-         "EOC_TFHE_INT_SLICE_ROWS", "EOC_TFHE_TABLE_WS_BYTES", "EOC_TFHE_PACK_WS_BYTES")
+         "EOC_TFHE_INT_SLICE_ROWS", "EOC_TFHE_TABLE_WS_BYTES", "EOC_TFHE_PACK_WS_BYTES", "EOC_TFHE_SLICE_SAMPLES")
 # The sensitivity run (module docstring of test_gpu_capture.py): disturb() makes this many calls of the captured shape on the
 # two live disturbance buffer sets and nothing else, so that every slot of the descriptor ring ends up holding a descriptor
 # of the captured type that points to live buffers.  0: the ordinary disturbance.

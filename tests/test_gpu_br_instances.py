@@ -34,7 +34,8 @@ from gpu_util import dev_empty, sync, to_dev, torch_cuda
 
 pytestmark = pytest.mark.gpu
 N = 1024
-ENV_KNOBS = ("EOC_TFHE_BR_WIDE", "EOC_TFHE_BR_TABLES_LDS", "EOC_TFHE_SCALAR_ABAR", "EOC_TFHE_BR_SLICE", "EOC_TFHE_BR_PARTS")
+ENV_KNOBS = ("EOC_TFHE_BR_WIDE", "EOC_TFHE_BR_TABLES_LDS", "EOC_TFHE_SCALAR_ABAR", "EOC_TFHE_BR_SLICE", "EOC_TFHE_BR_PARTS",
+             "EOC_TFHE_SLICE_SAMPLES")
 
 # shape -> (template arguments in the kernel's name, (l, Bgbit), environment at engine creation)
 SHAPES = {

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 N = 1024
 EOC_OK, EOC_ERR_ARG, EOC_ERR_NO_KEY = 0, -1, -4
 ENV_KNOBS = ("EOC_TFHE_BR_WIDE", "EOC_TFHE_BR_TABLES_LDS", "EOC_TFHE_SCALAR_ABAR", "EOC_TFHE_BR_SLICE", "EOC_TFHE_BR_PARTS",
-             "EOC_TFHE_PACK_WS_BYTES")
+             "EOC_TFHE_PACK_WS_BYTES", "EOC_TFHE_SLICE_SAMPLES")
 
 
 @pytest.fixture(scope="module")
