@@ -275,6 +275,10 @@ def lib():
         "eoc_automaton_run_device": (C.c_int, [vp, vp, sz, vp, vp, sz, vp, sz, C.c_int, vp, sz, vp]),
         "eoc_engine_automaton_launches": (u64, [vp]),
         "eoc_automaton_run": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, C.c_int, vp, sz]),
+        # rounding mode of the leveled calls
+        "eoc_engine_set_leveled_rounding": (C.c_int, [vp, C.c_int]),
+        "eoc_engine_leveled_rounding": (C.c_int, [vp]),
+        "eoc_global_set_leveled_rounding": (C.c_int, [C.c_int]),
         # packing key switch: LWE samples -> compact lists
         "eoc_packing_key_blob_bytes": (sz, [PP]),
         "eoc_packing_key_export": (C.c_int, [vp, vp, sz]),
@@ -1034,6 +1038,19 @@ class Engine:
         (eoc_tgsw_to_fft_device; tgsw_fft_bytes each).  Needs no key."""
         _check(self.L.eoc_tgsw_to_fft_device(self.h, d_tgsw, count, d_fft, stream), "eoc_tgsw_to_fft_device")
 
+    @property
+    def leveled_rounding(self):
+        """the rounding mode of the leveled calls (eoc_engine_set_leveled_rounding): False, the default, is the
+        oracle's truncating gadget; True makes cmux_device, table_read_device, demux_device, table_update_device,
+        automaton_step_device and automaton_run_device round, which removes the mean that bounds long leveled chains
+        (noise.automaton_budget(rounding=True)).  Nothing else is governed by it.  Setting it while a graph capture holds
+        leveled calls of this engine raises EocError."""
+        return bool(self.L.eoc_engine_leveled_rounding(self.h))
+
+    @leveled_rounding.setter
+    def leveled_rounding(self, on):
+        _check(self.L.eoc_engine_set_leveled_rounding(self.h, 1 if on else 0), "eoc_engine_set_leveled_rounding")
+
     def cmux_device(self, d_sel_fft, d_in0, d_in1, d_out, count, stream=None):
         """out[i] = in0[i] + C[i] (x) (in1[i] - in0[i]) on TLWE samples [count][2][N], one converted selector per item
         (eoc_cmux_device): in1 where the bit is 1, in0 otherwise.  Needs no key."""
@@ -1510,6 +1527,12 @@ def compact_expand(lists, count=None):
     out = np.empty((count, _global_n("compact_expand") + 1), np.int32)
     _check(lib().eoc_compact_expand(lists.ctypes.data, count, out.ctypes.data), "eoc_compact_expand")
     return out
+
+
+def set_leveled_rounding(on):
+    """eoc_global_set_leveled_rounding: the rounding mode of the leveled calls (Engine.leveled_rounding) on every engine of the
+    global context and on those it creates later; table_read, table_update and automaton_run follow it"""
+    _check(lib().eoc_global_set_leveled_rounding(1 if on else 0), "eoc_global_set_leveled_rounding")
 
 
 def table_read(table, log2_lists, log2_width, selectors):

@@ -62,7 +62,7 @@ def build_stamps(verbose=False):
 def build(force=False, verbose=False, extra_hip_flags=()):
     os.makedirs(OBJ, exist_ok=True)
     hdrs = [os.path.join(CSRC, f) for f in ("kernels.hip.h", "blind_rotate_pair.inc", "blind_rotate_wide.inc",
-                                             "ext_product_pair.inc", "leveled_pair.inc", "canon_twiddles.h", "common.h")]
+                                             "ext_product_pair.inc", "leveled_pair.inc", "leveled_kernels.inc", "canon_twiddles.h", "common.h")]
     hdrs.append(os.path.join(ROOT, "include", "eoc_tfhe_gpu.h"))
     eng_src, eng_obj = os.path.join(CSRC, "engine.hip"), os.path.join(OBJ, "engine.o")
     mul_src, mul_obj = os.path.join(CSRC, "multi.hip"), os.path.join(OBJ, "multi.o")

@@ -107,6 +107,10 @@ struct eoc_engine {
     uint64_t cmux_launches = 0; // k_cmux launches
     uint64_t demux_launches = 0; // k_demux launches
     uint64_t automaton_launches = 0; // k_automaton_step launches
+    // the rounding mode of the leveled calls: the twins k_rcmux / k_rdemux / k_rstep run instead and bump the
+    // three counters above; the stream on which a leveled launch was last captured (the mode is frozen while it captures)
+    bool leveled_rounding = false;
+    hipStream_t leveled_capture_st = nullptr;
     // packing key switch: the packing key's image [n][4][2][512] complex scaled by 2^-9 (the engine's own),
     // the gathered mask columns [lists of a slice][n][N], and the byte budget that buffer is held to (lists are sliced to
     // fit; EOC_TFHE_PACK_WS_BYTES, diagnostics)
@@ -707,6 +711,15 @@ static const LeveledFamily<CmuxArgs> kCmuxFamily = {"k_cmux", &eoc_engine::cmux_
 static const LeveledFamily<DemuxArgs> kDemuxFamily = {"k_demux", &eoc_engine::demux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE, k_demux)}};
 static const LeveledFamily<AutoStepArgs> kAutomatonFamily = {"k_automaton_step", &eoc_engine::automaton_launches,
                                                              {EOC_PAIR_SHAPES(EOC_INSTANCE, k_automaton_step)}};
+// The rounding twins, behind the last family above: an engine in rounding mode (eoc_engine_set_leveled_rounding)
+// launches these instead, through the same launcher and into the same counters.
+static const LeveledFamily<CmuxArgs> kRCmuxFamily = {"k_rcmux", &eoc_engine::cmux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE, k_rcmux)}};
+static const LeveledFamily<DemuxArgs> kRDemuxFamily = {"k_rdemux", &eoc_engine::demux_launches, {EOC_PAIR_SHAPES(EOC_INSTANCE, k_rdemux)}};
+static const LeveledFamily<AutoStepArgs> kRStepFamily = {"k_rstep", &eoc_engine::automaton_launches,
+                                                         {EOC_PAIR_SHAPES(EOC_INSTANCE, k_rstep)}};
+static const LeveledFamily<CmuxArgs> &rounding_twin(const LeveledFamily<CmuxArgs> &) { return kRCmuxFamily; }
+static const LeveledFamily<DemuxArgs> &rounding_twin(const LeveledFamily<DemuxArgs> &) { return kRDemuxFamily; }
+static const LeveledFamily<AutoStepArgs> &rounding_twin(const LeveledFamily<AutoStepArgs> &) { return kRStepFamily; }
 #undef EOC_INSTANCE
 // the instance of a leveled family for gadget (l, bg); nullptr: none
 static const void *leveled_kernel(const void *const (&instances)[6], int l, int bg)
@@ -746,6 +759,9 @@ static void set_kernel_attrs(eoc_engine *e)
     set(kCmuxFamily);
     set(kDemuxFamily);
     set(kAutomatonFamily);
+    set(kRCmuxFamily);
+    set(kRDemuxFamily);
+    set(kRStepFamily);
     // k_pack_rows and k_dot_mask: tables + four transpose scratches as well
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kPackLds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dot_mask<kDotChunk>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2120,8 +2136,12 @@ extern "C" int eoc_tgsw_to_fft_device(eoc_engine *e, const int32_t *d_tgsw, size
 
 // one launch of a family over nx x ny items: a.Bgbit is set here
 template <class Args>
-static int launch_leveled(eoc_engine *e, const LeveledFamily<Args> &family, const Args &a, uint32_t ny, hipStream_t st)
+static int launch_leveled(eoc_engine *e, const LeveledFamily<Args> &truncating, const Args &a, uint32_t ny, hipStream_t st)
 {
+    // the engine's mode picks the family (under e->mu, as every caller holds it): a captured launch keeps the kernel it was
+    // captured with, and the stream of a capture is remembered so that the mode cannot change under an open capture
+    const LeveledFamily<Args> &family = e->leveled_rounding ? rounding_twin(truncating) : truncating;
+    if (stream_is_capturing(st)) e->leveled_capture_st = st;
     const void *fn = leveled_kernel(family.fn, e->p.l, e->p.Bgbit);
     if (!fn) {
         eoc_set_error("%s: no kernel for gadget length %d", family.name, e->p.l);
@@ -2137,6 +2157,33 @@ static int launch_leveled(eoc_engine *e, const LeveledFamily<Args> &family, cons
     (e->*family.launches)++;
     return EOC_OK;
 }
+
+// The rounding mode of the leveled calls: which family launch_leveled takes, and nothing else.
+extern "C" int eoc_engine_set_leveled_rounding(eoc_engine *e, int on)
+{
+    if (!e) {
+        eoc_set_error("eoc_engine_set_leveled_rounding: null engine");
+        return EOC_ERR_ARG;
+    }
+    if (on != 0 && on != 1) {
+        eoc_set_error("eoc_engine_set_leveled_rounding: on = %d is neither 0 nor 1", on);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->leveled_capture_st) {
+        HIP_TRY(hipSetDevice(e->device));
+        if (stream_is_capturing(e->leveled_capture_st)) {
+            eoc_set_error("eoc_engine_set_leveled_rounding: a graph capture that holds leveled calls of this engine is open; the mode "
+                          "(now %d) is set before the capture begins or after it ends", (int)e->leveled_rounding);
+            return EOC_ERR_STATE;
+        }
+        (void)hipGetLastError(); // a stream destroyed since is no capture
+        e->leveled_capture_st = nullptr;
+    }
+    e->leveled_rounding = on != 0;
+    return EOC_OK;
+}
+extern "C" int eoc_engine_leveled_rounding(const eoc_engine *e) { return e && e->leveled_rounding; }
 
 extern "C" int eoc_cmux_device(eoc_engine *e, const void *d_sel_fft, const int32_t *d_in0, const int32_t *d_in1, int32_t *d_out,
                                size_t count, void *hip_stream)

@@ -917,6 +917,8 @@ constexpr int kBRLds = (kTwEntries + kNH + 2 * kScr) * 16 + kAbarLds; // 37 632 
 //     that two parts would do instead of three, changed all eighteen in 42 to 365 lines.  Of the small pieces, the row
 //     loader (load_selector_row) and the store phases' cmulc + wrap_trunc pair (leveled_words) change nothing as
 //     force-inlined functions; the negacyclic gather does (EOC_NEGACYCLIC, a macro);
+//   * the three leveled kernels' whole texts as included text (leveled_kernels.inc, included twice each: the truncating
+//     kernel and its rounding twin): all eighteen shipped instances and the 120 other kernels identical;
 //   * kernels are compared modulo the function's number in the code object (tools/isa_diff.py drops it from the block
 //     labels): a new kernel may be plain and may stand where it belongs, here and in engine.hip.
 // The body's constant TV selects the accumulator: false = the gate test vector (mu, ..., mu),
@@ -1665,39 +1667,14 @@ __device__ __forceinline__ uint2 leveled_words(const d2 &s, const d2 &u)
 // byte-identical and changes every k_automaton_step in 45 to 680 lines (tools/isa_diff.py).
 #define EOC_NEGACYCLIC(idx, v) (((idx) & kN) ? 0u - (v) : (v))
 
-template <int L, int BGBIT = 0>
-__global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_cmux(CmuxArgs A, const d2 *__restrict__ g_tw,
-                                                                    const d2 *__restrict__ g_twist)
-{
-#define EOC_LEVELED_PART 1
-#include "leveled_pair.inc"
-    const int32_t *pa = A.in0 + ix * A.in0_x + iy * A.in0_y + (size_t)h * kN;
-    const int32_t *pb = A.in1 + ix * A.in1_x + iy * A.in1_y + (size_t)h * kN;
-    const d2 *sel = A.sel + ix * A.sel_x + iy * A.sel_y;
-#define EOC_LEVELED_PART 2
-#include "leveled_pair.inc"
-    // offset + (X^rot B_h - A_h).  The rotation is index arithmetic on B's loads (X^N = -1: the upper half of the 2N-period
-    // is negated)
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
-        const int idx = (j - A.rot) & (2 * kN - 1);
-        const uint32_t b = (uint32_t)pb[idx & (kN - 1)];
-        const uint32_t v = offset + EOC_NEGACYCLIC(idx, b) - (uint32_t)pa[j];
-        if (r < 8) dlo[r] = v;
-        else dhi[r - 8] = v;
-    }
-#define EOC_LEVELED_PART 3
-#include "leveled_pair.inc"
-    int32_t *po = A.out + ix * A.out_x + iy * A.out_y + (size_t)h * kN;
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int j = lane + 64 * r;
-        const uint2 e = leveled_words(S[r], ut[r]);
-        po[j] = (int32_t)((uint32_t)pa[j] + e.x);
-        po[j + kNH] = (int32_t)((uint32_t)pa[j + kNH] + e.y);
-    }
-}
+// The kernel's text is in leveled_kernels.inc, included twice: k_cmux<L, BGBIT> with the oracle's truncating gadget, and
+// k_rcmux<L, BGBIT>, its rounding twin: the same lines with 2^(31 - L Bgbit) more in the gadget's offset.
+#define EOC_LEVELED_KERNEL 1
+#define EOC_LEVELED_ROUND 0
+#include "leveled_kernels.inc"
+#define EOC_LEVELED_KERNEL 1
+#define EOC_LEVELED_ROUND 1
+#include "leveled_kernels.inc"
 
 // k_compact_expand's sibling behind a table read: sample (q, w), w < W, is slot w of query q's TLWE sample
 // `lists + q * list_stride` and becomes key-switch operand row q W + w (ubar) and output row q W + w (0, ..., 0, b').  The
@@ -1912,48 +1889,13 @@ struct DemuxArgs {
     int Bgbit;
 };
 
-template <int L, int BGBIT = 0>
-__global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_demux(DemuxArgs A, const d2 *__restrict__ g_tw,
-                                                                     const d2 *__restrict__ g_twist)
-{
-#define EOC_LEVELED_PART 1
-#include "leveled_pair.inc"
-    const int32_t *px = A.in + ix * A.in_x + iy * A.in_y + (size_t)h * kN;
-    const d2 *sel = A.sel + ix * A.sel_x + iy * A.sel_y;
-#define EOC_LEVELED_PART 2
-#include "leveled_pair.inc"
-    // offset + x_h
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        dlo[r] = offset + (uint32_t)px[lane + 64 * r];
-        dhi[r] = offset + (uint32_t)px[lane + 64 * r + kNH];
-    }
-#define EOC_LEVELED_PART 3
-#include "leveled_pair.inc"
-    const size_t oo = ix * A.out_x + iy * A.out_y + (size_t)h * kN;
-    int32_t *p0 = A.out0 + oo, *p1 = A.out1 + oo;
-    if (A.accumulate) {
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const int j = lane + 64 * r;
-            const uint2 e = leveled_words(S[r], ut[r]);
-            atomicAdd(p1 + j, (int)e.x);
-            atomicAdd(p1 + j + kNH, (int)e.y);
-            atomicAdd(p0 + j, (int)((uint32_t)px[j] - e.x));
-            atomicAdd(p0 + j + kNH, (int)((uint32_t)px[j + kNH] - e.y));
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const int j = lane + 64 * r;
-            const uint2 e = leveled_words(S[r], ut[r]);
-            p1[j] = (int32_t)e.x;
-            p1[j + kNH] = (int32_t)e.y;
-            p0[j] = (int32_t)((uint32_t)px[j] - e.x);
-            p0[j + kNH] = (int32_t)((uint32_t)px[j + kNH] - e.y);
-        }
-    }
-}
+// k_demux<L, BGBIT> and its rounding twin k_rdemux<L, BGBIT>: one text, leveled_kernels.inc
+#define EOC_LEVELED_KERNEL 2
+#define EOC_LEVELED_ROUND 0
+#include "leveled_kernels.inc"
+#define EOC_LEVELED_KERNEL 2
+#define EOC_LEVELED_ROUND 1
+#include "leveled_kernels.inc"
 
 // table[0] += sample_q for q = 0 .. queries - 1: the update of a one-list table, where no demultiplexer runs (DESIGN.md
 // 15).  V = 4: one 16-byte load per lane (both pointers 16-byte aligned); V = 1: word loads.  Integer atomics either way:
@@ -2159,47 +2101,13 @@ struct AutoStepArgs {
     int Bgbit;
 };
 
-template <int L, int BGBIT = 0>
-__global__ __launch_bounds__(128 * kCmuxItemsPerWG, 2) void k_automaton_step(AutoStepArgs A, const d2 *__restrict__ g_tw,
-                                                                              const d2 *__restrict__ g_twist)
-{
-#define EOC_LEVELED_PART 1
-#include "leveled_pair.inc"
-    const AutoTrans tr = A.trans[ix]; // uniform: one record per wave pair
-    const int32_t *pv = A.prev + iy * A.prev_y + (size_t)h * kN;
-    const int32_t *pa = pv + (size_t)tr.next0 * (2 * kN);
-    const int32_t *pb = pv + (size_t)tr.next1 * (2 * kN);
-    const int w0 = tr.w0 & (2 * kN - 1), w1 = tr.w1 & (2 * kN - 1);
-    const d2 *sel = A.sel + iy * A.sel_y;
-#define EOC_LEVELED_PART 2
-#include "leveled_pair.inc"
-    // offset + (X^(-w1) B_h - X^(-w0) A_h)
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int j = lane + 64 * (r & 7) + (r >> 3) * kNH;
-        const int ia = (j + w0) & (2 * kN - 1), ib = (j + w1) & (2 * kN - 1);
-        const uint32_t a = (uint32_t)pa[ia & (kN - 1)], b = (uint32_t)pb[ib & (kN - 1)];
-        const uint32_t v = offset + EOC_NEGACYCLIC(ib, b) - EOC_NEGACYCLIC(ia, a);
-        if (r < 8) dlo[r] = v;
-        else dhi[r - 8] = v;
-    }
-#define EOC_LEVELED_PART 3
-#include "leveled_pair.inc"
-    int32_t *po = A.next + ix * (size_t)(2 * kN) + iy * A.next_y + (size_t)h * kN;
-    // the gather indices are formed again from a value the compiler cannot match with the load phase's: carried across the
-    // product, those sixteen registers are what spills <3,7>
-    int w0s = w0;
-    asm volatile("" : "+s"(w0s));
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int j = lane + 64 * r;
-        const uint2 e = leveled_words(S[r], ut[r]);
-        const int i0 = (j + w0s) & (2 * kN - 1), i1 = (j + kNH + w0s) & (2 * kN - 1);
-        const uint32_t a0 = (uint32_t)pa[i0 & (kN - 1)], a1 = (uint32_t)pa[i1 & (kN - 1)];
-        po[j] = (int32_t)(EOC_NEGACYCLIC(i0, a0) + e.x);
-        po[j + kNH] = (int32_t)(EOC_NEGACYCLIC(i1, a1) + e.y);
-    }
-}
+// k_automaton_step<L, BGBIT> and its rounding twin k_rstep<L, BGBIT>: one text, leveled_kernels.inc
+#define EOC_LEVELED_KERNEL 3
+#define EOC_LEVELED_ROUND 0
+#include "leveled_kernels.inc"
+#define EOC_LEVELED_KERNEL 3
+#define EOC_LEVELED_ROUND 1
+#include "leveled_kernels.inc"
 #undef EOC_NEGACYCLIC
 
 // =================================================================================================

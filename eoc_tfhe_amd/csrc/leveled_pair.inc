@@ -1,5 +1,5 @@
 // The frame of a LEVELED kernel: one external product of a converted selector with a TLWE sample, run by one wave pair per
-// item.  k_cmux, k_demux and k_automaton_step include this one text, a part at a time (EOC_LEVELED_PART), around the three
+// item.  k_cmux, k_demux and k_automaton_step (and their rounding twins: leveled_kernels.inc) include this one text, a part at a time (EOC_LEVELED_PART), around the three
 // things in which they differ, so the mapping, the LDS plan, the dead pair's rule and the product are the same by construction:
 //     part 1;  the operand pointers and `sel`, formed from ix, iy, h;  part 2;  dlo / dhi filled;  part 3;  the store phase.
 // A text and not a function: the frame as a struct returned by a force-inlined function (the row loader a function template)
@@ -10,8 +10,8 @@
 //   Out: s_tw, s_twist, scr, scr_partner (the LDS carve: the tables, then one transpose scratch per wave); tid, lane, wv, h;
 //   the table load, issued (part 3 waits for it); live, ix, iy: a pair past the end of the grid computes the last item again
 //   and stores nothing, so every barrier is reached by all waves.
-// Part 2, the gadget.  In scope: L, BGBIT, A (Bgbit).
-//   Out: offset (Bg/2 at every digit position), gd; dlo[8], dhi[8], declared: the kernel leaves coefficient lane + 64 r of
+// Part 2, the gadget.  In scope: L, BGBIT, A (Bgbit); EOC_LEVELED_ROUND of the includer (leveled_kernels.inc).
+//   Out: offset (Bg/2 at every digit position; in a rounding twin 2^(31 - L Bgbit) more, where L Bgbit < 32), gd; dlo[8], dhi[8], declared: the kernel leaves coefficient lane + 64 r of
 //   offset + its operand in dlo[r], coefficient lane + 64 r + 512 in dhi[r].
 // Part 3, the product and the dead pair's exit.  In scope: all of the above, and sel (the item's converted selector).
 //   Out: S[8], ut[8] as ext_product_pair.inc leaves them: cmulc(S[r], ut[r]) holds coefficients lane + 64 r (x) and
@@ -36,6 +36,9 @@
     uint32_t offset = 0;
 #pragma unroll
     for (int p = 1; p <= L; p++) offset += ((1u << Bgbit) >> 1) << (32 - p * Bgbit);
+#if EOC_LEVELED_ROUND
+    if (L * Bgbit < 32) offset += 1u << (31 - L * Bgbit); // half of what the gadget drops: the rounding twins (DESIGN.md 21)
+#endif
     const Gadget<BGBIT> gd = make_gadget<BGBIT>(Bgbit);
     uint32_t dlo[8], dhi[8];
 #elif EOC_LEVELED_PART == 3

@@ -153,6 +153,7 @@ struct Global {
     double bcast_s = 0.0;
     std::string bcast_method = "none";
     bool key_loaded = false;
+    int leveled_rounding = 0; // eoc_global_set_leveled_rounding: the mode of every engine, those created later included
 };
 Global G;
 
@@ -933,6 +934,7 @@ extern "C" int eoc_gpu_init_multi(const int *devices, int n_devices, const eoc_p
         Slot &s = G.slots[i];
         s.device = devices[i];
         int rc = eoc_engine_create(devices[i], p, &s.e);
+        if (rc == EOC_OK) rc = eoc_engine_set_leveled_rounding(s.e, G.leveled_rounding);
         if (rc == EOC_OK) {
             if (hipSetDevice(s.device) != hipSuccess || hipStreamCreateWithFlags(&s.st[0], hipStreamNonBlocking) != hipSuccess ||
                 hipStreamCreateWithFlags(&s.st[1], hipStreamNonBlocking) != hipSuccess ||
@@ -1017,6 +1019,23 @@ extern "C" eoc_engine *eoc_global_engine_at(int i)
     return (i >= 0 && (size_t)i < G.slots.size()) ? G.slots[i].e : nullptr;
 }
 extern "C" eoc_engine *eoc_global_engine(void) { return eoc_global_engine_at(0); }
+
+// the leveled calls' rounding mode on every engine of the context, and on those it creates later
+extern "C" int eoc_global_set_leveled_rounding(int on)
+{
+    if (on != 0 && on != 1) {
+        eoc_set_error("eoc_global_set_leveled_rounding: on = %d is neither 0 nor 1", on);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(G.mu);
+    for (auto &s : G.slots)
+        if (int rc = eoc_engine_set_leveled_rounding(s.e, on)) {
+            for (auto &t : G.slots) (void)eoc_engine_set_leveled_rounding(t.e, G.leveled_rounding); // all engines or none
+            return rc;
+        }
+    G.leveled_rounding = on;
+    return EOC_OK;
+}
 
 extern "C" void eoc_gpu_shutdown(void)
 {

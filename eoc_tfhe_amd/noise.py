@@ -366,7 +366,10 @@ def cmux_var(params, tlwe_key, bit=1):
                  sigma_eff^2 the truncation-corrected variance of gaussian32 at bk_stdev)
       remainder  (1 + |s'|) q^2 / 12, q = Bg^-l: what the decomposition drops, low_b - low_a s' -- only where the bit is 1
                  (a selector of 0 multiplies it by nothing)
-    This is the spread around the CMux's mean.  The mean is not zero where the bit is 1: see cmux_mean."""
+    This is the spread around the CMux's mean.  The mean is not zero where the bit is 1: see cmux_mean.
+    The rounding mode of the leveled calls has the same variance, which is why this function takes no
+    `rounding`: the mode adds a constant to the decomposed word, so the dropped part is uniform on an interval of the same
+    length q, [-q/2, q/2) instead of [0, q), and the digits run over the same Bg values; only the mean moves."""
     l, Bgbit = int(params.l), int(params.Bgbit)
     Bg = 1 << Bgbit
     q = 2.0 ** (-l * Bgbit)
@@ -374,13 +377,23 @@ def cmux_var(params, tlwe_key, bit=1):
     return 2 * l * N * ((Bg * Bg + 2) / 12.0) * _sig2(params) + (1 if bit else 0) * (1 + hw) * q * q / 12.0
 
 
-def cmux_mean(params, tlwe_key, slot=0, bit=1):
+def _dropped_mean(params, rounding=False):
+    """mean (torus units) of the part of a pseudo-random word that the gadget drops: q/2 when it truncates (uniform on
+    [0, q)); -2^-33, half an LSB of Torus32, in the rounding mode (uniform on the integers of [-q/2, q/2)), which
+    changes nothing where l Bgbit = 32"""
+    lb = int(params.l) * int(params.Bgbit)
+    return -(2.0 ** -33) if rounding and lb < 32 else 2.0 ** (-lb) / 2
+
+
+def cmux_mean(params, tlwe_key, slot=0, bit=1, rounding=False):
     """mean error (torus units) of coefficient `slot` behind one CMux whose bit is 1: the decomposition TRUNCATES, the dropped
     parts low_x[j] are uniform on [0, q) with mean q/2, and the output loses low_b - low_a s': -(q/2) (J (1 - s'))[slot], the
     polynomial whose coefficient 0 is the blind rotation's M_BR (`predict`).  About -(q/2) (1 + |s'|) at slot 0, falling
-    linearly to +(q/2) (|s'| - 1) at slot N - 1.  `slot` may be an array.  Zero where the bit is 0."""
-    q = 2.0 ** (-int(params.l) * int(params.Bgbit))
-    return -(q / 2) * _Jv(tlwe_key)[np.asarray(slot)] * (1 if bit else 0)
+    linearly to +(q/2) (|s'| - 1) at slot N - 1.  `slot` may be an array.  Zero where the bit is 0.
+    rounding=True: the leveled calls' rounding mode (eoc_engine_set_leveled_rounding), whose dropped parts are uniform on
+    [-q/2, q/2) with mean -1/2 LSB: the residual is 2^-33 (J (1 - s'))[slot], the same polynomial 2^(32 - l Bgbit) times
+    smaller and of the other sign."""
+    return -_dropped_mean(params, rounding) * _Jv(tlwe_key)[np.asarray(slot)] * (1 if bit else 0)
 
 
 def table_read_var(params, lwe_key, tlwe_key, depth, table_var=0.0, ksk=None):
@@ -402,12 +415,13 @@ def table_read_slots(index, log2_lists, log2_width):
     return out
 
 
-def table_read_mean(params, tlwe_key, index, log2_lists, log2_width, w=0):
+def table_read_mean(params, tlwe_key, index, log2_lists, log2_width, w=0, rounding=False):
     """mean error (torus units) of slot w of the read of entry `index`, before the key switch's own mean: the sum of cmux_mean
     over the CMuxes whose bit is 1, each at the slot the entry occupied behind it.  Up to depth x (q/2) (1 + |s'|) in
-    magnitude: unlike a blind rotation's, these means are not spread by later rotations."""
+    magnitude: unlike a blind rotation's, these means are not spread by later rotations.  rounding: as
+    cmux_mean's."""
     slots = np.asarray(table_read_slots(index, log2_lists, log2_width), np.int64) + int(w)
-    return float(cmux_mean(params, tlwe_key, slots).sum()) if len(slots) else 0.0
+    return float(cmux_mean(params, tlwe_key, slots, rounding=rounding).sum()) if len(slots) else 0.0
 
 
 # ---- encrypted-index table updates: rotations and a demultiplexer tree (DESIGN.md 15) -------------------------------------------
@@ -442,13 +456,13 @@ def table_update_var(params, tlwe_key, index, log2_lists, log2_width, lst=None, 
     return v
 
 
-def table_update_mean(params, tlwe_key, index, log2_lists, log2_width, slot=None, lst=None):
+def table_update_mean(params, tlwe_key, index, log2_lists, log2_width, slot=None, lst=None, rounding=False):
     """mean error (torus units) ONE update of entry `index` adds to slot `slot` (0 .. N-1, default the entry's first slot) of
     list `lst` (default the selected one).  Rotation i with bit 1 leaves cmux_mean at every slot behind it, and the later
     rotations with bit 1 carry it along (negated where it wraps past X^N = -1): seen from the final slot it sits at
     slot - sum of the later shifts.  A stage under bit 1 leaves cmux_mean(slot) in child 2j + 1 and -cmux_mean(slot) in child
     2j, whose other errors are gone; a stage under bit 0 has no mean and clears child 2j + 1.  Linear in the number of
-    updates of one list: the term that bounds how often a list can be updated before a refresh."""
+    updates of one list: the term that bounds how often a list can be updated before a refresh.  rounding: as cmux_mean's."""
     d, r, W, bits = _update_bits(index, log2_lists, log2_width)
     sel = int(index) >> r
     lst = sel if lst is None else int(lst)
@@ -458,8 +472,8 @@ def table_update_mean(params, tlwe_key, index, log2_lists, log2_width, slot=None
         if not bits[i]:
             continue
         pos = (slot - sum((W << k) for k in range(i + 1, r) if bits[k])) % (2 * N)
-        m += float(cmux_mean(params, tlwe_key, pos % N)) * (-1.0 if pos >= N else 1.0)
-    here = float(cmux_mean(params, tlwe_key, slot))
+        m += float(cmux_mean(params, tlwe_key, pos % N, rounding=rounding)) * (-1.0 if pos >= N else 1.0)
+    here = float(cmux_mean(params, tlwe_key, slot, rounding=rounding))
     for t in range(d):
         b, g = bits[r + d - 1 - t], (lst >> (d - 1 - t)) & 1
         if b:
@@ -470,20 +484,20 @@ def table_update_mean(params, tlwe_key, index, log2_lists, log2_width, slot=None
 
 
 def table_update_budget(params, lwe_key, tlwe_key, p, log2_lists, log2_width, sigmas=6.0, value_var=0.0, table_var=0.0,
-                        ksk=None):
+                        ksk=None, rounding=False):
     """how many updates a TABLE tolerates before a read of it no longer decodes with margin -- every update reaches every
     list: the selected one gains the value and the most noise, the others an encryption of 0 with at most as much (the bound
     below covers both, so U counts updates at any index): the largest U with
         |mean| + sigmas sqrt(variance) <= 1 / (4p)        (half a step of the grid m / (2p) decrypt_ints rounds on)
     for the worst index (every bit 1), where variance = table_var + U table_update_var + table_read_var(depth) and
     |mean| = (U + 1) depth (q/2) (1 + |s'|) + |ks_mean|: every update and the read leave their largest mean at the slot.
-    0 if not even the read alone fits.  Computed from the model; nothing fitted."""
+    0 if not even the read alone fits.  Computed from the model; nothing fitted.  rounding=True: updates and read in the
+    leveled calls' rounding mode, |mean| = (U + 1) depth 2^-33 (1 + |s'|) + |ks_mean|; the variances are the same."""
     d, lw = int(log2_lists), int(log2_width)
     depth = d + 10 - lw
     worst = (1 << depth) - 1
     hw = int(np.asarray(tlwe_key, np.int64).sum())
-    q = 2.0 ** (-int(params.l) * int(params.Bgbit))
-    m1 = depth * (q / 2) * (1 + hw)
+    m1 = depth * abs(_dropped_mean(params, rounding)) * (1 + hw)
     v1 = table_update_var(params, tlwe_key, worst, d, lw, value_var=value_var)
     pr = predict(params, lwe_key, tlwe_key, ksk)
     v0 = float(table_var) + table_read_var(params, lwe_key, tlwe_key, depth, 0.0, ksk)
@@ -515,28 +529,29 @@ def automaton_var(params, tlwe_key, bits, final_var=0.0):
     return float(final_var) + float(sum(cmux_var(params, tlwe_key, int(b) & 1) for b in bits))
 
 
-def automaton_mean_bound(params, tlwe_key, steps):
+def automaton_mean_bound(params, tlwe_key, steps, rounding=False):
     """bound on |mean error| (torus units) of any slot of a run of `steps` steps, before the key switch: steps (q/2)(1 + |s'|).
     One step whose bit is 1 leaves cmux_mean, a polynomial whose entries are at most (q/2)(1 + |s'|) in magnitude; the later
     steps' rotations permute and negate its entries, so the per-step bound holds at whatever slot is read.  Linear in the
-    number of steps, as the variance is (automaton_var)."""
-    q = 2.0 ** (-int(params.l) * int(params.Bgbit))
+    number of steps, as the variance is (automaton_var).  rounding=True: steps 2^-33 (1 + |s'|), the rounding mode's residual
+    (cmux_mean)."""
     hw = int(np.asarray(tlwe_key, np.int64).sum())
-    return int(steps) * (q / 2) * (1 + hw)
+    return int(steps) * abs(_dropped_mean(params, rounding)) * (1 + hw)
 
 
-def automaton_budget(params, lwe_key, tlwe_key, p, sigmas=6.0, final_var=0.0, ksk=None):
+def automaton_budget(params, lwe_key, tlwe_key, p, sigmas=6.0, final_var=0.0, ksk=None, rounding=False):
     """how many steps (input bits) a run tolerates before its key-switched output no longer decodes with margin on the message
     space p (p = 2: a boolean at +-1/8): the largest number of steps with
         automaton_mean_bound(steps) + |ks_mean| + sigmas sqrt(automaton_var(all-ones, steps) + ks_var) <= 1 / (4p)
     Mean and variance both grow linearly in the steps; on the default sets the mean term is the one that binds.  0 if not even
-    the key switch alone fits.  Computed from the model (`predict`, cmux_var); nothing fitted."""
+    the key switch alone fits.  Computed from the model (`predict`, cmux_var); nothing fitted.  rounding=True: the run in the
+    leveled calls' rounding mode, where the mean bound is 2^(32 - l Bgbit) times smaller and the variance binds."""
     pr = predict(params, lwe_key, tlwe_key, ksk)
     v1 = cmux_var(params, tlwe_key, 1)
     margin = 1.0 / (4 * int(p))
 
     def fits(s):
-        return (automaton_mean_bound(params, tlwe_key, s) + abs(pr["ks_mean"])
+        return (automaton_mean_bound(params, tlwe_key, s, rounding) + abs(pr["ks_mean"])
                 + float(sigmas) * np.sqrt(float(final_var) + s * v1 + pr["ks_var"]) <= margin)
     if not fits(0):
         return 0

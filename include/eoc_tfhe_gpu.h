@@ -792,6 +792,31 @@ int eoc_automaton_run(const int32_t *trans, size_t states, const int32_t *final_
                       const int32_t *starts, size_t n_starts, int log2_width, int32_t *out, size_t queries);
 
 /* ------------------------------------------------------------------------------------------------
+ * rounding mode of the leveled calls: an opt-in gadget decomposition that rounds where the oracle's truncates.
+ *   rule        with h = 2^(31 - l Bgbit) where l Bgbit < 32 and h = 0 otherwise, every external product C (x) D of the calls
+ *               below becomes C (x) (D + h), h added to every coefficient word of both polynomials, wrapping: the CMux is
+ *               out = in0 + C (x) ((X^rot in1 - in0) + h), the demux E = C (x) (in + h), the automaton step likewise.  The part
+ *               of a word the gadget drops then lies in [-q/2, q/2), q = 2^(32 - l Bgbit), and not in [0, q): the mean it
+ *               leaves in every product whose bit is 1 falls from -(q/2) (J (1 - s')) to -2^-33 (J (1 - s')) per slot; the
+ *               variance (noise.cmux_var) is unchanged.  Long leveled chains -- automata, tables updated many times -- are
+ *               bound by that mean in the default mode (noise.automaton_budget, noise.table_update_budget).
+ *   mode        off (0) at engine creation: every word is the oracle's.  eoc_engine_set_leveled_rounding(e, 1) makes
+ *               eoc_cmux_device, eoc_table_read_device, eoc_demux_device, eoc_table_update_device,
+ *               eoc_automaton_step_device and eoc_automaton_run_device launch the rounding twins of their kernels (k_rcmux,
+ *               k_rdemux, k_rstep; the launch counters are shared with the default kernels).  Nothing else is governed by it:
+ *               no blind rotation (the encrypted-seed one included), no key switch, no packing call.  Where l Bgbit = 32 the
+ *               mode changes no word.  A sample produced in one mode is an ordinary input of the other.
+ *   capture     a captured graph replays the mode it was captured under.  While a capture that already holds one of the
+ *               calls above is open on the engine, the setter returns EOC_ERR_STATE and changes nothing.
+ *   global      eoc_global_set_leveled_rounding(on) sets every engine of the global context and is remembered for engines
+ *               the context creates later (it may be called before eoc_gpu_init); eoc_table_read, eoc_table_update and
+ *               eoc_automaton_run follow it.  Any engine count gives the single-engine words of the same mode.
+ * EOC_ERR_ARG for a null engine or an `on` other than 0 and 1. */
+int eoc_engine_set_leveled_rounding(eoc_engine *e, int on);
+int eoc_engine_leveled_rounding(const eoc_engine *e);   /* 0 or 1; 0 for a null engine */
+int eoc_global_set_leveled_rounding(int on);
+
+/* ------------------------------------------------------------------------------------------------
  * packing key switch: LWE samples under the LWE key s (gate or LUT outputs) -> compact TLWE lists under s',
  * the layout of eoc_pk_encrypt_*, eoc_table_trivial and the table of eoc_table_read_device.  1 024 results leave in 8 KiB
  * instead of 2 MB (Set A) / 2.5 MB (Set B), and a value the server computed can become a table.
