@@ -302,6 +302,10 @@ def lib():
         "eoc_tv_pack_device": (C.c_int, [vp, C.c_int, vp, sz, sz, vp, vp]),
         "eoc_lut2_batch_device": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, sz, vp]),
         "eoc_lut2_batch": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp, vp, sz]),
+        "eoc_tv_pack_exact_device": (C.c_int, [vp, C.c_int, vp, sz, sz, vp, vp]),
+        "eoc_lut_tree_test_polynomials": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp]),
+        "eoc_lut_tree_batch_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, sz, vp]),
+        "eoc_lut_tree_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, sz]),
         # seeded ciphertexts, selectors and cloud key
         "eoc_seeded_encrypt_bits": (C.c_int, [vp, vp, sz, vp, vp]),
         "eoc_seeded_encrypt_ints": (C.c_int, [vp, C.c_int, vp, sz, vp, vp]),
@@ -835,6 +839,21 @@ def lut2_test_polynomials(p, table, n_tables=1):
     return tv
 
 
+def lut_tree_test_polynomials(p, d, table, n_tables=1):
+    """Level-1 test polynomials [p^(d-1) / T][N] int32 of ONE function on Z_p^d (eoc_lut_tree_test_polynomials):
+    table of p^d Torus32 output values (any shape), table[x_1]..[x_d].  Level-1 table J = j_2 + p j_3 + p^2 j_4 (j_2 fastest)
+    is x_1 -> F(x_1, j_2, .., j_d); polynomial g holds the tables J = g T .. g T + T - 1."""
+    p, d = int(p), int(d)
+    table = np.ascontiguousarray(np.asarray(table, np.int64).astype(np.int32)).reshape(-1)
+    if not 2 <= d <= 4 or table.size != p ** d:
+        raise EocError(f"lut_tree_test_polynomials: table must hold p^d values with 2 <= d <= 4, got {table.size} for p = {p}, d = {d}")
+    T = max(int(n_tables), 1)
+    tv = np.empty((max(p ** (d - 1) // T, 1), N), np.int32)
+    _check(lib().eoc_lut_tree_test_polynomials(p, d, int(n_tables), table.ctypes.data, tv.ctypes.data),
+           "eoc_lut_tree_test_polynomials")
+    return tv
+
+
 class Engine:
     """One HIP engine (one GPU).  All array arguments are DEVICE pointers (ints) unless noted."""
 
@@ -1193,6 +1212,18 @@ class Engine:
         key."""
         _check(self.L.eoc_tv_pack_device(self.h, int(p), d_vals, n_funcs, count, d_lists, stream), "eoc_tv_pack_device")
 
+    def tv_pack_exact_device(self, p, d_vals, n_funcs, count, d_lists, stream=None):
+        """tv_pack_device's arguments and layouts, evaluated EXACTLY in wrapping integers on the matrix cores
+        (eoc_tv_pack_exact_device): the value tv_pack_device gives within the rounding of its transforms."""
+        _check(self.L.eoc_tv_pack_exact_device(self.h, int(p), d_vals, n_funcs, count, d_lists, stream), "eoc_tv_pack_exact_device")
+
+    def lut_tree_batch_device(self, p, d, n_tables, d_tv0, n_funcs, d_digits, d_out, count, stream=None):
+        """d-digit lookups F(x_1, .., x_d) (eoc_lut_tree_batch_device): d_tv0 [n_funcs][p^(d-1) / T][N]
+        (lut_tree_test_polynomials per function), d_digits [d][count][n+1] (x_1 first) at message space p, d_out
+        [n_funcs][count][n+1].  Needs the cloud key and the packing key."""
+        _check(self.L.eoc_lut_tree_batch_device(self.h, int(p), int(d), int(n_tables), d_tv0, n_funcs, d_digits, d_out, count, stream),
+               "eoc_lut_tree_batch_device")
+
     def lut2_batch_device(self, p, n_tables, d_tv0, n_funcs, d_x, d_y, d_out, count, stream=None):
         """Two-input lookups F(x, y) (eoc_lut2_batch_device): d_tv0 [n_funcs][p / T][N] (lut2_test_polynomials
         per function), d_x, d_y [count][n+1] at message space p, d_out [n_funcs][count][n+1].  Needs the cloud key and the
@@ -1458,6 +1489,24 @@ def lut2_batch(p, tables, x, y, n_tables=1):
     out = np.empty((tables.shape[0],) + x.shape, np.int32)
     _check(lib().eoc_lut2_batch(int(p), int(n_tables), tables.ctypes.data, tables.shape[0], x.ctypes.data, y.ctypes.data,
                                 out.ctypes.data, x.shape[0]), "eoc_lut2_batch")
+    return out
+
+
+def lut_tree_batch(p, d, tables, digits, n_tables=1):
+    """eoc_lut_tree_batch on the global context (cloud key + packing key): tables [n_funcs][p^d] (or one function's p^d values,
+    any shape with p^d entries per function given as [n_funcs][...]) Torus32 output values, tables[f][x_1]..[x_d]; digits
+    [d][count][n+1] at message space p, x_1 first.  Returns [n_funcs][count][n+1]."""
+    p, d = int(p), int(d)
+    tables = np.asarray(tables, np.int64).astype(np.int32)
+    if not 2 <= d <= 4 or tables.size == 0 or tables.size % (p ** d):
+        raise EocError(f"lut_tree_batch: tables must hold n_funcs x p^d values with 2 <= d <= 4, got {tables.shape} for p = {p}, d = {d}")
+    tables = np.ascontiguousarray(tables.reshape(-1, p ** d))
+    digits = np.ascontiguousarray(digits, np.int32)
+    if digits.ndim != 3 or digits.shape[0] != d:
+        raise EocError("lut_tree_batch: digits is a 3-d array [d][count][n+1]")
+    out = np.empty((tables.shape[0],) + digits.shape[1:], np.int32)
+    _check(lib().eoc_lut_tree_batch(p, d, int(n_tables), tables.ctypes.data, tables.shape[0], digits.ctypes.data, out.ctypes.data,
+                                    digits.shape[1]), "eoc_lut_tree_batch")
     return out
 
 

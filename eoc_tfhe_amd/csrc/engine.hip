@@ -116,10 +116,17 @@ struct eoc_engine {
     // fit; EOC_TFHE_PACK_WS_BYTES, diagnostics)
     d2 *d_pks = nullptr;
     Scratch pack_cols;
+    // the exact test-polynomial pack: the packing key's int32 rows once more, as signed byte limbs in
+    // k_tvpack_mm's operand order (the engine's own, replaced with the key), and the constant-slot samples
+    // [lists of a slice][p + 1][2][N] between its two kernels (sliced by the same byte budget as the columns)
+    void *d_pkl = nullptr;
+    Scratch tv_s;
     size_t pack_ws_bytes = (size_t)256 << 20;
     uint64_t pack_launches = 0, packed_samples = 0; // k_pack_rows launches; samples packed
     // two-input lookups: the lists and the level-1 outputs of a slice of rows, one buffer
     Scratch lut2;
+    // d-digit lookups: a slice's level outputs and lists, one buffer
+    Scratch lut_tree;
     // seeded selectors: the expanded torus-form rows [rows][2][N] in front of the key-load transform
     Scratch seed_stage;
     uint64_t seed_launches = 0; // k_seed_masks launches
@@ -292,7 +299,8 @@ extern "C" void eoc_engine_destroy(eoc_engine *e)
     }
     hipFree(e->d_ksl);
     hipFree(e->d_pks);
-    for (Scratch *s : {&e->cmux[0], &e->cmux[1], &e->pack_cols, &e->lut2, &e->seed_stage, &e->dot_specs, &e->conv_lists}) hipFree(s->p);
+    hipFree(e->d_pkl);
+    for (Scratch *s : {&e->cmux[0], &e->cmux[1], &e->pack_cols, &e->tv_s, &e->lut2, &e->lut_tree, &e->seed_stage, &e->dot_specs, &e->conv_lists}) hipFree(s->p);
     free_ws(e->ws);
     hipFree(e->d_stamps);
     delete e;
@@ -1710,6 +1718,60 @@ extern "C" int eoc_tv_pack_device(eoc_engine *e, int p, const int32_t *d_vals, s
     return tv_pack_locked(e, "eoc_tv_pack_device", p, d_vals, n_funcs, count, d_lists, (hipStream_t)hip_stream);
 }
 
+// The exact pack: k_tvpack_mm + k_tv_spread over n_funcs x count lists, sliced by the byte budget of the
+// constant-slot samples; the engine's lock is held by the caller
+static int tv_pack_exact_locked(eoc_engine *e, const char *who, int p, const int32_t *d_vals, size_t n_funcs, size_t count,
+                                int32_t *d_lists, hipStream_t st)
+{
+    if (!e->d_pks || !e->d_pkl) {
+        eoc_set_error("%s: no packing key loaded (eoc_engine_set_packing_key)", who);
+        return EOC_ERR_NO_KEY;
+    }
+    const size_t per_list = (size_t)(p + 1) * 2 * kN * sizeof(int32_t), n_lists = n_funcs * count;
+    if (!n_lists) return EOC_OK;
+    if (e->pack_ws_bytes < per_list) {
+        eoc_set_error("%s: one list needs %zu bytes of workspace, the budget (EOC_TFHE_PACK_WS_BYTES) is %zu", who, per_list,
+                      e->pack_ws_bytes);
+        return EOC_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    // at most 2^20 lists a slice whatever the budget: the sample count and both grids stay far inside 32 bits
+    const size_t ls = std::min({n_lists, e->pack_ws_bytes / per_list, (size_t)1 << 20});
+    int rc = scratch_reserve(e, e->tv_s, ls * per_list, "constant-slot samples", st);
+    if (rc) return rc;
+    const int n = e->p.n;
+    for (size_t l0 = 0; l0 < n_lists; l0 += ls) {
+        const size_t L = std::min(ls, n_lists - l0);
+        const uint32_t M = (uint32_t)(L * (size_t)(p + 1));
+        {
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            hipLaunchKernelGGL(k_tvpack_mm<4>, dim3((M + 255u) / 256u * kTvpColTiles), dim3(256), 0, st, d_vals, (uint32_t)count,
+                               (uint32_t)l0, M, p, n, static_cast<const i4 *>(e->d_pkl), tvp_ksteps(n), e->tv_s.i32());
+            HIP_TRY(hipGetLastError());
+        }
+        {
+            SpanGuard span(e, st, KIND_KEYSWITCH);
+            auto kfn = p == 2 ? k_tv_spread<2> : (p == 4 ? k_tv_spread<4> : k_tv_spread<8>);
+            hipLaunchKernelGGL(kfn, dim3((unsigned)(2 * L)), dim3(256), 0, st, (const int32_t *)e->tv_s.i32(), d_vals,
+                               (uint32_t)count, (uint32_t)l0, n, d_lists + l0 * 2 * kN);
+            HIP_TRY(hipGetLastError());
+        }
+        e->pack_launches++;
+    }
+    e->packed_samples += n_lists * (size_t)p; // the samples read, as tv_pack_locked counts them
+    return EOC_OK;
+}
+extern "C" int eoc_tv_pack_exact_device(eoc_engine *e, int p, const int32_t *d_vals, size_t n_funcs, size_t count,
+                                        int32_t *d_lists, void *hip_stream)
+{
+    if (!e || !d_vals || !d_lists || !(p == 2 || p == 4 || p == 8) || n_funcs == 0 || n_funcs * (uint64_t)count > 0xffffffffull) {
+        eoc_set_error("eoc_tv_pack_exact_device: null argument, p = %d not one of 2, 4, 8, no function, or more than 2^32 lists", p);
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    return tv_pack_exact_locked(e, "eoc_tv_pack_exact_device", p, d_vals, n_funcs, count, d_lists, (hipStream_t)hip_stream);
+}
+
 // F(x, y): level 1 (the existing _tv / many-LUT path) on x against the p tables x -> F(x, j), the pack of each row's p values
 // into one encrypted test polynomial, level 2 (k_br_enc*) on y from that polynomial.
 extern "C" int eoc_lut2_batch_device(eoc_engine *e, int p, int n_tables, const int32_t *d_tv0, size_t n_funcs, const int32_t *d_x,
@@ -1753,6 +1815,62 @@ extern "C" int eoc_lut2_batch_device(eoc_engine *e, int p, int n_tables, const i
         if (!rc) rc = tv_pack_locked(e, "eoc_lut2_batch_device", p, d_vals, n_funcs, S, d_lists, st);
         if (!rc) rc = lut_levels_locked(e, "eoc_lut2_batch_device", 0, 2, d_lists, n_funcs, d_y + r0 * stride, d_out + r0 * stride, S,
                                         count, st);
+        if (rc) return rc;
+    }
+    return EOC_OK;
+}
+
+// F(x_1, .., x_d): level 1 on x_1 against the p^(d-1) tables x_1 -> F(x_1, j_2, .., j_d) (j_2 fastest), then
+// per further digit k the exact pack of the p values that differ only in j_k and a blind rotation of those lists by x_k.
+// With that table order a level's output block [groups][p][rows] IS the next pack's d_vals: nothing is gathered.
+extern "C" int eoc_lut_tree_batch_device(eoc_engine *e, int p, int d, int n_tables, const int32_t *d_tv0, size_t n_funcs,
+                                         const int32_t *d_digits, int32_t *d_out, size_t count, void *hip_stream)
+{
+    const int T = n_tables > 1 ? n_tables : 1;
+    const bool p_ok = p == 2 || p == 4 || p == 8, t_ok = n_tables >= 0 && (T == 1 || T == 2 || T == 4 || T == 8);
+    size_t n1 = 1; // level-1 tables per function
+    for (int k = 1; p_ok && k < d && k < 4; k++) n1 *= (size_t)p;
+    if (!e || !d_tv0 || !d_digits || !d_out || !p_ok || d < 2 || d > 4 || n1 > 64 || !t_ok || p % T != 0 || (T > 1 && p * T > 16) ||
+        n_funcs == 0 || n_funcs > kMaxGatesPerLaunch / n1) {
+        eoc_set_error("eoc_lut_tree_batch_device: null argument, (p, d, n_tables) = (%d, %d, %d) not supported (p in {2, 4, 8}, "
+                      "2 <= d <= 4, p^(d-1) <= 64, T in {1, 2, 4, 8}, T divides p, p T <= 16 for T > 1) or n_funcs x p^(d-1) "
+                      "outside [1, %zu]", p, d, n_tables, kMaxGatesPerLaunch);
+        return EOC_ERR_ARG;
+    }
+    if (!count) return EOC_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    const char *who = "eoc_lut_tree_batch_device";
+    if (!e->bkfft || !e->ksk) {
+        eoc_set_error("%s: no cloud key loaded", who);
+        return EOC_ERR_NO_KEY;
+    }
+    if (!e->d_pks || !e->d_pkl) {
+        eoc_set_error("%s: no packing key loaded (eoc_engine_set_packing_key)", who);
+        return EOC_ERR_NO_KEY;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t stride = (size_t)e->p.n + 1;
+    // per row: n_funcs x p^(d-1) level-1 outputs (every later level's block is smaller and re-uses their place) and
+    // n_funcs x p^(d-2) lists of 8 KiB (the first pack's; later ones fewer); a slice holds at most 2^20 level-1 outputs
+    // (lut_levels' rule) and at most kTreeWsBytes of both
+    constexpr size_t kTreeWsBytes = (size_t)256 << 20;
+    const size_t row_vals = n_funcs * n1 * stride * sizeof(int32_t), row_lists = n_funcs * (n1 / (size_t)p) * 2 * kN * sizeof(int32_t);
+    const size_t rows = std::min({count, std::max<size_t>(1, e->slice_samples / (n_funcs * n1)),
+                                  std::max<size_t>(1, kTreeWsBytes / (row_vals + row_lists))});
+    int rc = scratch_reserve(e, e->lut_tree, rows * (row_vals + row_lists), "multi-digit lookup workspace", st);
+    if (rc) return rc;
+    int32_t *d_lists = e->lut_tree.i32(), *d_vals = d_lists + rows * (row_lists / sizeof(int32_t));
+    for (size_t r0 = 0; r0 < count; r0 += rows) {
+        const size_t S = std::min(rows, count - r0);
+        rc = lut_levels_locked(e, who, T > 1 ? T : 0, 0, d_tv0, n_funcs * (n1 / (size_t)T), d_digits + r0 * stride, d_vals, S, S, st);
+        size_t groups = n_funcs * n1 / (size_t)p; // lists of the next pack = jobs of the next level, per row
+        for (int k = 2; !rc && k <= d; k++, groups /= (size_t)p) {
+            rc = tv_pack_exact_locked(e, who, p, d_vals, groups, S, d_lists, st);
+            const bool last = k == d; // groups == n_funcs: the call's output block [n_funcs][count]
+            if (!rc) rc = lut_levels_locked(e, who, 0, 2, d_lists, groups, d_digits + ((size_t)(k - 1) * count + r0) * stride,
+                                            last ? d_out + r0 * stride : d_vals, S, last ? count : S, st);
+        }
         if (rc) return rc;
     }
     return EOC_OK;
@@ -2653,15 +2771,27 @@ extern "C" int eoc_engine_set_packing_key(eoc_engine *e, const void *blob, size_
     const size_t npoly = (size_t)p.n * kPackT * 2;
     HIP_TRY(hipDeviceSynchronize()); // nothing in flight may still read the image that is about to be replaced
     hipFree(e->d_pks);
+    hipFree(e->d_pkl);
     e->d_pks = nullptr;
-    DevTmp d_rows, d_img;
+    e->d_pkl = nullptr;
+    DevTmp d_rows, d_img, d_limbs;
     HIP_TRY(d_rows.alloc(npoly * kN * sizeof(int32_t)));
     HIP_TRY(d_img.alloc(npoly * kNH * sizeof(d2)));
+    if (d_limbs.alloc(tvp_limb_bytes(p.n)) != hipSuccess) {
+        (void)hipGetLastError();
+        eoc_set_error("eoc_engine_set_packing_key: no device memory for the limb image (%zu bytes)", tvp_limb_bytes(p.n));
+        return EOC_ERR_ALLOC;
+    }
     HIP_TRY(hipMemcpy(d_rows.p, rows, npoly * kN * sizeof(int32_t), hipMemcpyHostToDevice));
+    // the limb image of the same rows for the exact test-polynomial pack; NULL stream, drained with the transform
+    hipLaunchKernelGGL(k_pks_limbs, dim3((unsigned)(tvp_ksteps(p.n) * kTvpColTiles * 4)), dim3(256), 0, nullptr, d_rows.i32(),
+                       static_cast<uint32_t *>(d_limbs.p), p.n);
+    HIP_TRY(hipGetLastError());
     // the key-load transform (build_cloud_key_images, eoc_tgsw_to_fft_device); NULL stream, drained inside
     int rc = key_image(e, d_rows.i32(), d_img.p, npoly);
     if (rc) return rc;
     e->d_pks = static_cast<d2 *>(d_img.release());
+    e->d_pkl = d_limbs.release();
     return EOC_OK;
 }
 

@@ -651,6 +651,31 @@ extern "C" int eoc_lut2_test_polynomials(int p, int n_tables, const int32_t *tab
     return EOC_OK;
 }
 
+// d-digit lookups: the level-1 polynomials of ONE function on Z_p^d, table[(..(x_1 p + x_2) p + ..) p + x_d].
+// Level-1 table J = j_2 + p j_3 + p^2 j_4 (j_2 fastest, j_d slowest) is x_1 -> F(x_1, j_2, .., j_d); polynomial g holds the
+// tables J = g T .. g T + T - 1.  In this order every level's output block [groups][p][rows] is the next pack's input.
+extern "C" int eoc_lut_tree_test_polynomials(int p, int d, int n_tables, const int32_t *table, int32_t *tv)
+{
+    const int T = n_tables > 1 ? n_tables : 1;
+    const bool t_ok = n_tables >= 0 && (T == 1 || T == 2 || T == 4 || T == 8);
+    if (!table || !tv || !lut_p_ok(p) || d < 2 || d > 4 || !t_ok || p % T != 0 || (T > 1 && p * T > 16)) return EOC_ERR_ARG;
+    int n1 = 1; // p^(d-1) level-1 tables
+    for (int k = 1; k < d; k++) n1 *= p;
+    if (n1 > 64) return EOC_ERR_ARG;
+    int32_t cols[8 * 8]; // [T][p]: table J of the polynomial as a function of x_1
+    for (int g = 0; g < n1 / T; g++) {
+        for (int j = 0; j < T; j++) {
+            int J = g * T + j, tail = 0, w = n1 / p; // tail = sum_k j_k p^(d-k): j_2 carries the largest weight
+            for (int k = 2; k <= d; k++, J /= p, w /= p) tail += (J % p) * w;
+            for (int x = 0; x < p; x++) cols[j * p + x] = table[x * n1 + tail];
+        }
+        const int rc = T == 1 ? eoc_lut_test_polynomial(p, cols, tv + (size_t)g * EOC_N)
+                              : eoc_lut_many_test_polynomial(p, T, cols, tv + (size_t)g * EOC_N);
+        if (rc != EOC_OK) return rc;
+    }
+    return EOC_OK;
+}
+
 // ---- seeded ciphertexts, selectors and cloud key (include/eoc_tfhe_gpu.h) --------------------------------
 // The mask of a seeded object is words 0 .. len-1 of the ChaCha20 stream (seed, tag, idx) under a PUBLIC 32-byte seed --
 // ChaCha20 also for test-mode keys --, so only the bodies travel.  The noise comes from a stream of the SECRET side (the

@@ -1863,6 +1863,204 @@ __global__ __launch_bounds__(256) void k_tvpack_cols(const int32_t *__restrict__
     if (blockIdx.y == 0 && ty == 0) lists[list * 2 * kN + i0 + tx] = 0;
 }
 
+// ---- the EXACT test-polynomial pack on the matrix cores ----------------------------------------------
+// The digit polynomials of k_tvpack_cols' batch are piecewise constant: p + 1 distinct samples per list (the p values and
+// value 0 negated), each spread over one window of coefficients.  So the list factors, in wrapping 32-bit integers, into
+//   S_s  = (0, b_s X^0) - sum_m sum_j d_(s,m,j) Row(m, j)       an integer matrix product: M = samples, K = 4 n, 2 N columns
+//   list = sum_s Win_s(X) S_s                                   negacyclic sums over public windows of ones
+// Win_0 = X^0 .. X^(h-1), Win_s = X^(s w - h) .. X^(s w + h - 1) (0 < s < p), Win_p = X^(N-h) .. X^(N-1), h = N / 2p, w = N / p.
+// The product runs as k_keyswitch_mfma's does: the int32 key rows split into four signed byte limbs (k_ksk_limbs' rule), four
+// int8 products with int32 accumulators (at most 4 n terms of magnitude <= 8 x 128: |acc| < 2^22), recombined in-lane.
+
+// The limb image of the packing key's int32 rows [n][4][2][N]: [K step of 8 key indices][column tile of 32][limb][lane][16 B].
+// Lane (h = lane >> 5, r = lane & 31) holds column 32 ct + r of the 2 N columns (polynomial c0 first); its byte 4 q + jj is
+// Row(m, j) with m = 8 step + 4 h + q and j = 4 - jj: the order in which tvp_digit_dword leaves the digits of one mask word.
+// Key indices m >= n are zero rows.  One thread per dword; grid: ksteps * 64 * 4 workgroups of 256 (one 1 KiB fragment each)
+constexpr int kTvpCols = 2 * kN, kTvpColTiles = kTvpCols / 32;
+__global__ __launch_bounds__(256) void k_pks_limbs(const int32_t *__restrict__ rows, uint32_t *__restrict__ limbs, int n)
+{
+    const uint32_t limb = blockIdx.x & 3u, ct = (blockIdx.x >> 2) % kTvpColTiles, step = (blockIdx.x >> 2) / kTvpColTiles;
+    const int q = threadIdx.x & 3, lane = threadIdx.x >> 2, r = lane & 31, h = lane >> 5;
+    const int m = 8 * (int)step + 4 * h + q;
+    const int col = (int)ct * 32 + r;
+    uint32_t o = 0;
+    if (m < n) {
+#pragma unroll
+        for (int jj = 0; jj < 4; jj++) {
+            const int j = 4 - jj;
+            int32_t v = rows[(((size_t)m * kPackT + (j - 1)) * 2 + (col >> 10)) * kN + (col & (kN - 1))];
+            int32_t l = 0;
+            for (uint32_t k = 0; k <= limb; k++) {
+                l = (int32_t)(((uint32_t)v + 128u) & 255u) - 128;
+                v = (int32_t)((uint32_t)v - (uint32_t)l) >> 8;
+            }
+            o |= ((uint32_t)l & 255u) << (8 * jj);
+        }
+    }
+    limbs[(size_t)blockIdx.x * 256 + threadIdx.x] = o;
+}
+static inline int tvp_ksteps(int n) { return (n + 7) / 8; }
+static inline size_t tvp_limb_bytes(int n) { return (size_t)tvp_ksteps(n) * kTvpColTiles * 4096; }
+
+// The four signed base-16 digits of one mask word as four signed bytes: digit j (bits 32 - 4 j .. 35 - 4 j of
+// a + 2^15 + sum 8 2^(32 - 4 j), minus 8) in byte 4 - j
+__device__ __forceinline__ int tvp_digit_dword(uint32_t a)
+{
+    const uint32_t t = (a + 0x88888000u) >> 16;
+    uint32_t u = (t | (t << 8)) & 0x00FF00FFu;
+    u = ((u | (u << 4)) & 0x0F0F0F0Fu) ^ 0x08080808u; // nibble - 8 = (nibble ^ 8) sign-extended from bit 3 ...
+    return (int)(u | ((u & 0x08080808u) * 0x1Eu));    // ... 8 x 0x1E = 0xF0: no carry between the bytes
+}
+
+// S[row][2 N] = -(sum_m sum_j d Row(m, j)) for the rows (list l, sample s) = l (p + 1) + s of a slice of lists; sample s < p is
+// value s of the list's row, sample p is value 0 negated word by word (formed here, never stored).  A is never stored: lane
+// (h, r) reads the mask words m = 8 step + 4 h + q, q < 4, of its row and forms one digit dword each, so one K = 32 instruction
+// covers 8 key indices; m >= n gives zero digits against the image's zero rows.  Workgroup = NWV waves stacked along M (64 rows
+// each: 2 x 4 tiles of 32 x 32, A reused over the limbs, B over the two row tiles) x one column tile x all of K; the four 1 KiB
+// fragments of a step go through LDS (two buffers, one barrier per step, the loads of step s + 2 in flight during step s).
+// No K slices: every word of S is written exactly once, by a plain store.
+// vals: [n_funcs][p][rows][n + 1]; list l of the slice is (f, row) = divmod(list0 + l, rows).
+// grid: x = ceil(M / (64 NWV)) * 64, column tile fastest (workgroups b and b + 8 share an L2: 8 of the 64 column tiles each)
+template <int NWV>
+__global__ __launch_bounds__(64 * NWV, 2) void k_tvpack_mm(const int32_t *__restrict__ vals, uint32_t rows, uint32_t list0,
+                                                            uint32_t M, int p, int n, const i4 *__restrict__ limbs, int ksteps,
+                                                            int32_t *__restrict__ S)
+{
+    static_assert(NWV == 4, "one 1 KiB fragment (limb) per wave and step");
+    constexpr int MT = 64 * NWV;
+    __shared__ i4 s_b[2][4 * 64];
+
+    const uint32_t ct = blockIdx.x % kTvpColTiles, tile = blockIdx.x / kTvpColTiles;
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t row0 = tile * MT + (uint32_t)w * 64u;
+
+    const int32_t *ap[2];
+    bool neg[2];
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+        uint32_t row = row0 + 32u * m + r;
+        row = row < M ? row : M - 1;
+        const uint32_t l = row / (uint32_t)(p + 1), s = row - l * (uint32_t)(p + 1);
+        const uint32_t gl = list0 + l, f = gl / rows, sr = gl - f * rows;
+        neg[m] = s == (uint32_t)p;
+        ap[m] = vals + (((size_t)f * p + (neg[m] ? 0u : s)) * rows + sr) * ((size_t)n + 1) + 4 * h;
+    }
+    // the digit dwords of K step `st`: mask words m = 8 st + 4 h + q of both row tiles
+    auto a_load = [&](int st, i4 (&a)[2]) {
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int idx = 8 * st + q; // + 4 h in ap
+                const bool in = idx + 4 * h < n;
+                const uint32_t wd = in ? (uint32_t)ap[m][idx] : 0u;
+                a[m][q] = in ? tvp_digit_dword(neg[m] ? 0u - wd : wd) : 0;
+            }
+    };
+    const i4 *bsrc = limbs + ((size_t)ct * 4 + w) * 64 + lane; // wave w fetches limb w of every step
+    auto b_load = [&](int st) { return bsrc[(size_t)st * kTvpColTiles * 256]; };
+
+    i16 acc[2][4];
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int q = 0; q < 16; q++) acc[m][k][q] = 0;
+
+    i4 stg = b_load(0), ac[2], an[2];
+    a_load(0, ac);
+    s_b[0][w * 64 + lane] = stg;
+    stg = b_load(ksteps > 1 ? 1 : 0);
+    __syncthreads();
+#pragma unroll 1
+    for (int st = 0; st < ksteps; st++) {
+        const int buf = st & 1;
+        a_load(st + 1 < ksteps ? st + 1 : st, an);
+        i4 b[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) b[k] = s_b[buf][k * 64 + lane];
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) acc[m][k] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ac[m], b[k], acc[m][k], 0, 0, 0);
+        // unconditional, as in k_keyswitch_mfma: the last steps re-load the last fragment and store it where nobody reads
+        s_b[buf ^ 1][w * 64 + lane] = stg; // (its readers of step st - 1 are behind the last barrier)
+        stg = b_load(st + 2 < ksteps ? st + 2 : ksteps - 1);
+        __syncthreads();
+        ac[0] = an[0];
+        ac[1] = an[1];
+    }
+
+    // S = -(acc_0 + (acc_1 << 8) + (acc_2 << 16) + (acc_3 << 24)); a store instruction covers two rows of 32 columns
+    const int col = (int)ct * 32 + r;
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int q = 0; q < 16; q++) {
+            const uint32_t row = row0 + 32u * m + (uint32_t)((q & 3) + 8 * (q >> 2) + 4 * h);
+            const uint32_t v = (uint32_t)acc[m][0][q] + ((uint32_t)acc[m][1][q] << 8) + ((uint32_t)acc[m][2][q] << 16) +
+                               ((uint32_t)acc[m][3][q] << 24);
+            if (row < M) S[(size_t)row * kTvpCols + col] = (int32_t)(0u - v);
+        }
+}
+
+// list[c] = sum_s Win_s(X) (S_s[c] + [c = 1] b_s X^0) for one polynomial c of one list: per sample the inclusive prefix sums
+// C[t] of the 1 024 words (four consecutive words per thread, a wave scan, the wave totals through LDS); with S~[t] = S[t]
+// (t >= 0), -S[t + N] (t < 0) and E(t) = sum_(u = -N .. t) S~[u] = -C[t + N] (t < 0), C[t] - C[N - 1] (t >= 0), a window
+// [lo, hi) gives coefficient k the running-sum difference E(k - lo) - E(k - hi).  The list is WRITTEN (plain stores, 256
+// contiguous bytes per wave and instruction), not accumulated into.  grid: x = 2 * lists of the slice; block = 256.
+template <int p>
+__global__ __launch_bounds__(256) void k_tv_spread(const int32_t *__restrict__ S, const int32_t *__restrict__ vals, uint32_t rows,
+                                                   uint32_t list0, int n, int32_t *__restrict__ lists)
+{
+    static_assert(p == 2 || p == 4 || p == 8, "the message spaces of k_tvpack_cols");
+    constexpr int hw = kN / (2 * p), wd = kN / p;
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    __shared__ u4 s_c[kN / 4];
+    __shared__ uint32_t s_w[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t l = blockIdx.x >> 1, c = blockIdx.x & 1u;
+    const uint32_t gl = list0 + l, f = gl / rows, sr = gl - f * rows;
+    const uint32_t *sc = reinterpret_cast<const uint32_t *>(s_c);
+    uint32_t out[4] = {0, 0, 0, 0};
+#pragma unroll 1
+    for (int s = 0; s <= p; s++) {
+        u4 x = *reinterpret_cast<const u4 *>(S + (((size_t)l * (p + 1) + s) * 2 + c) * kN + 4 * tid);
+        if (c == 1 && tid == 0) {
+            const uint32_t b = (uint32_t)vals[(((size_t)f * p + (s < p ? s : 0)) * rows + sr) * ((size_t)n + 1) + n];
+            x.x += s < p ? b : 0u - b;
+        }
+        x.y += x.x;
+        x.z += x.y;
+        x.w += x.z;
+        uint32_t t = x.w;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(t, d, 64);
+            if (lane >= d) t += o;
+        }
+        if (lane == 63) s_w[wv] = t;
+        __syncthreads(); // also: the readers of s_c of sample s - 1 are done
+        uint32_t base = t - x.w;
+        for (int k = 0; k < wv; k++) base += s_w[k];
+        s_c[tid] = x + base;
+        __syncthreads(); // also: the readers of s_w are done before sample s + 1 writes it
+        const uint32_t total = sc[kN - 1];
+        const int lo = s == 0 ? 0 : (s == p ? kN - hw : s * wd - hw), hi = s == p ? kN : s * wd + hw;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int k = tid + 256 * i, t0 = k - lo, t1 = k - hi;
+            const uint32_t e0 = t0 < 0 ? 0u - sc[t0 + kN] : sc[t0] - total;
+            const uint32_t e1 = t1 < 0 ? 0u - sc[t1 + kN] : sc[t1] - total;
+            out[i] += e0 - e1;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) lists[((size_t)l * 2 + c) * kN + tid + 256 * i] = (int32_t)out[i];
+}
+
 // =================================================================================================
 // Encrypted-index table updates: the demultiplexer, a table read's CMux run backwards.
 //   E = C (x) x,  out1 = E,  out0 = x - E (word by word)

@@ -480,6 +480,23 @@ int slot_lut2_block(Slot &s, int p, int n_tables, const int32_t *tv0, size_t n_f
     });
 }
 
+// one device's block [lo, hi) of a d-digit lookup batch: tv0 [n_funcs][tv_polys][N], digits [d][count][stride] on
+// the host (the block's rows of every digit go in), out [n_funcs][count][stride]
+int slot_lut_tree_block(Slot &s, int p, int d, int n_tables, const int32_t *tv0, size_t tv_polys, size_t n_funcs,
+                        const int32_t *digits, int32_t *out, size_t count, size_t lo, size_t hi, size_t stride_ints)
+{
+    const size_t blk = hi - lo, row = blk * stride_ints, tv_ints = n_funcs * tv_polys * EOC_N;
+    int32_t *d_tv, *d_dig, *d_out;
+    return slot_block(s, blk, Staging().take(d_tv, tv_ints).take(d_dig, (size_t)d * row).take(d_out, n_funcs * row),
+                      [&](hipStream_t st) {
+        int rc = copy_in(d_tv, tv0, tv_ints, st);
+        for (int k = 0; !rc && k < d; k++) rc = copy_in(d_dig + (size_t)k * row, digits + ((size_t)k * count + lo) * stride_ints, row, st);
+        if (!rc) rc = eoc_lut_tree_batch_device(s.e, p, d, n_tables, d_tv, n_funcs, d_dig, d_out, blk, st);
+        if (!rc) rc = copy_out_2d(out + lo * stride_ints, count * stride_ints, d_out, row, n_funcs, st);
+        return rc;
+    });
+}
+
 // one device's block [lo, hi) of an integer circuit's instances: wires [n_wires][instances][stride] on the host, every wire's
 // rows of the block in, the netlist, every wire's rows out; tv = the nodes' test polynomials [n_tv][N] on the host
 int slot_int_block(Slot &s, const eoc_inode *nodes, size_t n_nodes, const int32_t *tv, size_t n_tv, int32_t *wires,
@@ -1347,6 +1364,37 @@ extern "C" int eoc_lut2_batch(int p, int n_tables, const int32_t *tables, size_t
     const int32_t *tvp = tv.data();
     return run_blocks_locked("eoc_lut2_batch", count, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
         return slot_lut2_block(s, p, n_tables, tvp, n_funcs, x, y, out, count, lo, hi, stride);
+    });
+}
+
+// d-digit lookups (key mode 2 with an imported packing key, as eoc_lut2_batch): tables [n_funcs][p^d], digits
+// [d][count][n+1], x_1 first; the level-1 polynomials are built on the host
+extern "C" int eoc_lut_tree_batch(int p, int d, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *digits,
+                                  int32_t *out, size_t count)
+{
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
+    if (int rc = enter_locked("eoc_lut_tree_batch", ENGINES)) return rc;
+    if (!tables || !digits || !out || n_funcs == 0) {
+        eoc_set_error("eoc_lut_tree_batch: null argument or no function");
+        return EOC_ERR_ARG;
+    }
+    const int T = n_tables > 1 ? n_tables : 1;
+    size_t n1 = 1; // p^(d-1): the level-1 tables of a function; p^d words of table
+    if (p > 0 && p <= 8 && d >= 2 && d <= 4)
+        for (int k = 1; k < d; k++) n1 *= (size_t)p;
+    const size_t tv_polys = std::max<size_t>(1, n1 / (size_t)T), per_func = tv_polys * EOC_N;
+    std::vector<int32_t> tv(n_funcs * per_func);
+    for (size_t f = 0; f < n_funcs; f++)
+        if (eoc_lut_tree_test_polynomials(p, d, n_tables, tables + f * n1 * (size_t)p, tv.data() + f * per_func) != EOC_OK) {
+            eoc_set_error("eoc_lut_tree_batch: (p, d, n_tables) = (%d, %d, %d) is not supported (p in {2, 4, 8}, 2 <= d <= 4, "
+                          "p^(d-1) <= 64, T in {1, 2, 4, 8}, T divides p, p T <= 16 for T > 1)", p, d, n_tables);
+            return EOC_ERR_ARG;
+        }
+    if (!count) return EOC_OK;
+    const int32_t *tvp = tv.data();
+    return run_blocks_locked("eoc_lut_tree_batch", count, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
+        return slot_lut_tree_block(s, p, d, n_tables, tvp, tv_polys, n_funcs, digits, out, count, lo, hi, stride);
     });
 }
 

@@ -655,6 +655,36 @@ def lut2_margin_sigma(p, n_tables, params, lwe_key, tlwe_key, x_var=None, y_var=
     return (lut_margin_sigma_var(p, max(int(n_tables), 1), vx, lwe_key), lut_margin_sigma_var(p, 1, vy, lwe_key))
 
 
+# ---- multi-digit table lookups: deeper trees -----------------------------------------------------------------------
+def lut_tree_var(params, lwe_key, tlwe_key, d, ksk=None):
+    """variance (torus units) of the error of a d-digit lookup's output (eoc_lut_tree_batch_device) around lut_tree_mean, for a
+    fixed key, lut2_var's composition once per further digit: the level-1 output (predict()['total_var']) + (d - 1) x (the
+    pack of a full list + a regular blind rotation + the key switch).  The exact pack evaluates eoc_tv_pack_device's rule
+    without the transforms' rounding, so pack_var stands unchanged.  d = 2 is lut2_var.  Nothing fitted."""
+    pr = predict(params, lwe_key, tlwe_key, ksk)
+    per_level = pack_var(params, lwe_key, N) + br_enc_var(params, lwe_key, tlwe_key) + pr["ks_var"]
+    return pr["total_var"] + (int(d) - 1) * per_level
+
+
+def lut_tree_mean(params, lwe_key, tlwe_key, d, ksk=None):
+    """mean error (torus units) of a d-digit lookup's output: the level-1 output's total_mean + (d - 1) x (a blind rotation's
+    br_mean + its key switch's ks_mean); the packs' mean is 0.  d = 2 is lut2_mean."""
+    pr = predict(params, lwe_key, tlwe_key, ksk)
+    return pr["total_mean"] + (int(d) - 1) * (pr["br_mean"] + pr["ks_mean"])
+
+
+def lut_tree_margin_sigma(p, d, n_tables, params, lwe_key, tlwe_key, digit_vars=None):
+    """one margin per level of a d-digit lookup at message space p, in predicted standard deviations: level 1 mod-switches
+    x_1 on the grid of T = n_tables, every level k >= 2 is a T = 1 lookup on x_k.  digit_vars: the variances of the d digit
+    samples in front of the call (None, or None entries: a gate-bootstrap output, predict()['total_var'])."""
+    v_out = predict(params, lwe_key, tlwe_key)["total_var"]
+    dv = [None] * int(d) if digit_vars is None else list(digit_vars)
+    if len(dv) != int(d):
+        raise ValueError("lut_tree_margin_sigma: one variance per digit")
+    dv = [v_out if v is None else float(v) for v in dv]
+    return tuple(lut_margin_sigma_var(p, max(int(n_tables), 1) if k == 0 else 1, dv[k], lwe_key) for k in range(int(d)))
+
+
 # ---- inner products with public integer weights on compact lists (DESIGN.md 18) ---------------------------------------------
 def linear_var(params, w_row, slot_var):
     """variance (torus units) of the phase of one output of eoc_dot_device around its mean: ||w||^2 slot_var for independent

@@ -917,6 +917,44 @@ int eoc_lut2_batch_device(eoc_engine *e, int p, int n_tables, const int32_t *d_t
 int eoc_lut2_batch(int p, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *x, const int32_t *y, int32_t *out,
                    size_t count);
 
+/* ---- multi-digit table lookups: deeper trees on an exact matrix-core pack ----------------------------------
+ * F on Z_p^d, p in {2, 4, 8}, 2 <= d <= 4, p^(d-1) <= 64: level 1 bootstraps x_1 against the p^(d-1) public tables
+ * x_1 -> F(x_1, j_2, .., j_d); for every further digit k the EXACT pack puts the p values that differ only in j_k into one
+ * encrypted test polynomial and a blind rotation by x_k (eoc_lut_enc_batch_device's family) selects one of them.
+ *   eoc_tv_pack_exact_device    arguments, layouts and checks of eoc_tv_pack_device.  Per list, with the values v_0 .. v_(p-1),
+ *               h = N / (2p), w = N / p, in wrapping 32-bit integers: samples u_s = v_s (s < p), u_p = v_0 negated word by word;
+ *               S_s = (0, b_s X^0) - sum_m sum_j d_(s,m,j) Row(m, j) with the signed base-16 digits of eoc_pack_device (offset
+ *               2^15 + sum 8 2^(32 - 4j), values in [-8, 8)) and Row the int32 rows of the EOCPKS1 blob; list = sum_s Win_s(X) S_s
+ *               as negacyclic products, Win_0 = X^0 + .. + X^(h-1), Win_s = X^(s w - h) + .. + X^(s w + h - 1) (0 < s < p),
+ *               Win_p = X^(N-h) + .. + X^(N-1).  This is the EXACT value of the rule eoc_tv_pack_device evaluates within the
+ *               rounding of its transforms (at most 8 LSB per chunk of 16 key indices); same noise (noise.pack_var at N filled
+ *               slots).  The constant-slot samples S ((p + 1) x 8 KiB per list) live in a scratch buffer under
+ *               eoc_engine_reserve's rule (EOC_ERR_STATE if it would grow under capture), lists sliced by
+ *               EOC_TFHE_PACK_WS_BYTES (no word depends on it; below one list's need: EOC_ERR_ARG).  Stats as
+ *               eoc_tv_pack_device: one pack launch per slice, packed samples += n_funcs x count x p.  count == 0 is a no-op.
+ *   eoc_lut_tree_test_polynomials   host: table [p^d] of Torus32 output values, table[(..(x_1 p + x_2) p + ..) p + x_d] (at
+ *               d = 2: eoc_lut2_test_polynomials' table); writes tv [p^(d-1) / T][N].  Level-1 table J = j_2 + p j_3 + p^2 j_4
+ *               (j_2 FASTEST, j_d slowest) is x_1 -> F(x_1, j_2, .., j_d); polynomial g holds the tables J = g T .. g T + T - 1.
+ *               EOC_ERR_ARG for a null pointer, p outside {2, 4, 8}, d outside [2, 4], p^(d-1) > 64, T outside {1, 2, 4, 8}, T
+ *               not dividing p, or p T > 16 at T > 1.
+ *   eoc_lut_tree_batch_device   d_tv0 DEVICE [n_funcs][p^(d-1) / T][N], d_digits DEVICE [d][count][n+1] (x_1 first) at message
+ *               space p, d_out DEVICE [n_funcs][count][n+1].  Rows are sliced so that a slice's level-1 outputs (at most 2^20)
+ *               and first-pack lists fit 256 MiB; that buffer grows by eoc_engine_reserve's rule.  Needs the cloud key and the
+ *               packing key (EOC_ERR_NO_KEY).  Stats: bootstraps += n_funcs x count x (p^(d-1) / T + sum_(k=2..d) p^(d-k)),
+ *               keyswitches += n_funcs x count x sum_(k=1..d) p^(d-k).  EOC_ERR_ARG as eoc_lut_tree_test_polynomials, for
+ *               n_tables < 0 and for n_funcs x p^(d-1) outside [1, 32 768].  count == 0 is a no-op.  Nothing is refused on
+ *               noise grounds: noise.lut_tree_var / lut_tree_margin_sigma give the budget.
+ *   eoc_lut_tree_batch          global context, host buffers, synchronous: tables [n_funcs][p^d], digits [d][count][n+1], out
+ *               [n_funcs][count][n+1]; rows are cut into eoc_shard_range blocks, one per engine.  Works in key mode 2 once
+ *               eoc_global_import_packing_key_blob has run; EOC_ERR_NO_KEY otherwise. */
+int eoc_tv_pack_exact_device(eoc_engine *e, int p, const int32_t *d_vals, size_t n_funcs, size_t count, int32_t *d_lists,
+                             void *hip_stream);
+int eoc_lut_tree_test_polynomials(int p, int d, int n_tables, const int32_t *table, int32_t *tv);
+int eoc_lut_tree_batch_device(eoc_engine *e, int p, int d, int n_tables, const int32_t *d_tv0, size_t n_funcs,
+                              const int32_t *d_digits, int32_t *d_out, size_t count, void *hip_stream);
+int eoc_lut_tree_batch(int p, int d, int n_tables, const int32_t *tables, size_t n_funcs, const int32_t *digits, int32_t *out,
+                       size_t count);
+
 /* ---- seeded ciphertexts, selectors and cloud key: masks expanded on the GPU ---------------------------------
  * Every LWE sample, TGSW row and key row is a uniform mask plus a body.  In the seeded forms the holder of the secret key
  * sends the bodies and a PUBLIC 32-byte seed; the receiver regenerates the masks.  No key, no key switch, no extra noise.
