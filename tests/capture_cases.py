@@ -315,6 +315,20 @@ class LutMany(Lut):
 
 
 # ---- integer circuits -------------------------------------------------------------------------------------------------------
+def int_netlist(eoc):
+    """(the circuit, its four inputs): two levels -- a free node in level 1's pre-pass, a 4-term node, a T = 2 node behind the
+    free node, a level-2 node and a last free node.  Shared with tests/interleave_cases.py"""
+    u = eoc.int_circuits.units
+    c = eoc.IntCircuit()
+    x = [c.input(4, fresh=True) for _ in range(4)]
+    f = c.lin([(1, x[0]), (1, x[1])], cst=u(1, 4))
+    n4 = c.lut([x[0], x[1], x[2], (2, x[3])], lambda m: (3 * m + 1) % 4, 4, 4, allow_padding=True)
+    m2 = c.lut_many([f], [lambda m: m % 2, lambda m: (m + 1) % 4], 4, 4, allow_padding=True)
+    n2 = c.lut([(1, n4), (2, m2[0])], lambda m: 3 - m, 4, 4, allow_padding=True)
+    c.lin([(1, n2), (-1, m2[1])], cst=u(2, 4))
+    return c, x
+
+
 class IntCircuit(Case):
     """two levels, 5 rows: a free node in level 1's pre-pass, a 4-term node, a T = 2 node behind the free node, a level-2 node
     and a last free node: LinDescs and k_tv_gather's polynomial indices through the arena"""
@@ -325,14 +339,7 @@ class IntCircuit(Case):
         eoc = self.eoc
         self.p, self.sk, self.orc, self.eng2 = small_keys(eoc, 0, self.n, self.seed)
         self.fresh(self.p).load_cloud_key(self.sk)
-        u = eoc.int_circuits.units
-        c = eoc.IntCircuit()
-        x = [c.input(4, fresh=True) for _ in range(4)]
-        f = c.lin([(1, x[0]), (1, x[1])], cst=u(1, 4))
-        n4 = c.lut([x[0], x[1], x[2], (2, x[3])], lambda m: (3 * m + 1) % 4, 4, 4, allow_padding=True)
-        m2 = c.lut_many([f], [lambda m: m % 2, lambda m: (m + 1) % 4], 4, 4, allow_padding=True)
-        n2 = c.lut([(1, n4), (2, m2[0])], lambda m: 3 - m, 4, 4, allow_padding=True)
-        c.lin([(1, n2), (-1, m2[1])], cst=u(2, 4))
+        c, x = int_netlist(eoc)
         assert c.levels()[1:] == (2, 3)
         self.c, self.nodes, self.tv = c, c.nodes(), c.test_polynomials()
         self.written = sorted({w for k in range(len(self.nodes)) for w in c.node_outputs(k)})

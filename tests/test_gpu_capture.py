@@ -20,6 +20,7 @@ carried as kernel arguments).  A replay varies only what sits in the device buff
 test relies on: after a capture, no call on that engine may grow a buffer.
 
 Every comparison is byte for byte; there is no tolerance in this module.
+The families interleaved on one engine, eagerly, are tests/test_gpu_interleave.py's subject.
 
 Sensitivity (not part of the suite): with push_descs sending captured descriptors through the ring instead of the arena, and
 EOC_CAPTURE_TEST_SAME_SHAPE_CALLS=1100 in the environment -- disturb() then makes that many calls of the captured shape on its

@@ -38,6 +38,20 @@ def test_soak_slice_all_six_kinds(eoc):
     assert cases >= 40
 
 
+def test_soak_slice_every_call_family_interleaved(eoc):
+    """the kinds that joined with the API: every device call family of tests/interleave_cases.py, visited in
+    order twice over on one key context, queued in random windows with random widths and leveled modes (input set 0: the
+    slice's time is its references; the free-running soak draws both sets)"""
+    import soak_parity
+    lines = []
+    calls = 2 * len(soak_parity.family_kinds())
+    cases, bad, per_kind = soak_parity.soak_families(budget_s=30.0, seed=4, max_contexts=1, calls_per_context=calls, round_robin=True,
+                                                     input_sets=(0,), log=lines.append)
+    assert bad == 0, [ln for ln in lines if "MISMATCH" in ln][:8]
+    assert set(per_kind) == set(soak_parity.family_kinds()) and min(per_kind.values()) >= 2, per_kind
+    assert cases >= 40
+
+
 def test_fresh_contexts_whose_first_call_grows_the_workspace(eoc):
     """>= 50 FRESH global contexts; the first call of each is a host-buffer batch, i.e. the call that allocates and
     zero-fills the key-switch operand buffer (engine.hip ensure_ws) right before launching on non-blocking streams"""

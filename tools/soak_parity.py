@@ -11,7 +11,11 @@ Kinds: uniform (one opcode, device pointers), mixed (opcode per row), circuit (r
 through eoc_netlist_optimize; the rewritten netlist runs on the GPU and must equal the oracle's evaluation of that rewritten
 netlist bit for bit, and its outputs must DECRYPT to what the ORIGINAL netlist computes on the plaintext bits), host
 (a FRESH global context whose first call is a host-buffer batch: the path that grows the workspace -- where round 3's
-NULL-stream memset race lived), async (fresh context, three submissions two deep on pinned buffers)."""
+NULL-stream memset race lived), async (fresh context, three submissions two deep on pinned buffers).
+
+soak_families(...) interleaves the device call families that joined since (lookups, expansions, leveled calls, packing, linear
+stages: the registry of tests/interleave_cases.py) on one engine per key context; SOAK_KINDS=families runs it from the command
+line."""
 import os
 import sys
 import time
@@ -208,10 +212,72 @@ def soak(budget_s=120.0, seed=1, kinds=KINDS, max_contexts=None, cases_per_conte
     return cases, bad, per_kind
 
 
+def family_kinds():
+    """the kinds of soak_families: the device call families of tests/interleave_cases.py, drawn from its registry"""
+    import interleave_cases as ic
+    return ic.NAMES
+
+
+def soak_families(budget_s=120.0, seed=1, kinds=None, max_contexts=None, calls_per_context=96, round_robin=False, input_sets=(0, 1),
+                  log=print):
+    """The call families of tests/interleave_cases.py interleaved at random on one engine per key context: random parameter
+    set, LWE dimension and key seed; windows of 1 .. 24 calls queued back to back on a side stream or the NULL stream with
+    no host synchronisation inside; random input set (of `input_sets`), width and leveled-rounding mode; every output compared word for word
+    with the family's reference, guard rows and poison included.  A case is one call.  Returns (cases, mismatches,
+    per_kind_counts); round_robin visits the kinds in order (a short slice then covers every kind)."""
+    import torch
+    import eoc_tfhe_amd as eoc
+    import interleave_cases as ic
+    kinds = tuple(kinds or ic.NAMES)
+    rng = np.random.default_rng(seed)
+    t_end = time.time() + budget_s
+    cases = bad = contexts = 0
+    per_kind = {k: 0 for k in kinds}
+    while time.time() < t_end and (max_contexts is None or contexts < max_contexts):
+        contexts += 1
+        pset, n, kseed = int(rng.integers(0, 2)), int(rng.choice([17, 24, 40])), int(rng.integers(1, 1 << 30))
+        ks = ic.KeySet(eoc, pset, kseed, n=n)
+        eng = eoc.Engine(ks.p)
+        ks.install(eng)
+        runner = ic.Runner(ic.registry(ks), eng)
+        side = torch.cuda.Stream()
+        left, prev = calls_per_context, None
+        while left > 0 and time.time() < t_end:
+            size = min(left, int(rng.integers(1, 25)))
+            mode = bool(rng.integers(0, 2))
+            win = []
+            for _ in range(size):
+                kind = kinds[(cases + len(win)) % len(kinds)] if round_robin else str(rng.choice(list(kinds)))
+                if rng.integers(0, 4) == 0:
+                    mode = not mode
+                win.append((kind, int(rng.choice(list(input_sets))), ic.WIDTHS[int(rng.integers(0, 2))], mode))
+            positions = runner.window(win, side.cuda_stream if rng.integers(0, 2) else None, first_index=calls_per_context - left)
+            torch.cuda.synchronize()
+            wrong = runner.failures(positions, prev)
+            for f in wrong:
+                log(f"set={'AB'[pset]} n={n} seed={kseed} MISMATCH {f}")
+            failed = {f[0] for f in wrong}
+            bad += len(failed)
+            for kind, _, _, _ in win:
+                per_kind[kind] += 1
+            cases, left, prev = cases + size, left - size, win[-1][0]
+            log(f"[{cases}] set={'AB'[pset]} n={n} seed={kseed} window of {size}: {'ok' if not wrong else 'MISMATCH'}")
+        spoiled = runner.inputs_intact()
+        if spoiled:
+            bad += 1
+            log(f"set={'AB'[pset]} n={n} seed={kseed} MISMATCH read-only inputs were written: {spoiled}")
+        eng.close()
+        ks.close()
+    return cases, bad, per_kind
+
+
 if __name__ == "__main__":
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     kinds = tuple(os.environ.get("SOAK_KINDS", ",".join(KINDS)).split(","))
-    cases, bad, per_kind = soak(budget, seed, kinds, log=lambda s: print(s, flush=True))
+    if kinds == ("families",):                                  # SOAK_KINDS=families: the interleaved call families alone
+        cases, bad, per_kind = soak_families(budget, seed, log=lambda s: print(s, flush=True))
+    else:
+        cases, bad, per_kind = soak(budget, seed, kinds, log=lambda s: print(s, flush=True))
     print(f"soak: {cases} cases, {bad} mismatches, per kind {per_kind}")
     sys.exit(1 if bad else 0)
