@@ -1572,10 +1572,8 @@ static inline void ks_mfma_launch(const KSMPlan &pl, uint32_t ngates, const Gate
                                   const void *limbs, hipStream_t st)
 {
     const i4 *lp = static_cast<const i4 *>(limbs);
-    if (pl.nwv == 8)
-        hipLaunchKernelGGL(k_keyswitch_mfma<8>, dim3(pl.gx, ngates), dim3(512), 0, st, descs, a, lp, pl.nsl);
-    else
-        hipLaunchKernelGGL(k_keyswitch_mfma<4>, dim3(pl.gx, ngates), dim3(256), 0, st, descs, a, lp, pl.nsl);
+    // the plan's nwv is 4: the <8> instance no plan could pick is no longer compiled
+    hipLaunchKernelGGL(k_keyswitch_mfma<4>, dim3(pl.gx, ngates), dim3(256), 0, st, descs, a, lp, pl.nsl);
 }
 
 // =================================================================================================

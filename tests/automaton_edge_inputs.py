@@ -42,10 +42,13 @@ def weight_pair(k):
     return W_ALL[m // 8], W_ALL[m % 8]
 
 
-def derived_rows(l, Bgbit):
-    """[(name, D_k)]: every row of cmux_differences but `alternating`, in the order edge_automaton lays the pairs out"""
-    return [(f"{nm}[{i}]", row) for nm, D in lei.cmux_differences(l, Bgbit).items() if nm != "alternating"
-            for i, row in enumerate(D)]
+def derived_rows(l, Bgbit, extra=(), shift=0):
+    """[(name, D_k)]: every row of cmux_differences but `alternating`, in the order edge_automaton lays the pairs out, then the
+    rows of `extra` ((name, uint32 [2][N]) pairs); every word minus `shift`, wrapping (tests/leveled_round_cases.py: the
+    rounding twins add it back)"""
+    rows = [(f"{nm}[{i}]", row) for nm, D in lei.cmux_differences(l, Bgbit).items() if nm != "alternating"
+            for i, row in enumerate(D)] + [(nm, np.asarray(row, np.uint32)) for nm, row in extra]
+    return [(nm, lei._i32(row.astype(np.int64) - shift).view(np.uint32)) for nm, row in rows] if shift else rows
 
 
 def _turn(poly, w):
@@ -53,11 +56,12 @@ def _turn(poly, w):
     return successor(poly[None], 0, (2 * N - w) % (2 * N))
 
 
-def edge_automaton(l, Bgbit, seed=0):
+def edge_automaton(l, Bgbit, seed=0, extra=(), shift=0):
     """(trans [Q][4] int32, prev [Q][2][N] int32, names [Q]).  Pair k = states (2k, 2k + 1) holds (P0, P1) with
     X^(-w1) P1 - X^(-w0) P0 = D_k in wrapping arithmetic: P0 random full-range words, P1 = X^(w1) (D_k + X^(-w0) P0).
     State 2k = (2k, w0, 2k+1, w1) decomposes D_k, state 2k+1 = (2k+1, w1, 2k, w0) decomposes -D_k.  `seed` changes the random
-    words only: the differences are the same."""
+    words only: the differences are the same.  `extra` and `shift`: derived_rows; the rows of `extra` follow the derived ones,
+    ahead of the alternating pairs, and draw their random words after them."""
     rng = np.random.default_rng(17000 + 1000 * l + Bgbit + seed)
     trans, prev, names = [], [], []
 
@@ -67,7 +71,7 @@ def edge_automaton(l, Bgbit, seed=0):
         prev.extend([P0, P1])
         names.extend([name, name + " negated"])
 
-    for k, (name, D) in enumerate(derived_rows(l, Bgbit)):
+    for k, (name, D) in enumerate(derived_rows(l, Bgbit, extra, shift)):
         w0, w1 = weight_pair(k)
         P0 = lei._i32(rng.integers(-2**31, 2**31, (2, N)))
         P1 = _turn(lei._i32(D.astype(np.int64) + successor(P0[None], 0, w0)), w1)
@@ -98,9 +102,9 @@ def weight_sweep(seed=0):
     return trans.astype(np.int32), np.ascontiguousarray(lei._i32(prev))
 
 
-def full_scale_states(l, Bgbit, seed=0):
+def full_scale_states(l, Bgbit, seed=0, shift=0):
     """(trans [4][4], prev [4][2][N], names [4]): the digits_min and digits_max pairs of edge_automaton, renumbered"""
-    trans, prev, names = edge_automaton(l, Bgbit, seed)
+    trans, prev, names = edge_automaton(l, Bgbit, seed, shift=shift)
     keep = [q for q, nm in enumerate(names) if nm.startswith(("digits_min", "digits_max"))]
     assert len(keep) == 4
     new = {q: i for i, q in enumerate(keep)}

@@ -35,6 +35,24 @@ def engine_isa():
     return _ISA[0]
 
 
+def multi_isa():
+    """Assembly text of eoc_tfhe_amd/csrc/multi.hip, the library's second code object (one small kernel: not remembered)"""
+    if not os.path.exists(HIPCC):
+        import pytest
+        pytest.skip("no hipcc")
+    with tempfile.TemporaryDirectory(prefix="eoc_isa_") as tmp:
+        out = os.path.join(tmp, "multi.s")
+        subprocess.run([HIPCC, *ISA_FLAGS, "-o", out, os.path.join(ROOT, "eoc_tfhe_amd", "csrc", "multi.hip")], check=True, cwd=tmp)
+        with open(out) as f:
+            return f.read()
+
+
+def demangled(names):
+    """the mangled names `names` demangled by c++filt (binutils), in order"""
+    out = subprocess.run([shutil.which("c++filt") or "c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
+    return out.stdout.splitlines()
+
+
 def kernel_meta(text):
     """mangled kernel name -> the code object's metadata: registers, spills, scratch and LDS bytes"""
     meta = {}

@@ -1,5 +1,5 @@
-"""ISA guards of the matrix-core key switch (hipcc cross-compiles gfx950 here; no GPU): k_keyswitch_mfma exists in both
-instances ks_mfma_launch dispatches (4 waves per workgroup: the shipped plan; 8: the alternative tools/ubench_ks_mfma.hip measures), runs on v_mfma_i32_32x32x32_i8, keeps its 128 accumulator registers and everything else
+"""ISA guards of the matrix-core key switch (hipcc cross-compiles gfx950 here; no GPU): k_keyswitch_mfma exists in the one
+instance ks_mfma_launch dispatches (4 waves per workgroup: the shipped plan; the alternative of 8 is instantiated by tools/ubench_ks_mfma.hip alone), runs on v_mfma_i32_32x32x32_i8, keeps its 128 accumulator registers and everything else
 in the register file (no spill, no scratch) at two waves per SIMD, and the limb-image builder k_ksk_limbs exists.
 tests/test_isa_guard.py (unchanged) checks the whole library for the stores that must not be there."""
 import re
@@ -17,7 +17,7 @@ def isa():
 def test_mfma_key_switch_exists_without_spill_or_scratch(isa):
     meta, bodies = kernel_meta(isa), kernel_bodies(isa)
     names = sorted(k for k in meta if "16k_keyswitch_mfma" in k)
-    assert len(names) == 2 and any("ILi4E" in k for k in names) and any("ILi8E" in k for k in names), names
+    assert len(names) == 1 and "ILi4E" in names[0], names              # <8>: never dispatched, no longer compiled
     for name in names:
         m = meta[name]
         assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (name, m)

@@ -57,4 +57,5 @@ def test_results_leave_through_plain_vector_dword_stores(isa, sub):
 def test_earlier_kernel_counts_are_unchanged(isa):
     meta, _ = isa
     assert len([k for k in meta if "k_tvpack_cols" in k]) == 3 and len([k for k in meta if "k_ksk_limbs" in k]) == 1
-    assert len([k for k in meta if "k_keyswitch_mfma" in k]) == 2 and len([k for k in meta if "k_pack_rows" in k]) == 1
+    # k_keyswitch_mfma: one since the <8> instance no launch could reach is no longer compiled
+    assert len([k for k in meta if "k_keyswitch_mfma" in k]) == 1 and len([k for k in meta if "k_pack_rows" in k]) == 1

@@ -274,6 +274,60 @@ def test_short_truncating_run_stays_inside_the_truncating_model(eoc):
     check_run(eoc, sk, p, aut, table, bits, tl[0, 0], out, False)
 
 
+# ---- the references of the twins' instance tests, ahead of the device ------------------------------------------------------------
+INSTANCE_SHAPES = [(name, cfg["l"], cfg["Bgbit"]) for name, cfg in le.cmux_full_scale.items()] + [("k_cmux<4,0>", 4, 7)]
+
+
+@pytest.mark.parametrize("name,l,Bgbit", INSTANCE_SHAPES, ids=[f"{n}@({l},{b})" for n, l, b in INSTANCE_SHAPES])
+def test_instance_references_keep_the_contract_and_the_shifted_row_identities(eoc, name, l, Bgbit):
+    """what tests/test_gpu_leveled_round_instances.py sends to the MI355X at this shape, on the reference alone: every
+    computation under test_gpu_br_instances.reference (recorded maximum below 2^51, asserted there), the full-scale ones in the
+    instance's [lo, hi) (asserted in tests/leveled_round_cases.py), and the rounding reference of a row less h equal to the
+    TRUNCATING reference of the row: the identity the device test uses as its second route"""
+    import leveled_round_cases as lrc
+    from test_gpu_br_instances import custom_params, reference
+    from test_gpu_cmux_instances import pool_map
+    p = custom_params(eoc, l, Bgbit, 16)
+    op = cx.orc_params(p)
+    h = lr.half(p)
+    assert h == lrc.half(l, Bgbit) == ((1 << (31 - l * Bgbit)) if l * Bgbit < 32 else 0)
+    tag = lrc.tag_of(name, l, Bgbit)
+    sk = eoc.SecretKey(p, 83, with_cloud_key=False)
+    fft = cx.to_fft(sk.encrypt_selector_bits([0, 1], enc_seed=5))
+
+    # the CMux: in1 - h
+    names, in0, in1, items_t = lrc.cmux_rows(l, Bgbit)
+    assert len(in0) == 2 * len(names) and items_t == 2 * sum(len(a) for a, _ in le.cmux_inputs(l, Bgbit).values())
+    want_t = lrc.cmux_truncating(tag, op, fft, in0, in1, items_t)
+    want_r = lrc.cmux_rounding(tag, op, fft, in0, in1)
+    assert (not np.array_equal(want_r[:items_t], want_t)) == (h != 0)
+    shifted = lrc.minus(in1[:items_t], h)
+    got = reference(("rcmux", tag, "shifted"),
+                    lambda: np.stack(pool_map(lambda k: lr.cmux(op, fft[k % 2], in0[k], shifted[k]), items_t)))
+    assert np.array_equal(got, want_t)
+
+    # the demultiplexer: x - h
+    names, x, items_t = lrc.demux_rows(l, Bgbit)
+    want_t = lrc.demux_truncating(tag, op, fft, x, items_t)
+    want_r = lrc.demux_rounding(tag, op, fft, x)
+    assert (not np.array_equal(want_r[:items_t], want_t)) == (h != 0)
+    shifted = lrc.minus(x[:items_t], h)
+    got = reference(("rdemux", tag, "shifted"),
+                    lambda: np.stack(pool_map(lambda k: np.stack(lr.demux(op, fft[k % 2], shifted[k])), items_t)))
+    assert np.array_equal(got[:, 1], want_t[:, 1]) and np.array_equal(got[:, 0], lrc.minus(want_t[:, 0], h))
+
+    # the step: its rows and, at the instance's own shape, the three full-scale references
+    vectors = lrc.step_vectors(l, Bgbit)
+    cut, want_of = lrc.step_edges(tag, op, fft, vectors)
+    states = len(vectors[0][2])
+    assert want_of(2, 1, states).shape == (states, 2, N)
+    if tag == name:
+        kfft = cx.to_fft(le.constant_selector(l, le.cmux_full_scale[name]["K"])[None])[0]
+        assert lrc.cmux_full_scale(name, op, kfft, l, Bgbit)[2].shape == (2, 2, N)
+        assert lrc.demux_full_scale(name, op, kfft, l, Bgbit)[1].shape == (2, 2, 2, N)
+        assert lrc.step_full_scale(name, op, kfft, l, Bgbit)[3].shape == (4, 2, N)
+
+
 # ---- API ----------------------------------------------------------------------------------------------------------------------
 def test_symbols_and_wrappers(eoc):
     L = eoc.lib()

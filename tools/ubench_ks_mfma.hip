@@ -69,7 +69,11 @@ static KSMPlan plan_of(uint32_t S, int n1p)
 }
 static void launch_new(const KSArgs &a, uint32_t S, const int8_t *limbs)
 {
-    ks_mfma_launch(plan_of(S, a.n1p), 1, nullptr, a, limbs, 0);
+    const KSMPlan pl = plan_of(S, a.n1p);
+    if (pl.nwv == 8) // the alternative the library's plan never picks and the library no longer compiles: instantiated here
+        hipLaunchKernelGGL(k_keyswitch_mfma<8>, dim3(pl.gx, 1), dim3(512), 0, 0, nullptr, a, reinterpret_cast<const i4 *>(limbs), pl.nsl);
+    else
+        ks_mfma_launch(pl, 1, nullptr, a, limbs, 0);
 }
 
 int main(int argc, char **argv)
