@@ -343,6 +343,12 @@ def lib():
         "eoc_conv_extract_device": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, vp]),
         "eoc_engine_conv_launches": (u64, [vp]),
         "eoc_conv_linear": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, sz, vp]),
+        # dense layers on LWE samples (include/eoc_tfhe_lwe.h)
+        "eoc_lwe_weights_image_bytes": (sz, [sz, sz]),
+        "eoc_lwe_weights_to_device": (C.c_int, [vp, vp, sz, sz, vp, vp]),
+        "eoc_lwe_matmul_device": (C.c_int, [vp, vp, sz, sz, vp, sz, sz, vp, vp, vp]),
+        "eoc_engine_lwe_matmul_launches": (u64, [vp]),
+        "eoc_lwe_matmul": (C.c_int, [vp, sz, sz, vp, sz, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1166,6 +1172,35 @@ class Engine:
         """k_dot_mask launches so far (eoc_engine_dot_launches): one per slice of a call's input vectors"""
         return int(self.L.eoc_engine_dot_launches(self.h))
 
+    def lwe_weights_image_bytes(self, rows, cols):
+        """bytes of the device image of a rows x cols model of lwe_matmul_device (eoc_lwe_weights_image_bytes; 0 for a shape
+        that is refused: rows in [1, 2^20], cols in [1, 2^16])"""
+        return int(self.L.eoc_lwe_weights_image_bytes(int(rows), int(cols)))
+
+    def lwe_weights_to_device(self, weights, d_image, stream=None):
+        """Public int8 weights [rows][cols], every value in [-127, 127] -> the matrix-core operand image at d_image
+        (eoc_lwe_weights_to_device; lwe_weights_image_bytes(rows, cols) bytes).  A model load: no key, synchronous.
+        Returns (rows, cols)."""
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.size == 0 or not np.issubdtype(w.dtype, np.integer) or np.abs(w.astype(np.int64)).max() > 127:
+            raise EocError(f"lwe_weights_to_device: weights must be a non-empty integer matrix [rows][cols] in [-127, 127], got "
+                           f"{w.dtype} {w.shape}")
+        w = np.ascontiguousarray(w, np.int8)
+        _check(self.L.eoc_lwe_weights_to_device(self.h, w.ctypes.data, w.shape[0], w.shape[1], d_image, stream),
+               "eoc_lwe_weights_to_device")
+        return w.shape
+
+    def lwe_matmul_device(self, d_image, rows, cols, d_cts, width, batch, d_bias, d_out, stream=None):
+        """A public int8 matrix on LWE samples (eoc_lwe_matmul_device): d_cts [batch][cols][width] int32, d_bias
+        [rows] Torus32 or None, d_out [batch][rows][width]: out[b][r] = sum_k w[r][k] cts[b][k] word by word mod 2^32, the bias
+        on the body (last) word -- samples under the same key.  No key, no workspace; legal under capture."""
+        _check(self.L.eoc_lwe_matmul_device(self.h, d_image, rows, cols, d_cts, width, batch, d_bias, d_out, stream),
+               "eoc_lwe_matmul_device")
+
+    def lwe_matmul_launches(self):
+        """k_lwe_matmul launches so far (eoc_engine_lwe_matmul_launches): one per call of up to 65 535 vectors"""
+        return int(self.L.eoc_engine_lwe_matmul_launches(self.h))
+
     def conv_slots_to_device(self, slots, lists_per_vec, d_slots, stream=None):
         """A public slot table [n_slots] (entry s: slot s mod N of list s / N of a vector's lists_per_vec lists; any order,
         repeats allowed) -> the device table at d_slots, n_slots uint32 (eoc_conv_slots_to_device).  Every entry is checked
@@ -1742,6 +1777,28 @@ def linear(weights, lists, bias=None):
     out = np.empty((lists.shape[0], rows, _global_n("linear") + 1), np.int32)
     _check(lib().eoc_linear(w.ctypes.data, rows, cols, lists.ctypes.data, lists.shape[0],
                             None if bias is None else bias.ctypes.data, out.ctypes.data), "eoc_linear")
+    return out
+
+
+def lwe_matmul(weights, cts, bias=None):
+    """eoc_lwe_matmul on the global context (no key needed): public int8 weights [rows][cols] in [-127, 127], LWE samples
+    cts [batch][cols][width], bias [rows] Torus32 or None -> [batch][rows][width], out[b][r] = sum_k w[r][k] cts[b][k] word
+    by word mod 2^32, the bias on the body (last) word"""
+    w = np.asarray(weights)
+    if w.ndim != 2 or w.size == 0 or not np.issubdtype(w.dtype, np.integer) or np.abs(w.astype(np.int64)).max() > 127:
+        raise EocError(f"lwe_matmul: weights must be a non-empty integer matrix [rows][cols] in [-127, 127], got {w.dtype} {w.shape}")
+    w = np.ascontiguousarray(w, np.int8)
+    rows, cols = w.shape
+    cts = np.ascontiguousarray(cts, np.int32)
+    if cts.ndim != 3 or cts.shape[1] != cols or cts.shape[2] < 1:
+        raise EocError(f"lwe_matmul: cts must be [batch][{cols}][width], got {cts.shape}")
+    if bias is not None:
+        bias = np.ascontiguousarray(bias, np.int32)
+        if bias.shape != (rows,):
+            raise EocError(f"lwe_matmul: bias must be [{rows}], got {bias.shape}")
+    out = np.empty((cts.shape[0], rows, cts.shape[2]), np.int32)
+    _check(lib().eoc_lwe_matmul(w.ctypes.data, rows, cols, cts.ctypes.data, cts.shape[2], cts.shape[0],
+                                None if bias is None else bias.ctypes.data, out.ctypes.data), "eoc_lwe_matmul")
     return out
 
 

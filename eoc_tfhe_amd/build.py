@@ -54,7 +54,10 @@ def build_stamps(verbose=False):
     mul_obj = os.path.join(OBJ, "multi.o")
     if not os.path.exists(mul_obj):
         _run([HIPCC, *HIP_FLAGS, "-c", os.path.join(CSRC, "multi.hip"), "-o", mul_obj], verbose)
-    _run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", eng_obj, mul_obj, host_obj, leg_obj, "-o", out,
+    lmm_obj = os.path.join(OBJ, "lwe_matmul.o")
+    if not os.path.exists(lmm_obj):
+        _run([HIPCC, *HIP_FLAGS, "-c", os.path.join(CSRC, "lwe_matmul.hip"), "-o", lmm_obj], verbose)
+    _run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", eng_obj, mul_obj, lmm_obj, host_obj, leg_obj, "-o", out,
           "-lgomp", "-ldl", "-Wl,-rpath,/opt/rocm/lib"], verbose)
     return out
 
@@ -64,8 +67,11 @@ def build(force=False, verbose=False, extra_hip_flags=()):
     hdrs = [os.path.join(CSRC, f) for f in ("kernels.hip.h", "blind_rotate_pair.inc", "blind_rotate_wide.inc",
                                              "ext_product_pair.inc", "leveled_pair.inc", "leveled_kernels.inc", "canon_twiddles.h", "common.h")]
     hdrs.append(os.path.join(ROOT, "include", "eoc_tfhe_gpu.h"))
+    hdrs.append(os.path.join(ROOT, "include", "eoc_tfhe_lwe.h"))
+    hdrs.append(os.path.join(CSRC, "lwe_matmul.h"))
     eng_src, eng_obj = os.path.join(CSRC, "engine.hip"), os.path.join(OBJ, "engine.o")
     mul_src, mul_obj = os.path.join(CSRC, "multi.hip"), os.path.join(OBJ, "multi.o")
+    lmm_src, lmm_obj = os.path.join(CSRC, "lwe_matmul.hip"), os.path.join(OBJ, "lwe_matmul.o")
     host_src, host_obj = os.path.join(CSRC, "host.cpp"), os.path.join(OBJ, "host.o")
     leg_src, leg_obj = os.path.join(CSRC, "legacy.cpp"), os.path.join(OBJ, "legacy.o")
     hdrs.append(os.path.join(CSRC, "host_internal.h"))
@@ -73,12 +79,15 @@ def build(force=False, verbose=False, extra_hip_flags=()):
         _run([HIPCC, *HIP_FLAGS, *extra_hip_flags, "-c", eng_src, "-o", eng_obj], verbose)
     if force or _newer(mul_obj, [mul_src] + hdrs):
         _run([HIPCC, *HIP_FLAGS, "-c", mul_src, "-o", mul_obj], verbose)
+    # the third code object: k_lwe_matmul alone; it reads its own header only
+    if force or _newer(lmm_obj, [lmm_src, os.path.join(CSRC, "lwe_matmul.h")]):
+        _run([HIPCC, *HIP_FLAGS, "-c", lmm_src, "-o", lmm_obj], verbose)
     if force or _newer(host_obj, [host_src] + hdrs):
         _run([GXX, *CXX_FLAGS, "-c", host_src, "-o", host_obj], verbose)
     if force or _newer(leg_obj, [leg_src] + hdrs):
         _run([GXX, *CXX_FLAGS, "-c", leg_src, "-o", leg_obj], verbose)
-    if force or _newer(LIB, [eng_obj, mul_obj, host_obj, leg_obj]):
-        _run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", eng_obj, mul_obj, host_obj, leg_obj, "-o", LIB,
+    if force or _newer(LIB, [eng_obj, mul_obj, lmm_obj, host_obj, leg_obj]):
+        _run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", eng_obj, mul_obj, lmm_obj, host_obj, leg_obj, "-o", LIB,
               "-lgomp", "-ldl", "-Wl,-rpath,/opt/rocm/lib"], verbose)
     return LIB
 

@@ -8,6 +8,8 @@
 #include "canon_twiddles.h"
 #include "common.h"
 #include "../../include/eoc_tfhe_gpu.h"
+#include "../../include/eoc_tfhe_lwe.h"
+#include "lwe_matmul.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -139,6 +141,7 @@ struct eoc_engine {
     // eoc_conv_linear_device, between k_conv_lists and k_conv_extract; held to EOC_TFHE_DOT_WS_BYTES together with the spectra
     Scratch conv_lists;
     uint64_t conv_launches = 0; // k_conv_lists launches
+    uint64_t lwe_matmul_launches = 0; // k_lwe_matmul launches (the kernel is in lwe_matmul.hip)
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline)
     bool profiling = false;
     struct Span { hipEvent_t a, b; int kind; };
@@ -3224,6 +3227,75 @@ extern "C" int eoc_conv_extract_device(eoc_engine *e, const int32_t *d_lists, si
                                  d_out + b0 * n_slots * stride, st);
     return rc;
 }
+
+// ---- dense layers on LWE samples: a public int8 matrix on the matrix cores (include/eoc_tfhe_lwe.h) ----
+// Host code only: the kernel, its image format and its launcher are the library's third code object (lwe_matmul.hip).
+extern "C" size_t eoc_lwe_weights_image_bytes(size_t rows, size_t cols) { return lwe_image_bytes(rows, cols); }
+
+// A model load, as eoc_weights_to_device: validated on the host, no key; the image is built on the host and is on the device
+// when the call returns (`hip_stream` is drained)
+extern "C" int eoc_lwe_weights_to_device(eoc_engine *e, const int8_t *h_w, size_t rows, size_t cols, void *d_image, void *hip_stream)
+try {
+    if (!e || !h_w || !d_image) {
+        eoc_set_error("eoc_lwe_weights_to_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!lwe_shape_ok(rows, cols)) {
+        eoc_set_error("eoc_lwe_weights_to_device: rows = %zu, cols = %zu: rows must lie in [1, 2^20], cols in [1, 2^16]", rows, cols);
+        return EOC_ERR_ARG;
+    }
+    for (size_t k = 0; k < rows * cols; k++)
+        if (h_w[k] == -128) {
+            eoc_set_error("eoc_lwe_weights_to_device: weight (%zu, %zu) is -128; weights lie in [-127, 127]", k / cols, k % cols);
+            return EOC_ERR_ARG;
+        }
+    const size_t bytes = lwe_image_bytes(rows, cols);
+    std::vector<char> img(bytes);
+    lwe_image_build(h_w, rows, cols, img.data());
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (stream_is_capturing(st)) {
+        eoc_set_error("eoc_lwe_weights_to_device: a model load synchronises; it cannot be captured");
+        return EOC_ERR_STATE;
+    }
+    HIP_TRY(hipMemcpyAsync(d_image, img.data(), bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st)); // the host image ends with this call
+    return EOC_OK;
+} catch (...) {
+    eoc_set_error("eoc_lwe_weights_to_device: out of memory");
+    return EOC_ERR_ALLOC;
+}
+
+// No key, no workspace, no descriptor ring slot: legal under capture whatever ran before
+extern "C" int eoc_lwe_matmul_device(eoc_engine *e, const void *d_image, size_t rows, size_t cols, const int32_t *d_cts, size_t width,
+                                     size_t batch, const int32_t *d_bias, int32_t *d_out, void *hip_stream)
+{
+    if (e && batch * rows == 0) return EOC_OK;
+    if (!e || !d_image || !d_cts || !d_out) {
+        eoc_set_error("eoc_lwe_matmul_device: null argument");
+        return EOC_ERR_ARG;
+    }
+    if (!lwe_shape_ok(rows, cols) || width < 1 || width > kLweMaxWidth) {
+        eoc_set_error("eoc_lwe_matmul_device: rows = %zu, cols = %zu, width = %zu: rows must lie in [1, 2^20], cols in [1, 2^16], "
+                      "width in [1, 4096]", rows, cols, width);
+        return EOC_ERR_ARG;
+    }
+    const size_t out_bytes = batch * rows * width * 4;
+    if (dot_ranges_overlap(d_out, out_bytes, d_cts, batch * cols * width * 4) ||
+        dot_ranges_overlap(d_out, out_bytes, d_image, lwe_image_bytes(rows, cols)) ||
+        dot_ranges_overlap(d_out, out_bytes, d_bias, rows * 4)) {
+        eoc_set_error("eoc_lwe_matmul_device: the output must not overlap the samples, the weight image or the bias");
+        return EOC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    SpanGuard span(e, st, KIND_KEYSWITCH);
+    HIP_TRY(lwe_matmul_launch(d_image, rows, cols, d_cts, width, batch, d_bias, d_out, st, &e->lwe_matmul_launches));
+    return EOC_OK;
+}
+extern "C" uint64_t eoc_engine_lwe_matmul_launches(eoc_engine *e) { return e ? e->lwe_matmul_launches : 0; }
 
 // ---- introspection: profiling, statistics, counters ------------------------------------------
 extern "C" int eoc_engine_set_profiling(eoc_engine *e, int on)

@@ -13,6 +13,7 @@
 // the result by one asynchronous copy; pageable caller buffers go through the runtime's staged copies.
 #include "common.h"
 #include "host_internal.h"
+#include "../../include/eoc_tfhe_lwe.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: the library is dlopen'ed when a broadcast is wanted
@@ -653,6 +654,25 @@ int slot_conv_block(Slot &s, const int8_t *h_w, size_t rows, size_t cols, const 
         if (!rc) rc = copy_in(d_lists, lists + lo * vec_ints, blk * vec_ints, st);
         if (!rc && bias) rc = copy_in(d_bias, bias, rows, st);
         if (!rc) rc = eoc_conv_linear_device(s.e, d_img, rows, cols, d_lists, blk, bias ? d_bias : nullptr, d_tab, n_slots, d_out, st);
+        if (!rc) rc = copy_out(out + lo * out_ints, d_out, blk * out_ints, st);
+        return rc;
+    });
+}
+
+// one device's block of WHOLE input vectors [lo, hi) of a public int8 matrix on LWE samples: the weights become
+// the device image here (every engine builds its own), cts [batch][cols][width] and bias [rows] (or NULL) in,
+// out [batch][rows][width] on the host.  The width is the call's, not the engine's n + 1
+int slot_lwe_matmul_block(Slot &s, const int8_t *h_w, size_t rows, size_t cols, const int32_t *cts, size_t width, const int32_t *bias,
+                          int32_t *out, size_t lo, size_t hi)
+{
+    const size_t blk = hi - lo, vec_ints = cols * width, out_ints = rows * width;
+    int32_t *d_img, *d_cts, *d_bias, *d_out;
+    return slot_block(s, blk, Staging().take(d_img, eoc_lwe_weights_image_bytes(rows, cols) / 4).take(d_cts, blk * vec_ints)
+                                  .take(d_bias, rows).take(d_out, blk * out_ints), [&](hipStream_t st) {
+        int rc = eoc_lwe_weights_to_device(s.e, h_w, rows, cols, d_img, st);
+        if (!rc) rc = copy_in(d_cts, cts + lo * vec_ints, blk * vec_ints, st);
+        if (!rc && bias) rc = copy_in(d_bias, bias, rows, st);
+        if (!rc) rc = eoc_lwe_matmul_device(s.e, d_img, rows, cols, d_cts, width, blk, bias ? d_bias : nullptr, d_out, st);
         if (!rc) rc = copy_out(out + lo * out_ints, d_out, blk * out_ints, st);
         return rc;
     });
@@ -1529,6 +1549,29 @@ extern "C" int eoc_linear(const int8_t *h_w, size_t rows, size_t cols, const int
     if (!batch) return EOC_OK;
     return run_blocks_locked("eoc_linear", batch, [=](Slot &s, size_t lo, size_t hi, size_t stride) {
         return slot_linear_block(s, h_w, rows, cols, h_lists, h_bias, h_out, lo, hi, stride);
+    });
+}
+
+// a public int8 matrix on LWE samples (the engines need no key at all): WHOLE input vectors are cut over the
+// engines; the model is validated by every engine's load before it touches its device
+extern "C" int eoc_lwe_matmul(const int8_t *h_w, size_t rows, size_t cols, const int32_t *h_cts, size_t width, size_t batch,
+                              const int32_t *h_bias, int32_t *h_out)
+{
+    if (!h_w || !h_cts || !h_out) {
+        eoc_set_error("eoc_lwe_matmul: null argument");
+        return EOC_ERR_ARG;
+    }
+    KeyedCall call;
+    if (call.key.rc) return call.key.rc;
+    if (int rc = enter_locked("eoc_lwe_matmul", ENGINES)) return rc;
+    if (eoc_lwe_weights_image_bytes(rows, cols) == 0 || width < 1 || width > 4096) {
+        eoc_set_error("eoc_lwe_matmul: rows = %zu, cols = %zu, width = %zu: rows must lie in [1, 2^20], cols in [1, 2^16], width in "
+                      "[1, 4096]", rows, cols, width);
+        return EOC_ERR_ARG;
+    }
+    if (!batch) return EOC_OK;
+    return run_blocks_locked("eoc_lwe_matmul", batch, [=](Slot &s, size_t lo, size_t hi, size_t) {
+        return slot_lwe_matmul_block(s, h_w, rows, cols, h_cts, width, h_bias, h_out, lo, hi);
     });
 }
 

@@ -15,7 +15,11 @@ Convolution layers: a ConvLayer is Engine.conv_linear_device -- e
 coefficient of ONE negacyclic product, so a layer costs one spectral product per (output channel, input channel) and one key
 switch per output position that is kept --, the same activation, and one Engine.pack_device per (vector, channel): channel c's
 activations land in slots 0 ... of list c, and the next layer is a ConvLayer on the smaller grid or a DenseLayer with
-cols = channels * N (pad_dense_weights)."""
+cols = channels * N (pad_dense_weights).
+
+Dense layers on LWE samples (opt-in): with hidden="lwe" a DenseLayer behind a DenseLayer is
+Engine.lwe_matmul_device on the LUT outputs before it -- no pack, no packing key, no key switch behind the sum, and an error of
+exactly sum_k w_k e_k (noise.lwe_linear_var); Network.run_device_samples runs layer 0 that way too, on LWE inputs."""
 import numpy as np
 
 N = 1024
@@ -240,19 +244,39 @@ class Network:
         return (v, pres) if return_pre else v
 
     # ---- pricing: ranges and decision margins before anything runs -----------------------------------------------------
-    def layer_sigma(self, params, lwe_key, tlwe_key, pk=None, ksk=None):
+    def _lwe_link(self, i, hidden, input_var=None):
+        """whether layer i reads LWE samples through Engine.lwe_matmul_device: layer 0 when the inputs are
+        samples (input_var given), a DenseLayer behind a DenseLayer under hidden="lwe".  A link behind a ConvLayer keeps the
+        pack: its next layer reads padded list columns."""
+        if hidden not in ("pack", "lwe"):
+            raise ValueError(f"hidden must be 'pack' or 'lwe', got {hidden!r}")
+        if i == 0:
+            return input_var is not None
+        return hidden == "lwe" and isinstance(self.layers[i], DenseLayer) and isinstance(self.layers[i - 1], DenseLayer)
+
+    def layer_sigma(self, params, lwe_key, tlwe_key, pk=None, ksk=None, hidden="pack", input_var=None):
         """per layer, the predicted standard deviation [rows] (torus units) of the sample in front of the activation's mod
         switch, rounding included: sqrt(||w||^2 V_slot + V_ks + V_ms), V_slot = noise.compact_var for the fresh lists of layer
         0 (with pk: noise.linear_var_row, exact for the row, in place of ||w||^2 V_slot) and a bootstrap output's total_var +
         noise.pack_var behind a pack; and the predicted |mean| per row.  A ConvLayer is priced per output channel -- every slot
         of a channel has the channel's ||taps||^2 (with pk: linear_var_row of the channel's row, the same for every slot, since
         noise.conv_row only multiplies the weight polynomial by a power of X) -- and its arrays are per output, channel-major;
-        on layer 0 with pk the |mean| of a slot is the correlation of the taps with noise.compact_offset"""
+        on layer 0 with pk the |mean| of a slot is the correlation of the taps with noise.compact_offset.
+        hidden="lwe": a DenseLayer behind a DenseLayer reads the LUT outputs themselves (Engine.lwe_matmul_device): slot
+        variance total_var with no pack_var, no key switch behind the sum (neither ks_var nor ks_mean), mean
+        w.sum(1) total_mean -- noise.lwe_linear_var.  input_var (run_device_samples): layer 0 reads LWE samples of that
+        variance and zero mean, priced the same way; None: fresh lists, as above."""
         from . import noise
         pr = noise.predict(params, lwe_key, tlwe_key, ksk)
         out = []
         for i, ly in enumerate(self.layers):
             w = ly.weights.astype(np.float64)
+            if self._lwe_link(i, hidden, input_var):
+                slot = float(input_var) if i == 0 else pr["total_var"]
+                mean = np.zeros(ly.n_out) if i == 0 else w.sum(1) * pr["total_mean"]
+                lin = np.array([noise.lwe_linear_var(r, slot) for r in w])
+                out.append((np.sqrt(lin + noise.modswitch_var(lwe_key)), np.abs(mean)))
+                continue
             if i == 0:
                 slot = noise.compact_var(params, tlwe_key, pk)
                 mean = ly.fresh_offset(params, pk, tlwe_key) if pk is not None else np.zeros(ly.n_out)
@@ -267,7 +291,7 @@ class Network:
             out.append((np.sqrt(var), np.abs(mean + pr["ks_mean"])))
         return out
 
-    def check(self, params, lwe_key, tlwe_key, x=None, pk=None, min_sigma=None, ksk=None):
+    def check(self, params, lwe_key, tlwe_key, x=None, pk=None, min_sigma=None, ksk=None, hidden="pack", input_var=None):
         """Prices every layer for this key, as IntCircuit.check does, before anything runs.
         RANGE: sum_k |w_k| max|input| + |bias| must stay below 1/4 for every row (max|input| = x_max delta_in for layer 0, the
         largest activation value of the layer before otherwise); a layer that reaches 1/4 is refused (ValueError).
@@ -277,8 +301,9 @@ class Network:
         x every value bias + s g, |s g| inside the range, g the gcd of the possible input values, is taken as reachable
         (conservative).  Layers without an activation have no margin.  min_sigma: refuse (ValueError) when the smallest
         margin is below it.  Returns {"layers": [{"range": largest bound / 2^32, "sigma": [rows], "margin_sigma": smallest
-        margin of the layer}], "worst_sigma", "vector_sigma" (with x)}."""
-        sig = self.layer_sigma(params, lwe_key, tlwe_key, pk, ksk)
+        margin of the layer}], "worst_sigma", "vector_sigma" (with x)}.  hidden and input_var: the route the network will run
+        (run_device(hidden=...), run_device_samples), as layer_sigma takes them."""
+        sig = self.layer_sigma(params, lwe_key, tlwe_key, pk, ksk, hidden=hidden, input_var=input_var)
         max_in, g = self.x_max * abs(self.delta_in), abs(self.delta_in)
         pres = None if x is None else self.evaluate_plain(x, return_pre=True)[1]
         res, vec = [], None
@@ -345,25 +370,66 @@ class Network:
             self._images[key] = (d, engine)
         return self._images[key][0]
 
-    def run_device(self, engine, lists, stream=None, return_layers=False):
+    def _lwe_image(self, engine, i):
+        """the matrix-core operand image of DenseLayer i (Engine.lwe_weights_to_device), its bias and its activation"""
+        import torch
+        key = (id(engine), i, "lwe")
+        if key not in self._images:
+            ly = self.layers[i]
+            img = torch.empty(engine.lwe_weights_image_bytes(ly.rows, ly.cols), dtype=torch.uint8, device=f"cuda:{engine.device}")
+            engine.lwe_weights_to_device(ly.weights, img.data_ptr())
+            bias = None if ly.bias is None else torch.from_numpy(ly.bias).to(img.device)
+            tv = None if ly.tv is None else torch.from_numpy(ly.tv).to(img.device)
+            self._images[key] = (img, bias, tv, engine)
+        return self._images[key][:3]
+
+    def run_device_samples(self, engine, cts, stream=None, return_layers=False):
+        """cts [batch][cols][n+1] int32 (numpy, or a torch tensor on the engine's device): LWE samples of the messages
+        x_k * delta_in (eoc_lwe_encrypt, or Engine.seeded_expand_device for the integer encodings) -> the last layer's LWE
+        samples [batch][rows][n+1].  Every layer is Engine.lwe_matmul_device on samples -- layer 0 on the inputs, every later
+        one on the LUT outputs before it -- then lut_batch_device: no list, no packing key, no key switch behind a sum.
+        DenseLayer-only networks (ValueError otherwise).  Price it with check(..., hidden="lwe", input_var=...): a fresh
+        sample's variance is params.ks_stdev ** 2.  return_layers: also every layer's outputs and the tensors the layers read."""
+        import torch
+        if not all(isinstance(ly, DenseLayer) for ly in self.layers):
+            raise ValueError("run_device_samples: DenseLayer-only networks (a ConvLayer reads compact lists)")
+        dev = f"cuda:{engine.device}"
+        cur = cts if isinstance(cts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cts, np.int32)).to(dev)
+        cur = cur.reshape(-1, self.layers[0].cols, engine.n + 1).contiguous()
+        return self._run(engine, cur, True, "lwe", stream, return_layers)
+
+    def run_device(self, engine, lists, stream=None, return_layers=False, hidden="pack"):
         """lists [batch][ceil(cols / N)][2][N] int32 (numpy, or a torch tensor on the engine's device) -> the last layer's
         LWE samples [batch][rows][n+1] as a torch tensor on the device, not packed.  Per layer: linear_device, then
         lut_batch_device with the activation, then (between layers) pack_device, one list per vector.  A ConvLayer runs
         conv_linear_device instead ([batch][n_out][n+1], channel-major) and is packed with one call per (vector, channel).
-        Needs the cloud key, and the packing key for more than one layer.  return_layers: also every layer's outputs."""
+        Needs the cloud key, and the packing key for more than one layer.  return_layers: also every layer's outputs.
+        hidden="lwe": a DenseLayer behind a DenseLayer runs as lwe_matmul_device on the LUT outputs before it -- no pack_device
+        call, no key switch behind the sum; a network whose links are all of that kind needs no packing key -- and
+        return_layers gives (last, outputs per layer, the tensor every layer read)."""
         import torch
+        self._lwe_link(0, hidden)
         dev = f"cuda:{engine.device}"
         cur = lists if isinstance(lists, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(lists, np.int32)).to(dev)
         L0 = -(-self.layers[0].cols // N)
         cur = cur.reshape(-1, L0, 2, N).contiguous()
+        return self._run(engine, cur, False, hidden, stream, return_layers)
+
+    def _run(self, engine, cur, samples_in, hidden, stream, return_layers):
+        import torch
+        dev = f"cuda:{engine.device}"
         batch, stride = cur.shape[0], engine.n + 1
-        outs = []
+        outs, ins = [], []
         for i, ly in enumerate(self.layers):
-            img, bias, tv = self._image(engine, i)
+            lwe = self._lwe_link(i, hidden, 0.0 if samples_in else None)
+            img, bias, tv = self._lwe_image(engine, i) if lwe else self._image(engine, i)
             conv = isinstance(ly, ConvLayer)
             lin = torch.empty((batch, ly.n_out, stride), dtype=torch.int32, device=dev)
             d_bias = None if bias is None else bias.data_ptr()
-            if conv:
+            ins.append(cur)
+            if lwe:
+                engine.lwe_matmul_device(img.data_ptr(), ly.rows, ly.cols, cur.data_ptr(), stride, batch, d_bias, lin.data_ptr(), stream)
+            elif conv:
                 engine.conv_linear_device(img.data_ptr(), ly.rows, ly.cols, cur.data_ptr(), batch, d_bias,
                                           self._slots(engine, i).data_ptr(), ly.n_out, lin.data_ptr(), stream)
             else:
@@ -373,7 +439,9 @@ class Network:
                 out = torch.empty_like(lin)
                 engine.lut_batch_device(tv.data_ptr(), 1, lin.data_ptr(), out.data_ptr(), batch * ly.n_out, stream)
             outs.append(out)
-            if i + 1 < len(self.layers):
+            if i + 1 < len(self.layers) and self._lwe_link(i + 1, hidden):
+                cur = out                                                   # [batch][rows][n+1]: the next layer's samples
+            elif i + 1 < len(self.layers):
                 Ln = -(-ly.out_cols // N)
                 cur = torch.empty((batch, Ln, 2, N), dtype=torch.int32, device=dev)
                 for b in range(batch):
@@ -382,4 +450,6 @@ class Network:
                             engine.pack_device(out[b, c * ly.pack_filled].data_ptr(), ly.pack_filled, cur[b, c].data_ptr(), stream)
                     else:
                         engine.pack_device(out[b].data_ptr(), ly.rows, cur[b].data_ptr(), stream)
-        return (outs[-1], outs) if return_layers else outs[-1]
+        if not return_layers:
+            return outs[-1]
+        return (outs[-1], outs) if hidden == "pack" and not samples_in else (outs[-1], outs, ins)

@@ -697,6 +697,16 @@ def linear_var(params, w_row, slot_var):
     return float((w * w).sum()) * float(slot_var)
 
 
+def lwe_linear_var(w_row, input_var):
+    """variance (torus units) of the phase of one output of eoc_lwe_matmul_device: ||w||^2 input_var for
+    independent input samples of variance input_var each.  Nothing else enters: the output's error is exactly
+    sum_k w_k e_k -- no packing error on the inputs, no key switch behind the sum.  A bootstrap output has
+    predict()['total_var'] (and mean total_mean, which the sum multiplies by sum_k w_k); a fresh sample of eoc_lwe_encrypt or
+    eoc_encrypt_ints has params.ks_stdev ** 2."""
+    w = np.asarray(w_row, np.float64).ravel()
+    return float((w * w).sum()) * float(input_var)
+
+
 def linear_offset(params, pk_or_key, w_row, tlwe_key=None):
     """mean error (torus units) of one output of eoc_dot_device on FRESH lists under one public key: every list's slots
     carry compact_offset (a fresh binary u per list has mean 1/2, the key's e is the same for all of them), so the output
